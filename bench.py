@@ -219,6 +219,31 @@ def cpu_baseline(batch_np, n_iter, budget_s=20.0):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all .npy files of the job together
+
+
+def dump_outputs(out, names, directory, rank, world):
+    """--dump-outputs: the result tensors the last timed step filled (what a caller of the timed path receives) -> DIR/<name>.npy, float32
+    results as float32 and integer ones (iters, status) as float64 (exact).  Past DUMP_LIMIT_BYTES / world per rank, the same fixed,
+    seeded sample of frames from every array, its indices (into this rank's batch) in DIR/frame_index.npy.  N > 1: every rank its own
+    shard's results, file names suffixed _rank<r>."""
+    arrs = {}
+    for n in names:
+        a = out[n].cpu().numpy()
+        arrs[n] = a if a.dtype == np.float32 else a.astype(np.float64)
+    B = len(arrs[names[0]])
+    limit = DUMP_LIMIT_BYTES // world - 64 * 1024  # (less the .npy headers)
+    if sum(a.nbytes for a in arrs.values()) > limit:
+        per_frame = sum(a.nbytes for a in arrs.values()) // B + 8  # (+ the frame index)
+        keep = np.sort(np.random.default_rng(1234).choice(B, limit // per_frame, replace=False))
+        arrs = {n: a[keep] for n, a in arrs.items()}
+        arrs["frame_index"] = keep.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for n, a in arrs.items():
+        np.save(os.path.join(directory, n + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 PRECONDITION_MS = 60.0  # of the measured launch, back to back, before the warm-up steps (see timed_pass)
 
 
@@ -245,7 +270,12 @@ def main():
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--all-ranks-on-device0", action="store_true", help="rehearsal on a 1-GPU box (with --backend gloo)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the results of the last one as DIR/<name>.npy (float32 / float64, at most 64 MB in all: "
+                         "a fixed, seeded sample of the frames beyond that); the inputs depend on the arguments only, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -360,6 +390,8 @@ def main():
 
     dt, kern_ms, sclk, out, idle = timed_pass(batch, args.kernel, args.steps, args.warmup, from_idle=True)
     fpb, tpb, lds_bytes = opt.kernel_geometry()
+    if args.dump_outputs:  # (`clock` is the launch's own timing stamp, not a result)
+        dump_outputs(out, [n for n in names if n != "clock"], args.dump_outputs, rank, world)
 
     # ---- parity on a sample (rank-local), reduced with the timing
     err_mm = float("nan")

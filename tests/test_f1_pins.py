@@ -3,9 +3,9 @@
 The reference's BVH I/O, Euler / dual-quaternion conventions and FK come from `upc-pymotion`, which is absent here, and the
 reference holds no evaluation output: those conventions stay UNPINNED against the reference.  What its data
 does pin: the three motion files it ships (python/data/example/{train,eval}/example{,_2,_3}.bvh -- the two folders are
-byte-identical; staged by __graft_entry__.build() into tests/data/_local) must survive our reader / writer unchanged, must
-look like the training data in the units of data.pt, must be reconstructed by the trained VAE, and the metric of
-eval_metrics.py must behave as its definition says."""
+byte-identical; committed as tests/golden/<name>.npz, unpacked by __graft_entry__.build() into tests/data/_local) must
+survive our reader / writer unchanged, must look like the training data in the units of data.pt, must be reconstructed by
+the trained VAE, and the metric of eval_metrics.py must behave as its definition says."""
 import os
 
 import numpy as np
@@ -25,8 +25,7 @@ FILES = {"example.bvh": 5052, "example_2.bvh": 2920, "example_3.bvh": 3047}
 
 def _path(name):
     p = os.path.join(ROOT, "tests", "data", "_local", name)
-    if not os.path.exists(p):
-        pytest.skip(f"{name} not staged (python -c 'import __graft_entry__ as g; g.build()' where the reference is mounted)")
+    assert os.path.exists(p), f"{name} not unpacked from tests/golden/{name}.npz (__graft_entry__.build())"
     return p
 
 

@@ -38,8 +38,7 @@ def load(golden_dir, name):
 def bvh_path(g):
     name = g["meta"]["bvh"]
     p = os.path.join(ROOT, "tests", "data", name) if name == "example_clip.bvh" else os.path.join(ROOT, "tests", "data", "_local", name)
-    if not os.path.exists(p):
-        pytest.skip(f"{name} not staged (python -c 'import __graft_entry__ as g; g.build()' where the reference is mounted)")
+    assert os.path.exists(p), f"{name} not unpacked from tests/golden/{name}.npz (__graft_entry__.build())"
     return p
 
 

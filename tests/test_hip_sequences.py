@@ -249,7 +249,7 @@ def test_sequence_launch_ragged_counts_and_target_root(S):
 def test_config1_full_example(tmp_path):
     """BASELINE config 1 at full size: eval_drag on data/example/eval/example.bvh (5052 frames, 120 Hz), 6-tracker config,
     the reference's early-stop settings (eval_drag.py:210-214), one sequential sequence.  The clip is data of the reference,
-    staged by __graft_entry__.build() into tests/data/_local/ (git-ignored, travels with the snapshot).  lambda_temporal is 0
+    committed as tests/golden/example.bvh.npz and unpacked by __graft_entry__.build() into tests/data/_local/.  lambda_temporal is 0
     because temporal.pt is missing from the reference mount; accuracy bounds: the paper reports a few cm."""
     import os
     import time
@@ -258,8 +258,7 @@ def test_config1_full_example(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     path = os.path.join(root, "tests", "data", "_local", "example.bvh")
-    if not os.path.exists(path):
-        pytest.skip("example.bvh not staged (build() copies it where /root/reference is mounted)")
+    assert os.path.exists(path), "example.bvh not unpacked from tests/golden/example.bvh.npz (__graft_entry__.build())"
     cfg6 = os.path.join(root, "dragposer_amd", "config", "6_trackers_config.json")
     per = eval_drag.main([path, "--config", cfg6, "--out-dir", str(tmp_path / "per_frame"), "--per-frame"])[0]  # the host drives every frame
     t0 = time.time()
@@ -278,7 +277,7 @@ def test_config1_full_example(tmp_path):
 def test_cli_with_the_reference_model_folder(tmp_path, capsys, monkeypatch):
     """The reference's CLI contract (eval_drag.py:255-293): model_path = a FOLDER with generator.pt / data.pt, input_path = a
     directory of .bvh files, results in data/eval_<name> under the working directory, the four result lines printed verbatim.
-    Run on the other two motion files the reference ships (example_2, example_3; staged like example.bvh)."""
+    Run on the other two motion files the reference ships (example_2, example_3; unpacked like example.bvh)."""
     import os
     import shutil
 
@@ -287,8 +286,7 @@ def test_cli_with_the_reference_model_folder(tmp_path, capsys, monkeypatch):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     local = os.path.join(root, "tests", "data", "_local")
     names = ["example_2.bvh", "example_3.bvh"]
-    if not all(os.path.exists(os.path.join(local, n)) for n in names):
-        pytest.skip("example_2 / example_3 not staged (build() copies them where /root/reference is mounted)")
+    assert all(os.path.exists(os.path.join(local, n)) for n in names), "example_2 / example_3 not unpacked from tests/golden/ (__graft_entry__.build())"
     raw = np.load(R.DEFAULT_MODEL)
     folder = tmp_path / "model_dancedb"
     folder.mkdir()
