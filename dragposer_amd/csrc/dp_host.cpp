@@ -26,6 +26,7 @@ struct dp_ctx {
     float* d_w4img = nullptr;
     float* d_w4bias = nullptr;
     dpw4::Pair* d_w4pairs = nullptr;
+    bool w4_bp = false; // the w4 image / pairs are in the body-part layout (dp_w4_bp.hip), not the dense one (dp_w4.hip)
     unsigned* d_w16img = nullptr; // 16-frames-per-wave kernel (dp_w16.hip); NULL when the skeleton is not the one its slot map is for
     float* d_w16bias = nullptr;
     dpw16::SlotConst* d_w16slots = nullptr;
@@ -264,7 +265,9 @@ static int w4_src_row(const ItemPlan& pl, int item, int c)
     return -1;
 }
 
-extern "C" int dp_debug_pack_w4(const dp_folded* f, const dp_model* m, float* img, float* bias)
+// The body-part layout (dp_w4.h) runs only some K-groups of layer 2 per block; it is packed only when every weight it leaves out is
+// exactly zero (else DP_ERR_UNSUPPORTED, and dp_create keeps the dense layout).
+static int pack_w4(const dp_folded* f, const dp_model* m, float* img, float* bias, bool bp)
 {
     if (!f || !model_ptrs_ok(m) || !img || !bias) return DP_ERR_INVALID;
     ItemPlan pl;
@@ -290,13 +293,27 @@ extern "C" int dp_debug_pack_w4(const dp_folded* f, const dp_model* m, float* im
         const int c0ch = dpw4::h0_channel(l); // the first hidden layer's channel in row l (dp_w4.h), or -1
         for (int k = 0; k < 24; ++k) put(dpw4::S_L0 + k, l, c0ch >= 0 ? f->A0[c0ch * 24 + k] : 0.f);
         for (int k = 0; k < 40; ++k) put(dpw4::S_L1 + k, l, l < 60 ? f->A1[l * 40 + k] : 0.f); // (K-step k = channel k: quads 0..4, 8..12)
-        // layer 2: row l of block blk = channel l2_channel(blk, l & 3) of the side-l2_side(l & 3) item of quad l >> 2 (dp_w4.h)
-        const int it2 = dpw4::item_of(dpw4::l2_side(l & 3), l >> 2);
-        const int ch2[2] = {dpw4::l2_channel(0, l & 3), dpw4::l2_channel(1, l & 3)};
-        const int r2[2] = {w4_src_row(pl, it2, ch2[0]), w4_src_row(pl, it2, ch2[1])};
-        for (int k = 0; k < 60; ++k) {
-            put(dpw4::S_L2A + k, l, r2[0] >= 0 ? (float)(sd_of(it2, ch2[0]) * (double)f->A2[r2[0] * 60 + k]) : 0.f);
-            put(dpw4::S_L2B + k, l, r2[1] >= 0 ? (float)(sd_of(it2, ch2[1]) * (double)f->A2[r2[1] * 60 + k]) : 0.f);
+        // layer 2, dense: row l of block blk = channel l2_channel(blk, l & 3) of the side-l2_side(l & 3) item of quad l >> 2;
+        // body-part: channel l & 3 of the side-blk item of quad l >> 2, K-groups BP_GROUPS_A / _B of the block only (dp_w4.h)
+        int it2b[2], ch2[2];
+        for (int blk = 0; blk < 2; ++blk) {
+            it2b[blk] = bp ? dpw4::bp_item_of(blk, l >> 2) : dpw4::item_of(dpw4::l2_side(l & 3), l >> 2);
+            ch2[blk] = bp ? (l & 3) : dpw4::l2_channel(blk, l & 3);
+        }
+        const int r2[2] = {w4_src_row(pl, it2b[0], ch2[0]), w4_src_row(pl, it2b[1], ch2[1])};
+        for (int blk = 0; blk < 2; ++blk) {
+            const int s0 = blk ? dpw4::S_L2B : dpw4::S_L2A;
+            int kept = 0; // (body-part: K-steps packed so far)
+            for (int k = 0; k < 60; ++k) {
+                const float v = r2[blk] >= 0 ? (float)(sd_of(it2b[blk], ch2[blk]) * (double)f->A2[r2[blk] * 60 + k]) : 0.f;
+                if (!bp) { put(s0 + k, l, v); continue; }
+                bool run = false;
+                for (int g = 0; g < (blk ? dpw4::BP_NG_B : dpw4::BP_NG_A); ++g) run = run || (blk ? dpw4::BP_GROUPS_B[g] : dpw4::BP_GROUPS_A[g]) == k / 4;
+                if (run) put(s0 + kept++, l, v);
+                else if (v != 0.f)
+                    return fail(nullptr, DP_ERR_UNSUPPORTED, "w4 body-part layout: K-group " + std::to_string(k / 4) + " of item " +
+                                                                 std::to_string(it2b[blk]) + " is not zero");
+            }
         }
         for (int k = 0; k < 104; ++k) { // column k = channel k & 3 of an item of dL/dr (side A quads 0..15, then side B quads 1..10)
             const int item = k < 64 ? dpw4::item_of(0, k >> 2) : dpw4::item_of(1, dpw4::B2_ABID0_B + ((k - 64) >> 2));
@@ -309,7 +326,24 @@ extern "C" int dp_debug_pack_w4(const dp_folded* f, const dp_model* m, float* im
         bias[l] = c0ch >= 0 ? f->c0[c0ch] : 0.f;
         bias[64 + l] = l < 60 ? f->b1[l] : 0.f;
         for (int blk = 0; blk < 2; ++blk) // (idle items: sigma 0, mu (1, 0, 0, 0) -- they decode to the unit quaternion)
-            bias[128 + 64 * blk + l] = (float)(sd_of(it2, ch2[blk]) * (r2[blk] >= 0 ? (double)f->b2[r2[blk]] : 0.0) + mu_of(it2, ch2[blk]));
+            bias[128 + 64 * blk + l] = (float)(sd_of(it2b[blk], ch2[blk]) * (r2[blk] >= 0 ? (double)f->b2[r2[blk]] : 0.0) + mu_of(it2b[blk], ch2[blk]));
+    }
+    return DP_OK;
+}
+
+extern "C" int dp_debug_pack_w4(const dp_folded* f, const dp_model* m, float* img, float* bias) { return pack_w4(f, m, img, bias, false); }
+extern "C" int dp_debug_pack_w4_bp(const dp_folded* f, const dp_model* m, float* img, float* bias) { return pack_w4(f, m, img, bias, true); }
+
+// host-only, exported for the CPU tests: the body-part placement (dp_w4.h) -- items [2][16] (side, quad; -1 idle), the K-groups of layer 2
+// each block runs [2][15] (-1 beyond BP_NG_A / BP_NG_B)
+extern "C" int dp_debug_w4_bp_layout(int* items, int* groups)
+{
+    if (!items || !groups) return DP_ERR_INVALID;
+    for (int s = 0; s < 2; ++s)
+        for (int b = 0; b < 16; ++b) items[16 * s + b] = dpw4::bp_item_of(s, b);
+    for (int g = 0; g < 15; ++g) {
+        groups[g] = g < dpw4::BP_NG_A ? dpw4::BP_GROUPS_A[g] : -1;
+        groups[15 + g] = g < dpw4::BP_NG_B ? dpw4::BP_GROUPS_B[g] : -1;
     }
     return DP_OK;
 }
@@ -317,7 +351,7 @@ extern "C" int dp_debug_pack_w4(const dp_folded* f, const dp_model* m, float* im
 extern "C" int dp_debug_items(const dp_model* m, void* out_items);
 
 // host-only, exported for the CPU tests: kinematics constants of the wave-private kernel, one dpw4::Pair per lane quad
-extern "C" int dp_debug_pairs_w4(const dp_model* m, void* out_pairs /* 16 x 144 B */)
+static int pairs_w4(const dp_model* m, void* out_pairs, bool bp)
 {
     if (!model_ptrs_ok(m) || !out_pairs) return fail(nullptr, DP_ERR_INVALID, "dp_debug_pairs_w4: NULL pointer");
     std::vector<ItemConst> items(32);
@@ -328,7 +362,7 @@ extern "C" int dp_debug_pairs_w4(const dp_model* m, void* out_pairs /* 16 x 144 
     for (int b = 0; b < 16; ++b)
         for (int s = 0; s < 2; ++s) {
             dpw4::Pair& p = pr[b];
-            const int item = dpw4::item_of(s, b);
+            const int item = bp ? dpw4::bp_item_of(s, b) : dpw4::item_of(s, b);
             p.item[s] = item;
             p.kind[s] = KIND_IDLE;
             p.mu[0][s] = 1.f; // idle: a unit quaternion, whatever the (zero) decoder channels say
@@ -346,6 +380,8 @@ extern "C" int dp_debug_pairs_w4(const dp_model* m, void* out_pairs /* 16 x 144 
         }
     return DP_OK;
 }
+extern "C" int dp_debug_pairs_w4(const dp_model* m, void* out_pairs /* 16 x 144 B */) { return pairs_w4(m, out_pairs, false); }
+extern "C" int dp_debug_pairs_w4_bp(const dp_model* m, void* out_pairs /* 16 x 144 B */) { return pairs_w4(m, out_pairs, true); }
 
 // host-only, exported for the CPU tests: P3 per-item constants [32]
 extern "C" int dp_debug_items(const dp_model* m, void* out_items /* 32 x 128 B */)
@@ -438,10 +474,16 @@ extern "C" int dp_create(dp_ctx** out, const dp_model* model, int device)
     std::vector<ItemConst> items(32);
     std::vector<float> w4img(dpw4::IMG_FLOATS), w4bias(dpw4::BIAS_FLOATS);
     if (rc == DP_OK) rc = dp_debug_pack(&ctx->folded, model->parents, wfrag.data(), bfrag.data(), ctx->smask.data());
-    if (rc == DP_OK) rc = dp_debug_pack_w4(&ctx->folded, model, w4img.data(), w4bias.data());
+    // the w4 family: the body-part layout when the decoder's block sparsity fits it (every K-group it leaves out exactly zero), else dense
+    if (rc == DP_OK) {
+        const std::string prev_err = g_create_err; // (a model the body-part layout does not fit is no error)
+        ctx->w4_bp = pack_w4(&ctx->folded, model, w4img.data(), w4bias.data(), true) == DP_OK;
+        g_create_err = prev_err;
+    }
+    if (rc == DP_OK && !ctx->w4_bp) rc = pack_w4(&ctx->folded, model, w4img.data(), w4bias.data(), false);
     if (rc == DP_OK) rc = dp_debug_items(model, items.data());
     std::vector<dpw4::Pair> pairs(16);
-    if (rc == DP_OK) rc = dp_debug_pairs_w4(model, pairs.data());
+    if (rc == DP_OK) rc = pairs_w4(model, pairs.data(), ctx->w4_bp);
     const bool w16 = rc == DP_OK && dp_w16_supported(model);
     std::vector<unsigned> w16img(w16 ? dpw16::IMG_U32 : 0);
     std::vector<float> w16bias(dpw16::BIAS_FLOATS);
@@ -664,7 +706,8 @@ static int launch(dp_ctx* ctx, KArgs& k, void* stream, int kernel = DP_KERNEL_W4
     // (8 waves, 128 frames per workgroup): one wave's matrix phases under the other's vector phases
     const int w16_waves = k.n_frames > ctx->n_cu * 4 * dp_w16_frames_per_wave() ? 8 : 4;
     if (kernel == DP_KERNEL_W16) ctx->last_kernel = 16 * (w16_waves / 4);
-    hipError_t e = kernel == DP_KERNEL_W16 ? dp_launch_w16(&k, (hipStream_t)stream, w16_waves) : dp_launch_w4(&k, (hipStream_t)stream);
+    hipError_t e = kernel == DP_KERNEL_W16 ? dp_launch_w16(&k, (hipStream_t)stream, w16_waves) : ctx->w4_bp ? dp_launch_w4_bp(&k, (hipStream_t)stream)
+                                                                                               : dp_launch_w4(&k, (hipStream_t)stream);
 #endif
     if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("kernel launch: ") + hipGetErrorString(e));
     return DP_OK;

@@ -73,6 +73,7 @@ extern "C" hipError_t dp_launch_optimize(const KArgs* args, hipStream_t stream);
 extern "C" int dp_kernel_lds_bytes(void);
 // dp_w4.hip: wave-private kernel, 4 frames per wave, no workgroup barrier inside the loop
 extern "C" hipError_t dp_launch_w4(const KArgs* args, hipStream_t stream);
+extern "C" hipError_t dp_launch_w4_bp(const KArgs* args, hipStream_t stream); // body-part layout (dp_w4_bp.hip)
 extern "C" int dp_w4_lds_bytes(void);
 extern "C" int dp_w4_frames_per_block(void);
 // dp_w16*.hip: 16 frames per wave, decoder on v_mfma_f32_16x16x32_bf16 in split precision (fixed iteration count, or KArgs.early_stop: the per-frame while-condition)

@@ -45,7 +45,7 @@ constexpr int BIAS_FLOATS = 4 * 64;
 DP_HD constexpr int h0_row(int c) { return c < 20 ? c : 12 + c; }
 DP_HD constexpr int h0_channel(int row) { return row < 20 ? row : (row >= 32 && row < 52 ? row - 12 : -1); }
 
-// Rows of layer 2's two 64-row blocks: row 4b + r of block `blk` is channel 2 blk + (r >> 1) of the side-(r & 1) item of quad
+// Dense rows of layer 2's two 64-row blocks (dp_w4.hip; the body-part rows of dp_w4_bp.hip are below): row 4b + r of block `blk` is channel 2 blk + (r >> 1) of the side-(r & 1) item of quad
 // b.  The transposed result of a block then has the SAME channel of the quad's two items in each even/odd register pair,
 // which is what the packed kinematics arithmetic (both items of a quad per instruction) reads -- no moves in between.
 DP_HD constexpr int l2_side(int r) { return r & 1; }
@@ -57,6 +57,28 @@ DP_HD constexpr int l2_channel(int blk, int r) { return 2 * blk + (r >> 1); }
 constexpr int ITEMS_A = 16;
 DP_HD constexpr int item_of(int side, int b) { return side == 0 ? b : (b >= 1 && b <= 10 ? 15 + b : -1); }
 constexpr int B2_GROUPS_A = 16, B2_GROUPS_B = 10, B2_ABID0_B = 1; // bL2: K groups of side A (ABID 0..15), side B (ABID 1..10)
+
+// ---- The "body-part" layout (dp_w4_bp.hip).  The folded A2 = (W2 . M2) U2 is block sparse: the SkeletonConv mask and the 0/1
+// unpooling leave each item's rows non-zero in a few aligned groups of 4 hidden channels (= K-groups of layer 2) only, those of the
+// pooled nodes of its own body part.  The dense rows above mix every item into both blocks, so both run all 15 K-groups.  Here row
+// 4b + c of block s is channel c of the side-s item of quad b: block A = the legs (joints 0..8, the root alone on quad 0) and the root
+// displacement, block B = the spine, the arms and the two virtual copies of joint 11 -- and each block runs the K-groups of its own
+// items only: 7 + 13 instead of 15 + 15 (the Xsens tree of the shipped model; the placement was found by an exhaustive search,
+// tools/w4_placement.py).  dp_create takes this layout only when every group left out is exactly zero for the model it is given.
+//   side A, quad b: joint b (b = 0..8), the displacement (9), the third virtual item (10: unused by the Xsens tree), idle (11..15)
+//   side B, quad b: idle (0: the root's quad carries nothing else, as in the dense layout), joints 9..21 (1..13), virtual 23, 24 (14, 15)
+// After the transposes a lane holds (A.c0..c3) and (B.c0..c3); the packed kinematics pairs them per channel.  bL2 (K = items) keeps
+// the dense K order -- items 0..25 -- and the dense image; only the operand (side) and the quad (ABID) of an item's group differ.
+DP_HD constexpr int bp_item_of(int side, int b)
+{
+    return side == 0 ? (b <= 8 ? b : b == 9 ? 22 : b == 10 ? 25 : -1) : (b >= 1 && b <= 13 ? 8 + b : b == 14 ? 23 : b == 15 ? 24 : -1);
+}
+DP_HD constexpr int bp_side(int item) { return (item <= 8 || item == 22 || item == 25) ? 0 : 1; }
+DP_HD constexpr int bp_quad(int item) { return item <= 8 ? item : item == 22 ? 9 : item == 25 ? 10 : item <= 21 ? item - 8 : item - 9; }
+constexpr int BP_NG_A = 7, BP_NG_B = 13; // K-groups of layer 2 each block runs, in this order (the dense chain's order without the others)
+constexpr int BP_GROUPS_A[BP_NG_A] = {0, 1, 2, 3, 4, 5, 14};
+constexpr int BP_GROUPS_B[BP_NG_B] = {0, 1, 3, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14};
+// the image keeps the dense geometry: block A's kept groups at S_L2A, block B's at S_L2B, each packed to the front (zeros behind)
 
 // per-quad constants of the two items, side A / side B interleaved (the kernel keeps them as packed register pairs)
 struct Pair {

@@ -1,0 +1,27 @@
+// dp_w4_bp.hip -- the wave-private kernel (dp_w4_impl.h) in the BODY-PART row layout of layer 2 (dp_w4.h: block A = the legs and the
+// root displacement, block B = the spine, the arms and the virtual items): 7 + 13 K-groups of layer 2 instead of 15 + 15, 40 MFMAs fewer
+// per iteration, the same bits.  dp_create takes it when every K-group it leaves out is exactly zero for the model (dp_host.cpp).
+#define W4_BP 1
+// Layer 2 holds 80 accumulator registers here instead of 120: two more head groups of bL2 stay resident (5 + 2 in vector registers): -0.9 %
+// against 3 (profiles/r07_bp_tuning.txt; the dense unit keeps 3, its accumulator half is full)
+#define W4_B2_RES_A 5
+#define W4_KERNEL dp_w4_bp_kernel
+#include "dp_w4_impl.h"
+
+extern "C" hipError_t dp_launch_w4_bp(const KArgs* args, hipStream_t stream)
+{
+    constexpr int NW = 4;
+    const int grid = (args->n_frames + NW * FPW - 1) / (NW * FPW);
+    const bool lng = args->n_iter > MAX_ITERS;
+    if (args->seq.n_steps > 0) {
+        if (lng) hipLaunchKernelGGL((dp_w4_bp_kernel<NW, true, true, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+        else hipLaunchKernelGGL((dp_w4_bp_kernel<NW, true, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+    } else if (args->early_stop && args->mode == 0) {
+        if (lng) hipLaunchKernelGGL((dp_w4_bp_kernel<NW, true, false, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+        else hipLaunchKernelGGL((dp_w4_bp_kernel<NW, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+    } else {
+        if (lng) hipLaunchKernelGGL((dp_w4_bp_kernel<NW, false, false, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+        else hipLaunchKernelGGL((dp_w4_bp_kernel<NW, false>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+    }
+    return hipGetLastError();
+}

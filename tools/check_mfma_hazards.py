@@ -19,11 +19,12 @@ import __graft_entry__ as G
 NEED = {"C": 2, "AB": 4, "R": 4, "V": 2}
 
 
-def isa(extra, base_flags=None):
-    """the ISA of dp_w4.hip as $HIPCC (the compiler build() uses) generates it with the product's flags (or `base_flags`) + `extra`"""
-    out = os.path.join(tempfile.mkdtemp(prefix="w4isa_"), "dp_w4.s")
+def isa(extra, base_flags=None, source="dp_w4.hip"):
+    """the ISA of `source` (a unit of dp_w4_impl.h) as $HIPCC (the compiler build() uses) generates it with the product's flags (or
+    `base_flags`) + `extra`"""
+    out = os.path.join(tempfile.mkdtemp(prefix="w4isa_"), os.path.splitext(source)[0] + ".s")
     flags = [f for f in (G.HIPCC_FLAGS if base_flags is None else base_flags) if f not in ("-shared", "-fPIC")] + list(extra)
-    subprocess.check_call([os.environ.get("HIPCC", "hipcc"), *flags, "-S", "--cuda-device-only", "-o", out, os.path.join(G.CSRC, "dp_w4.hip")], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    subprocess.check_call([os.environ.get("HIPCC", "hipcc"), *flags, "-S", "--cuda-device-only", "-o", out, os.path.join(G.CSRC, source)], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return open(out).read()
 
 
