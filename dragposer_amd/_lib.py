@@ -190,6 +190,8 @@ def load(path=None):
     lib.dp_debug_pack.argtypes = [C.POINTER(DpFolded), _i, _f, _f, C.POINTER(C.c_uint)]
     lib.dp_debug_items.argtypes = [C.POINTER(DpModel), C.c_void_p]
     lib.dp_debug_pack_w16.argtypes = [C.POINTER(DpFolded), C.POINTER(DpModel), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dp_debug_last_launch.argtypes = [C.c_void_p, _i]
+    lib.dp_debug_set_w4_layout.argtypes = [C.c_void_p, C.c_int]
     _libs[path] = lib
     return lib
 

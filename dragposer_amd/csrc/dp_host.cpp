@@ -27,6 +27,8 @@ struct dp_ctx {
     float* d_w4bias = nullptr;
     dpw4::Pair* d_w4pairs = nullptr;
     bool w4_bp = false; // the w4 image / pairs are in the body-part layout (dp_w4_bp.hip), not the dense one (dp_w4.hip)
+    std::vector<float> w4img_h[2], w4bias_h[2]; // host copies of both layouts [dense, body-part] (empty: the model does not fit it),
+    std::vector<dpw4::Pair> w4pairs_h[2];       // for dp_debug_set_w4_layout
     unsigned* d_w16img = nullptr; // 16-frames-per-wave kernel (dp_w16.hip); NULL when the skeleton is not the one its slot map is for
     float* d_w16bias = nullptr;
     dpw16::SlotConst* d_w16slots = nullptr;
@@ -37,6 +39,7 @@ struct dp_ctx {
     std::string err;
     float mean_q0[4] = {0, 0, 0, 0}, std_q0[4] = {1, 1, 1, 1}; // root quaternion channels (sequence epilogue)
     int last_kernel = 0;   // what the last launch used: 4 = dp_w4.hip (8 in the test-only library, below)
+    LaunchPick last_pick{}; // the instantiation the last launch ran, as its launcher recorded it (dp_debug_last_launch)
 };
 
 // The product library has two optimise kernels: dp_w4.hip (4 frames per wave, fp32 MFMA) and dp_w16*.hip (16 frames per wave, bf16
@@ -472,18 +475,23 @@ extern "C" int dp_create(dp_ctx** out, const dp_model* model, int device)
     std::vector<float> wfrag(NWAVE * W_REGS * 64), bfrag(128);
     ctx->smask.assign(NWAVE * NGEMM, 0u);
     std::vector<ItemConst> items(32);
-    std::vector<float> w4img(dpw4::IMG_FLOATS), w4bias(dpw4::BIAS_FLOATS);
     if (rc == DP_OK) rc = dp_debug_pack(&ctx->folded, model->parents, wfrag.data(), bfrag.data(), ctx->smask.data());
-    // the w4 family: the body-part layout when the decoder's block sparsity fits it (every K-group it leaves out exactly zero), else dense
-    if (rc == DP_OK) {
+    // the w4 family: the body-part layout when the decoder's block sparsity fits it (every K-group it leaves out exactly zero), else dense.
+    // Both are packed and kept on the host (dp_debug_set_w4_layout switches between them).
+    for (int bp = 0; bp < 2 && rc == DP_OK; ++bp) {
+        std::vector<float> img(dpw4::IMG_FLOATS), bias(dpw4::BIAS_FLOATS);
         const std::string prev_err = g_create_err; // (a model the body-part layout does not fit is no error)
-        ctx->w4_bp = pack_w4(&ctx->folded, model, w4img.data(), w4bias.data(), true) == DP_OK;
-        g_create_err = prev_err;
+        const int prc = pack_w4(&ctx->folded, model, img.data(), bias.data(), bp == 1);
+        if (prc != DP_OK && bp == 1) { g_create_err = prev_err; continue; }
+        rc = prc;
+        std::vector<dpw4::Pair> pairs(16);
+        if (rc == DP_OK) rc = pairs_w4(model, pairs.data(), bp == 1);
+        ctx->w4img_h[bp].swap(img); ctx->w4bias_h[bp].swap(bias); ctx->w4pairs_h[bp].swap(pairs);
     }
-    if (rc == DP_OK && !ctx->w4_bp) rc = pack_w4(&ctx->folded, model, w4img.data(), w4bias.data(), false);
+    ctx->w4_bp = rc == DP_OK && !ctx->w4img_h[1].empty();
+    const std::vector<float>& w4img = ctx->w4img_h[ctx->w4_bp], &w4bias = ctx->w4bias_h[ctx->w4_bp];
+    const std::vector<dpw4::Pair>& pairs = ctx->w4pairs_h[ctx->w4_bp];
     if (rc == DP_OK) rc = dp_debug_items(model, items.data());
-    std::vector<dpw4::Pair> pairs(16);
-    if (rc == DP_OK) rc = pairs_w4(model, pairs.data(), ctx->w4_bp);
     const bool w16 = rc == DP_OK && dp_w16_supported(model);
     std::vector<unsigned> w16img(w16 ? dpw16::IMG_U32 : 0);
     std::vector<float> w16bias(dpw16::BIAS_FLOATS);
@@ -698,6 +706,7 @@ static int launch(dp_ctx* ctx, KArgs& k, void* stream, int kernel = DP_KERNEL_W4
 {
     DEVICE_GUARD(ctx);
     ctx->last_kernel = KERNEL_CHOICE;
+    ctx->last_pick = LaunchPick{};
 #ifdef DP_REF8_BUILD
     (void)kernel;
     hipError_t e = dp_launch_optimize(&k, (hipStream_t)stream);
@@ -706,11 +715,41 @@ static int launch(dp_ctx* ctx, KArgs& k, void* stream, int kernel = DP_KERNEL_W4
     // (8 waves, 128 frames per workgroup): one wave's matrix phases under the other's vector phases
     const int w16_waves = k.n_frames > ctx->n_cu * 4 * dp_w16_frames_per_wave() ? 8 : 4;
     if (kernel == DP_KERNEL_W16) ctx->last_kernel = 16 * (w16_waves / 4);
-    hipError_t e = kernel == DP_KERNEL_W16 ? dp_launch_w16(&k, (hipStream_t)stream, w16_waves) : ctx->w4_bp ? dp_launch_w4_bp(&k, (hipStream_t)stream)
-                                                                                               : dp_launch_w4(&k, (hipStream_t)stream);
+    LaunchPick* pick = &ctx->last_pick;
+    hipError_t e = kernel == DP_KERNEL_W16 ? dp_launch_w16(&k, (hipStream_t)stream, w16_waves, pick)
+                   : ctx->w4_bp            ? dp_launch_w4_bp(&k, (hipStream_t)stream, pick)
+                                           : dp_launch_w4(&k, (hipStream_t)stream, pick);
 #endif
     if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("kernel launch: ") + hipGetErrorString(e));
     return DP_OK;
+}
+
+// host-only, exported for the tests: the instantiation the context's last dp_optimize / dp_forward / dp_optimize_sequence launched, as the
+// launcher recorded it -- out[5] = unit (1 dp_w4.hip, 2 dp_w4_bp.hip, 3 dp_w16*.hip; 0: none yet, or the test-only library), waves per
+// workgroup, and the EARLY, SEQ and LONG template flags
+extern "C" int dp_debug_last_launch(const dp_ctx* ctx, int* out)
+{
+    if (!ctx || !out) return DP_ERR_INVALID;
+    const LaunchPick& p = ctx->last_pick;
+    out[0] = p.unit; out[1] = p.waves; out[2] = p.early; out[3] = p.seq; out[4] = p.lng;
+    return DP_OK;
+}
+
+// host-only, exported for the tests: upload the w4 image, bias rows and pairs in the dense (bp = 0) or the body-part (bp = 1) layout, so that
+// one model runs through both units; bp = -1 only queries.  Returns the layout now in place, or DP_ERR_UNSUPPORTED when the model does not fit
+// the body-part layout (dp_create found a left-out weight that is not zero).  The caller has no launch of the context in flight.
+extern "C" int dp_debug_set_w4_layout(dp_ctx* ctx, int bp)
+{
+    if (!ctx || bp < -1 || bp > 1) return DP_ERR_INVALID;
+    if (bp < 0) return ctx->w4_bp ? 1 : 0;
+    if (ctx->w4img_h[bp].empty()) return fail(ctx, DP_ERR_UNSUPPORTED, "dp_debug_set_w4_layout: the model does not fit the body-part layout");
+    DEVICE_GUARD(ctx);
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(ctx->d_w4img, ctx->w4img_h[bp].data(), ctx->w4img_h[bp].size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_w4bias, ctx->w4bias_h[bp].data(), ctx->w4bias_h[bp].size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_w4pairs, ctx->w4pairs_h[bp].data(), ctx->w4pairs_h[bp].size() * sizeof(dpw4::Pair), hipMemcpyHostToDevice));
+    ctx->w4_bp = bp == 1;
+    return bp;
 }
 
 // private extension used by the tests: same as dp_optimize, plus an optional debug dump

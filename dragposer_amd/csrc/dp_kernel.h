@@ -69,15 +69,27 @@ struct KArgs {
     AdamCont cont;
 };
 
+// Which template instantiation a launch ran (dp_debug_last_launch, for the tests): each launcher fills it at the branch that launches.
+enum { DP_UNIT_NONE = 0, DP_UNIT_W4 = 1, DP_UNIT_W4_BP = 2, DP_UNIT_W16 = 3 };
+struct LaunchPick {
+    int unit;  // DP_UNIT_*
+    int waves; // per workgroup
+    int early, seq, lng; // the EARLY, SEQ and LONG template flags
+};
+inline void set_pick(LaunchPick* p, int unit, int waves, bool early, bool seq, bool lng)
+{
+    if (p) *p = LaunchPick{unit, waves, early ? 1 : 0, seq ? 1 : 0, lng ? 1 : 0};
+}
+
 extern "C" hipError_t dp_launch_optimize(const KArgs* args, hipStream_t stream);
 extern "C" int dp_kernel_lds_bytes(void);
 // dp_w4.hip: wave-private kernel, 4 frames per wave, no workgroup barrier inside the loop
-extern "C" hipError_t dp_launch_w4(const KArgs* args, hipStream_t stream);
-extern "C" hipError_t dp_launch_w4_bp(const KArgs* args, hipStream_t stream); // body-part layout (dp_w4_bp.hip)
+extern "C" hipError_t dp_launch_w4(const KArgs* args, hipStream_t stream, LaunchPick* pick /* nullable */);
+extern "C" hipError_t dp_launch_w4_bp(const KArgs* args, hipStream_t stream, LaunchPick* pick); // body-part layout (dp_w4_bp.hip)
 extern "C" int dp_w4_lds_bytes(void);
 extern "C" int dp_w4_frames_per_block(void);
 // dp_w16*.hip: 16 frames per wave, decoder on v_mfma_f32_16x16x32_bf16 in split precision (fixed iteration count, or KArgs.early_stop: the per-frame while-condition)
-extern "C" hipError_t dp_launch_w16(const KArgs* args, hipStream_t stream, int waves /* 4 or 8 per workgroup */);
+extern "C" hipError_t dp_launch_w16(const KArgs* args, hipStream_t stream, int waves /* 4 or 8 per workgroup */, LaunchPick* pick);
 extern "C" int dp_w16_lds_bytes(void);
 extern "C" int dp_w16_frames_per_wave(void);
 extern "C" int dp_w16_supported(const dp_model* m);

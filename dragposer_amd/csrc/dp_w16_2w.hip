@@ -3,9 +3,8 @@
 // default instruction scheduler (dp_w16.hip says why).
 #include "dp_w16_impl.h"
 
-extern "C" hipError_t dp_launch_w16_2w(const KArgs* args, hipStream_t stream)
+extern "C" hipError_t dp_launch_w16_2w(const KArgs* args, hipStream_t stream, LaunchPick* pick)
 {
-    const int grid = (args->n_frames + 8 * FPW - 1) / (8 * FPW);
-    hipLaunchKernelGGL((dp_w16_kernel<8, 2>), dim3(grid), dim3(512), 0, stream, *args);
+    w16_launch<8, 2>(args, stream, pick);
     return hipGetLastError();
 }

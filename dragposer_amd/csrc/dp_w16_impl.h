@@ -642,3 +642,12 @@ __global__ __launch_bounds__(NW * 64, WPS) void dp_w16_kernel(const KArgs a)
     }
 }
 
+
+// one launch of a unit's kernel; what it records for dp_debug_last_launch is its own template arguments
+template <int NW, int WPS, bool EARLY = false, bool LONG = false>
+static void w16_launch(const KArgs* args, hipStream_t stream, LaunchPick* pick)
+{
+    set_pick(pick, DP_UNIT_W16, NW, EARLY, false, LONG);
+    const int grid = (args->n_frames + NW * FPW - 1) / (NW * FPW);
+    hipLaunchKernelGGL((dp_w16_kernel<NW, WPS, EARLY, LONG>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+}

@@ -3,20 +3,19 @@
 // dp_create takes the body-part unit (dp_w4_bp.hip) instead when the decoder's block sparsity fits its placement.
 #include "dp_w4_impl.h"
 
-extern "C" hipError_t dp_launch_w4(const KArgs* args, hipStream_t stream)
+extern "C" hipError_t dp_launch_w4(const KArgs* args, hipStream_t stream, LaunchPick* pick)
 {
     constexpr int NW = 4;
-    const int grid = (args->n_frames + NW * FPW - 1) / (NW * FPW);
     const bool lng = args->n_iter > MAX_ITERS;
     if (args->seq.n_steps > 0) {
-        if (lng) hipLaunchKernelGGL((dp_w4_kernel<NW, true, true, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
-        else hipLaunchKernelGGL((dp_w4_kernel<NW, true, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+        if (lng) w4_launch<NW, true, true, true>(args, stream, pick);
+        else w4_launch<NW, true, true>(args, stream, pick);
     } else if (args->early_stop && args->mode == 0) {
-        if (lng) hipLaunchKernelGGL((dp_w4_kernel<NW, true, false, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
-        else hipLaunchKernelGGL((dp_w4_kernel<NW, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+        if (lng) w4_launch<NW, true, false, true>(args, stream, pick);
+        else w4_launch<NW, true>(args, stream, pick);
     } else {
-        if (lng) hipLaunchKernelGGL((dp_w4_kernel<NW, false, false, true>), dim3(grid), dim3(NW * 64), 0, stream, *args);
-        else hipLaunchKernelGGL((dp_w4_kernel<NW, false>), dim3(grid), dim3(NW * 64), 0, stream, *args);
+        if (lng) w4_launch<NW, false, false, true>(args, stream, pick);
+        else w4_launch<NW, false>(args, stream, pick);
     }
     return hipGetLastError();
 }

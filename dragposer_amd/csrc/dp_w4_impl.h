@@ -1054,6 +1054,7 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
             if (!SEQ) bad_tgt |= (__ballot(lane < LAT && out_of_range(ztD[r])) != 0ull ? 1u : 0u) << r;
         }
         bad_tgt &= ~bad_state;
+        not_rot &= ~(bad_state | bad_tgt); // (a frame that cannot be optimised reports that alone -- per frame, not per tracker lane: dp_w16 the same)
         if (bad_state | bad_tgt) { // (uniform, rare)
             if (((bad_state | bad_tgt) >> i) & 1u) raw_neutral(raw);
             if ((bad_state >> i) & 1u) cv = f4{1.f, 0.f, 0.f, 0.f};
@@ -1224,6 +1225,7 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
 #pragma unroll
                 for (int r = 0; r < FPW; ++r) bad_tgt |= (__ballot(lane < LAT && out_of_range(ztD[r])) != 0ull ? 1u : 0u) << r;
                 bad_tgt &= ~bad_state;
+                not_rot &= ~(bad_state | bad_tgt); // (bad_state: sticky, an earlier step's too)
             }
             const bool my_bad = ((bad_state | bad_tgt) >> i) & 1u;
             if (bad_state | bad_tgt) { // (uniform, rare) neutral stand-ins: the frame's state stays finite, its results are poisoned in the epilogue
@@ -1655,4 +1657,13 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
     STAMP(11);
     prof.store(a.dbg, tid, blockIdx.x);
 #endif
+}
+
+// one launch of the unit's kernel; what it records for dp_debug_last_launch is its own template arguments
+template <int NW, bool EARLY, bool SEQ = false, bool LONG = false>
+static void w4_launch(const KArgs* args, hipStream_t stream, LaunchPick* pick)
+{
+    set_pick(pick, W4_BP ? DP_UNIT_W4_BP : DP_UNIT_W4, NW, EARLY, SEQ, LONG);
+    const int grid = (args->n_frames + NW * FPW - 1) / (NW * FPW);
+    hipLaunchKernelGGL((W4_KERNEL<NW, EARLY, SEQ, LONG>), dim3(grid), dim3(NW * 64), 0, stream, *args);
 }

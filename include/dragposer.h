@@ -210,7 +210,9 @@ typedef struct dp_result {
                                         121-124); the kernels use its quaternion form, which equals it for rotations only -- every reference
                                         caller passes rotations (eval_drag.py:199, run_drag.py:136).  The frame is computed as given (the matrix
                                         read as the rotation Shepperd's conversion makes of it): a report, not a refusal; costs the set-up six
-                                        dot products per tracker, the loop nothing, the caller no synchronisation */
+                                        dot products per tracker, the loop nothing, the caller no synchronisation.  Never set together
+                                        with DP_STATUS_BAD_STATE or DP_STATUS_BAD_TARGETS: a frame that cannot be optimised reports that
+                                        alone, whichever kernel runs it (in a sequence: every step after a bad one too) */
 #define DP_ROTATION_TOL 1.0e-3f
 #define DP_INPUT_LIMIT 1.0e4f        /* metres / weight units / latent units: keeps every intermediate of the loop finite in fp32 */
 

@@ -81,7 +81,9 @@ def test_temporal_kernel_variants_fit_their_occupancy(tmp_path):
     assert sorted(n["vgpr"] <= 128 for n in kernels.values()) == [False, False, True, True, True]  # the 2-waves-per-SIMD variants use the full file
 
 
-@pytest.mark.parametrize("src, one_wave", [("dp_w16.hip", True), ("dp_w16_es.hip", True), ("dp_w16_2w.hip", False), ("dp_w16_2w_es.hip", False)])
+@pytest.mark.parametrize("src, one_wave", [("dp_w16.hip", True), ("dp_w16_es.hip", True), ("dp_w16_2w.hip", False), ("dp_w16_2w_es.hip", False),
+                                           ("dp_w16_long.hip", True), ("dp_w16_es_long.hip", True), ("dp_w16_2w_long.hip", False),
+                                           ("dp_w16_2w_es_long.hip", False)])
 def test_w16_instantiations_keep_their_register_budget(tmp_path, src, one_wave):
     """the 16-frames-per-wave kernel, each instantiation with its own flags: one wave per SIMD has the whole register file and must
     not spill; two waves per SIMD run in 256 registers with a bounded spill (latency the partner wave covers); no packed fp32

@@ -233,3 +233,106 @@ def test_a_sequence_step_with_a_non_rotation_target_says_so():
     assert (np.asarray(c.last_status.cpu()) == want).all() and (a.last_status == 0).all(), c.last_status
     ok = [s_ for s_ in range(S) if s_ != 4]
     assert torch.equal(pc[:, ok], pa[:, ok]) and torch.equal(ic[:, ok], ia[:, ok]) and torch.isfinite(pc).all()
+
+
+# A frame that cannot be optimised reports that alone: DP_STATUS_TARGET_NOT_ROTATION is never set beside BAD_STATE / BAD_TARGETS (include/
+# dragposer.h), whichever kernel runs the frame and whichever frames share its launch.  Each frame below also has a scaled rotation on a
+# tracked joint; frames 49 and 50 share a wave of dp_w4.
+ST_NOT_ROT = 8
+MIXED = {5: ST_NONFINITE | ST_BAD_TARGETS,   # NaN tracker position + scaled rotation
+         22: ST_NONFINITE | ST_BAD_TARGETS,  # NaN z_tgt + scaled rotation
+         49: ST_NONFINITE | ST_BAD_STATE,    # NaN z0 + scaled rotation
+         50: ST_NOT_ROT}                     # the scaled rotation alone
+
+
+@pytest.fixture
+def fresh_opt():
+    from dragposer_amd.optimizer import LatentOptimizer
+
+    o = LatentOptimizer(device="cuda:0")
+    yield o
+    o.close()  # (also when the test fails)
+
+
+def _mixed(d):
+    bad = {k: v.clone() for k, v in d.items()}
+    bad["tgt_pos"][5, 13, 1] = float("nan")
+    bad["z_tgt"][22, 3] = float("nan")
+    bad["z0"][49, 5] = float("nan")
+    for f, j in ((5, 7), (22, 17), (49, 21), (50, 3)):
+        bad["tgt_rot"][f, j] *= 1.05
+    return bad
+
+
+@pytest.mark.parametrize("unit", ["w4_bp", "w4_dense", "w16_4w", "w16_8w"])
+@pytest.mark.parametrize("early", [False, True])
+def test_a_frame_that_cannot_be_optimised_does_not_also_report_a_non_rotation(fresh_opt, unit, early):
+    from instantiations import UNIT_W4, UNIT_W4_BP, UNIT_W16, last_launch, set_layout  # tests/instantiations.py
+
+    opt = fresh_opt
+    if unit == "w4_dense":
+        assert set_layout(opt, 0) == 0
+    B = torch.cuda.get_device_properties(0).multi_processor_count * 64 + 37 if unit == "w16_8w" else 64
+    d = _batch(B)
+    kw = dict(n_iter=20, lambda_tmp=0.02, kernel=unit[:unit.index("_")] if unit.startswith("w16") else "w4", outputs=PER_FRAME)
+    if early:
+        kw.update(stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5)
+    clean = opt.optimize(**d, **kw)
+    out = opt.optimize(**_mixed(d), **kw)
+    torch.cuda.synchronize()
+    ran = last_launch(opt)
+    assert (ran.unit, ran.waves) == {"w4_bp": (UNIT_W4_BP, 4), "w4_dense": (UNIT_W4, 4), "w16_4w": (UNIT_W16, 4), "w16_8w": (UNIT_W16, 8)}[unit], ran
+    st = out["status"].cpu().numpy()
+    assert {f: int(st[f]) for f in MIXED} == MIXED, {f: int(st[f]) for f in MIXED}
+    others = [i for i in range(B) if i not in MIXED]
+    assert (st[others] == 0).all() and (clean["status"] == 0).all()
+    _rows_equal(out, clean, others)
+    assert torch.isfinite(out["z"][50]).all()  # (computed as given)
+
+
+@pytest.mark.parametrize("layout", [1, 0])
+def test_a_sequence_step_after_a_bad_one_does_not_report_a_non_rotation(fresh_opt, layout):
+    """whole-sequence launches: the screening of each step, with a bad state carried over from an earlier step (sticky: the reference's
+    latent is NaN from then on).  Sequence 1 loses a tracker at step 1 and has a scaled rotation at steps 1 and 2; sequence 3 starts from a
+    NaN latent with a scaled rotation at step 0; sequence 2 has a scaled rotation alone at step 1"""
+    from instantiations import last_launch, set_layout  # tests/instantiations.py
+    from dragposer_amd.drag_pose import DragPose
+
+    T, S = 4, 6
+    b = R.synth_inputs(R.OracleModel(), T * S, seed=99)
+    idx = np.array(R.TRACK6)
+    w = np.array([R.W6[j] for j in R.TRACK6], np.float32)
+    tp = torch.tensor(b["tgt_pos"][:, idx]).reshape(T, S, 6, 3).cuda()
+    tR = torch.tensor(b["tgt_rot"][:, idx]).reshape(T, S, 6, 3, 3).cuda()
+    opt = fresh_opt
+    assert set_layout(opt, layout) == layout
+    kw = dict(stop_eps_pos=1e-4, stop_eps_rot=1e-2, max_iter=40, min_loss_incr=1e-5, learning_rate=1e-2, lambda_rot=1, lambda_temporal=0.0,
+              temporal_future_window=0)
+
+    def fresh(z0):
+        dp = DragPose(opt, None, np.zeros(24), np.ones(24), n_sequences=S)
+        dp.set_initial_state(z0, np.zeros((S, 3), np.float32), b["cur_rot"][:S], np.zeros((S, 6), np.float32))
+        return dp
+
+    z0 = b["z0"][:S].copy()
+    a = fresh(z0)
+    pa, ga, ia = a.run_frames(tp, tR, idx, w, **kw)
+    z0[3, 2] = float("nan")
+    c = fresh(z0)
+    tpb, tRb = tp.clone(), tR.clone()
+    tpb[1, 1, 4, 0] = float("nan")
+    tRb[1, 1, 2] *= 1.05; tRb[2, 1, 3] *= 1.05; tRb[0, 3, 1] *= 1.05; tRb[1, 2, 5] *= 1.05
+    pc, gc, ic = c.run_frames(tpb, tRb, idx, w, **kw)
+    torch.cuda.synchronize()
+    assert last_launch(opt).seq == 1
+    want = np.zeros((T, S), np.int64)
+    want[1, 1] = ST_NONFINITE | ST_BAD_TARGETS
+    want[2:, 1] = ST_NONFINITE | ST_BAD_STATE
+    want[:, 3] = ST_NONFINITE | ST_BAD_STATE
+    want[1, 2] = ST_NOT_ROT
+    got = c.last_status.cpu().numpy()
+    assert (got == want).all(), got
+    assert (a.last_status == 0).all()
+    ok = [0, 4, 5]
+    assert torch.equal(pc[:, ok], pa[:, ok]) and torch.equal(gc[:, ok], ga[:, ok]) and torch.equal(ic[:, ok], ia[:, ok])
+    assert torch.equal(pc[:1, 1:3], pa[:1, 1:3]) and torch.isfinite(pc[:, 2]).all()

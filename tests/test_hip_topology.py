@@ -19,6 +19,9 @@ TREES = {
     # a trunk 1-2-3 whose end carries FOUR two-bone limbs (three extra child bones on ONE joint), a 7-bone tail 12..18, a short third root child
     "four_limbs_on_one_joint": [0, 0, 1, 2, 3, 4, 3, 6, 3, 8, 3, 10, 0, 12, 13, 14, 15, 16, 17, 0, 19, 20],
 }
+# the row layout of dp_w4's layer 2 each tree loads with (1: body-part, dp_w4_bp.hip; 0: dense, dp_w4.hip): the body-part placement is the Xsens
+# tree's, and fits another tree only where every weight it leaves out is zero -- for the second tree K-group 2 of item 23 is not
+W4_LAYOUT = {"arms_at_two_levels": 1, "four_limbs_on_one_joint": 0}
 
 
 def _model_arrays(parents, seed):
@@ -38,6 +41,7 @@ def _model_arrays(parents, seed):
 def test_another_tree_through_dp_w4_against_the_c_oracle(name, tmp_path):
     from dragposer_amd import _lib
     from dragposer_amd.optimizer import LatentOptimizer, to_device_batch
+    from instantiations import UNIT_W4, UNIT_W4_BP, last_launch, set_layout  # tests/instantiations.py
     from oracle.analytic import AnalyticOracle
 
     parents = TREES[name]
@@ -47,6 +51,7 @@ def test_another_tree_through_dp_w4_against_the_c_oracle(name, tmp_path):
     ora = AnalyticOracle(model_path=path, precision="f32")
     ora64 = AnalyticOracle(model_path=path, precision="f64")
     opt = LatentOptimizer(device="cuda:0", arrays=raw)
+    assert set_layout(opt, -1) == W4_LAYOUT[name]
     B = 64
     g = torch.Generator().manual_seed(5)
     Zs, Z0 = (torch.randn(B, 24, generator=g) * 0.3).numpy(), (torch.randn(B, 24, generator=g) * 0.3).numpy()
@@ -77,6 +82,16 @@ def test_another_tree_through_dp_w4_against_the_c_oracle(name, tmp_path):
             assert (np.abs(out["z"].cpu().numpy() - want["z_final"]) > 1e-3).mean() <= 0.002
             np.testing.assert_allclose(out["loss"].cpu().numpy(), want["loss"], rtol=2e-5, atol=1e-7)
         assert np.sort(err)[-2] <= 0.05 and err.max() <= 5.0, err  # (one frame may sit on a LeakyReLU kink: BASELINE.md section 3)
+        assert last_launch(opt).unit == (UNIT_W4_BP if W4_LAYOUT[name] else UNIT_W4)
+        if W4_LAYOUT[name]:  # the same tree through the dense unit: the same bits
+            assert set_layout(opt, 0) == 0
+            dense = opt.optimize(**d, n_iter=n_iter, lambda_tmp=0.02, kernel="w4", outputs=("z", "pos", "loss", "status"))
+            torch.cuda.synchronize()
+            assert last_launch(opt).unit == UNIT_W4 and set_layout(opt, 1) == 1
+            for k in out:
+                assert torch.equal(out[k], dense[k]), (name, n_iter, k)
+        else:
+            assert set_layout(opt, 1) == _lib.DP_ERR_UNSUPPORTED and set_layout(opt, -1) == 0
     # the 16-frames-per-wave kernel is laid out for the reference's tree only
     with pytest.raises(_lib.DragPoserError) as e:
         opt.optimize(**d, n_iter=2, kernel="w16")
