@@ -133,6 +133,16 @@ PUBLIC_SYMBOLS = (
     "dp_temporal_create", "dp_temporal_destroy", "dp_temporal_last_error", "dp_temporal_predict", "dp_temporal_status",
 )
 
+# every symbol include/dragposer_grad.h declares (tests/test_grad_abi.py)
+GRAD_SYMBOLS = ("dp_forward_vjp",)
+
+
+class DpGradIn(_Sized):
+    """include/dragposer_grad.h: dp_grad_in (upstream gradients, device pointers; NULL = zero)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("pose", C.c_void_p), ("disp", C.c_void_p), ("world_disp", C.c_void_p),
+                ("world_rot", C.c_void_p), ("pos", C.c_void_p), ("rot", C.c_void_p)]
+
+
 _libs = {}
 
 
@@ -164,6 +174,8 @@ def load(path=None):
     lib.dp_destroy.argtypes = [C.c_void_p]
     lib.dp_optimize.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpResult), C.c_void_p]
     lib.dp_forward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpResult), C.c_void_p]
+    lib.dp_forward_vjp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpGradIn), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]
@@ -192,6 +204,7 @@ def load(path=None):
     lib.dp_debug_pack_w16.argtypes = [C.POINTER(DpFolded), C.POINTER(DpModel), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dp_debug_last_launch.argtypes = [C.c_void_p, _i]
     lib.dp_debug_set_w4_layout.argtypes = [C.c_void_p, C.c_int]
+    lib.dp_debug_host_ctx.argtypes = [C.POINTER(C.c_void_p)]
     _libs[path] = lib
     return lib
 

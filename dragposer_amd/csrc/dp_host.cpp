@@ -8,12 +8,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/dragposer.h"
+#include "../../include/dragposer_grad.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
+#include "dp_vjp.h"
 #include "dp_w4.h"
 
 using namespace dpl;
@@ -32,6 +35,7 @@ struct dp_ctx {
     unsigned* d_w16img = nullptr; // 16-frames-per-wave kernel (dp_w16.hip); NULL when the skeleton is not the one its slot map is for
     float* d_w16bias = nullptr;
     dpw16::SlotConst* d_w16slots = nullptr;
+    float* d_vjpimg = nullptr; // dp_forward_vjp's image (dp_vjp.h): folded decoder, de-normalisation, bones, skeleton walk
     int weight_dtype = DP_WEIGHTS_FP32;
     ItemConst* d_items = nullptr;
     dp_folded folded;
@@ -446,6 +450,39 @@ extern "C" int dp_debug_items(const dp_model* m, void* out_items /* 32 x 128 B *
     return DP_OK;
 }
 
+// dp_forward_vjp's image (dp_vjp.h), from the context's folded decoder
+static void pack_vjp(const dp_folded& fd, const dp_model* m, std::vector<float>& img)
+{
+    using dpvjp::NY; using dpvjp::OFF_A0; using dpvjp::OFF_C0; using dpvjp::OFF_A1; using dpvjp::OFF_B1; using dpvjp::OFF_A2;
+    using dpvjp::OFF_B2; using dpvjp::OFF_SD; using dpvjp::OFF_MU; using dpvjp::OFF_BONE; using dpvjp::OFF_PARENT;
+    img.assign(dpvjp::IMG_WORDS, 0.f);
+    std::memcpy(&img[OFF_A0], fd.A0, sizeof(fd.A0));
+    std::memcpy(&img[OFF_C0], fd.c0, sizeof(fd.c0));
+    std::memcpy(&img[OFF_A1], fd.A1, sizeof(fd.A1));
+    std::memcpy(&img[OFF_B1], fd.b1, sizeof(fd.b1));
+    std::memcpy(&img[OFF_A2], fd.A2, sizeof(fd.A2));
+    std::memcpy(&img[OFF_B2], fd.b2, sizeof(fd.b2));
+    for (int o = 0; o < NY; ++o) {
+        img[OFF_SD + o] = o < 4 * NJ ? m->std_q[o] : o < 4 * NJ + 3 ? m->std_disp[o - 4 * NJ] : 1.f;
+        img[OFF_MU + o] = o < 4 * NJ ? m->mean_q[o] : o < 4 * NJ + 3 ? m->mean_disp[o - 4 * NJ] : 0.f;
+    }
+    for (int k = 0; k < 3 * NJ; ++k) img[OFF_BONE + k] = m->offsets[k];
+    int walk[NJ + 1 + 2 * NJ]; // parent | cstart | clist (children in increasing order)
+    int* parent = walk;
+    int* cstart = walk + NJ;
+    int* clist = walk + 2 * NJ + 1;
+    int n = 0;
+    for (int p = 0; p < NJ; ++p) {
+        parent[p] = m->parents[p];
+        cstart[p] = n;
+        for (int c = 1; c < NJ; ++c)
+            if (m->parents[c] == p) clist[n++] = c;
+    }
+    cstart[NJ] = n;
+    for (int k = n; k < NJ; ++k) clist[k] = 0;
+    std::memcpy(&img[OFF_PARENT], walk, sizeof(walk));
+}
+
 // ------------------------------------------------------------------------------------------------
 #define HIP_TRY(ctx, expr)                                                                       \
     do {                                                                                         \
@@ -499,6 +536,8 @@ extern "C" int dp_create(dp_ctx** out, const dp_model* model, int device)
     if (w16) rc = dp_debug_pack_w16(&ctx->folded, model, w16img.data(), w16bias.data(), w16slots.data());
     ctx->weight_dtype = model->weight_dtype;
     if (rc != DP_OK) { delete ctx; return rc; }
+    std::vector<float> vjpimg;
+    pack_vjp(ctx->folded, model, vjpimg); // (the skeleton passed plan_items' checks above: parents[j] < j)
     int prev = 0;
     hipGetDevice(&prev);
     hipError_t e = hipSetDevice(device);
@@ -509,6 +548,8 @@ extern "C" int dp_create(dp_ctx** out, const dp_model* model, int device)
     if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w4bias, w4bias.size() * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w4pairs, pairs.size() * sizeof(dpw4::Pair));
     if (e == hipSuccess) e = hipMemcpy(ctx->d_w4pairs, pairs.data(), pairs.size() * sizeof(dpw4::Pair), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_vjpimg, vjpimg.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_vjpimg, vjpimg.data(), vjpimg.size() * sizeof(float), hipMemcpyHostToDevice);
     if (w16) {
         if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w16img, w16img.size() * sizeof(unsigned));
         if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w16bias, w16bias.size() * sizeof(float));
@@ -526,7 +567,7 @@ extern "C" int dp_create(dp_ctx** out, const dp_model* model, int device)
     if (e != hipSuccess) {
         std::string msg = std::string("dp_create: ") + hipGetErrorString(e);
         hipFree(ctx->d_wfrag); hipFree(ctx->d_bias); hipFree(ctx->d_items); hipFree(ctx->d_w4img); hipFree(ctx->d_w4bias); hipFree(ctx->d_w4pairs);
-        hipFree(ctx->d_w16img); hipFree(ctx->d_w16bias); hipFree(ctx->d_w16slots);
+        hipFree(ctx->d_w16img); hipFree(ctx->d_w16bias); hipFree(ctx->d_w16slots); hipFree(ctx->d_vjpimg);
         delete ctx;
         return fail(nullptr, DP_ERR_DEVICE, msg);
     }
@@ -547,6 +588,7 @@ extern "C" int dp_destroy(dp_ctx* ctx)
     hipFree(ctx->d_w16img);
     hipFree(ctx->d_w16bias);
     hipFree(ctx->d_w16slots);
+    hipFree(ctx->d_vjpimg);
     delete ctx;
     return DP_OK;
 }
@@ -831,6 +873,53 @@ extern "C" int dp_forward(dp_ctx* ctx, int n_frames, const float* z, const float
     k.z = nullptr; k.z_pre = nullptr; k.loss = nullptr; k.iters = nullptr; k.clk = nullptr;
     k.n_frames = n_frames; k.n_iter = 1; k.mode = 1;
     return launch(ctx, k, stream);
+}
+
+// host-only, exported for the CPU tests: a context with no device and no device memory -- argument checks run on it, every launch is
+// refused (DP_ERR_DEVICE); dp_destroy frees it
+extern "C" int dp_debug_host_ctx(dp_ctx** out)
+{
+    if (!out) return DP_ERR_INVALID;
+    *out = new (std::nothrow) dp_ctx();
+    return *out ? DP_OK : DP_ERR_DEVICE;
+}
+
+// include/dragposer_grad.h.  dp_grad_in as the caller compiled it: first version = the six pointers, a later caller's struct is read
+// up to what this build knows
+constexpr unsigned GRAD_IN_SIZE_V510 = offsetof(dp_grad_in, rot) + sizeof(void*);
+extern "C" int dp_forward_vjp(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_grad_in* g, float* dz, float* dcur_rot,
+                              int* status, void* stream)
+{
+    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_forward_vjp: ctx is NULL");
+    try {
+        if (n_frames <= 0) return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: n_frames must be positive");
+        if (!z || !cur_rot || !g || !dz) return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: NULL z, cur_rot, g or dz");
+        if (g->struct_size < GRAD_IN_SIZE_V510 || g->struct_size > 4096u || g->reserved0 != 0u)
+            return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: dp_grad_in.struct_size is " + std::to_string(g->struct_size) + " (reserved0 " +
+                                                 std::to_string(g->reserved0) + "), this library expects at least " + std::to_string(GRAD_IN_SIZE_V510) +
+                                                 " and reserved0 = 0  (dp_grad_in g = DP_GRAD_IN_INIT;)");
+        dp_grad_in gv;
+        std::memset(&gv, 0, sizeof(gv));
+        std::memcpy(&gv, g, std::min<size_t>(g->struct_size, sizeof(gv)));
+#ifdef DP_REF8_BUILD
+        (void)dcur_rot; (void)status; (void)stream;
+        return fail(ctx, DP_ERR_UNSUPPORTED, "dp_forward_vjp: not part of the test-only library");
+#else
+        if (!ctx->d_vjpimg) return fail(ctx, DP_ERR_DEVICE, "dp_forward_vjp: the context has no device image");
+        DEVICE_GUARD(ctx);
+        dpvjp::Args a;
+        a.img = ctx->d_vjpimg;
+        a.z = z; a.cur_rot = cur_rot;
+        a.g_pose = gv.pose; a.g_disp = gv.disp; a.g_wdisp = gv.world_disp; a.g_wrot = gv.world_rot; a.g_pos = gv.pos; a.g_rot = gv.rot;
+        a.dz = dz; a.dcur = dcur_rot; a.status = status;
+        a.n_frames = n_frames;
+        const hipError_t e = dp_launch_vjp(&a, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("dp_forward_vjp: kernel launch: ") + hipGetErrorString(e));
+        return DP_OK;
+#endif
+    } catch (...) {
+        return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: host-side failure");
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -29,6 +29,7 @@ _OUT_SPECS = {  # name -> (trailing shape, dtype)
     "iters": ((), torch.int32),
     "status": ((), torch.int32),  # DP_STATUS_* bits (include/dragposer.h)
 }
+_GRAD_NAMES = ("pose", "disp", "world_disp", "world_rot", "pos", "rot")  # the outputs forward_vjp takes gradients of
 _LAUNCH_SPECS = {  # results that are per launch, not per frame; only on request
     "clock": ((2,), torch.int64),  # shader cycles / 100 MHz ticks of workgroup 0's iteration loop: sclk_ghz()
 }
@@ -204,6 +205,32 @@ class LatentOptimizer:
             self._fail(rc)
         return tensors
 
+    def forward_vjp(self, z, cur_rot, grads, out=None):
+        """dL/dz [B,24] and dL/dcur_rot [B,4] of decode + FK at (z, cur_rot) for upstream gradients `grads` = {output name: dL/d(that
+        output)} over any subset of pose, disp, world_disp, world_rot, pos, rot (shapes as `forward` returns them; missing = zero):
+        include/dragposer_grad.h, dp_forward_vjp.  Returns dict(dz, dcur_rot, status) -- status: DP_STATUS_* bits per frame.
+        `out`: a dict of preallocated result tensors (any of the three).  Asynchronous on torch's current stream."""
+        B = int(z.shape[0])
+        dev = self.device
+        zp = _check(z, "z", (B, LATENT), torch.float32, dev)
+        cp = _check(cur_rot, "cur_rot", (B, 4), torch.float32, dev)
+        g = _lib.DpGradIn()
+        for name, t in grads.items():
+            if name not in _GRAD_NAMES:
+                raise ValueError(f"grads: unknown output {name!r} (one of {', '.join(_GRAD_NAMES)})")
+            if t is not None:
+                setattr(g, name, _check(t, "grads[" + name + "]", (B,) + _OUT_SPECS[name][0], torch.float32, dev))
+        res = {}
+        for name, shape, dtype in (("dz", (B, LATENT), torch.float32), ("dcur_rot", (B, 4), torch.float32), ("status", (B,), torch.int32)):
+            t = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
+            _check(t, name, shape, dtype, dev)
+            res[name] = t
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self.lib.dp_forward_vjp(self.ctx, B, C.c_void_p(zp), C.c_void_p(cp), C.byref(g), C.c_void_p(res["dz"].data_ptr()),
+                                     C.c_void_p(res["dcur_rot"].data_ptr()), C.c_void_p(res["status"].data_ptr()), stream)
+        if rc != _lib.DP_OK:
+            self._fail(rc)
+        return res
 
     def sequence_advance(self, frame, global_pos, global_rot, latent_buf, disp_buf, heights_buf, height_joints, pose_ret=None,
                          pos_ret=None, adjust=None, tgt_pos=None):
