@@ -143,6 +143,27 @@ class DpGradIn(_Sized):
                 ("world_rot", C.c_void_p), ("pos", C.c_void_p), ("rot", C.c_void_p)]
 
 
+# every symbol include/dragposer_constraints.h declares (tests/test_constraints_abi.py)
+CONSTRAINT_SYMBOLS = ("dp_optimize_constrained",)
+
+
+class DpConstraints(_Sized):
+    """include/dragposer_constraints.h: dp_constraints, with DP_CONSTRAINTS_INIT's defaults (every weight 0)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint),
+                ("w_feet_floor", C.c_float), ("w_head_hips_forward", C.c_float), ("w_head_hips_colinear", C.c_float), ("w_hips_feet_colinear", C.c_float),
+                ("floor_joints", C.c_int * 2), ("foot_joints", C.c_int * 2), ("head_joint", C.c_int), ("hips_joint", C.c_int), ("up_axis", C.c_int),
+                ("floor_one_sided", C.c_int), ("floor_level", C.c_float), ("fwd_axis", C.c_float * 3), ("fwd_threshold", C.c_float),
+                ("fwd_margin", C.c_float), ("feet_radius", C.c_float), ("global_pos", C.c_void_p), ("loss_extra", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.floor_joints[:] = (4, 8)
+        self.foot_joints[:] = (3, 7)
+        self.head_joint, self.hips_joint, self.up_axis = 13, 0, 1
+        self.fwd_axis[:] = (0.0, 0.0, 1.0)
+        self.fwd_threshold, self.fwd_margin, self.feet_radius = 0.5, 0.2, 0.2
+
+
 _libs = {}
 
 
@@ -176,6 +197,8 @@ def load(path=None):
     lib.dp_forward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpResult), C.c_void_p]
     lib.dp_forward_vjp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpGradIn), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
+    lib.dp_optimize_constrained.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpConstraints), C.POINTER(DpResult),
+                                            C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

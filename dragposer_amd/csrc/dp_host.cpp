@@ -14,6 +14,8 @@
 
 #include "../../include/dragposer.h"
 #include "../../include/dragposer_grad.h"
+#include "../../include/dragposer_constraints.h"
+#include "dp_cons.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
 #include "dp_vjp.h"
@@ -919,6 +921,77 @@ extern "C" int dp_forward_vjp(dp_ctx* ctx, int n_frames, const float* z, const f
 #endif
     } catch (...) {
         return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: host-side failure");
+    }
+}
+
+// include/dragposer_constraints.h.  dp_constraints as the caller compiled it (first version: up to loss_extra), checked like dp_grad_in
+constexpr unsigned CONS_SIZE_V510 = offsetof(dp_constraints, loss_extra) + sizeof(void*);
+extern "C" int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_constraints* c_in, const dp_result* out_in,
+                                       void* stream)
+{
+    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_optimize_constrained: ctx is NULL");
+    try {
+        const char* who = "dp_optimize_constrained";
+        if (!in || !p_in || !c_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: NULL batch, params, constraints or result");
+        dp_params pv; dp_result ov;
+        if (int rc = take_params(ctx, p_in, pv, who)) return rc;
+        if (int rc = take_result(ctx, out_in, ov, who)) return rc;
+        if (c_in->struct_size < CONS_SIZE_V510 || c_in->struct_size > 4096u || c_in->reserved0 != 0u)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: dp_constraints.struct_size is " + std::to_string(c_in->struct_size) + " (reserved0 " +
+                                                 std::to_string(c_in->reserved0) + "), this library expects at least " + std::to_string(CONS_SIZE_V510) +
+                                                 " and reserved0 = 0  (dp_constraints c = DP_CONSTRAINTS_INIT;)");
+        dp_constraints c;
+        std::memset(&c, 0, sizeof(c));
+        std::memcpy(&c, c_in, std::min<size_t>(c_in->struct_size, sizeof(c)));
+        const float wts[4] = {c.w_feet_floor, c.w_head_hips_forward, c.w_head_hips_colinear, c.w_hips_feet_colinear};
+        for (float x : wts)
+            if (!(x >= 0.f && x <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: a weight is negative or not finite");
+        const int joints[6] = {c.floor_joints[0], c.floor_joints[1], c.foot_joints[0], c.foot_joints[1], c.head_joint, c.hips_joint};
+        for (int jj : joints)
+            if (jj < 0 || jj >= NJ) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: joint index " + std::to_string(jj) + " outside 0..21");
+        if (c.up_axis < 0 || c.up_axis > 2) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: up_axis outside 0..2");
+        const float rest[7] = {c.floor_level, c.fwd_axis[0], c.fwd_axis[1], c.fwd_axis[2], c.fwd_threshold, c.fwd_margin, c.feet_radius};
+        for (float x : rest)
+            if (!(std::fabs(x) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: a constraint parameter is not finite");
+        if (c.w_feet_floor != 0.f && !c.global_pos) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: global_pos is NULL while feet_floor is on");
+        if (in->n_frames <= 0) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: n_frames must be positive");
+        if (!in->z0 || !in->z_tgt || !in->cur_rot || !in->tgt_pos || !in->tgt_rot || !in->w || !in->tracked)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: NULL input array");
+        if (!(pv.lr > 0.f) || !(pv.beta1 >= 0.f && pv.beta1 < 1.f) || !(pv.beta2 >= 0.f && pv.beta2 < 1.f))
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: bad Adam hyper-parameters");
+        if (!(pv.eps > 0.f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: Adam eps must be > 0");
+#ifdef DP_REF8_BUILD
+        (void)stream;
+        return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize_constrained: not part of the test-only library");
+#else
+        if (!ctx->d_vjpimg) return fail(ctx, DP_ERR_DEVICE, "dp_optimize_constrained: the context has no device image");
+        DEVICE_GUARD(ctx);
+        dpcons::Args a;
+        std::memset(&a, 0, sizeof(a));
+        a.img = ctx->d_vjpimg;
+        a.z0 = in->z0; a.z_tgt = in->z_tgt; a.cur_rot = in->cur_rot; a.tgt_pos = in->tgt_pos; a.tgt_rot = in->tgt_rot; a.w = in->w; a.tracked = in->tracked;
+        a.global_pos = c.global_pos;
+        a.z = ov.z; a.z_pre = ov.z_pre; a.pose = ov.pose; a.disp = ov.disp; a.world_disp = ov.world_disp; a.world_rot = ov.world_rot;
+        a.pos = ov.pos; a.rot = ov.rot; a.loss = ov.loss; a.loss_extra = c.loss_extra; a.iters = ov.iters; a.status = ov.status;
+        a.n_frames = in->n_frames; a.n_iter = pv.n_iter; a.early_stop = pv.early_stop ? 1 : 0;
+        a.stop_eps_pos = pv.stop_eps_pos; a.stop_eps_rot = pv.stop_eps_rot; a.min_loss_incr = pv.min_loss_incr;
+        a.lam_rot = pv.lambda_rot; a.lam_tmp = pv.lambda_tmp; a.ctmp = 2.f * pv.lambda_tmp / 24.f;
+        // torch passes (1-beta) as Python doubles into fp32 tensor ops; its bias corrections are Python doubles (dp_optimize: fill_adam)
+        a.one_m_b1 = (float)(1.0 - (double)pv.beta1); a.beta2 = pv.beta2; a.one_m_b2 = (float)(1.0 - (double)pv.beta2); a.eps = pv.eps;
+        a.beta1d = pv.beta1; a.beta2d = pv.beta2; a.lrd = pv.lr;
+        a.w_floor = c.w_feet_floor; a.w_fwd = c.w_head_hips_forward; a.w_hcol = c.w_head_hips_colinear; a.w_feet = c.w_hips_feet_colinear;
+        a.floor_j[0] = c.floor_joints[0]; a.floor_j[1] = c.floor_joints[1]; a.foot_j[0] = c.foot_joints[0]; a.foot_j[1] = c.foot_joints[1];
+        a.head = c.head_joint; a.hips = c.hips_joint; a.up = c.up_axis; a.one_sided = c.floor_one_sided ? 1 : 0;
+        a.floor_level = c.floor_level;
+        a.fwd[0] = c.fwd_axis[0]; a.fwd[1] = c.fwd_axis[1]; a.fwd[2] = c.fwd_axis[2];
+        a.fwd_thr = c.fwd_threshold; a.fwd_margin = c.fwd_margin;
+        a.feet_r2 = c.feet_radius * c.feet_radius; // (the reference: a Python float subtracted from a float32 tensor)
+        const hipError_t e = dp_launch_cons(&a, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("dp_optimize_constrained: kernel launch: ") + hipGetErrorString(e));
+        return DP_OK;
+#endif
+    } catch (...) {
+        return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: host-side failure");
     }
 }
 

@@ -205,6 +205,47 @@ class LatentOptimizer:
             self._fail(rc)
         return tensors
 
+    def optimize_constrained(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, constraints, global_pos=None, n_iter=50, lr=1e-2,
+                             betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.02, stop_eps_pos=0.0, stop_eps_rot=0.0,
+                             min_loss_incr=None, max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto"):
+        """`optimize` with the reference's extra loss terms (`constraints`: a dragposer_amd.Constraints) added to the loss and to the
+        while-condition's total: include/dragposer_constraints.h, dp_optimize_constrained (one launch).  `global_pos` [B,3] (device,
+        fp32): the root position before the frame (the reference's current_global_pos), required when the feet_floor term is on.
+        Returns `optimize`'s dict plus `loss_extra` [B,4] (the four weighted terms of the last forward pass).  `kernel` is ignored
+        (one kernel implements this operator); `validate_targets` as in `optimize`."""
+        B = int(z0.shape[0])
+        dev = self.device
+        if validate_targets:
+            check_rotation_targets(tgt_rot, tracked)
+        batch = _lib.DpBatch()
+        batch.n_frames = B
+        batch.z0 = _check(z0, "z0", (B, LATENT), torch.float32, dev)
+        batch.z_tgt = _check(z_tgt, "z_tgt", (B, LATENT), torch.float32, dev)
+        batch.cur_rot = _check(cur_rot, "cur_rot", (B, 4), torch.float32, dev)
+        batch.tgt_pos = _check(tgt_pos, "tgt_pos", (B, NJ, 3), torch.float32, dev)
+        batch.tgt_rot = _check(tgt_rot, "tgt_rot", (B, NJ, 9), torch.float32, dev)
+        batch.w = _check(w, "w", (B, NJ, 2), torch.float32, dev)
+        batch.tracked = _check(tracked, "tracked", (B, NJ), torch.uint8, dev)
+        early = min_loss_incr is not None or stop_eps_pos > 0 or stop_eps_rot > 0
+        p = _lib.DpParams(n_iter=int(n_iter), lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, lambda_rot=lambda_rot,
+                          lambda_tmp=lambda_tmp, early_stop=int(early), stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
+                          min_loss_incr=float("-inf") if min_loss_incr is None else min_loss_incr, max_trackers=int(max_trackers))
+        names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS)
+        res, tensors = self._outputs(B, [n for n in names if n != "loss_extra"], out)
+        le = out["loss_extra"] if out is not None and "loss_extra" in out else torch.empty(B, 4, dtype=torch.float32, device=dev)
+        tensors["loss_extra"] = le
+        gp = None
+        if global_pos is not None:
+            gp = _check(global_pos, "global_pos", (B, 3), torch.float32, dev)
+        elif constraints.needs_global_pos:
+            raise ValueError("optimize_constrained: the feet_floor term needs global_pos [B,3]")
+        c = constraints.to_struct(gp, _check(le, "loss_extra", (B, 4), torch.float32, dev))
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self.lib.dp_optimize_constrained(self.ctx, C.byref(batch), C.byref(p), C.byref(c), C.byref(res), stream)
+        if rc != _lib.DP_OK:
+            self._fail(rc)
+        return tensors
+
     def forward_vjp(self, z, cur_rot, grads, out=None):
         """dL/dz [B,24] and dL/dcur_rot [B,4] of decode + FK at (z, cur_rot) for upstream gradients `grads` = {output name: dL/d(that
         output)} over any subset of pose, disp, world_disp, world_rot, pos, rot (shapes as `forward` returns them; missing = zero):
