@@ -164,6 +164,39 @@ class DpConstraints(_Sized):
         self.fwd_threshold, self.fwd_margin, self.feet_radius = 0.5, 0.2, 0.2
 
 
+# every symbol include/dragposer_terms.h declares (tests/test_terms_abi.py)
+TERM_SYMBOLS = ("dp_optimize_terms",)
+DP_MAX_TERMS = 16
+DP_TERM_PLANE, DP_TERM_DISTANCE, DP_TERM_ALIGN = 1, 2, 3
+DP_TERM_ONE_SIDED, DP_TERM_DROP_UP = 1, 2
+
+
+class DpTerm(C.Structure):
+    """include/dragposer_terms.h: dp_term, with DP_TERM_INIT's defaults"""
+    _fields_ = [("type", C.c_int), ("joint_a", C.c_int), ("joint_b", C.c_int), ("flags", C.c_int), ("weight", C.c_float),
+                ("point", C.c_float * 3), ("dir", C.c_float * 3), ("axis_a", C.c_float * 3), ("axis_b", C.c_float * 3),
+                ("p0", C.c_float), ("p1", C.c_float), ("per_frame", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        if "joint_b" not in k:
+            self.joint_b = -1
+        self.dir[:] = (0.0, 1.0, 0.0)
+        self.axis_a[:] = (0.0, 0.0, 1.0)
+        self.axis_b[:] = (0.0, 0.0, 1.0)
+
+
+class DpTerms(_Sized):
+    """include/dragposer_terms.h: dp_terms, with DP_TERMS_INIT's defaults"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("n_terms", C.c_int), ("up_axis", C.c_int), ("terms", C.c_void_p),
+                ("global_pos", C.c_void_p), ("loss_terms", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        if "up_axis" not in k:
+            self.up_axis = 1
+
+
 _libs = {}
 
 
@@ -199,6 +232,7 @@ def load(path=None):
                                    C.c_void_p]
     lib.dp_optimize_constrained.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpConstraints), C.POINTER(DpResult),
                                             C.c_void_p]
+    lib.dp_optimize_terms.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpTerms), C.POINTER(DpResult), C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

@@ -37,6 +37,21 @@ constexpr int LDS_BYTES = 4 * LDS_FLOATS;           // 70 832 bytes: LDS alone w
                                                     // (2 waves per SIMD) allow one
 static_assert(LDS_BYTES == 70832, "the LDS budget stated in DESIGN.md section 13");
 
+// the table instantiation (dp_optimize_terms, include/dragposer_terms.h): the staged term table after the skeleton tables, and a block
+// of per-frame rows appended to each wave's block
+constexpr int MAX_TERMS = 16;                        // DP_MAX_TERMS
+constexpr int TW = 22;                               // words per staged term (T_* below)
+constexpr int T_TYPE = 0, T_JA = 1, T_JB = 2, T_FLAGS = 3, T_W = 4, T_PT = 5, T_DIR = 8, T_AXA = 11, T_AXB = 14, T_P0 = 17, T_P1 = 18,
+              T_ROW = 20;                            // (ints: type .. flags; T_ROW: the per-frame row pointer, 8-byte aligned)
+constexpr int L_TBL = L_WAVE0;                       // [MAX_TERMS][TW]
+constexpr int L_WAVE0_T = L_TBL + MAX_TERMS * TW;
+constexpr int W_ROW = W_FLOATS;                      // [MAX_TERMS][4] the frame's rows (vector, s_f), defaults filled in
+constexpr int W_FLOATS_T = W_ROW + 4 * MAX_TERMS;
+constexpr int LDS_FLOATS_T = L_WAVE0_T + WPB * W_FLOATS_T;
+constexpr int LDS_BYTES_T = 4 * LDS_FLOATS_T;       // 74 288 bytes: still one workgroup per CU
+static_assert(LDS_BYTES_T == 74288 && LDS_BYTES_T <= 76 * 1024, "the LDS budget stated in DESIGN.md section 13");
+static_assert(L_TBL % 2 == 0 && TW % 2 == 0 && T_ROW % 2 == 0, "per-frame row pointers are read from LDS as 8-byte words");
+
 struct Args {
     const float* img; // dp_vjp.h image (IMG_WORDS)
     const float *z0, *z_tgt, *cur_rot, *tgt_pos, *tgt_rot, *w;
@@ -55,6 +70,14 @@ struct Args {
     float floor_level, fwd[3], fwd_thr, fwd_margin, feet_r2;
 };
 
+// the table instantiation's arguments: Args (its four-term fields unused) and the term table, staged into LDS once per workgroup
+struct TermArgs : Args {
+    int n_terms, need_gp;            // need_gp: an active PLANE or point-DISTANCE term exists (global_pos is read)
+    float* loss_terms;               // [B][n_terms], nullable
+    unsigned tbl[MAX_TERMS * TW];    // T_* layout; DISTANCE's p0 / p1 hold lo^2 / hi^2
+};
+
 } // namespace dpcons
 
 hipError_t dp_launch_cons(const dpcons::Args* args, hipStream_t stream);
+hipError_t dp_launch_terms(const dpcons::TermArgs* args, hipStream_t stream);

@@ -14,12 +14,17 @@
 //             reduction gives the loss sums and the root's gradient together
 //   backward  F_j = subtree sums of dL/dP (subtree masks built at staging), dL/dR_j = R_0^T (dL/dG_j + sum_c F_c off_c^T) per joint
 //             lane, then A2^T, A1^T, A0^T with a lane per column; Adam per latent lane
+// Two instantiations share every phase above but the terms: dp_cons_kernel runs the four reference terms with their parameters in
+// the argument block (dp_optimize_constrained); dp_terms_kernel runs a table of up to 16 PLANE / DISTANCE / ALIGN terms
+// (dp_optimize_terms, include/dragposer_terms.h), staged into LDS with the skeleton tables, its per-frame rows read once per launch into
+// the wave's block, evaluated by a loop over the terms with a wave-uniform switch on the type.
 // Rotations: the reference takes quat.from_matrix(G) (x) f for the forward axes; G is a rotation matrix (cur_rot a unit quaternion, as
 // every reference caller passes it), so that is G f, which is what is computed.  The rotation loss is the element-wise |G - T|_F^2 of
 // the reference on the matrices themselves: DP_STATUS_TARGET_NOT_ROTATION is never set by this kernel.
 #include <hip/hip_runtime.h>
 
 #include "../../include/dragposer.h"
+#include "../../include/dragposer_terms.h"
 #include "dp_cons.h"
 #include "dp_vjp.h"
 
@@ -101,487 +106,35 @@ DEV void mv(const float* M, const float* v, float* o)
     for (int r = 0; r < 3; ++r) o[r] = M[3 * r] * v[0] + M[3 * r + 1] * v[1] + M[3 * r + 2] * v[2];
 }
 
+// global_pos is read: the floor term is on (four terms) / an active PLANE or point-DISTANCE term exists (table)
+DEV bool reads_gp(const Args& a) { return a.w_floor != 0.f; }
+DEV bool reads_gp(const TermArgs& a) { return a.need_gp != 0; }
+
+DEV int uni_i(int x) { return __builtin_amdgcn_readfirstlane(x); } // (an int the wave holds in every lane)
+
 } // namespace
 
+
 __global__ __launch_bounds__(WPB * 64) void dp_cons_kernel(Args a)
-{
-    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
-    const float* __restrict__ W = a.img;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int* par = (int*)(lds + L_PAR);
-    unsigned* sub = (unsigned*)(lds + L_SUB);
-    const int* cst = (const int*)(lds + L_CST);
-    const int* cls = (const int*)(lds + L_CLS);
-    const int* Ti = (const int*)W;
+#define DP_CONS_TABLE 0
+#include "dp_cons_body.h"
+#undef DP_CONS_TABLE
 
-    // ---- staging (once per workgroup): padded weight rows, skeleton tables, subtree masks
-    for (int i = tid; i < H0 * LAT; i += WPB * 64) lds[L_A0 + (i / LAT) * S0 + i % LAT] = W[dpvjp::OFF_A0 + i];
-    for (int i = tid; i < H1 * H0; i += WPB * 64) lds[L_A1 + (i / H0) * S1 + i % H0] = W[dpvjp::OFF_A1 + i];
-    for (int i = tid; i < dpvjp::NY * H1; i += WPB * 64) lds[L_A2 + (i / H1) * S2 + i % H1] = W[dpvjp::OFF_A2 + i];
-    if (tid < NJ) par[tid] = Ti[dpvjp::OFF_PARENT + tid];
-    if (tid < NJ + 1) ((int*)(lds + L_CST))[tid] = Ti[dpvjp::OFF_CSTART + tid];
-    if (tid < NJ) ((int*)(lds + L_CLS))[tid] = Ti[dpvjp::OFF_CLIST + tid];
-    if (tid < 3 * NJ) lds[L_OFF + tid] = W[dpvjp::OFF_BONE + tid];
-    __syncthreads();
-    if (tid < NJ) { // ancestors of tid (itself included), parked in sub[] for the moment
-        unsigned anc = 1u << tid;
-        int c = tid;
-        for (int s = 0; s < NJ && c != 0; ++s) { c = par[c]; anc |= 1u << c; } // (parents[j] < j: dp_create's check)
-        sub[tid] = anc;
-    }
-    __syncthreads();
-    unsigned mysub = 0u;
-    if (tid < NJ)
-        for (int d = 0; d < NJ; ++d) mysub |= ((sub[d] >> tid) & 1u) << d;
-    __syncthreads();
-    if (tid < NJ) sub[tid] = mysub;
-    __syncthreads();
-
-    const long long f = (long long)blockIdx.x * WPB + wv;
-    if (f >= a.n_frames) return;
-    float* wb = lds + L_WAVE0 + wv * W_FLOATS;
-    float *ZB = wb + W_Z, *HB0 = wb + W_H0, *HB1 = wb + W_H1, *QB = wb + W_Q, *DYB = wb + W_DY, *RB = wb + W_R, *BB = wb + W_B,
-          *PB = wb + W_P, *GB = wb + W_G, *GPB = wb + W_GP, *FB = wb + W_F;
-    const float nan = __builtin_nanf("");
-    const int j = lane; // joint of this lane (j < NJ)
-    const bool jl = lane < NJ;
-
-    // ---- screening (include/dragposer.h: DP_STATUS_*)
-    float cr[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) cr[k] = a.cur_rot[f * 4 + k];
-    float gp[3] = {0.f, 0.f, 0.f};
-    if (a.w_floor != 0.f)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) gp[k] = a.global_pos[f * 3 + k];
-    const float z0 = lane < LAT ? a.z0[f * LAT + lane] : 0.f;
-    const float zt = lane < LAT ? a.z_tgt[f * LAT + lane] : 0.f;
-    const bool trk = jl && a.tracked[f * NJ + j] != 0;
-    bool bs = refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]) || refused(gp[0]) || refused(gp[1]) ||
-              refused(gp[2]);
-    bool bt = refused(zt);
-    if (trk) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) bt = bt || refused(a.tgt_pos[(f * NJ + j) * 3 + k]);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) bt = bt || refused(a.tgt_rot[(f * NJ + j) * 9 + k]);
-        bt = bt || refused(a.w[(f * NJ + j) * 2]) || refused(a.w[(f * NJ + j) * 2 + 1]);
-    }
-    const bool bad_state = __ballot(bs) != 0ull;
-    const bool bad_tgt = !bad_state && __ballot(bt) != 0ull;
-    const int E = __popcll(__ballot(trk));
-    if (bad_state) { // every result NaN (the reference's latent is NaN from here on); the reference's loop ends after one pass
-        if (lane < LAT) {
-            if (a.z) a.z[f * LAT + lane] = nan;
-            if (a.z_pre) a.z_pre[f * LAT + lane] = nan;
-        }
-        if (jl) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) if (a.pose) a.pose[f * 88 + 4 * j + c] = nan;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) if (a.pos) a.pos[(f * NJ + j) * 3 + c] = nan;
-#pragma unroll
-            for (int c = 0; c < 9; ++c) if (a.rot) a.rot[(f * NJ + j) * 9 + c] = nan;
-        }
-        if (lane < 4) {
-            if (a.world_rot) a.world_rot[f * 4 + lane] = nan;
-            if (a.loss_extra) a.loss_extra[f * 4 + lane] = nan;
-        }
-        if (lane < 3) {
-            if (a.disp) a.disp[f * 3 + lane] = nan;
-            if (a.world_disp) a.world_disp[f * 3 + lane] = nan;
-            if (a.loss) a.loss[f * 3 + lane] = nan;
-        }
-        if (lane == 0) {
-            if (a.iters) a.iters[f] = a.early_stop ? 1 : a.n_iter;
-            if (a.status) a.status[f] = DP_STATUS_NONFINITE_RESULT | DP_STATUS_BAD_STATE;
-        }
-        return;
-    }
-
-    // per-lane constants of the frame loop
-    const float c0 = lane < H0 ? W[dpvjp::OFF_C0 + lane] : 0.f;
-    const float b1 = lane < H1 ? W[dpvjp::OFF_B1 + lane] : 0.f;
-    const int oB = 64 + lane; // second decoder row of lanes 0..26
-    const float b2A = W[dpvjp::OFF_B2 + lane], sdA = W[dpvjp::OFF_SD + lane], muA = W[dpvjp::OFF_MU + lane];
-    const float b2B = lane < NYU - 64 ? W[dpvjp::OFF_B2 + oB] : 0.f, sdB = lane < NYU - 64 ? W[dpvjp::OFF_SD + oB] : 1.f,
-                muB = lane < NYU - 64 ? W[dpvjp::OFF_MU + oB] : 0.f;
-    const int pj = jl ? par[j] : 0;
-    const unsigned mysubj = jl ? sub[j] : 0u;
-    float off[3] = {0.f, 0.f, 0.f};
-    float sdj[4] = {1.f, 1.f, 1.f, 1.f}, muj[4] = {0.f, 0.f, 0.f, 0.f};
-    if (jl) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) off[c] = lds[L_OFF + 3 * j + c];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { sdj[c] = W[dpvjp::OFF_SD + 4 * j + c]; muj[c] = W[dpvjp::OFF_MU + 4 * j + c]; }
-    }
-    const float cp = 2.f / (3.f * (float)E), crt = 2.f * a.lam_rot / (9.f * (float)E);
-    const int up = a.up;
-
-    float z = z0, m = 0.f, v = 0.f;
-    if (lane < LAT) ZB[lane] = z;
-    double b1t = 1.0, b2t = 1.0;
-    float prev = 10000000.f;
-    int it = 0;
-    const int n_iter = bad_tgt ? 1 : a.n_iter; // (a refused target: the loss is NaN, the reference's loop ends after one pass)
-    for (;; ++it) {
-        wave_sync();
-        // ---- decoder (autoencoder.py:224-256, folded), LeakyReLU(0.2) after layers 0 and 1
-        bool pos0 = false, pos1 = false;
-        if (lane < H0) {
-            float s = c0;
-#pragma unroll UNR
-            for (int k = 0; k < LAT; ++k) s = fmaf(lds[L_A0 + lane * S0 + k], ZB[k], s);
-            pos0 = s > 0.f;
-            HB0[lane] = pos0 ? s : s * 0.2f;
-        }
-        wave_sync();
-        if (lane < H1) {
-            float s = b1;
-#pragma unroll UNR
-            for (int k = 0; k < H0; ++k) s = fmaf(lds[L_A1 + lane * S1 + k], HB0[k], s);
-            pos1 = s > 0.f;
-            HB1[lane] = pos1 ? s : s * 0.2f;
-        }
-        wave_sync();
-        {
-            float s = b2A, t = b2B;
-#pragma unroll UNR
-            for (int k = 0; k < H1; ++k) {
-                const float h = HB1[k];
-                s = fmaf(lds[L_A2 + lane * S2 + k], h, s);
-                if (lane < NYU - 64) t = fmaf(lds[L_A2 + oB * S2 + k], h, t);
-            }
-            QB[lane] = fmaf(s, sdA, muA);
-            if (lane < NYU - 64) QB[oB] = fmaf(t, sdB, muB);
-        }
-        wave_sync();
-        // ---- kinematics, a lane per joint
-        float q[4], qn[4], rn = 1.f, R[9], wr[4] = {1.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) q[c] = jl ? QB[4 * j + c] : (c == 0 ? 1.f : 0.f);
-        rn = 1.f / sqrtf(fmaf(q[0], q[0], fmaf(q[1], q[1], fmaf(q[2], q[2], q[3] * q[3]))));
-#pragma unroll
-        for (int c = 0; c < 4; ++c) qn[c] = q[c] * rn;
-        if (j == 0) { quat_mul(cr, qn, wr); rotmat(wr, R); } // world root rotation, cur_rot as given (drag_pose.py:88)
-        else rotmat(qn, R);
-        if (jl)
-#pragma unroll
-            for (int k = 0; k < 9; ++k) RB[9 * j + k] = R[k];
-        wave_sync();
-        float R0[9], d[3], wd[3];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R0[k] = RB[k];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d[c] = QB[4 * NJ + c];
-        mv(R0, d, wd); // world displacement (drag_pose.py:102)
-        if (jl) {
-            float b[3] = {off[0], off[1], off[2]};
-            if (j == 0) b[0] = b[1] = b[2] = 0.f;
-            else if (pj != 0) mv(RB + 9 * pj, off, b);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) BB[4 * j + c] = b[c];
-        }
-        wave_sync();
-        float vj[3] = {0.f, 0.f, 0.f}, P[3], G[9];
-        if (jl) {
-            int c = j;
-            for (int s = 0; s < NJ && c != 0; ++s) { // the path from j to the root (<= 7 bones)
-                vj[0] += BB[4 * c]; vj[1] += BB[4 * c + 1]; vj[2] += BB[4 * c + 2];
-                c = par[c];
-            }
-        }
-        mv(R0, vj, P);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) P[c] += wd[c];
-        if (j == 0) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) G[k] = R0[k];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) G[3 * r + c] = R0[3 * r] * R[c] + R0[3 * r + 1] * R[3 + c] + R0[3 * r + 2] * R[6 + c];
-        }
-        if (jl) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) PB[4 * j + c] = P[c];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) GB[9 * j + k] = G[k];
-        }
-        wave_sync();
-
-        // ---- losses and upstream gradients (drag_pose.py:115-127 and the Additional Losses block, 129-183)
-        float dpj = 0.f, drj = 0.f, gPj[3] = {0.f, 0.f, 0.f}, gGj[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) gGj[k] = 0.f;
-        if (trk) { // (targets re-read every iteration: not held in registers)
-            const float wp = a.w[(f * NJ + j) * 2], wrr = a.w[(f * NJ + j) * 2 + 1];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float e = P[c] - a.tgt_pos[(f * NJ + j) * 3 + c];
-                dpj = fmaf(e, e, dpj);
-                gPj[c] = cp * wp * e;
-            }
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const float e = G[k] - a.tgt_rot[(f * NJ + j) * 9 + k];
-                drj = fmaf(e, e, drj);
-                gGj[k] = crt * wrr * e;
-            }
-            dpj *= wp;
-            drj *= wrr;
-        }
-        const float dz = z - zt;
-        const float dtj = lane < LAT ? dz * dz : 0.f;
-        // the constraint terms: every lane evaluates them on the same LDS values; a joint's lane keeps its own gradient
-        float ext[4] = {0.f, 0.f, 0.f, 0.f}; // weighted: feet_floor, head_hips_forward, head_hips_colinear, hips_feet_colinear
-        if (a.w_floor != 0.f) {
-            float t = 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int fj = a.floor_j[i];
-                const float h = comp(gp, up) + (PB[4 * fj + up] - a.floor_level);
-                float g;
-                if (a.one_sided) {
-                    const float r = h < 0.f ? -h : 0.f; // relu(floor_level - g_up - P_up)
-                    t = fmaf(r, r, t);
-                    g = -r;
-                } else {
-                    t = fmaf(h, h, t);
-                    g = h;
-                }
-                if (j == fj) // d/dP_up of w * mean_i (.)^2 over the two joints
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) gPj[c] += c == up ? a.w_floor * g : 0.f;
-            }
-            ext[0] = a.w_floor * (0.5f * t);
-        }
-        if (a.w_fwd != 0.f) {
-            float av[3], bv[3];
-            mv(GB + 9 * a.head, a.fwd, av);
-            flatten(av, up);
-            const float na = sqrtf(av[0] * av[0] + av[1] * av[1] + av[2] * av[2]);
-            if (na > a.fwd_thr) {
-                mv(GB + 9 * a.hips, a.fwd, bv);
-                flatten(bv, up);
-                const float nb = sqrtf(bv[0] * bv[0] + bv[1] * bv[1] + bv[2] * bv[2]);
-                float ah[3], bh[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { ah[c] = av[c] / na; bh[c] = bv[c] / nb; }
-                const float cs = ah[0] * bh[0] + ah[1] * bh[1] + ah[2] * bh[2];
-                const float s = cs + a.fwd_margin;
-                if (s < 1.f) {
-                    const float u = 1.f - s;
-                    ext[1] = a.w_fwd * (u * u);
-                    const float ds = -2.f * u * a.w_fwd;
-                    if (j == a.head || j == a.hips) {
-                        float da[3]; // d s / d(projected axis) of this joint
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) da[c] = j == a.head ? (bh[c] - ah[c] * cs) / na : (ah[c] - bh[c] * cs) / nb;
-                        if (a.head == a.hips)
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) da[c] = (bh[c] - ah[c] * cs) / na + (ah[c] - bh[c] * cs) / nb;
-                        flatten(da, up);
-#pragma unroll
-                        for (int r = 0; r < 3; ++r)
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) gGj[3 * r + c] += ds * da[r] * a.fwd[c];
-                    }
-                }
-            }
-        }
-        if (a.w_hcol != 0.f) {
-            float u[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) u[c] = PB[4 * a.head + c] - PB[4 * a.hips + c];
-            flatten(u, up);
-            ext[2] = a.w_hcol * (u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-            const float sgn = (j == a.head ? 1.f : 0.f) - (j == a.hips ? 1.f : 0.f);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) gPj[c] += sgn * 2.f * a.w_hcol * u[c];
-        }
-        if (a.w_feet != 0.f) {
-            float t = 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int fj = a.foot_j[i];
-                float u[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) u[c] = PB[4 * a.hips + c] - PB[4 * fj + c];
-                flatten(u, up);
-                const float x = (u[0] * u[0] + u[1] * u[1] + u[2] * u[2]) - a.feet_r2;
-                if (x > 0.f) {
-                    t += x;
-                    const float sgn = (j == a.hips ? 1.f : 0.f) - (j == fj ? 1.f : 0.f);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) gPj[c] += sgn * 2.f * a.w_feet * u[c];
-                }
-            }
-            ext[3] = a.w_feet * t;
-        }
-        if (jl)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) GPB[4 * j + c] = gPj[c];
-        // dL/dR_0 terms of this joint: dL/dG_j R_j^T (root: dL/dG_0) + dL/dP_j v_j^T; summed over the joints with the losses
-        float red[15];
-        if (j == 0) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) red[k] = gGj[k];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) red[3 * r + c] = gGj[3 * r] * R[3 * c] + gGj[3 * r + 1] * R[3 * c + 1] + gGj[3 * r + 2] * R[3 * c + 2];
-        }
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) red[3 * r + c] = fmaf(gPj[r], vj[c], red[3 * r + c]);
-        if (!jl)
-#pragma unroll
-            for (int k = 0; k < 9; ++k) red[k] = 0.f;
-        red[9] = gPj[0]; red[10] = gPj[1]; red[11] = gPj[2]; // dL/dworld_disp = sum_j dL/dP_j
-        red[12] = dpj; red[13] = drj; red[14] = dtj;
-#pragma unroll
-        for (int k = 0; k < 15; ++k) red[k] = wsum(red[k]);
-        // (every lane computed the constraint terms on the same values, lanes below 32 hold the sums: lane 0's copy makes them uniform)
-        const float lp = uni(red[12]) / (3.f * (float)E), lr = a.lam_rot * (uni(red[13]) / (9.f * (float)E)), lt = a.lam_tmp * (uni(red[14]) / 24.f);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ext[k] = uni(ext[k]);
-        const float extra = ((ext[1] + ext[2]) + ext[0]) + ext[3]; // the reference's order (drag_pose.py:178-183)
-        const float tot = ((lp + lr) + lt) + extra;
-        const bool last = it + 1 >= n_iter;
-        const bool stop = last || (a.early_stop && !((lp > a.stop_eps_pos || lr > a.stop_eps_rot) && (prev - tot > a.min_loss_incr)));
-        prev = tot;
-        if (stop) { // results of this, the last, forward pass (drag_pose.py:309-312)
-            const bool pz = bad_tgt && !(a.early_stop || a.n_iter == 1); // (fixed count: the reference would decode the NaN latent)
-            if (lane < LAT && a.z_pre) a.z_pre[f * LAT + lane] = pz ? nan : z;
-            if (jl) {
-                if (a.pose)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) a.pose[f * 88 + 4 * j + c] = pz ? nan : (qn[c] - muj[c]) / sdj[c];
-                if (a.pos)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) a.pos[(f * NJ + j) * 3 + c] = pz ? nan : P[c];
-                if (a.rot)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) a.rot[(f * NJ + j) * 9 + k] = pz ? nan : G[k];
-            }
-            if (lane == 0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    if (a.disp) a.disp[f * 3 + c] = pz ? nan : d[c];
-                    if (a.world_disp) a.world_disp[f * 3 + c] = pz ? nan : wd[c];
-                }
-                if (a.world_rot)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) a.world_rot[f * 4 + c] = pz ? nan : wr[c];
-                if (a.loss) {
-                    a.loss[f * 3] = bad_tgt ? nan : lp; a.loss[f * 3 + 1] = bad_tgt ? nan : lr; a.loss[f * 3 + 2] = bad_tgt ? nan : lt;
-                }
-                if (a.loss_extra)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) a.loss_extra[f * 4 + c] = bad_tgt ? nan : ext[c];
-            }
-        }
-        wave_sync();
-
-        // ---- backward: subtree sums, per-joint rotations, root
-        if (jl) {
-            float F[3] = {0.f, 0.f, 0.f};
-            for (int dj = 0; dj < NJ; ++dj)
-                if ((mysubj >> dj) & 1u) { F[0] += GPB[4 * dj]; F[1] += GPB[4 * dj + 1]; F[2] += GPB[4 * dj + 2]; }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) FB[4 * j + c] = F[c];
-        }
-        wave_sync();
-        if (jl && j != 0) {
-            float M[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) M[k] = gGj[k];
-            for (int k = cst[j]; k < cst[j + 1]; ++k) { // child bones: M += F_c off_c^T
-                const int c = cls[k];
-                const float F0 = FB[4 * c], F1 = FB[4 * c + 1], F2 = FB[4 * c + 2];
-                const float o0 = lds[L_OFF + 3 * c], o1 = lds[L_OFF + 3 * c + 1], o2 = lds[L_OFF + 3 * c + 2];
-                M[0] = fmaf(F0, o0, M[0]); M[1] = fmaf(F0, o1, M[1]); M[2] = fmaf(F0, o2, M[2]);
-                M[3] = fmaf(F1, o0, M[3]); M[4] = fmaf(F1, o1, M[4]); M[5] = fmaf(F1, o2, M[5]);
-                M[6] = fmaf(F2, o0, M[6]); M[7] = fmaf(F2, o1, M[7]); M[8] = fmaf(F2, o2, M[8]);
-            }
-            float dR[9], dqn[4];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) dR[3 * r + c] = R0[r] * M[c] + R0[3 + r] * M[3 + c] + R0[6 + r] * M[6 + c];
-            rotmat_vjp(qn, dR, dqn);
-            const float dot = qn[0] * dqn[0] + qn[1] * dqn[1] + qn[2] * dqn[2] + qn[3] * dqn[3];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) DYB[4 * j + c] = (dqn[c] - qn[c] * dot) * rn * sdj[c];
-        }
-        if (lane == 0) { // root: world_rot = cur_rot (x) q_0, world_disp = R_0 d
-            float dR0[9], dw[4], dq0[4];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) dR0[3 * r + c] = fmaf(red[9 + r], d[c], red[3 * r + c]);
-            rotmat_vjp(wr, dR0, dw);
-            dq0[0] = dw[0] * cr[0] + dw[1] * cr[1] + dw[2] * cr[2] + dw[3] * cr[3];
-            dq0[1] = -dw[0] * cr[1] + dw[1] * cr[0] + dw[2] * cr[3] - dw[3] * cr[2];
-            dq0[2] = -dw[0] * cr[2] - dw[1] * cr[3] + dw[2] * cr[0] + dw[3] * cr[1];
-            dq0[3] = -dw[0] * cr[3] + dw[1] * cr[2] - dw[2] * cr[1] + dw[3] * cr[0];
-            const float dot = qn[0] * dq0[0] + qn[1] * dq0[1] + qn[2] * dq0[2] + qn[3] * dq0[3];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) DYB[c] = (dq0[c] - qn[c] * dot) * rn * sdj[c];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) // dL/dd = R_0^T dL/dworld_disp
-                DYB[4 * NJ + c] = (R0[c] * red[9] + R0[3 + c] * red[10] + R0[6 + c] * red[11]) * W[dpvjp::OFF_SD + 4 * NJ + c];
-        }
-        wave_sync();
-        // ---- decoder backward: A2^T, A1^T, A0^T with the LeakyReLU slopes of this pass
-        if (lane < H1) {
-            float s = 0.f;
-#pragma unroll UNR
-            for (int o = 0; o < NYU; ++o) s = fmaf(lds[L_A2 + o * S2 + lane], DYB[o], s);
-            HB1[lane] = pos1 ? s : s * 0.2f;
-        }
-        wave_sync();
-        if (lane < H0) {
-            float s = 0.f;
-#pragma unroll UNR
-            for (int k = 0; k < H1; ++k) s = fmaf(lds[L_A1 + k * S1 + lane], HB1[k], s);
-            HB0[lane] = pos0 ? s : s * 0.2f;
-        }
-        wave_sync();
-        // ---- Adam (torch.optim.Adam defaults re-created per frame, drag_pose.py:218), a lane per latent component
-        b1t *= a.beta1d;
-        b2t *= a.beta2d;
-        const float step = (float)(a.lrd / (1.0 - b1t)), rbc2s = (float)(1.0 / sqrt(1.0 - b2t));
-        if (lane < LAT) {
-            float s = 0.f;
-#pragma unroll UNR
-            for (int i = 0; i < H0; ++i) s = fmaf(lds[L_A0 + i * S0 + lane], HB0[i], s);
-            const float g = fmaf(a.ctmp, dz, s);
-            m = m + a.one_m_b1 * (g - m);
-            v = v * a.beta2 + a.one_m_b2 * (g * g);
-            const float den = sqrtf(v) * rbc2s + a.eps;
-            z = z - step * (m / den);
-            ZB[lane] = z;
-        }
-        if (stop) break;
-    }
-    const bool pz = bad_tgt;
-    if (lane < LAT && a.z) a.z[f * LAT + lane] = pz ? nan : z;
-    const bool nonfin = pz || __ballot(lane < LAT && !(fabsf(z) <= 3.0e38f)) != 0ull;
-    if (lane == 0) {
-        if (a.iters) a.iters[f] = bad_tgt && !a.early_stop ? a.n_iter : it + 1;
-        if (a.status) a.status[f] = (nonfin ? DP_STATUS_NONFINITE_RESULT : 0) | (bad_tgt ? DP_STATUS_BAD_TARGETS : 0);
-    }
-}
+__global__ __launch_bounds__(WPB * 64) void dp_terms_kernel(TermArgs a)
+#define DP_CONS_TABLE 1
+#include "dp_cons_body.h"
+#undef DP_CONS_TABLE
 
 hipError_t dp_launch_cons(const Args* args, hipStream_t stream)
 {
     const unsigned grid = (unsigned)((args->n_frames + WPB - 1) / WPB);
     hipLaunchKernelGGL(dp_cons_kernel, dim3(grid), dim3(WPB * 64), 0, stream, *args);
+    return hipGetLastError();
+}
+
+hipError_t dp_launch_terms(const TermArgs* args, hipStream_t stream)
+{
+    const unsigned grid = (unsigned)((args->n_frames + WPB - 1) / WPB);
+    hipLaunchKernelGGL(dp_terms_kernel, dim3(grid), dim3(WPB * 64), 0, stream, *args);
     return hipGetLastError();
 }

@@ -15,6 +15,7 @@
 #include "../../include/dragposer.h"
 #include "../../include/dragposer_grad.h"
 #include "../../include/dragposer_constraints.h"
+#include "../../include/dragposer_terms.h"
 #include "dp_cons.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -992,6 +993,119 @@ extern "C" int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp
 #endif
     } catch (...) {
         return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: host-side failure");
+    }
+}
+
+// include/dragposer_terms.h.  dp_terms as the caller compiled it (first version: up to loss_terms), checked like dp_constraints
+constexpr unsigned TERMS_SIZE_V510 = offsetof(dp_terms, loss_terms) + sizeof(void*);
+static_assert(DP_MAX_TERMS == dpcons::MAX_TERMS, "dp_cons.h's table holds DP_MAX_TERMS terms");
+
+// one term of the table: "" when it is well-formed, otherwise what is wrong with it
+static std::string check_term(const dp_term& t)
+{
+    const auto fin = [](float x) { return std::fabs(x) <= 3.0e38f; };
+    const auto unit = [](const float* v) {
+        const double n = std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]);
+        return std::fabs(n - 1.0) <= 1e-4;
+    };
+    const auto zero = [](const float* v) { return v[0] == 0.f && v[1] == 0.f && v[2] == 0.f; };
+    if (t.type != DP_TERM_PLANE && t.type != DP_TERM_DISTANCE && t.type != DP_TERM_ALIGN) return "unknown type " + std::to_string(t.type);
+    if (t.flags & ~(DP_TERM_ONE_SIDED | DP_TERM_DROP_UP)) return "unknown flag bits " + std::to_string(t.flags);
+    if (t.joint_a < 0 || t.joint_a >= NJ) return "joint_a " + std::to_string(t.joint_a) + " outside 0..21";
+    if (t.joint_b < -1 || t.joint_b >= NJ) return "joint_b " + std::to_string(t.joint_b) + " outside -1..21";
+    if (t.type == DP_TERM_PLANE && t.joint_b != -1) return "a PLANE has no second joint (joint_b must be -1)";
+    if (!(t.weight >= 0.f && t.weight <= 3.0e38f)) return "the weight is negative or not finite";
+    for (int c = 0; c < 3; ++c)
+        if (!fin(t.point[c]) || !fin(t.dir[c]) || !fin(t.axis_a[c]) || !fin(t.axis_b[c])) return "a point, dir or axis is not finite";
+    if (!fin(t.p0) || !fin(t.p1)) return "p0 or p1 is not finite";
+    if (t.type == DP_TERM_PLANE && !unit(t.dir)) return "the plane's normal (dir) is not unit length";
+    if (t.type == DP_TERM_DISTANCE && !(t.p0 >= 0.f && t.p0 <= t.p1)) return "DISTANCE needs 0 <= lo (p0) <= hi (p1)";
+    if (t.type == DP_TERM_ALIGN) {
+        if (!(t.p0 >= 0.f)) return "ALIGN's threshold (p0) is negative";
+        if (zero(t.axis_a) || (t.joint_b >= 0 && zero(t.axis_b))) return "ALIGN's axis is zero";
+        if (t.joint_b < 0 && !t.per_frame && !unit(t.dir)) return "ALIGN's world direction (dir) is not unit length";
+    }
+    return "";
+}
+
+extern "C" int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_terms* t_in, const dp_result* out_in, void* stream)
+{
+    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_optimize_terms: ctx is NULL");
+    try {
+        const char* who = "dp_optimize_terms";
+        if (!in || !p_in || !t_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: NULL batch, params, terms or result");
+        dp_params pv; dp_result ov;
+        if (int rc = take_params(ctx, p_in, pv, who)) return rc;
+        if (int rc = take_result(ctx, out_in, ov, who)) return rc;
+        if (t_in->struct_size < TERMS_SIZE_V510 || t_in->struct_size > 4096u || t_in->reserved0 != 0u)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: dp_terms.struct_size is " + std::to_string(t_in->struct_size) + " (reserved0 " +
+                                                 std::to_string(t_in->reserved0) + "), this library expects at least " + std::to_string(TERMS_SIZE_V510) +
+                                                 " and reserved0 = 0  (dp_terms t = DP_TERMS_INIT;)");
+        dp_terms ts;
+        std::memset(&ts, 0, sizeof(ts));
+        std::memcpy(&ts, t_in, std::min<size_t>(t_in->struct_size, sizeof(ts)));
+        if (ts.n_terms < 0 || ts.n_terms > DP_MAX_TERMS)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: n_terms " + std::to_string(ts.n_terms) + " outside 0..16");
+        if (ts.n_terms > 0 && !ts.terms) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: NULL terms with n_terms > 0");
+        if (ts.up_axis < 0 || ts.up_axis > 2) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: up_axis outside 0..2");
+        bool need_gp = false;
+        for (int k = 0; k < ts.n_terms; ++k) {
+            const dp_term& t = ts.terms[k];
+            const std::string why = check_term(t);
+            if (!why.empty()) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: term " + std::to_string(k) + ": " + why);
+            need_gp = need_gp || (t.weight != 0.f && (t.type == DP_TERM_PLANE || (t.type == DP_TERM_DISTANCE && t.joint_b < 0)));
+        }
+        if (need_gp && !ts.global_pos)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: global_pos is NULL while an active PLANE or point-DISTANCE term needs it");
+        if (in->n_frames <= 0) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: n_frames must be positive");
+        if (!in->z0 || !in->z_tgt || !in->cur_rot || !in->tgt_pos || !in->tgt_rot || !in->w || !in->tracked)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: NULL input array");
+        if (!(pv.lr > 0.f) || !(pv.beta1 >= 0.f && pv.beta1 < 1.f) || !(pv.beta2 >= 0.f && pv.beta2 < 1.f))
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: bad Adam hyper-parameters");
+        if (!(pv.eps > 0.f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: Adam eps must be > 0");
+#ifdef DP_REF8_BUILD
+        (void)stream;
+        return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize_terms: not part of the test-only library");
+#else
+        if (!ctx->d_vjpimg) return fail(ctx, DP_ERR_DEVICE, "dp_optimize_terms: the context has no device image");
+        DEVICE_GUARD(ctx);
+        dpcons::TermArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.img = ctx->d_vjpimg;
+        a.z0 = in->z0; a.z_tgt = in->z_tgt; a.cur_rot = in->cur_rot; a.tgt_pos = in->tgt_pos; a.tgt_rot = in->tgt_rot; a.w = in->w; a.tracked = in->tracked;
+        a.global_pos = need_gp ? ts.global_pos : nullptr;
+        a.z = ov.z; a.z_pre = ov.z_pre; a.pose = ov.pose; a.disp = ov.disp; a.world_disp = ov.world_disp; a.world_rot = ov.world_rot;
+        a.pos = ov.pos; a.rot = ov.rot; a.loss = ov.loss; a.iters = ov.iters; a.status = ov.status;
+        a.n_frames = in->n_frames; a.n_iter = pv.n_iter; a.early_stop = pv.early_stop ? 1 : 0;
+        a.stop_eps_pos = pv.stop_eps_pos; a.stop_eps_rot = pv.stop_eps_rot; a.min_loss_incr = pv.min_loss_incr;
+        a.lam_rot = pv.lambda_rot; a.lam_tmp = pv.lambda_tmp; a.ctmp = 2.f * pv.lambda_tmp / 24.f;
+        a.one_m_b1 = (float)(1.0 - (double)pv.beta1); a.beta2 = pv.beta2; a.one_m_b2 = (float)(1.0 - (double)pv.beta2); a.eps = pv.eps;
+        a.beta1d = pv.beta1; a.beta2d = pv.beta2; a.lrd = pv.lr;
+        a.up = ts.up_axis;
+        a.n_terms = ts.n_terms; a.need_gp = need_gp ? 1 : 0; a.loss_terms = ts.loss_terms;
+        for (int k = 0; k < ts.n_terms; ++k) { // dp_cons.h's T_* layout
+            const dp_term& t = ts.terms[k];
+            unsigned* w = a.tbl + k * dpcons::TW;
+            float* wf = (float*)w;
+            w[dpcons::T_TYPE] = (unsigned)t.type; w[dpcons::T_JA] = (unsigned)t.joint_a; w[dpcons::T_JB] = (unsigned)t.joint_b;
+            w[dpcons::T_FLAGS] = (unsigned)t.flags;
+            wf[dpcons::T_W] = t.weight;
+            for (int c = 0; c < 3; ++c) {
+                wf[dpcons::T_PT + c] = t.point[c]; wf[dpcons::T_DIR + c] = t.dir[c];
+                wf[dpcons::T_AXA + c] = t.axis_a[c]; wf[dpcons::T_AXB + c] = t.axis_b[c];
+            }
+            // DISTANCE: lo^2, hi^2 (float products, as the reference's feet_radius ** 2 meets a float32 tensor)
+            wf[dpcons::T_P0] = t.type == DP_TERM_DISTANCE ? t.p0 * t.p0 : t.p0;
+            wf[dpcons::T_P1] = t.type == DP_TERM_DISTANCE ? t.p1 * t.p1 : t.p1;
+            const float* pf = t.per_frame;
+            std::memcpy(w + dpcons::T_ROW, &pf, sizeof(pf));
+        }
+        const hipError_t e = dp_launch_terms(&a, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("dp_optimize_terms: kernel launch: ") + hipGetErrorString(e));
+        return DP_OK;
+#endif
+    } catch (...) {
+        return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: host-side failure");
     }
 }
 

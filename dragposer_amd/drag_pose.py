@@ -262,12 +262,16 @@ class DragPose:
     def run(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, offsets=None, stop_eps_pos=1e-2,
             stop_eps_rot=1e-2, max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1,
             temporal_future_window=60, height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None,
-            joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None):
+            joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None):
         """One frame for every sequence: one launch for the optimise loop and the epilogue, one for the history buffers, plus two
         row scatters of the targets.  `out_pose` [S,88] / `out_pos` [S,3]: optional caller storage for the returned tensors.
         `constraints` (a dragposer_amd.Constraints): the reference's extra loss terms (drag_pose.py:129-183) join the loss -- the frame
         is then dp_optimize_constrained followed by dp_sequence_advance (two launches), with this frame's current_global_pos as the
-        floor term's global position; None runs the path above unchanged."""
+        floor term's global position; None runs the path above unchanged.  `terms` (a dragposer_amd.Terms): a table of user-defined
+        terms instead, the same two launches with dp_optimize_terms (a term's per-frame rows: its [S,4] `per_frame` tensor, read at
+        this call); not together with `constraints`."""
+        if constraints is not None and terms is not None:
+            raise ValueError("DragPose.run: pass constraints or terms, not both")
         dev, S = self.device, self.S
         squeeze = torch.as_tensor(target_ee_pos).dim() == 2
         tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=dev).reshape(S, -1, 3)
@@ -302,8 +306,8 @@ class DragPose:
         o = self._out[self._flip]
         z_tgt = self.target_latent_buffer[:, self.current_index:]
         pull = self.temporal is not None and float(lambda_temporal) != 0.0  # (no predictor: the buffer is zeros, the term is off; run_frames() alike)
-        if constraints is not None:
-            return self._run_constrained(constraints, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot,
+        if constraints is not None or terms is not None:
+            return self._run_constrained(constraints if terms is None else terms, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot,
                                          lambda_temporal if pull else 0.0, stop_eps_pos, stop_eps_rot, min_loss_incr, temporal_future_window,
                                          verbose, squeeze)
         self.opt.optimize_sequence(self.latent, trk["tgt_pos"].unsqueeze(0), trk["tgt_rot"].unsqueeze(0), None, trk["w"], trk["tracked"], z_tgt,
@@ -326,23 +330,33 @@ class DragPose:
 
     def _run_constrained(self, constraints, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot, lambda_tmp,
                          stop_eps_pos, stop_eps_rot, min_loss_incr, window, verbose, squeeze):
-        """run()'s frame with the extra loss terms: the optimise loop (dp_optimize_constrained) and run()'s epilogue (dp_sequence_advance)"""
+        """run()'s frame with extra loss terms: the optimise loop (dp_optimize_constrained for a Constraints, dp_optimize_terms for a
+        Terms table) and run()'s epilogue (dp_sequence_advance)"""
+        from .terms import Terms
+
         S = self.S
+        table = isinstance(constraints, Terms)
         if o.get("frame") is None:
             o["frame"] = self.opt.allocate_outputs(S, ("z", "z_pre", "pose", "disp", "world_disp", "world_rot", "pos", "loss", "iters", "status"))
-            o["frame"]["loss_extra"] = torch.empty(S, 4, device=self.device)
         fr = o["frame"]
+        key, width = ("loss_terms", len(constraints)) if table else ("loss_extra", 4)
+        fr.pop("loss_terms" if not table else "loss_extra", None)
+        if fr.get(key) is None or fr[key].shape[1] != width:
+            fr[key] = torch.empty(S, width, device=self.device)
         z_tgt = self.target_latent_buffer[:, self.current_index].contiguous()
-        self.opt.optimize_constrained(self.latent, z_tgt, self.current_global_rot, trk["tgt_pos"], trk["tgt_rot"], trk["w"], trk["tracked"],
-                                      constraints, global_pos=self.current_global_pos, n_iter=max_iter, lr=learning_rate,
-                                      lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_tmp), stop_eps_pos=stop_eps_pos,
-                                      stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, out=fr, outputs=tuple(fr))
+        run = self.opt.optimize_terms if table else self.opt.optimize_constrained
+        run(self.latent, z_tgt, self.current_global_rot, trk["tgt_pos"], trk["tgt_rot"], trk["w"], trk["tracked"], constraints,
+            global_pos=self.current_global_pos, n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_tmp),
+            stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, out=fr, outputs=tuple(fr))
         self.opt.sequence_advance(fr, self.current_global_pos, self.current_global_rot, self.latent_buffer, self.displacement_buffer,
                                   self.heights_buffer, tuple(int(h) for h in height_indices), pose_ret=pose, pos_ret=gpos, adjust=adjust,
                                   tgt_pos=trk["tgt_pos"] if adjust is not None else None)
         self.latent.copy_(fr["z"])
         o["z"].copy_(self.latent)
-        self.last = dict(iters=fr["iters"], loss=fr["loss"], z=o["z"], pose=pose, pos=gpos, status=fr["status"], loss_extra=fr["loss_extra"])
+        self.last = dict(iters=fr["iters"], loss=fr["loss"], z=o["z"], pose=pose, pos=gpos, status=fr["status"])
+        self.last[key] = fr[key]
+        if table:
+            self.last["joint_pos"] = fr["pos"]  # [S,22,3] P_j of the frame (world: the current_global_pos before the call + P_j)
         if verbose:
             l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
             print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "

@@ -246,6 +246,50 @@ class LatentOptimizer:
             self._fail(rc)
         return tensors
 
+    def optimize_terms(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, terms, global_pos=None, n_iter=50, lr=1e-2,
+                       betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.02, stop_eps_pos=0.0, stop_eps_rot=0.0, min_loss_incr=None,
+                       max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto"):
+        """`optimize` with a table of user-defined terms (`terms`: a dragposer_amd.Terms) added to the loss and to the while-condition's
+        total: include/dragposer_terms.h, dp_optimize_terms (one launch).  `global_pos` [B,3] (device, fp32): the root position before
+        the frame, required when an active PLANE or point-DISTANCE term exists.  A term's per-frame rows are its `per_frame` [B,4]
+        device tensor.  Returns `optimize`'s dict plus `loss_terms` [B, len(terms)] (each weighted term of the last forward pass).
+        `kernel` is ignored; `validate_targets` as in `optimize`."""
+        B = int(z0.shape[0])
+        dev = self.device
+        terms.check()
+        if validate_targets:
+            check_rotation_targets(tgt_rot, tracked)
+        batch = _lib.DpBatch()
+        batch.n_frames = B
+        batch.z0 = _check(z0, "z0", (B, LATENT), torch.float32, dev)
+        batch.z_tgt = _check(z_tgt, "z_tgt", (B, LATENT), torch.float32, dev)
+        batch.cur_rot = _check(cur_rot, "cur_rot", (B, 4), torch.float32, dev)
+        batch.tgt_pos = _check(tgt_pos, "tgt_pos", (B, NJ, 3), torch.float32, dev)
+        batch.tgt_rot = _check(tgt_rot, "tgt_rot", (B, NJ, 9), torch.float32, dev)
+        batch.w = _check(w, "w", (B, NJ, 2), torch.float32, dev)
+        batch.tracked = _check(tracked, "tracked", (B, NJ), torch.uint8, dev)
+        early = min_loss_incr is not None or stop_eps_pos > 0 or stop_eps_rot > 0
+        p = _lib.DpParams(n_iter=int(n_iter), lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, lambda_rot=lambda_rot,
+                          lambda_tmp=lambda_tmp, early_stop=int(early), stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
+                          min_loss_incr=float("-inf") if min_loss_incr is None else min_loss_incr, max_trackers=int(max_trackers))
+        names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS)
+        res, tensors = self._outputs(B, [n for n in names if n != "loss_terms"], out)
+        n = len(terms)
+        lt = out["loss_terms"] if out is not None and "loss_terms" in out else torch.empty(B, n, dtype=torch.float32, device=dev)
+        tensors["loss_terms"] = lt
+        gp = None
+        if global_pos is not None:
+            gp = _check(global_pos, "global_pos", (B, 3), torch.float32, dev)
+        elif terms.needs_global_pos:
+            raise ValueError("optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]")
+        s, keep = terms.to_struct(B, dev, gp, _check(lt, "loss_terms", (B, n), torch.float32, dev) if n else None)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = self.lib.dp_optimize_terms(self.ctx, C.byref(batch), C.byref(p), C.byref(s), C.byref(res), stream)
+        del keep
+        if rc != _lib.DP_OK:
+            self._fail(rc)
+        return tensors
+
     def forward_vjp(self, z, cur_rot, grads, out=None):
         """dL/dz [B,24] and dL/dcur_rot [B,4] of decode + FK at (z, cur_rot) for upstream gradients `grads` = {output name: dL/d(that
         output)} over any subset of pose, disp, world_disp, world_rot, pos, rot (shapes as `forward` returns them; missing = zero):
