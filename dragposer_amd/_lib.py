@@ -197,6 +197,16 @@ class DpTerms(_Sized):
             self.up_axis = 1
 
 
+# every symbol include/dragposer_skeleton.h declares (tests/test_skeleton_abi.py)
+SKELETON_SYMBOLS = ("dp_optimize_skeleton", "dp_forward_skeleton", "dp_optimize_sequence_skeleton")
+DP_SKELETON_STRIDE = 66
+
+
+class DpSkeletonIn(_Sized):
+    """include/dragposer_skeleton.h: dp_skeleton_in (per-frame bone offsets, a device pointer; stride 66 or 0)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("offsets", C.c_void_p), ("stride", C.c_int)]
+
+
 _libs = {}
 
 
@@ -233,6 +243,10 @@ def load(path=None):
     lib.dp_optimize_constrained.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpConstraints), C.POINTER(DpResult),
                                             C.c_void_p]
     lib.dp_optimize_terms.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpTerms), C.POINTER(DpResult), C.c_void_p]
+    lib.dp_optimize_skeleton.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpSkeletonIn), C.POINTER(DpResult), C.c_void_p]
+    lib.dp_forward_skeleton.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpSkeletonIn), C.POINTER(DpResult), C.c_void_p]
+    lib.dp_optimize_sequence_skeleton.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSkeletonIn),
+                                                  C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

@@ -16,6 +16,7 @@
 #include "../../include/dragposer_grad.h"
 #include "../../include/dragposer_constraints.h"
 #include "../../include/dragposer_terms.h"
+#include "../../include/dragposer_skeleton.h"
 #include "dp_cons.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -747,13 +748,14 @@ static void fill_results(const dp_result* out, KArgs& k)
 // Which kernel runs a launch: the wave-private kernel of dp_w4.hip (4 frames per wave, no workgroup barrier in the
 // loop); in the test-only library the previous decomposition (dp_kernel.hip: 16 frames per 8-wave workgroup).  Both
 // implement the same operator within the tolerance of tests/test_hip_w4.py.
-static int launch(dp_ctx* ctx, KArgs& k, void* stream, int kernel = DP_KERNEL_W4)
+// skel: the per-frame skeleton units of the same layout (dp_w4_skel.hip, dp_w4_bp_skel.hip: include/dragposer_skeleton.h), never with DP_KERNEL_W16
+static int launch(dp_ctx* ctx, KArgs& k, void* stream, int kernel = DP_KERNEL_W4, bool skel = false)
 {
     DEVICE_GUARD(ctx);
     ctx->last_kernel = KERNEL_CHOICE;
     ctx->last_pick = LaunchPick{};
 #ifdef DP_REF8_BUILD
-    (void)kernel;
+    (void)kernel; (void)skel;
     hipError_t e = dp_launch_optimize(&k, (hipStream_t)stream);
 #else
     // dp_w16: one wave per SIMD (4 waves, 64 frames per workgroup) until every SIMD of the chip has a wave; beyond that two
@@ -762,6 +764,7 @@ static int launch(dp_ctx* ctx, KArgs& k, void* stream, int kernel = DP_KERNEL_W4
     if (kernel == DP_KERNEL_W16) ctx->last_kernel = 16 * (w16_waves / 4);
     LaunchPick* pick = &ctx->last_pick;
     hipError_t e = kernel == DP_KERNEL_W16 ? dp_launch_w16(&k, (hipStream_t)stream, w16_waves, pick)
+                   : skel                  ? (ctx->w4_bp ? dp_launch_w4sk_bp(&k, (hipStream_t)stream, pick) : dp_launch_w4sk(&k, (hipStream_t)stream, pick))
                    : ctx->w4_bp            ? dp_launch_w4_bp(&k, (hipStream_t)stream, pick)
                                            : dp_launch_w4(&k, (hipStream_t)stream, pick);
 #endif
@@ -770,7 +773,7 @@ static int launch(dp_ctx* ctx, KArgs& k, void* stream, int kernel = DP_KERNEL_W4
 }
 
 // host-only, exported for the tests: the instantiation the context's last dp_optimize / dp_forward / dp_optimize_sequence launched, as the
-// launcher recorded it -- out[5] = unit (1 dp_w4.hip, 2 dp_w4_bp.hip, 3 dp_w16*.hip; 0: none yet, or the test-only library), waves per
+// launcher recorded it -- out[5] = unit (1 dp_w4.hip, 2 dp_w4_bp.hip, 3 dp_w16*.hip, 4 dp_w4_skel.hip, 5 dp_w4_bp_skel.hip; 0: none yet, or the test-only library), waves per
 // workgroup, and the EARLY, SEQ and LONG template flags
 extern "C" int dp_debug_last_launch(const dp_ctx* ctx, int* out)
 {
@@ -797,28 +800,65 @@ extern "C" int dp_debug_set_w4_layout(dp_ctx* ctx, int bp)
     return bp;
 }
 
-// private extension used by the tests: same as dp_optimize, plus an optional debug dump
-// [B][240] = y(104) | dL/dy(104) | dL/dz(24) | pad, all of iteration 0.
-extern "C" int dp_optimize_debug(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_result* out_in, float* dbg, void* stream)
+// include/dragposer_skeleton.h: dp_skeleton_in as the caller compiled it (first version: up to stride), checked like dp_grad_in -> what goes
+// into KArgs::skel / skel_stride.  Also refuses a context without device memory (dp_debug_host_ctx) before anything reads it.
+constexpr unsigned SKEL_IN_SIZE_V510 = offsetof(dp_skeleton_in, stride) + sizeof(int);
+static int take_skeleton(dp_ctx* ctx, const dp_skeleton_in* s, const float*& off, int& stride, const char* who)
+{
+    if (!s) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": the skeleton is NULL");
+    if (s->struct_size < SKEL_IN_SIZE_V510 || s->struct_size > 4096u || s->reserved0 != 0u)
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_skeleton_in.struct_size is " + std::to_string(s->struct_size) + " (reserved0 " +
+                                             std::to_string(s->reserved0) + "), this library expects at least " + std::to_string(SKEL_IN_SIZE_V510) +
+                                             " and reserved0 = 0  (dp_skeleton_in s = DP_SKELETON_IN_INIT;)");
+    dp_skeleton_in sv;
+    std::memset(&sv, 0, sizeof(sv));
+    std::memcpy(&sv, s, std::min<size_t>(s->struct_size, sizeof(sv)));
+    if (!sv.offsets) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_skeleton_in.offsets is NULL");
+    if (sv.stride != 0 && sv.stride != DP_SKELETON_STRIDE)
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_skeleton_in.stride is " + std::to_string(sv.stride) +
+                                             ", expected 66 (one [22][3] skeleton per frame / sequence) or 0 (one for the launch)");
+    off = sv.offsets;
+    stride = sv.stride;
+    return DP_OK;
+}
+
+// dp_optimize (sk = NULL) and dp_optimize_skeleton (who names the caller in the messages)
+static int optimize_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_result* out_in, float* dbg, void* stream,
+                         const dp_skeleton_in* sk, const char* who)
 {
     if (!ctx) return DP_ERR_INVALID;
-    if (!in || !p_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize: NULL batch/params");
+    if (!in || !p_in) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": NULL batch/params");
     dp_params pv; dp_result ov;
-    if (int rc = take_params(ctx, p_in, pv, "dp_optimize")) return rc;
-    if (int rc = take_result(ctx, out_in, ov, "dp_optimize")) return rc;
+    if (int rc = take_params(ctx, p_in, pv, who)) return rc;
+    if (int rc = take_result(ctx, out_in, ov, who)) return rc;
     const dp_params* p = &pv;
     const dp_result* out = &ov;
-    if (in->n_frames <= 0) return fail(ctx, DP_ERR_INVALID, "dp_optimize: n_frames must be positive");
+    const std::string w = who;
+    if (in->n_frames <= 0) return fail(ctx, DP_ERR_INVALID, w + ": n_frames must be positive");
     if (!in->z0 || !in->z_tgt || !in->cur_rot || !in->tgt_pos || !in->tgt_rot || !in->w || !in->tracked)
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize: NULL input array");
+        return fail(ctx, DP_ERR_INVALID, w + ": NULL input array");
 #ifdef DP_REF8_BUILD
-    if (p->n_iter < 1 || p->n_iter > MAX_ITERS) return fail(ctx, DP_ERR_INVALID, "dp_optimize: n_iter out of range [1,256] (the test-only kernel reads the argument table only)");
+    if (p->n_iter < 1 || p->n_iter > MAX_ITERS) return fail(ctx, DP_ERR_INVALID, w + ": n_iter out of range [1,256] (the test-only kernel reads the argument table only)");
 #else
-    if (p->n_iter < 1 || p->n_iter > DP_MAX_ITERS) return fail(ctx, DP_ERR_INVALID, "dp_optimize: n_iter out of range [1, DP_MAX_ITERS]");
+    if (p->n_iter < 1 || p->n_iter > DP_MAX_ITERS) return fail(ctx, DP_ERR_INVALID, w + ": n_iter out of range [1, DP_MAX_ITERS]");
 #endif
     if (!(p->lr > 0.f) || !(p->beta1 >= 0.f && p->beta1 < 1.f) || !(p->beta2 >= 0.f && p->beta2 < 1.f))
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize: bad Adam hyper-parameters");
-    if (!(p->eps > 0.f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize: Adam eps must be > 0 (include/dragposer.h: dp_params.eps)");
+        return fail(ctx, DP_ERR_INVALID, w + ": bad Adam hyper-parameters");
+    if (!(p->eps > 0.f)) return fail(ctx, DP_ERR_INVALID, w + ": Adam eps must be > 0 (include/dragposer.h: dp_params.eps)");
+    const float* sk_off = nullptr;
+    int sk_stride = 0;
+    if (sk) { // (include/dragposer_skeleton.h: the dp_w4sk units, at every batch size)
+        if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
+        if (p->kernel != DP_KERNEL_AUTO && p->kernel != DP_KERNEL_W4 && p->kernel != DP_KERNEL_W16)
+            return fail(ctx, DP_ERR_INVALID, w + ": unknown kernel selector");
+        if (p->kernel == DP_KERNEL_W16)
+            return fail(ctx, DP_ERR_UNSUPPORTED, w + ": DP_KERNEL_W16 keeps the bone offsets in per-slot constants; per-frame skeletons run on "
+                                                     "DP_KERNEL_W4 (DP_KERNEL_AUTO takes it)");
+#ifdef DP_REF8_BUILD
+        return fail(ctx, DP_ERR_UNSUPPORTED, w + ": not part of the test-only library");
+#endif
+        if (!ctx->d_w4img) return fail(ctx, DP_ERR_DEVICE, w + ": the context has no device image");
+    }
     KArgs k;
     fill_model_args(ctx, k);
     k.z0 = in->z0; k.z_tgt = in->z_tgt; k.cur_rot = in->cur_rot; k.tgt_pos = in->tgt_pos; k.tgt_rot = in->tgt_rot;
@@ -836,12 +876,24 @@ extern "C" int dp_optimize_debug(dp_ctx* ctx, const dp_batch* in, const dp_param
     // which kernel (include/dragposer.h: DP_KERNEL_*)
     const bool w16_can = ctx->d_w16img != nullptr;
     if (p->kernel != DP_KERNEL_AUTO && p->kernel != DP_KERNEL_W4 && p->kernel != DP_KERNEL_W16)
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize: unknown kernel selector");
+        return fail(ctx, DP_ERR_INVALID, w + ": unknown kernel selector");
+    if (sk) {
+        k.skel = sk_off;
+        k.skel_stride = sk_stride;
+        return launch(ctx, k, stream, DP_KERNEL_W4, true);
+    }
     if (p->kernel == DP_KERNEL_W16 && !w16_can)
         return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize: DP_KERNEL_W16 is laid out for the reference's 22-joint skeleton only");
     // (beyond the argument table of Adam scalars, n_iter > 256, both kernels have LONG instantiations that continue them on the device)
     const int kernel = p->kernel == DP_KERNEL_AUTO ? dp_auto_kernel(ctx, in->n_frames) : p->kernel;
     return launch(ctx, k, stream, kernel);
+}
+
+// private extension used by the tests: same as dp_optimize, plus an optional debug dump
+// [B][240] = y(104) | dL/dy(104) | dL/dz(24) | pad, all of iteration 0.
+extern "C" int dp_optimize_debug(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_result* out_in, float* dbg, void* stream)
+{
+    return optimize_impl(ctx, in, p_in, out_in, dbg, stream, nullptr, "dp_optimize");
 }
 
 extern "C" int dp_auto_kernel(const dp_ctx* ctx, int n_frames)
@@ -862,20 +914,36 @@ extern "C" int dp_optimize(dp_ctx* ctx, const dp_batch* in, const dp_params* p, 
     return dp_optimize_debug(ctx, in, p, out, nullptr, stream);
 }
 
-extern "C" int dp_forward(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_result* out, void* stream)
+static int forward_impl(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* sk, const dp_result* out, void* stream,
+                        const char* who)
 {
     if (!ctx) return DP_ERR_INVALID;
-    if (n_frames <= 0 || !z || !cur_rot || !out) return fail(ctx, DP_ERR_INVALID, "dp_forward: bad arguments");
+    if (n_frames <= 0 || !z || !cur_rot || !out) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": bad arguments");
     dp_result ov;
-    if (int rc = take_result(ctx, out, ov, "dp_forward")) return rc;
+    if (int rc = take_result(ctx, out, ov, who)) return rc;
     out = &ov;
+    const float* sk_off = nullptr;
+    int sk_stride = 0;
+    if (sk) {
+        if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
+#ifdef DP_REF8_BUILD
+        return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": not part of the test-only library");
+#endif
+        if (!ctx->d_w4img) return fail(ctx, DP_ERR_DEVICE, std::string(who) + ": the context has no device image");
+    }
     KArgs k;
     fill_model_args(ctx, k);
+    k.skel = sk_off; k.skel_stride = sk_stride;
     k.z0 = z; k.cur_rot = cur_rot;
     fill_results(out, k);
     k.z = nullptr; k.z_pre = nullptr; k.loss = nullptr; k.iters = nullptr; k.clk = nullptr;
     k.n_frames = n_frames; k.n_iter = 1; k.mode = 1;
-    return launch(ctx, k, stream);
+    return launch(ctx, k, stream, DP_KERNEL_W4, sk != nullptr);
+}
+
+extern "C" int dp_forward(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_result* out, void* stream)
+{
+    return forward_impl(ctx, n_frames, z, cur_rot, nullptr, out, stream, "dp_forward");
 }
 
 // host-only, exported for the CPU tests: a context with no device and no device memory -- argument checks run on it, every launch is
@@ -1111,11 +1179,12 @@ extern "C" int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_param
 
 // ------------------------------------------------------------------------------------------------
 // n_steps frames of S sequences in one launch (+ one for the history buffers), see include/dragposer.h
-extern "C" int dp_optimize_sequence(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_seq_state* st,
-                                    const dp_seq_step* adj, const dp_seq_results* out, void* stream)
+static int sequence_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
+                         const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out, void* stream)
 {
     if (!ctx) return DP_ERR_INVALID;
 #ifdef DP_REF8_BUILD
+    (void)n_seq; (void)latent; (void)fr; (void)p_in; (void)sk; (void)st; (void)adj; (void)out; (void)stream;
     return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize_sequence: not part of the test-only library");
 #else
     if (n_seq <= 0 || !latent || !fr || !p_in || !st || !out) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: bad arguments");
@@ -1147,8 +1216,18 @@ extern "C" int dp_optimize_sequence(dp_ctx* ctx, int n_seq, float* latent, const
     if (!(p->lr > 0.f) || !(p->beta1 >= 0.f && p->beta1 < 1.f) || !(p->beta2 >= 0.f && p->beta2 < 1.f))
         return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: bad Adam hyper-parameters");
     if (!(p->eps > 0.f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: Adam eps must be > 0 (include/dragposer.h: dp_params.eps)");
+    const float* sk_off = nullptr;
+    int sk_stride = 0;
+    if (sk) {
+        if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, "dp_optimize_sequence_skeleton")) return rc;
+        if (p->kernel == DP_KERNEL_W16)
+            return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize_sequence_skeleton: DP_KERNEL_W16 keeps the bone offsets in per-slot constants; per-frame "
+                                                 "skeletons run on DP_KERNEL_W4 (DP_KERNEL_AUTO takes it)");
+        if (!ctx->d_w4img) return fail(ctx, DP_ERR_DEVICE, "dp_optimize_sequence_skeleton: the context has no device image");
+    }
     KArgs k;
     fill_model_args(ctx, k);
+    k.skel = sk_off; k.skel_stride = sk_stride;
     k.z0 = latent; k.z_tgt = fr->z_tgt; k.cur_rot = st->global_rot; k.tgt_pos = fr->tgt_pos; k.tgt_rot = fr->tgt_rot; k.w = fr->w; k.tracked = fr->tracked;
     k.z = latent; k.pose = out->pose_ret; k.world_rot = out->world_rot; k.iters = out->iters; k.loss = out->loss; k.status = out->status;
     k.n_frames = n_seq; k.n_iter = p->n_iter; k.mode = 0;
@@ -1167,7 +1246,7 @@ extern "C" int dp_optimize_sequence(dp_ctx* ctx, int n_seq, float* latent, const
     q.adjust_target_joint = adj ? adj->adjust_target_joint : -1;
     q.adjust_weight = adj ? adj->adjust_weight : 0.f;
     for (int c = 0; c < 4; ++c) { q.mean_q0[c] = ctx->mean_q0[c]; q.std_q0[c] = ctx->std_q0[c]; }
-    int rc = launch(ctx, k, stream, DP_KERNEL_W4);
+    int rc = launch(ctx, k, stream, DP_KERNEL_W4, sk != nullptr);
     if (rc != DP_OK) return rc;
     DEVICE_GUARD(ctx);
     HistArgs h;
@@ -1177,6 +1256,49 @@ extern "C" int dp_optimize_sequence(dp_ctx* ctx, int n_seq, float* latent, const
     if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("history launch: ") + hipGetErrorString(e));
     return DP_OK;
 #endif
+}
+
+extern "C" int dp_optimize_sequence(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_seq_state* st,
+                                    const dp_seq_step* adj, const dp_seq_results* out, void* stream)
+{
+    return sequence_impl(ctx, n_seq, latent, fr, p_in, nullptr, st, adj, out, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// include/dragposer_skeleton.h: the three calls above with per-frame (per-sequence) bone offsets, on the dp_w4sk units
+extern "C" int dp_optimize_skeleton(dp_ctx* ctx, const dp_batch* in, const dp_params* p, const dp_skeleton_in* skel, const dp_result* out, void* stream)
+{
+    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_optimize_skeleton: ctx is NULL");
+    try {
+        if (!skel) return fail(ctx, DP_ERR_INVALID, "dp_optimize_skeleton: the skeleton is NULL");
+        return optimize_impl(ctx, in, p, out, nullptr, stream, skel, "dp_optimize_skeleton");
+    } catch (...) {
+        return fail(ctx, DP_ERR_INVALID, "dp_optimize_skeleton: host-side failure");
+    }
+}
+
+extern "C" int dp_forward_skeleton(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* skel, const dp_result* out,
+                                   void* stream)
+{
+    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_forward_skeleton: ctx is NULL");
+    try {
+        if (!skel) return fail(ctx, DP_ERR_INVALID, "dp_forward_skeleton: the skeleton is NULL");
+        return forward_impl(ctx, n_frames, z, cur_rot, skel, out, stream, "dp_forward_skeleton");
+    } catch (...) {
+        return fail(ctx, DP_ERR_INVALID, "dp_forward_skeleton: host-side failure");
+    }
+}
+
+extern "C" int dp_optimize_sequence_skeleton(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p, const dp_skeleton_in* skel,
+                                             const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out, void* stream)
+{
+    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_optimize_sequence_skeleton: ctx is NULL");
+    try {
+        if (!skel) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_skeleton: the skeleton is NULL");
+        return sequence_impl(ctx, n_seq, latent, fr, p, skel, st, adj, out, stream);
+    } catch (...) {
+        return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_skeleton: host-side failure");
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -67,10 +67,13 @@ struct KArgs {
     unsigned smask[dpl::NWAVE][dpl::NGEMM]; // bit i: step i of the wave's chain has a non-zero weight block
     AdamTab tab;
     AdamCont cont;
+    // per-frame skeletons (include/dragposer_skeleton.h; read by the dp_w4sk units only, appended so that nothing above moves)
+    const float* skel; // [N][22][3] bone offsets, row `frame * skel_stride` (SEQ: sequence) of frame / sequence `frame`
+    int skel_stride;   // 66: one skeleton per frame (sequence), 0: one for the launch
 };
 
 // Which template instantiation a launch ran (dp_debug_last_launch, for the tests): each launcher fills it at the branch that launches.
-enum { DP_UNIT_NONE = 0, DP_UNIT_W4 = 1, DP_UNIT_W4_BP = 2, DP_UNIT_W16 = 3 };
+enum { DP_UNIT_NONE = 0, DP_UNIT_W4 = 1, DP_UNIT_W4_BP = 2, DP_UNIT_W16 = 3, DP_UNIT_W4_SKEL = 4, DP_UNIT_W4_BP_SKEL = 5 };
 struct LaunchPick {
     int unit;  // DP_UNIT_*
     int waves; // per workgroup
@@ -86,6 +89,9 @@ extern "C" int dp_kernel_lds_bytes(void);
 // dp_w4.hip: wave-private kernel, 4 frames per wave, no workgroup barrier inside the loop
 extern "C" hipError_t dp_launch_w4(const KArgs* args, hipStream_t stream, LaunchPick* pick /* nullable */);
 extern "C" hipError_t dp_launch_w4_bp(const KArgs* args, hipStream_t stream, LaunchPick* pick); // body-part layout (dp_w4_bp.hip)
+// dp_w4_skel.hip / dp_w4_bp_skel.hip: the same two layouts with the bone offsets read per frame from KArgs::skel (dp_w4_impl.h: W4_SKEL)
+extern "C" hipError_t dp_launch_w4sk(const KArgs* args, hipStream_t stream, LaunchPick* pick);
+extern "C" hipError_t dp_launch_w4sk_bp(const KArgs* args, hipStream_t stream, LaunchPick* pick);
 extern "C" int dp_w4_lds_bytes(void);
 extern "C" int dp_w4_frames_per_block(void);
 // dp_w16*.hip: 16 frames per wave, decoder on v_mfma_f32_16x16x32_bf16 in split precision (fixed iteration count, or KArgs.early_stop: the per-frame while-condition)

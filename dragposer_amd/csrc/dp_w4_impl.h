@@ -26,9 +26,15 @@
 // The kernel body, included by one translation unit per row layout of layer 2 (dp_w4.h): dp_w4.hip (W4_BP 0, "dense": every quad's
 // two items in both 64-row blocks) and dp_w4_bp.hip (W4_BP 1, "body-part": block A = the side-A items, block B = the side-B items,
 // each product running only the K-groups its own items touch).  W4_KERNEL names the kernel of the unit.
+// W4_SKEL 1 (dp_w4_skel.hip, dp_w4_bp_skel.hip): the bone offsets come per frame (SEQ: per sequence) from KArgs::skel instead of the
+// context's constants (include/dragposer_skeleton.h) -- they enter the set-up only: the child bones of the quad's two items (PairC::off)
+// and the root's children (init_off); the iteration loop is the same.
 #pragma once
 #ifndef W4_BP
 #define W4_BP 0
+#endif
+#ifndef W4_SKEL
+#define W4_SKEL 0
 #endif
 #ifndef W4_KERNEL
 #define W4_KERNEL dp_w4_kernel
@@ -1001,6 +1007,29 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
     const int Emax = max(max(__builtin_amdgcn_readlane(E, 0), __builtin_amdgcn_readlane(E, 1)),
                          max(__builtin_amdgcn_readlane(E, 2), __builtin_amdgcn_readlane(E, 3)));
     TRaw raw = tracker_fetch(a, optimise, gfi, tmask, E, b);
+#if W4_SKEL
+    // my frame's skeleton row (SEQ: my sequence's, for every step): the rule of pairs_w4 / dp_debug_items -- a bone slot below NJ is the row of
+    // that child joint, any other slot (idle, root, displacement, leaf: a trash slot) carries zero.  Row 0 (the root) is never read.
+    // (they replace the context's values outright -- pc.off, init_off -- so that the set-up holds no more registers than the plain unit's)
+    // (one unconditional 12-byte load per row, clamped into the skeleton, the zeros selected after: no masked loads to keep addresses for)
+    // (the row's offset is opaque: what it is computed from is not to be shared with -- and kept alive for -- the epilogue's addresses)
+    struct Row3 { float x, y, z; };
+    size_t sk_row = (size_t)gfi * a.skel_stride; // (64-bit, as the other per-frame loads: beyond 2^31 / 66 frames a 32-bit product wraps)
+    asm volatile("" : "+v"(sk_row));
+    const Row3* skr = (const Row3*)(a.skel + sk_row);
+    const Row3 ra = skr[min(slotA, NJ - 1)], rb = skr[min(slotB, NJ - 1)], ri = skr[min(init_id, NJ - 1)];
+    const bool ha = slotA < NJ, hb = slotB < NJ, hi = b < MAX_ROOT_CH && init_id < NJ;
+    // screened here, per lane (the frame's 21 bones are every lane's child bones and root children together: the frame is refused in the
+    // input screening below); a refused row is replaced by zero on the spot -- a neutral stand-in that keeps the frame's arithmetic finite
+    const bool sk_bad = (ha && (out_of_range(ra.x) || out_of_range(ra.y) || out_of_range(ra.z))) ||
+                        (hb && (out_of_range(rb.x) || out_of_range(rb.y) || out_of_range(rb.z))) ||
+                        (hi && (out_of_range(ri.x) || out_of_range(ri.y) || out_of_range(ri.z)));
+    const bool ua = ha && !sk_bad, ub = hb && !sk_bad, ui = hi && !sk_bad;
+    pc.off[0] = f2{ua ? ra.x : 0.f, ub ? rb.x : 0.f};
+    pc.off[1] = f2{ua ? ra.y : 0.f, ub ? rb.y : 0.f};
+    pc.off[2] = f2{ua ? ra.z : 0.f, ub ? rb.z : 0.f};
+    const f4 sk_init = ui ? f4{ri.x, ri.y, ri.z, 0.f} : f4{0.f, 0.f, 0.f, 0.f};
+#endif
     SETUP_STAMP(0);
     __builtin_amdgcn_sched_barrier(0);
 
@@ -1045,7 +1074,12 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
                 nr = nr || (rx.act && not_rotation(rx.m));
             }
         not_rot = frames_of(__ballot(nr && !tb)); // (a non-finite target is DP_STATUS_BAD_TARGETS, not this)
+#if W4_SKEL
+        // (every row 1..21 is some lane's child bone or root child: the frame's 21 bones are screened by its 16 lanes together)
+        const bool cb = out_of_range(cv.x) || out_of_range(cv.y) || out_of_range(cv.z) || out_of_range(cv.w) || sk_bad;
+#else
         const bool cb = out_of_range(cv.x) || out_of_range(cv.y) || out_of_range(cv.z) || out_of_range(cv.w);
+#endif
         bad_tgt = frames_of(__ballot(tb));
         bad_state = frames_of(__ballot(cb));
 #pragma unroll
@@ -1120,7 +1154,11 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
         }
     }
     if (b == 0) *(f4*)(fb + FB_QS + 4 * QS_IDENT) = f4{1.f, 0.f, 0.f, 0.f};
+#if W4_SKEL
+    if (b < MAX_ROOT_CH) *(f4*)(fb + FB_BN + 4 * init_id) = sk_init;
+#else
     if (b < MAX_ROOT_CH) *(f4*)(fb + FB_BN + 4 * init_id) = init_off;
+#endif
     SETUP_STAMP(1);
 
     f4 zfinD = zD;               // early stop: latent after a frame's last step
@@ -1663,7 +1701,7 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
 template <int NW, bool EARLY, bool SEQ = false, bool LONG = false>
 static void w4_launch(const KArgs* args, hipStream_t stream, LaunchPick* pick)
 {
-    set_pick(pick, W4_BP ? DP_UNIT_W4_BP : DP_UNIT_W4, NW, EARLY, SEQ, LONG);
+    set_pick(pick, W4_SKEL ? (W4_BP ? DP_UNIT_W4_BP_SKEL : DP_UNIT_W4_SKEL) : W4_BP ? DP_UNIT_W4_BP : DP_UNIT_W4, NW, EARLY, SEQ, LONG);
     const int grid = (args->n_frames + NW * FPW - 1) / (NW * FPW);
     hipLaunchKernelGGL((W4_KERNEL<NW, EARLY, SEQ, LONG>), dim3(grid), dim3(NW * 64), 0, stream, *args);
 }

@@ -26,7 +26,8 @@ from .temporal import HISTORY, PAST_FRAMES, SAMPLE_STEP
 def arrays_from_generator_model(generator_model, offsets):
     """The reference's Generator_Model (generator_architecture.py: `.autoencoder`, `.data`, `.parents`) -> the array dict
     dragposer_amd.model.HostModel / PoseEncoder read (same keys as data/model_dancedb.npz).  `offsets` [22,3] is the
-    skeleton's OFFSET table: the reference hands it to every run() (drag_pose.py:201), the kernel context wants it once."""
+    skeleton's OFFSET table: the reference hands it to every run() (drag_pose.py:201); the context is created with it, and run(offsets=...)
+    may still pass another performer's on any call."""
     sd = generator_model.autoencoder.state_dict()
     arrs = {k: v.detach().cpu().numpy() for k, v in sd.items()}
     d = generator_model.data
@@ -94,7 +95,7 @@ class DragPose:
         self._trk_cache = {}
         self._out = [None, None]
         self._flip = 0
-        self._offsets_checked = False
+        self._skel_obj, self._skel_dev = None, None  # the last `offsets` object run() / run_frames() was given, and what it decided (_skeleton)
 
     def _index(self, values):
         """device index tensor for a Python list, created once (no host->device copy inside a captured step)"""
@@ -102,6 +103,26 @@ class DragPose:
         if key not in self._idx_cache:
             self._idx_cache[key] = torch.tensor(key, dtype=torch.int64, device=self.device)
         return self._idx_cache[key]
+
+    def _skeleton(self, offsets):
+        """run()'s / run_frames()'s `offsets` ([22,3] for every sequence, or [S,22,3]) -> None when they are the context's skeleton (rows
+        1..21 within 1e-6: the plain launches, unchanged) or the fp32 device copy the skeleton launches read (include/dragposer_skeleton.h).
+        Decided once per distinct object -- one host synchronisation then, none on the frames that pass the same object again; the object's
+        contents are read at that point."""
+        if offsets is None:
+            return None
+        if offsets is self._skel_obj:
+            return self._skel_dev
+        t = torch.as_tensor(offsets, dtype=torch.float32).to(self.device)
+        if t.dim() == 2 and tuple(t.shape) == (NJ, 3):
+            pass
+        elif t.dim() == 3 and tuple(t.shape) == (self.S, NJ, 3):
+            pass
+        else:
+            raise ValueError(f"offsets: expected [22,3] or [{self.S},22,3] bone offsets, got {tuple(t.shape)}")
+        same = bool(torch.isclose(t[..., 1:, :], self.offsets[1:].expand_as(t[..., 1:, :]), atol=1e-6).all())  # (row 0 is ignored, as in dp_model)
+        self._skel_obj, self._skel_dev = offsets, (None if same else t.contiguous().clone())
+        return self._skel_dev
 
     # ------------------------------------------------------------------ state (drag_pose.py:47-64)
     def set_initial_pose(self, initial_pose, init_global_pos, initial_global_rot, initial_heights, eps=None, generator=None):
@@ -205,13 +226,15 @@ class DragPose:
 
     def run_frames(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, target_root=None, stop_eps_pos=1e-2, stop_eps_rot=1e-2,
                    max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1, temporal_future_window=60,
-                   height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01):
+                   height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01, offsets=None):
         """T consecutive frames of every sequence -- T calls of run() -- with the frame loop on the device: one kernel launch per
         stretch of frames between two temporal predictions (all T of them when there is no predictor or lambda_temporal is 0).
         target_ee_pos [T,S,E,3], target_ee_rot [T,S,E,3,3]; `target_root` [T,S,3] or None: given, the position targets of frame t
         are target_ee_pos[t] + (target_root[t] - current_global_pos) as eval_drag builds them (eval_drag.py:186-199), which no
-        caller can do ahead of time.  Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
+        caller can do ahead of time.  `offsets`: the performers' bone offsets as in run() -- [22,3] or [S,22,3], kept for all T frames.
+        Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
         dev, S = self.device, self.S
+        skel = self._skeleton(offsets)
         tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=dev)
         T = int(tp.shape[0])
         tp = tp.reshape(T, S, -1, 3)
@@ -253,7 +276,7 @@ class DragPose:
                                        self.latent_buffer, self.displacement_buffer, self.heights_buffer, tuple(int(h) for h in height_indices),
                                        n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_temporal) if pull else 0.0,
                                        stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, adjust=adjust,
-                                       pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n])
+                                       pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n], offsets=skel)
             t += n
             self.current_index = 0 if window == 0 else (self.current_index + n) % window
         self.last_status = status  # [T,S] DP_STATUS_* bits (include/dragposer.h): non-zero where a frame's inputs were not finite
@@ -269,9 +292,18 @@ class DragPose:
         is then dp_optimize_constrained followed by dp_sequence_advance (two launches), with this frame's current_global_pos as the
         floor term's global position; None runs the path above unchanged.  `terms` (a dragposer_amd.Terms): a table of user-defined
         terms instead, the same two launches with dp_optimize_terms (a term's per-frame rows: its [S,4] `per_frame` tensor, read at
-        this call); not together with `constraints`."""
+        this call); not together with `constraints`.
+        `offsets`: the performer's bone offsets, as the reference takes them on every call (drag_pose.py:202) -- [22,3] for every sequence
+        or [S,22,3] one per sequence.  The context's own skeleton (or None) runs the launches above unchanged; any other runs the same frame
+        with those bones (dp_optimize_sequence_skeleton, include/dragposer_skeleton.h), not together with `constraints` / `terms`.  Passing
+        the same object frame after frame costs one host synchronisation in all (DragPose._skeleton)."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
+        skel = self._skeleton(offsets)
+        if skel is not None and (constraints is not None or terms is not None):
+            raise ValueError("DragPose.run: offsets other than the context's skeleton cannot be combined with " +
+                             ("constraints=" if constraints is not None else "terms=") + ": dp_optimize_constrained / dp_optimize_terms have no "
+                             "per-frame-skeleton form (include/dragposer_skeleton.h); create the DragPose from this skeleton instead")
         dev, S = self.device, self.S
         squeeze = torch.as_tensor(target_ee_pos).dim() == 2
         tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=dev).reshape(S, -1, 3)
@@ -280,10 +312,6 @@ class DragPose:
         E = trk["mj"].numel()
         if tp.shape[1] != E or tR.shape[1] != E:
             raise ValueError("target_ee_pos / target_ee_rot / weights_joints must have one row per entry of mask_joints")
-        if offsets is not None and not self._offsets_checked:
-            if not torch.allclose(torch.as_tensor(offsets, dtype=torch.float32, device=dev).reshape(NJ, 3), self.offsets, atol=1e-6):
-                raise ValueError("offsets differ from the skeleton the optimiser context was created with")
-            self._offsets_checked = True  # (a device->host round trip: once, not per frame)
 
         self._temporal_targets(temporal_future_window)
         trk["tgt_pos"].index_copy_(1, trk["mj"], tp)
@@ -316,7 +344,7 @@ class DragPose:
                                    n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_temporal) if pull else 0.0,
                                    stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, adjust=adjust,
                                    pose_ret=pose.unsqueeze(0), pos_ret=gpos.unsqueeze(0), iters=o["iters"], loss=o["loss"], scratch=o["scratch"],
-                                   status=o["status"])
+                                   status=o["status"], offsets=skel)
         o["z"].copy_(self.latent)  # (self.latent is advanced in place by the next frame; `last` must not move with it)
         self.last = dict(iters=o["iters"][0], loss=o["loss"][0], z=o["z"], pose=pose, pos=gpos, status=o["status"][0])
         if verbose:

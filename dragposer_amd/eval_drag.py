@@ -84,8 +84,10 @@ def prepare_file(args, input_path, opt, encoder, cfg, raw):
     stds = {"dqs": raw["stds.dqs"], "displacement": raw["stds.displacement"]}
     bvh = BVH().load(input_path)
     m = prepare_motion(bvh, means, stds, HEIGHT_INDICES)
-    if not np.allclose(m["offsets"], opt.host_model.arrays["offsets"], atol=1e-5) or list(m["parents"]) != list(opt.host_model.parents):
-        raise SystemExit(f"{input_path}: skeleton differs from the one the model fixture was exported with")
+    if list(m["parents"]) != list(opt.host_model.parents):
+        raise SystemExit(f"{input_path}: skeleton topology differs from the one the model fixture was exported with")
+    # (other bone lengths are the clip's own: they drive its targets below and, as the reference's run(offsets=...), the optimisation --
+    #  DragPose.run_frames / run(offsets=...), include/dragposer_skeleton.h)
     n_frames = len(m["dqs"]) if args.max_frames is None else min(args.max_frames, len(m["dqs"]))
     mask_idx = np.nonzero(np.asarray(cfg["mask"]))[0]
     # targets (eval_drag.py:164-202): FK of the ground-truth pose with the root at the origin, per frame; the
@@ -99,6 +101,7 @@ def prepare_file(args, input_path, opt, encoder, cfg, raw):
         gen = torch.Generator(device="cpu").manual_seed(2222)  # train.param["seed"]
         z0 = encoder.sample(torch.tensor(m["dqs"][0:1], device=dev), generator=gen)  # drag_pose.py:50
     return dict(path=input_path, bvh=bvh, m=m, n_frames=n_frames, means=means, stds=stds, z0=z0,
+                offsets=torch.tensor(np.asarray(m["offsets"], np.float32).reshape(NJ, 3), device=dev),
                 tp_rel=torch.tensor(p_rel, dtype=torch.float32, device=dev), tR=torch.tensor(r_mats, dtype=torch.float32, device=dev),
                 gpos=torch.tensor(m["global_pos"][:n_frames], dtype=torch.float32, device=dev))
 
@@ -118,6 +121,7 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
     tp_rel = torch.stack([pad(q["tp_rel"]) for q in seqs], dim=1).contiguous()  # [T, S, E, 3]
     tR = torch.stack([pad(q["tR"]) for q in seqs], dim=1).contiguous()
     gpos = torch.stack([pad(q["gpos"]) for q in seqs], dim=1).contiguous()      # [T, S, 3]
+    offsets = torch.stack([q["offsets"] for q in seqs]).contiguous()             # [S, 22, 3]: each clip's own skeleton (eval_drag.py:48,135,209)
 
     drag = DragPose(opt, temporal, means_latent, stds_latent, n_sequences=S, native_temporal=not getattr(args, "torch_temporal", False))
     drag.set_initial_state(torch.cat([q["z0"] for q in seqs], dim=0), np.stack([q["m"]["global_pos"][0] for q in seqs]),
@@ -134,12 +138,12 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
         poses, out_pos, iters = drag.run_frames(tp_rel, tR.reshape(T, S, -1, 3, 3), mask_idx, weights, target_root=gpos, stop_eps_pos=0.01 * 0.01,
                                                 stop_eps_rot=0.01, max_iter=args.max_iter, min_loss_incr=0.00001, learning_rate=1e-2, lambda_rot=1,
                                                 lambda_temporal=lam_tmp, temporal_future_window=window, height_indices=HEIGHT_INDICES,
-                                                joint_adjustment_indices=ja, joint_adjustment_weight=cfg["joint_adjustment_weight"])
+                                                joint_adjustment_indices=ja, joint_adjustment_weight=cfg["joint_adjustment_weight"], offsets=offsets)
     for i in range(T if getattr(args, "per_frame", False) else 0):
         if i % 1000 == 0:
             print(f"Frame: {i + 1} out of {T}", flush=True)
         tp = tp_rel[i] + (gpos[i] - drag.current_global_pos).unsqueeze(1)  # eval_drag.py:186-199
-        drag.run(tp, tR[i], mask_idx, weights, stop_eps_pos=0.01 * 0.01, stop_eps_rot=0.01, max_iter=args.max_iter,
+        drag.run(tp, tR[i], mask_idx, weights, offsets=offsets, stop_eps_pos=0.01 * 0.01, stop_eps_rot=0.01, max_iter=args.max_iter,
                  min_loss_incr=0.00001, learning_rate=1e-2, lambda_rot=1, lambda_temporal=lam_tmp,
                  temporal_future_window=window, height_indices=HEIGHT_INDICES, joint_adjustment_indices=ja,
                  joint_adjustment_weight=cfg["joint_adjustment_weight"], verbose=args.verbose, out_pose=poses[i], out_pos=out_pos[i])

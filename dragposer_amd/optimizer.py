@@ -55,17 +55,25 @@ class LaunchPlan:
     """A dp_optimize call with its arguments already checked and marshalled (LatentOptimizer.plan).  Holds the input and result
     tensors alive; `plan()` launches on torch's current stream of the optimiser's device and returns the result tensors."""
 
-    __slots__ = ("_opt", "_b", "_p", "_r", "results", "_inputs", "_fn", "_dev")
+    __slots__ = ("_opt", "_b", "_p", "_r", "results", "_inputs", "_fn", "_dev", "_s")
 
-    def __init__(self, opt, batch, params, res, tensors, inputs):
+    def __init__(self, opt, batch, params, res, tensors, inputs, skel=None):
         self._opt, self.results, self._inputs = opt, tensors, inputs
         self._b, self._p, self._r = C.byref(batch), C.byref(params), C.byref(res)  # (byref objects keep their structs alive)
         self._fn, self._dev = opt.lib.dp_optimize, opt.device
+        self._s = None
+        if skel is not None:  # per-frame skeletons (include/dragposer_skeleton.h)
+            self._s, self._fn = C.byref(skel), opt.lib.dp_optimize_skeleton
 
     def __call__(self):
         ctx = self._opt.ctx  # (read per call: after LatentOptimizer.close() it is NULL and the library refuses, instead of a freed context being used)
         if not ctx.value:
             raise _lib.DragPoserError(_lib.DP_ERR_INVALID, "LaunchPlan: the optimiser it was made by has been closed")
+        if self._s is not None:
+            rc = self._fn(ctx, self._b, self._p, self._s, self._r, torch.cuda.current_stream(self._dev).cuda_stream)
+            if rc != _lib.DP_OK:
+                self._opt._fail(rc)
+            return self.results
         rc = self._fn(ctx, self._b, self._p, self._r, torch.cuda.current_stream(self._dev).cuda_stream)
         if rc != _lib.DP_OK:
             self._opt._fail(rc)
@@ -140,9 +148,25 @@ class LatentOptimizer:
             tensors[name] = t
         return res, tensors
 
+    def _skeleton(self, offsets, n, who):
+        """`offsets` -> (dp_skeleton_in, the tensor it points to): [22,3] = one skeleton for the launch (stride 0), [n,22,3] = one per frame
+        (per sequence in a sequence launch; stride 66); contiguous fp32 on the optimiser's device (include/dragposer_skeleton.h)"""
+        if not isinstance(offsets, torch.Tensor):
+            raise TypeError(f"{who}: offsets must be a torch.Tensor on {self.device}, [22,3] or [{n},22,3]")
+        if offsets.dim() == 2:
+            shape, stride = (NJ, 3), 0
+        elif offsets.dim() == 3:
+            shape, stride = (n, NJ, 3), _lib.DP_SKELETON_STRIDE
+        else:
+            raise ValueError(f"{who}: offsets must be [22,3] (one skeleton) or [{n},22,3] (one per frame / sequence), got {tuple(offsets.shape)}")
+        s = _lib.DpSkeletonIn()
+        s.offsets = _check(offsets, "offsets", shape, torch.float32, self.device)
+        s.stride = stride
+        return s
+
     def optimize(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, n_iter=50, lr=1e-2, betas=(0.9, 0.999),
                  eps=1e-8, lambda_rot=1.0, lambda_tmp=0.02, stop_eps_pos=0.0, stop_eps_rot=0.0, min_loss_incr=None,
-                 max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto", _debug=None):
+                 max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto", _debug=None, offsets=None):
         """All inputs are device tensors: z0/z_tgt [B,24], cur_rot [B,4], tgt_pos [B,22,3],
         tgt_rot [B,22,9], w [B,22,2] (fp32) and tracked [B,22] (uint8).  Returns a dict of device
         tensors (see include/dragposer.h: dp_result).  Asynchronous on torch's current stream.
@@ -153,10 +177,15 @@ class LatentOptimizer:
         precision; what "auto" picks beyond 8192 frames: two rounds of "w4") -- include/dragposer.h: DP_KERNEL_*.
         `validate_targets`: check that every tracked joint's tgt_rot is a rotation matrix (the kernel evaluates the
         reference's |R - T|^2 in its quaternion form, equal only for orthonormal det +1 targets: include/dragposer.h) --
-        costs a device reduction and a host synchronisation, so it is off by default."""
+        costs a device reduction and a host synchronisation, so it is off by default.
+        `offsets`: the performers' bone offsets, [22,3] for every frame or [B,22,3] one per frame (contiguous fp32 on the device; row 0
+        ignored): dp_optimize_skeleton (include/dragposer_skeleton.h), on the "w4" kernel at every batch size; None = the context's skeleton
+        (dp_optimize, unchanged)."""
         plan = self.plan(z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos,
-                         stop_eps_rot, min_loss_incr, max_trackers, outputs, out, validate_targets, kernel)
+                         stop_eps_rot, min_loss_incr, max_trackers, outputs, out, validate_targets, kernel, offsets=offsets)
         if _debug is not None:
+            if offsets is not None:
+                raise ValueError("optimize: the debug dump has no per-frame-skeleton form (offsets)")
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             rc = self.lib.dp_optimize_debug(self.ctx, plan._b, plan._p, plan._r, C.c_void_p(_debug.data_ptr()), stream)
             if rc != _lib.DP_OK:
@@ -166,12 +195,19 @@ class LatentOptimizer:
 
     def plan(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, n_iter=50, lr=1e-2, betas=(0.9, 0.999),
              eps=1e-8, lambda_rot=1.0, lambda_tmp=0.02, stop_eps_pos=0.0, stop_eps_rot=0.0, min_loss_incr=None,
-             max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto"):
-        """`optimize`'s arguments checked and marshalled ONCE: returns a LaunchPlan whose call launches dp_optimize over the same
+             max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto", offsets=None):
+        """`optimize`'s arguments checked and marshalled ONCE: returns a LaunchPlan whose call launches dp_optimize (dp_optimize_skeleton with
+        `offsets`, as in `optimize`) over the same
         tensors (read at launch time: refill them in place between calls) into the same result tensors, on torch's current stream --
         a caller that steps the same buffers every frame pays one ctypes call per launch instead of the checks and struct filling."""
         B = int(z0.shape[0])
         dev = self.device
+        skel = None
+        if offsets is not None:
+            if kernel == "w16":
+                raise ValueError('optimize: kernel="w16" has no per-frame skeletons (its slot map keeps the bone offsets in per-slot constants); '
+                                 'use "w4" or "auto" with offsets')
+            skel = self._skeleton(offsets, B, "optimize")
         if validate_targets:
             check_rotation_targets(tgt_rot, tracked)
         batch = _lib.DpBatch()
@@ -191,15 +227,24 @@ class LatentOptimizer:
                           kernel={"auto": _lib.DP_KERNEL_AUTO, "w4": _lib.DP_KERNEL_W4, "w16": _lib.DP_KERNEL_W16}[kernel])
         names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS)
         res, tensors = self._outputs(B, names, out)
+        if skel is not None:
+            return LaunchPlan(self, batch, p, res, tensors, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, offsets), skel=skel)
         return LaunchPlan(self, batch, p, res, tensors, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked))
 
-    def forward(self, z, cur_rot, outputs=("pose", "disp", "world_disp", "world_rot", "pos", "rot"), out=None):
-        """decode + FK of z [B,24] under cur_rot [B,4] (no loss, no update)."""
+    def forward(self, z, cur_rot, outputs=("pose", "disp", "world_disp", "world_rot", "pos", "rot"), out=None, offsets=None):
+        """decode + FK of z [B,24] under cur_rot [B,4] (no loss, no update).  `offsets` [22,3] / [B,22,3]: per-frame skeletons as in
+        `optimize` (dp_forward_skeleton)."""
         B = int(z.shape[0])
+        skel = self._skeleton(offsets, B, "forward") if offsets is not None else None
         zp = _check(z, "z", (B, LATENT), torch.float32, self.device)
         cp = _check(cur_rot, "cur_rot", (B, 4), torch.float32, self.device)
         res, tensors = self._outputs(B, tuple(outputs), out)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if skel is not None:
+            rc = self.lib.dp_forward_skeleton(self.ctx, B, C.c_void_p(zp), C.c_void_p(cp), C.byref(skel), C.byref(res), stream)
+            if rc != _lib.DP_OK:
+                self._fail(rc)
+            return tensors
         rc = self.lib.dp_forward(self.ctx, B, C.c_void_p(zp), C.c_void_p(cp), C.byref(res), stream)
         if rc != _lib.DP_OK:
             self._fail(rc)
@@ -357,15 +402,18 @@ class LatentOptimizer:
 def _optimize_sequence(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
                        heights_buf, height_joints, n_iter=100, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.0,
                        stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
-                       loss=None, scratch=None, status=None):
+                       loss=None, scratch=None, status=None, offsets=None):
     """T consecutive frames of S sequences in one launch (include/dragposer.h: dp_optimize_sequence): the optimise loop with the
     reference's while-condition and run()'s epilogue per frame, state carried on the device.  tgt_pos [T,S,22,3] / tgt_rot
     [T,S,22,9] dense per joint; tgt_root [T,S,3] or None (position targets are then tgt_pos + (tgt_root[t] - running global
     position), eval_drag.py:186-199); w [S,22,2], tracked [S,22]; z_tgt any fp32 device tensor addressed with `z_tgt_strides` =
     (floats between steps, floats between sequences).  `latent` [S,24], `global_pos`, `global_rot` and the three history
-    buffers are updated IN PLACE.  Returns dict(pose_ret [T,S,88], pos_ret [T,S,3], iters [T,S], loss [T,S,3], status [T,S]: DP_STATUS_* bits)."""
+    buffers are updated IN PLACE.  Returns dict(pose_ret [T,S,88], pos_ret [T,S,3], iters [T,S], loss [T,S,3], status [T,S]: DP_STATUS_* bits).
+    `offsets` [22,3] / [S,22,3]: one skeleton for every sequence / one per sequence, kept for every step (dp_optimize_sequence_skeleton,
+    include/dragposer_skeleton.h); None = the context's."""
     T, S = int(tgt_pos.shape[0]), int(tgt_pos.shape[1])
     dev = self.device
+    skel = self._skeleton(offsets, S, "optimize_sequence") if offsets is not None else None
     H, NH = int(latent_buf.shape[1]), len(height_joints)
     fr = _lib.DpSeqFrames()
     fr.n_steps = T
@@ -405,6 +453,12 @@ def _optimize_sequence(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_t
                       early_stop=1, stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
                       min_loss_incr=float("-inf") if min_loss_incr is None else min_loss_incr, max_trackers=0, kernel=_lib.DP_KERNEL_AUTO)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    if skel is not None:
+        rc = self.lib.dp_optimize_sequence_skeleton(self.ctx, S, C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev)), C.byref(fr),
+                                                    C.byref(p), C.byref(skel), C.byref(st), C.byref(step), C.byref(res), stream)
+        if rc != _lib.DP_OK:
+            self._fail(rc)
+        return outs
     rc = self.lib.dp_optimize_sequence(self.ctx, S, C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev)), C.byref(fr),
                                        C.byref(p), C.byref(st), C.byref(step), C.byref(res), stream)
     if rc != _lib.DP_OK:

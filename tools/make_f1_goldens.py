@@ -217,6 +217,14 @@ def main():
         "f1_clip4_t": (clip, "4_trackers_config.json", True, 1),   #   joint adjustment [0, 0] with weight 1, lambda 0.125, window 16)
         "f1_example": (full, "6_trackers_config.json", False, 8),
     }
+    if "f1_clip6_scaled" in todo:  # the clip of another performer: every OFFSET line x1.12 (plain text rewriting, tests/skeleton_cases.py)
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        from skeleton_cases import SCALED_CLIP_FACTOR, scaled_bvh_text
+
+        scaled = os.path.join(tempfile.mkdtemp(prefix="f1s_"), "example_clip_scaled.bvh")
+        with open(scaled, "w") as f:
+            f.write(scaled_bvh_text(open(clip).read(), SCALED_CLIP_FACTOR))
+        jobs["f1_clip6_scaled"] = (scaled, "6_trackers_config.json", False, 1)
     for name, (path, cfgname, ton, stride) in jobs.items():
         if name in todo:
             PERTURB["eps"] = 0.0

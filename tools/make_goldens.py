@@ -195,8 +195,18 @@ def draw_recipe(B, mixed):
     return Zs, Z0, ZT, CR, tracked
 
 
+def skeleton_set(offsets_t, n, seed=91):
+    """[n,22,3]: item k takes skeleton k % 4 -- the model's, a uniform x0.85, a uniform x1.2, per-bone length factors in [0.8, 1.25]
+    (seeded) -- the skeletons of the skel fixtures (include/dragposer_skeleton.h: the reference's run(offsets=...) on every call)"""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    per_bone = 0.8 + 0.45 * torch.rand(NJ, 1, generator=g)
+    four = torch.stack([offsets_t, offsets_t * 0.85, offsets_t * 1.2, offsets_t * per_bone]).to(offsets_t.dtype)
+    return four[torch.arange(n) % 4].contiguous()
+
+
 def run_recipe(name, B, track, cfg_weights, lam_tmp, n_iter, offsets_t, parents,
-               mixed=False, weight_rounding=None, early_stop=False):
+               mixed=False, weight_rounding=None, early_stop=False, offsets_frames=None):
+    """offsets_frames [B,22,3]: frame b's skeleton -- its targets are the FK of that skeleton and DragPose.run gets it as `offsets`"""
     gm, td, drag, stub = build_reference(parents, weight_rounding)
     Zs, Z0, ZT, CR, tracked = draw_recipe(B, mixed)
     out = dict(
@@ -215,7 +225,8 @@ def run_recipe(name, B, track, cfg_weights, lam_tmp, n_iter, offsets_t, parents,
         tr = tracked[b] if mixed else track
         idx = torch.tensor(tr, dtype=torch.int64)
         wj = cfg_weights[idx]
-        pos_t, rot_t, _, _ = forward_fk(drag, td, Zs[b], CR[b], offsets_t)
+        off_b = offsets_t if offsets_frames is None else offsets_frames[b]
+        pos_t, rot_t, _, _ = forward_fk(drag, td, Zs[b], CR[b], off_b)
         tp, tR = pos_t[idx].clone(), rot_t[idx].clone()
         out["w"][b, tr] = wj.numpy()
         out["tracked"][b, tr] = 1
@@ -239,7 +250,7 @@ def run_recipe(name, B, track, cfg_weights, lam_tmp, n_iter, offsets_t, parents,
             kw = dict(stop_eps_pos=0.0, stop_eps_rot=0.0, max_iter=n_iter, min_loss_incr=-float("inf"))
         pose_ret, gpos_ret = drag.run(
             target_ee_pos=tp, target_ee_rot=tR, mask_joints=idx, weights_joints=wj,
-            offsets=offsets_t, learning_rate=1e-2, lambda_rot=1, lambda_temporal=lam_tmp,
+            offsets=off_b, learning_rate=1e-2, lambda_rot=1, lambda_temporal=lam_tmp,
             temporal_future_window=0, height_indices=[0, 4, 8, 13, 17, 21],
             joint_adjustment_indices=None, joint_adjustment_weight=0.0, verbose=False, **kw
         )
@@ -267,6 +278,8 @@ def run_recipe(name, B, track, cfg_weights, lam_tmp, n_iter, offsets_t, parents,
                 stop_eps_pos=1e-4 if early_stop else 0.0, stop_eps_rot=1e-2 if early_stop else 0.0,
                 min_loss_incr=1e-5 if early_stop else None, torch=torch.__version__)
     out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
+    if offsets_frames is not None:
+        out["offsets"] = offsets_frames.numpy().astype(np.float32)
     return out
 
 
@@ -462,11 +475,12 @@ def anchors(parents, offsets_t):
 TEMPORAL_SMALL = dict(n_encoder_layers=1, n_decoder_layers=1, dim_feedforward=32)  # keeps the fixture small
 
 
-def run_sequences(name, K, T, cfg, offsets_t, parents, seed):
+def run_sequences(name, K, T, cfg, offsets_t, parents, seed, offsets_seq=None):
     """K sequences x T frames through the REAL DragPose.run with all its state (warm-started latent, global
     position / rotation, ring buffers, temporal target block, joint adjustment, early stop) -- SURVEY rows a11-a13.
     The temporal predictor is the reference's Temporal class with seeded random weights (temporal.pt is
-    missing from the mount) and a reduced width so that its state_dict fits a fixture."""
+    missing from the mount) and a reduced width so that its state_dict fits a fixture.  offsets_seq [K,22,3]: sequence k's skeleton (its
+    targets and every run() of it)."""
     import copy
 
     import train_temporal as ref_tt
@@ -497,6 +511,8 @@ def run_sequences(name, K, T, cfg, offsets_t, parents, seed):
         mask_idx=idx.numpy().astype(np.int32), weights=wj.numpy(), means_latent=means_latent.numpy(), stds_latent=stds_latent.numpy(),
     )
     for k in range(K):
+        if offsets_seq is not None:
+            offsets_t = offsets_seq[k]
         zgt = torch.randn(24, generator=g) * 0.3
         cr = torch.randn(4, generator=g)
         cr = cr / torch.linalg.norm(cr)
@@ -549,6 +565,8 @@ def run_sequences(name, K, T, cfg, offsets_t, parents, seed):
         out["temporal." + key] = v.numpy()
     meta = dict(name=name, K=K, T=T, cfg=cfg, temporal_param=TEMPORAL_SMALL, seed=seed, torch=torch.__version__)
     out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
+    if offsets_seq is not None:
+        out["offsets"] = offsets_seq.numpy().astype(np.float32)
     return out
 
 
@@ -589,6 +607,18 @@ def main():
             path = os.path.join(gold, f"{name}.npz")
             np.savez_compressed(path, **out)
             print("wrote", path, os.path.getsize(path), "bytes", flush=True)
+    # "skel" / "skel_es": s1 / es with the skeleton varying frame by frame (skeleton_set): four skeletons in every four frames
+    for name, kw in (("skel", jobs["s1"]), ("skel_es", jobs["es"])):
+        if name in todo:
+            out = run_recipe(name, B, offsets_t=offsets_t, parents=parents, offsets_frames=skeleton_set(offsets_t, B), **kw)
+            path = os.path.join(gold, f"{name}.npz")
+            np.savez_compressed(path, **out)
+            print("wrote", path, os.path.getsize(path), "bytes", flush=True)
+    if "seqskel" in todo:  # seq6's shape, four sequences of 40 frames, each with its own skeleton
+        out = run_sequences("seqskel", 4, 40, cfg6, offsets_t, parents, 83, offsets_seq=skeleton_set(offsets_t, 4))
+        path = os.path.join(gold, "seqskel.npz")
+        np.savez_compressed(path, **out)
+        print("wrote", path, os.path.getsize(path), "bytes", flush=True)
     for name in ("s1", "s3", "s4"):
         if name + "_f64" in todo:  # adds the reference's own float64 run to a committed fixture
             add_f64(name, gold, offsets, parents, args.workers)
