@@ -134,7 +134,7 @@ PUBLIC_SYMBOLS = (
 )
 
 # every symbol include/dragposer_grad.h declares (tests/test_grad_abi.py)
-GRAD_SYMBOLS = ("dp_forward_vjp",)
+GRAD_SYMBOLS = ("dp_forward_vjp", "dp_forward_vjp_skeleton")
 
 
 class DpGradIn(_Sized):
@@ -240,6 +240,8 @@ def load(path=None):
     lib.dp_forward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpResult), C.c_void_p]
     lib.dp_forward_vjp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpGradIn), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
+    lib.dp_forward_vjp_skeleton.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpSkeletonIn), C.POINTER(DpGradIn), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dp_optimize_constrained.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpConstraints), C.POINTER(DpResult),
                                             C.c_void_p]
     lib.dp_optimize_terms.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpTerms), C.POINTER(DpResult), C.c_void_p]

@@ -958,38 +958,63 @@ extern "C" int dp_debug_host_ctx(dp_ctx** out)
 // include/dragposer_grad.h.  dp_grad_in as the caller compiled it: first version = the six pointers, a later caller's struct is read
 // up to what this build knows
 constexpr unsigned GRAD_IN_SIZE_V510 = offsetof(dp_grad_in, rot) + sizeof(void*);
+// dp_forward_vjp (sk = NULL, dp_vjp.hip) and dp_forward_vjp_skeleton (dp_vjp_skel.hip; who names the caller in the messages)
+static int vjp_impl(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* sk, const dp_grad_in* g, float* dz,
+                    float* dcur_rot, float* doffsets, int* status, void* stream, const char* who)
+{
+    const std::string w = who;
+    if (n_frames <= 0) return fail(ctx, DP_ERR_INVALID, w + ": n_frames must be positive");
+    if (!z || !cur_rot || !g || !dz) return fail(ctx, DP_ERR_INVALID, w + ": NULL z, cur_rot, g or dz");
+    if (g->struct_size < GRAD_IN_SIZE_V510 || g->struct_size > 4096u || g->reserved0 != 0u)
+        return fail(ctx, DP_ERR_INVALID, w + ": dp_grad_in.struct_size is " + std::to_string(g->struct_size) + " (reserved0 " +
+                                             std::to_string(g->reserved0) + "), this library expects at least " + std::to_string(GRAD_IN_SIZE_V510) +
+                                             " and reserved0 = 0  (dp_grad_in g = DP_GRAD_IN_INIT;)");
+    dp_grad_in gv;
+    std::memset(&gv, 0, sizeof(gv));
+    std::memcpy(&gv, g, std::min<size_t>(g->struct_size, sizeof(gv)));
+    const float* sk_off = nullptr;
+    int sk_stride = 0;
+    if (sk)
+        if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
+#ifdef DP_REF8_BUILD
+    (void)dcur_rot; (void)doffsets; (void)status; (void)stream;
+    return fail(ctx, DP_ERR_UNSUPPORTED, w + ": not part of the test-only library");
+#else
+    if (!ctx->d_vjpimg) return fail(ctx, DP_ERR_DEVICE, w + ": the context has no device image");
+    DEVICE_GUARD(ctx);
+    dpvjp::SkelArgs a;
+    a.img = ctx->d_vjpimg;
+    a.z = z; a.cur_rot = cur_rot;
+    a.g_pose = gv.pose; a.g_disp = gv.disp; a.g_wdisp = gv.world_disp; a.g_wrot = gv.world_rot; a.g_pos = gv.pos; a.g_rot = gv.rot;
+    a.dz = dz; a.dcur = dcur_rot; a.status = status;
+    a.n_frames = n_frames;
+    a.skel = sk_off; a.skel_stride = sk_stride; a.doff = doffsets;
+    const hipError_t e = sk ? dp_launch_vjp_skel(&a, (hipStream_t)stream) : dp_launch_vjp(&a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(e));
+    return DP_OK;
+#endif
+}
+
 extern "C" int dp_forward_vjp(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_grad_in* g, float* dz, float* dcur_rot,
                               int* status, void* stream)
 {
     if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_forward_vjp: ctx is NULL");
     try {
-        if (n_frames <= 0) return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: n_frames must be positive");
-        if (!z || !cur_rot || !g || !dz) return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: NULL z, cur_rot, g or dz");
-        if (g->struct_size < GRAD_IN_SIZE_V510 || g->struct_size > 4096u || g->reserved0 != 0u)
-            return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: dp_grad_in.struct_size is " + std::to_string(g->struct_size) + " (reserved0 " +
-                                                 std::to_string(g->reserved0) + "), this library expects at least " + std::to_string(GRAD_IN_SIZE_V510) +
-                                                 " and reserved0 = 0  (dp_grad_in g = DP_GRAD_IN_INIT;)");
-        dp_grad_in gv;
-        std::memset(&gv, 0, sizeof(gv));
-        std::memcpy(&gv, g, std::min<size_t>(g->struct_size, sizeof(gv)));
-#ifdef DP_REF8_BUILD
-        (void)dcur_rot; (void)status; (void)stream;
-        return fail(ctx, DP_ERR_UNSUPPORTED, "dp_forward_vjp: not part of the test-only library");
-#else
-        if (!ctx->d_vjpimg) return fail(ctx, DP_ERR_DEVICE, "dp_forward_vjp: the context has no device image");
-        DEVICE_GUARD(ctx);
-        dpvjp::Args a;
-        a.img = ctx->d_vjpimg;
-        a.z = z; a.cur_rot = cur_rot;
-        a.g_pose = gv.pose; a.g_disp = gv.disp; a.g_wdisp = gv.world_disp; a.g_wrot = gv.world_rot; a.g_pos = gv.pos; a.g_rot = gv.rot;
-        a.dz = dz; a.dcur = dcur_rot; a.status = status;
-        a.n_frames = n_frames;
-        const hipError_t e = dp_launch_vjp(&a, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("dp_forward_vjp: kernel launch: ") + hipGetErrorString(e));
-        return DP_OK;
-#endif
+        return vjp_impl(ctx, n_frames, z, cur_rot, nullptr, g, dz, dcur_rot, nullptr, status, stream, "dp_forward_vjp");
     } catch (...) {
         return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: host-side failure");
+    }
+}
+
+extern "C" int dp_forward_vjp_skeleton(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* skel,
+                                       const dp_grad_in* g, float* dz, float* dcur_rot, float* doffsets, int* status, void* stream)
+{
+    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_forward_vjp_skeleton: ctx is NULL");
+    try {
+        if (!skel) return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp_skeleton: the skeleton is NULL");
+        return vjp_impl(ctx, n_frames, z, cur_rot, skel, g, dz, dcur_rot, doffsets, status, stream, "dp_forward_vjp_skeleton");
+    } catch (...) {
+        return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp_skeleton: host-side failure");
     }
 }
 

@@ -42,6 +42,14 @@ struct Args {
     int n_frames;
 };
 
+// dp_vjp_skel_kernel (dp_vjp_skel.hip): the same, with the bones of each frame's own skeleton (include/dragposer_skeleton.h)
+struct SkelArgs : Args {
+    const float* skel; // [N][22][3]: frame f reads skel + f * skel_stride (rows 1..21)
+    int skel_stride;   // 66 (one skeleton per frame) or 0 (one for the launch)
+    float* doff;       // [B][22][3] dL/d(offsets) per frame, or NULL
+};
+
 } // namespace dpvjp
 
 hipError_t dp_launch_vjp(const dpvjp::Args* args, hipStream_t stream);
+hipError_t dp_launch_vjp_skel(const dpvjp::SkelArgs* args, hipStream_t stream);

@@ -335,13 +335,20 @@ class LatentOptimizer:
             self._fail(rc)
         return tensors
 
-    def forward_vjp(self, z, cur_rot, grads, out=None):
+    def forward_vjp(self, z, cur_rot, grads, out=None, offsets=None, doffsets=False):
         """dL/dz [B,24] and dL/dcur_rot [B,4] of decode + FK at (z, cur_rot) for upstream gradients `grads` = {output name: dL/d(that
         output)} over any subset of pose, disp, world_disp, world_rot, pos, rot (shapes as `forward` returns them; missing = zero):
         include/dragposer_grad.h, dp_forward_vjp.  Returns dict(dz, dcur_rot, status) -- status: DP_STATUS_* bits per frame.
-        `out`: a dict of preallocated result tensors (any of the three).  Asynchronous on torch's current stream."""
+        `offsets` [22,3] / [B,22,3]: per-frame skeletons as in `forward` (dp_forward_vjp_skeleton); with them, `doffsets=True` (or a
+        "doffsets" tensor in `out`) adds "doffsets" [B,22,3], dL/d(offsets) of each frame (row 0 zero; for one [22,3] skeleton the
+        caller sums over the frames).  `out`: a dict of preallocated result tensors (any of these).  Asynchronous on torch's current
+        stream."""
         B = int(z.shape[0])
         dev = self.device
+        skel = self._skeleton(offsets, B, "forward_vjp") if offsets is not None else None
+        if doffsets and skel is None:
+            raise ValueError("forward_vjp: doffsets is the gradient of the offsets passed in the same call (offsets=None)")
+        want_doff = skel is not None and (bool(doffsets) or (out is not None and "doffsets" in out))
         zp = _check(z, "z", (B, LATENT), torch.float32, dev)
         cp = _check(cur_rot, "cur_rot", (B, 4), torch.float32, dev)
         g = _lib.DpGradIn()
@@ -351,11 +358,20 @@ class LatentOptimizer:
             if t is not None:
                 setattr(g, name, _check(t, "grads[" + name + "]", (B,) + _OUT_SPECS[name][0], torch.float32, dev))
         res = {}
-        for name, shape, dtype in (("dz", (B, LATENT), torch.float32), ("dcur_rot", (B, 4), torch.float32), ("status", (B,), torch.int32)):
+        specs = (("dz", (B, LATENT), torch.float32), ("dcur_rot", (B, 4), torch.float32), ("status", (B,), torch.int32))
+        for name, shape, dtype in specs + ((("doffsets", (B, NJ, 3), torch.float32),) if want_doff else ()):
             t = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
             _check(t, name, shape, dtype, dev)
             res[name] = t
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if skel is not None:
+            rc = self.lib.dp_forward_vjp_skeleton(self.ctx, B, C.c_void_p(zp), C.c_void_p(cp), C.byref(skel), C.byref(g),
+                                                  C.c_void_p(res["dz"].data_ptr()), C.c_void_p(res["dcur_rot"].data_ptr()),
+                                                  C.c_void_p(res["doffsets"].data_ptr() if want_doff else None),
+                                                  C.c_void_p(res["status"].data_ptr()), stream)
+            if rc != _lib.DP_OK:
+                self._fail(rc)
+            return res
         rc = self.lib.dp_forward_vjp(self.ctx, B, C.c_void_p(zp), C.c_void_p(cp), C.byref(g), C.c_void_p(res["dz"].data_ptr()),
                                      C.c_void_p(res["dcur_rot"].data_ptr()), C.c_void_p(res["status"].data_ptr()), stream)
         if rc != _lib.DP_OK:

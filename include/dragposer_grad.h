@@ -16,6 +16,9 @@
  *   the FK chain: `pos`, `rot` (utils.py:95-105,140-146).
  * Conventions are dragposer.h's (w-first quaternions, fp32, row-major, frame-major, 22 joints, latent 24); every skeleton
  * dp_create accepts is supported, with the weights of the context's own folded model (fp32 or bf16-rounded).
+ *   dp_forward_vjp_skeleton   the same with the performer's bone offsets passed per call (include/dragposer_skeleton.h: one skeleton per
+ *                    frame or one for the launch, the context's topology) -- the reference's fk_rotmat(..., offsets) -- and, on request,
+ *                    the gradient with respect to those offsets as well.
  *
  * The forward pass is recomputed inside the kernel: nothing is saved between dp_forward and dp_forward_vjp, and they may be
  * called in any order.  Asynchronous on the given HIP stream, no allocation, no host synchronisation, no host<->device copy
@@ -26,6 +29,7 @@
 #define DRAGPOSER_GRAD_H
 
 #include "dragposer.h"
+#include "dragposer_skeleton.h" /* dp_skeleton_in */
 
 #ifdef __cplusplus
 extern "C" {
@@ -51,6 +55,21 @@ typedef struct dp_grad_in {
  * DP_ERR_UNSUPPORTED from a library built without the kernel. */
 int dp_forward_vjp(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_grad_in* g,
                    float* dz, float* dcur_rot, int* status, void* hip_stream);
+
+/* dp_forward_vjp with per-frame skeletons: frame f's bones are row 1..21 of skeleton f (skel->stride 66) or of the single one (stride 0),
+ * under dragposer_skeleton.h's rules (row 0 ignored, the topology the context's).  Everything else is dp_forward_vjp's contract.
+ * doffsets: NULL, or a DEVICE [n_frames][22][3] that receives dL/d(offsets) of each frame -- written per frame even when stride is 0 (the
+ * caller sums over the frames); row 0 is written as 0 (no output depends on it).
+ * Screening, per frame (dp_forward_skeleton's rule): a skeleton row 1..21 with a component that is not finite or beyond DP_INPUT_LIMIT in
+ * magnitude refuses the frame -- status DP_STATUS_BAD_STATE (dp_forward_vjp's word for a refused z), dz, dcur_rot and every row of its
+ * doffsets NaN.  The refused frame is computed with zero in place of the bad rows, so its arithmetic stays finite; every other frame,
+ * lane neighbours included, is bit-identical to a launch without the fault.  Row 0 is never read: a NaN there leaves the frame clean.
+ * Bits: with the context's own skeleton (stride 0 or 66), dz, dcur_rot and status equal dp_forward_vjp's bits; a frame given skeleton X
+ * gets the bits dp_forward_vjp gives it on a context created with X.
+ * DP_ERR_INVALID: whatever dp_forward_vjp refuses, a NULL skeleton or NULL offsets, a stride other than 0 or 66, a bad struct_size or a
+ * non-zero reserved0 of the skeleton; DP_ERR_UNSUPPORTED from a library built without the kernel. */
+int dp_forward_vjp_skeleton(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* skel,
+                            const dp_grad_in* g, float* dz, float* dcur_rot, float* doffsets, int* status, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -21,8 +21,9 @@
  * set-up; its iteration loop is unchanged.  DP_KERNEL_AUTO takes DP_KERNEL_W4 at every batch size here -- beyond 8192 frames (two
  * rounds of 16 frames per CU on a 256-CU device) plain dp_optimize would switch to DP_KERNEL_W16, so such batches run extra rounds
  * of the 4-frames-per-wave kernel (about 1.3x the time of dp_w16 from three rounds on).  DP_KERNEL_W16 is refused
- * (DP_ERR_UNSUPPORTED): its slot map keeps the offsets in per-slot constants.  dp_forward_vjp, dp_optimize_constrained and
- * dp_optimize_terms read the bones from the context's own image and have no per-frame form (yet).
+ * (DP_ERR_UNSUPPORTED): its slot map keeps the offsets in per-slot constants.  dp_forward_vjp's per-frame form, with the gradient of the
+ * offsets, is dp_forward_vjp_skeleton (include/dragposer_grad.h).  dp_optimize_constrained and dp_optimize_terms read the bones from the
+ * context's own image and have no per-frame form.
  *
  * Returns DP_OK or a negative dp_status and never throws; message: dp_last_error(ctx).  DP_ERR_INVALID: a NULL skeleton or NULL
  * `offsets`, a `stride` other than 0 or 66, a bad struct_size or a non-zero reserved0 (checked like dp_grad_in's), and anything the
