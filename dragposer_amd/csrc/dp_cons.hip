@@ -26,6 +26,7 @@
 #include "../../include/dragposer.h"
 #include "../../include/dragposer_terms.h"
 #include "dp_cons.h"
+#include "dp_math.h"
 #include "dp_vjp.h"
 
 using namespace dpcons;
@@ -40,46 +41,11 @@ constexpr int NYU = 4 * NJ + 3; // decoder outputs that are used (the 92nd is no
 #define UNR 4 // (the dot products' loops: unrolled further, their loads stay in flight in registers and the frame loop spills)
 #endif
 
-DEV bool refused(float x) { return !(fabsf(x) <= DP_INPUT_LIMIT); } // NaN, Inf, or beyond the limit (dp_optimize's rule)
-
 DEV void wave_sync()
 { // orders this wave's LDS writes before its later LDS reads (other lanes' data); no instruction
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// rotmat, rotmat_vjp and quat_mul are copies of dp_vjp.hip's (kept apart so that dp_vjp_kernel's code stays exactly as it is).  A change
-// to one copy is a change to both: tests/test_hip_constraints.py holds this kernel's gradient to the fp64 oracle, tests/test_hip_vjp.py
-// holds dp_vjp's.
-// utils.py:49-74 (to_matrix_4, 3x3 block), w-first, no normalisation
-DEV void rotmat(const float* q, float* R)
-{
-    const float w = q[0], x = q[1], y = q[2], z = q[3];
-    const float x2 = x + x, y2 = y + y, z2 = z + z;
-    const float xx = x * x2, yy = y * y2, zz = z * z2, xy = x * y2, xz = x * z2, yz = y * z2, wx = w * x2, wy = w * y2, wz = w * z2;
-    R[0] = 1.f - (yy + zz); R[1] = xy - wz;         R[2] = xz + wy;
-    R[3] = xy + wz;         R[4] = 1.f - (xx + zz); R[5] = yz - wx;
-    R[6] = xz - wy;         R[7] = yz + wx;         R[8] = 1.f - (xx + yy);
-}
-
-// dL/dq of rotmat(q) for dL/dR = g (row-major)
-DEV void rotmat_vjp(const float* q, const float* g, float* dq)
-{
-    const float w = q[0], x = q[1], y = q[2], z = q[3];
-    dq[0] = 2.f * (z * (g[3] - g[1]) + y * (g[2] - g[6]) + x * (g[7] - g[5]));
-    dq[1] = 2.f * (y * (g[1] + g[3]) + z * (g[2] + g[6]) + w * (g[7] - g[5]) - 2.f * x * (g[4] + g[8]));
-    dq[2] = 2.f * (x * (g[1] + g[3]) + z * (g[5] + g[7]) + w * (g[2] - g[6]) - 2.f * y * (g[0] + g[8]));
-    dq[3] = 2.f * (x * (g[2] + g[6]) + y * (g[5] + g[7]) + w * (g[3] - g[1]) - 2.f * z * (g[0] + g[4]));
-}
-
-// (pymotion quat_torch.mul, w-first Hamilton) a (x) b
-DEV void quat_mul(const float* a, const float* b, float* o)
-{
-    o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-    o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-    o[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-    o[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
 }
 
 DEV float wsum(float x)

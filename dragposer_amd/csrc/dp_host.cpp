@@ -10,6 +10,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dragposer.h"
@@ -687,16 +688,55 @@ static void fill_model_args(const dp_ctx* ctx, KArgs& k)
     std::memcpy(k.smask, ctx->smask.data(), sizeof(k.smask));
 }
 
-// dp_params / dp_result as the caller compiled them (include/dragposer.h: struct_size): a copy of the first struct_size bytes over a zeroed
-// struct of THIS build -- a field the caller's header did not have reads as its default, a caller built against a pre-0.5 header is refused
-constexpr unsigned PARAMS_SIZE_V500 = offsetof(dp_params, kernel) + sizeof(int);
-constexpr unsigned RESULT_SIZE_V500 = offsetof(dp_result, clock) + sizeof(void*);
+// A sized struct as the caller compiled it (include/dragposer.h: struct_size) -- the library's defence against a caller built from another header.
+// check_sized: the size word must lie in [min_size, 4096] and reserved0 (every sized struct but dp_params has it) must be 0.  copy_sized: a copy
+// of the first struct_size bytes over a zeroed struct of THIS build -- a field the caller's header did not have reads as its default.
+//   name, init: the struct's name and its *_INIT hint, for the message;  pre05: the struct existed before 0.5 without its size word
+//   (dp_params, dp_result, dp_seq_results), so a small size is most likely a caller compiled against that header, and the message says so
+struct Sized {
+    const char *name, *init;
+    unsigned min_size;
+    bool pre05;
+};
+template <class T>
+static int check_sized(dp_ctx* ctx, const T* in, const Sized& s, const char* who)
+{
+    unsigned reserved0 = 0u;
+    constexpr bool has_reserved0 = !std::is_same<T, dp_params>::value;
+    if constexpr (has_reserved0) reserved0 = in->reserved0;
+    if (in->struct_size < s.min_size || in->struct_size > 4096u || reserved0 != 0u)
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": " + s.name + ".struct_size is " + std::to_string(in->struct_size) +
+                                             (has_reserved0 ? " (reserved0 " + std::to_string(reserved0) + ")" : "") + ", this library" +
+                                             (s.pre05 ? " (DP_VERSION " + std::to_string(DP_VERSION) + ")" : "") + " expects at least " +
+                                             std::to_string(s.min_size) + (has_reserved0 ? " and reserved0 = 0" : "") +
+                                             (s.pre05 ? " -- was the caller compiled against a pre-0.5 dragposer.h?" : "") + "  (" + s.init + ")");
+    return DP_OK;
+}
+template <class T>
+static void copy_sized(const T* in, T& o)
+{
+    std::memset(&o, 0, sizeof(o));
+    std::memcpy(&o, in, std::min<size_t>(in->struct_size, sizeof(o)));
+}
+template <class T>
+static int take_sized(dp_ctx* ctx, const T* in, T& o, const Sized& s, const char* who)
+{
+    if (int rc = check_sized(ctx, in, s, who)) return rc;
+    copy_sized(in, o);
+    return DP_OK;
+}
+// (each struct's minimum: its first version, up to the named field)
+constexpr Sized PARAMS_V500 = {"dp_params", "dp_params p = DP_PARAMS_INIT;", offsetof(dp_params, kernel) + sizeof(int), true};
+constexpr Sized RESULT_V500 = {"dp_result", "dp_result r = DP_RESULT_INIT;", offsetof(dp_result, clock) + sizeof(void*), true};
+constexpr Sized SEQ_RESULTS_V500 = {"dp_seq_results", "dp_seq_results r = DP_SEQ_RESULTS_INIT;", offsetof(dp_seq_results, status) + sizeof(void*), true};
+constexpr Sized SKEL_IN_V510 = {"dp_skeleton_in", "dp_skeleton_in s = DP_SKELETON_IN_INIT;", offsetof(dp_skeleton_in, stride) + sizeof(int), false};
+constexpr Sized GRAD_IN_V510 = {"dp_grad_in", "dp_grad_in g = DP_GRAD_IN_INIT;", offsetof(dp_grad_in, rot) + sizeof(void*), false};
+constexpr Sized CONS_V510 = {"dp_constraints", "dp_constraints c = DP_CONSTRAINTS_INIT;", offsetof(dp_constraints, loss_extra) + sizeof(void*), false};
+constexpr Sized TERMS_V510 = {"dp_terms", "dp_terms t = DP_TERMS_INIT;", offsetof(dp_terms, loss_terms) + sizeof(void*), false};
+
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
 {
-    if (p->struct_size < PARAMS_SIZE_V500 || p->struct_size > 4096u)
-        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_params.struct_size is " + std::to_string(p->struct_size) + ", this library (DP_VERSION " +
-                                             std::to_string(DP_VERSION) + ") expects at least " + std::to_string(PARAMS_SIZE_V500) +
-                                             " -- was the caller compiled against a pre-0.5 dragposer.h?  (dp_params p = DP_PARAMS_INIT;)");
+    if (int rc = check_sized(ctx, p, PARAMS_V500, who)) return rc;
     // A 0.4 caller's struct is 52 bytes and starts with n_iter: one that asks for 56 ... 4096 iterations passes the size test above.  Its SECOND word is
     // `lr`, whose bits read as an iteration count are beyond DP_MAX_ITERS for any learning rate above 1.4e-39 -- tested HERE, on the two words every
     // layout has, before anything is copied: the 52-byte struct is never read past.
@@ -704,20 +744,13 @@ static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char
         return fail(ctx, DP_ERR_INVALID, std::string(who) + ": n_iter " + std::to_string(p->n_iter) + " out of range [1, DP_MAX_ITERS] (dp_params.struct_size " +
                                              std::to_string(p->struct_size) + ": if that is the iteration count you meant, the caller was compiled against a pre-0.5 "
                                              "dragposer.h, whose dp_params starts with n_iter; dp_params p = DP_PARAMS_INIT;)");
-    std::memset(&o, 0, sizeof(o));
-    std::memcpy(&o, p, std::min<size_t>(p->struct_size, sizeof(o)));
+    copy_sized(p, o);
     return DP_OK;
 }
 static int take_result(dp_ctx* ctx, const dp_result* r, dp_result& o, const char* who)
 {
-    std::memset(&o, 0, sizeof(o));
-    if (!r) return DP_OK;
-    if (r->struct_size < RESULT_SIZE_V500 || r->struct_size > 4096u || r->reserved0 != 0u)
-        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_result.struct_size is " + std::to_string(r->struct_size) + " (reserved0 " +
-                                             std::to_string(r->reserved0) + "), this library (DP_VERSION " + std::to_string(DP_VERSION) + ") expects at least " +
-                                             std::to_string(RESULT_SIZE_V500) + " and reserved0 = 0 -- was the caller compiled against a pre-0.5 dragposer.h?  (dp_result r = DP_RESULT_INIT;)");
-    std::memcpy(&o, r, std::min<size_t>(r->struct_size, sizeof(o)));
-    return DP_OK;
+    std::memset(&o, 0, sizeof(o)); // (NULL: no result is wanted)
+    return r ? take_sized(ctx, r, o, RESULT_V500, who) : DP_OK;
 }
 
 // Adam's per-iteration scalars, as torch computes them in Python doubles: a table for the first MAX_ITERS iterations (in the kernel arguments), and
@@ -737,13 +770,65 @@ static void fill_adam(KArgs& k, const dp_params& p)
     k.cont.b1t = b1t; k.cont.b2t = b2t;
 }
 
-static void fill_results(const dp_result* out, KArgs& k)
+// The three parts every optimise kernel's argument block has under the same field names (KArgs: dp_kernel.h; dpcons::Args, dpcons::TermArgs: dp_cons.h)
+template <class A>
+static void fill_batch(A& a, const dp_batch& in)
 {
-    if (!out) return;
-    k.status = out->status; k.clk = out->clock;
-    k.z = out->z; k.z_pre = out->z_pre; k.pose = out->pose; k.disp = out->disp; k.world_disp = out->world_disp;
-    k.world_rot = out->world_rot; k.pos = out->pos; k.rot = out->rot; k.loss = out->loss; k.iters = out->iters;
+    a.z0 = in.z0; a.z_tgt = in.z_tgt; a.cur_rot = in.cur_rot; a.tgt_pos = in.tgt_pos; a.tgt_rot = in.tgt_rot; a.w = in.w; a.tracked = in.tracked;
+    a.n_frames = in.n_frames;
 }
+template <class A>
+static void fill_results(A& a, const dp_result& out)
+{ // (dp_result.clock: KArgs only, set where it is used)
+    a.z = out.z; a.z_pre = out.z_pre; a.pose = out.pose; a.disp = out.disp; a.world_disp = out.world_disp;
+    a.world_rot = out.world_rot; a.pos = out.pos; a.rot = out.rot; a.loss = out.loss; a.iters = out.iters; a.status = out.status;
+}
+template <class A>
+static void fill_loop(A& a, const dp_params& p, bool early_stop)
+{
+    a.n_iter = p.n_iter;
+    a.lam_rot = p.lambda_rot; a.lam_tmp = p.lambda_tmp; a.ctmp = 2.f * p.lambda_tmp / 24.f;
+    // torch passes (1-beta) as Python doubles into fp32 tensor ops
+    a.beta2 = p.beta2; a.one_m_b1 = (float)(1.0 - (double)p.beta1); a.one_m_b2 = (float)(1.0 - (double)p.beta2);
+    a.eps = p.eps;
+    a.early_stop = early_stop ? 1 : 0;
+    a.stop_eps_pos = p.stop_eps_pos; a.stop_eps_rot = p.stop_eps_rot; a.min_loss_incr = p.min_loss_incr;
+}
+
+// What every optimise entry point asks of its batch and of Adam's hyper-parameters
+static int check_batch(dp_ctx* ctx, const dp_batch* in, const char* who)
+{
+    if (in->n_frames <= 0) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": n_frames must be positive");
+    if (!in->z0 || !in->z_tgt || !in->cur_rot || !in->tgt_pos || !in->tgt_rot || !in->w || !in->tracked)
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": NULL input array");
+    return DP_OK;
+}
+static int check_adam(dp_ctx* ctx, const dp_params& p, const char* who)
+{
+    if (!(p.lr > 0.f) || !(p.beta1 >= 0.f && p.beta1 < 1.f) || !(p.beta2 >= 0.f && p.beta2 < 1.f))
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": bad Adam hyper-parameters");
+    if (!(p.eps > 0.f)) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": Adam eps must be > 0 (include/dragposer.h: dp_params.eps)");
+    return DP_OK;
+}
+
+// The shell of an entry point that reports a NULL context in words: the refusal, and no C++ exception (std::string, std::vector) crosses the C ABI
+template <class Body>
+static int entry(dp_ctx* ctx, const char* who, Body body)
+{
+    if (!ctx) return fail(nullptr, DP_ERR_INVALID, std::string(who) + ": ctx is NULL");
+    try {
+        return body();
+    } catch (...) {
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": host-side failure");
+    }
+}
+
+// The test-only library (DP_REF8_BUILD) has the round-1 kernel behind dp_optimize and dp_forward only: every other launch is refused, after its
+// argument checks (dp_optimize_sequence: before them).  A context without device memory (dp_debug_host_ctx) is refused by every launch, after
+// everything else, before anything of the image is read.
+constexpr bool REF8_BUILD = KERNEL_CHOICE == 8;
+static int refuse_ref8(dp_ctx* ctx, const char* who) { return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": not part of the test-only library"); }
+static int refuse_no_image(dp_ctx* ctx, const char* who) { return fail(ctx, DP_ERR_DEVICE, std::string(who) + ": the context has no device image"); }
 
 // Which kernel runs a launch: the wave-private kernel of dp_w4.hip (4 frames per wave, no workgroup barrier in the
 // loop); in the test-only library the previous decomposition (dp_kernel.hip: 16 frames per 8-wave workgroup).  Both
@@ -800,19 +885,12 @@ extern "C" int dp_debug_set_w4_layout(dp_ctx* ctx, int bp)
     return bp;
 }
 
-// include/dragposer_skeleton.h: dp_skeleton_in as the caller compiled it (first version: up to stride), checked like dp_grad_in -> what goes
-// into KArgs::skel / skel_stride.  Also refuses a context without device memory (dp_debug_host_ctx) before anything reads it.
-constexpr unsigned SKEL_IN_SIZE_V510 = offsetof(dp_skeleton_in, stride) + sizeof(int);
+// include/dragposer_skeleton.h: dp_skeleton_in as the caller compiled it (the entry point has refused a NULL one) -> what goes into
+// KArgs::skel / skel_stride
 static int take_skeleton(dp_ctx* ctx, const dp_skeleton_in* s, const float*& off, int& stride, const char* who)
 {
-    if (!s) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": the skeleton is NULL");
-    if (s->struct_size < SKEL_IN_SIZE_V510 || s->struct_size > 4096u || s->reserved0 != 0u)
-        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_skeleton_in.struct_size is " + std::to_string(s->struct_size) + " (reserved0 " +
-                                             std::to_string(s->reserved0) + "), this library expects at least " + std::to_string(SKEL_IN_SIZE_V510) +
-                                             " and reserved0 = 0  (dp_skeleton_in s = DP_SKELETON_IN_INIT;)");
     dp_skeleton_in sv;
-    std::memset(&sv, 0, sizeof(sv));
-    std::memcpy(&sv, s, std::min<size_t>(s->struct_size, sizeof(sv)));
+    if (int rc = take_sized(ctx, s, sv, SKEL_IN_V510, who)) return rc;
     if (!sv.offsets) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_skeleton_in.offsets is NULL");
     if (sv.stride != 0 && sv.stride != DP_SKELETON_STRIDE)
         return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_skeleton_in.stride is " + std::to_string(sv.stride) +
@@ -821,78 +899,57 @@ static int take_skeleton(dp_ctx* ctx, const dp_skeleton_in* s, const float*& off
     stride = sv.stride;
     return DP_OK;
 }
+static int refuse_null_skeleton(dp_ctx* ctx, const char* who) { return fail(ctx, DP_ERR_INVALID, std::string(who) + ": the skeleton is NULL"); }
+static int refuse_w16_skeleton(dp_ctx* ctx, const char* who)
+{
+    return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": DP_KERNEL_W16 keeps the bone offsets in per-slot constants; per-frame skeletons run on "
+                                                            "DP_KERNEL_W4 (DP_KERNEL_AUTO takes it)");
+}
 
 // dp_optimize (sk = NULL) and dp_optimize_skeleton (who names the caller in the messages)
 static int optimize_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_result* out_in, float* dbg, void* stream,
                          const dp_skeleton_in* sk, const char* who)
 {
-    if (!ctx) return DP_ERR_INVALID;
     if (!in || !p_in) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": NULL batch/params");
-    dp_params pv; dp_result ov;
-    if (int rc = take_params(ctx, p_in, pv, who)) return rc;
-    if (int rc = take_result(ctx, out_in, ov, who)) return rc;
-    const dp_params* p = &pv;
-    const dp_result* out = &ov;
-    const std::string w = who;
-    if (in->n_frames <= 0) return fail(ctx, DP_ERR_INVALID, w + ": n_frames must be positive");
-    if (!in->z0 || !in->z_tgt || !in->cur_rot || !in->tgt_pos || !in->tgt_rot || !in->w || !in->tracked)
-        return fail(ctx, DP_ERR_INVALID, w + ": NULL input array");
-#ifdef DP_REF8_BUILD
-    if (p->n_iter < 1 || p->n_iter > MAX_ITERS) return fail(ctx, DP_ERR_INVALID, w + ": n_iter out of range [1,256] (the test-only kernel reads the argument table only)");
-#else
-    if (p->n_iter < 1 || p->n_iter > DP_MAX_ITERS) return fail(ctx, DP_ERR_INVALID, w + ": n_iter out of range [1, DP_MAX_ITERS]");
-#endif
-    if (!(p->lr > 0.f) || !(p->beta1 >= 0.f && p->beta1 < 1.f) || !(p->beta2 >= 0.f && p->beta2 < 1.f))
-        return fail(ctx, DP_ERR_INVALID, w + ": bad Adam hyper-parameters");
-    if (!(p->eps > 0.f)) return fail(ctx, DP_ERR_INVALID, w + ": Adam eps must be > 0 (include/dragposer.h: dp_params.eps)");
+    dp_params p; dp_result out;
+    if (int rc = take_params(ctx, p_in, p, who)) return rc;
+    if (int rc = take_result(ctx, out_in, out, who)) return rc;
+    if (int rc = check_batch(ctx, in, who)) return rc;
+    if (REF8_BUILD && p.n_iter > MAX_ITERS)
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": n_iter out of range [1,256] (the test-only kernel reads the argument table only)");
+    if (int rc = check_adam(ctx, p, who)) return rc;
     const float* sk_off = nullptr;
     int sk_stride = 0;
-    if (sk) { // (include/dragposer_skeleton.h: the dp_w4sk units, at every batch size)
+    if (sk) // (include/dragposer_skeleton.h: the dp_w4sk units, at every batch size)
         if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
-        if (p->kernel != DP_KERNEL_AUTO && p->kernel != DP_KERNEL_W4 && p->kernel != DP_KERNEL_W16)
-            return fail(ctx, DP_ERR_INVALID, w + ": unknown kernel selector");
-        if (p->kernel == DP_KERNEL_W16)
-            return fail(ctx, DP_ERR_UNSUPPORTED, w + ": DP_KERNEL_W16 keeps the bone offsets in per-slot constants; per-frame skeletons run on "
-                                                     "DP_KERNEL_W4 (DP_KERNEL_AUTO takes it)");
-#ifdef DP_REF8_BUILD
-        return fail(ctx, DP_ERR_UNSUPPORTED, w + ": not part of the test-only library");
-#endif
-        if (!ctx->d_w4img) return fail(ctx, DP_ERR_DEVICE, w + ": the context has no device image");
-    }
+    // which kernel (include/dragposer.h: DP_KERNEL_*)
+    if (p.kernel != DP_KERNEL_AUTO && p.kernel != DP_KERNEL_W4 && p.kernel != DP_KERNEL_W16)
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": unknown kernel selector");
+    if (sk && p.kernel == DP_KERNEL_W16) return refuse_w16_skeleton(ctx, who);
+    if (sk && REF8_BUILD) return refuse_ref8(ctx, who);
+    if (!ctx->d_w4img) return refuse_no_image(ctx, who);
     KArgs k;
     fill_model_args(ctx, k);
-    k.z0 = in->z0; k.z_tgt = in->z_tgt; k.cur_rot = in->cur_rot; k.tgt_pos = in->tgt_pos; k.tgt_rot = in->tgt_rot;
-    k.w = in->w; k.tracked = in->tracked;
-    fill_results(out, k);
+    fill_batch(k, *in);
+    fill_results(k, out);
+    k.clk = out.clock;
     k.dbg = dbg;
-    k.n_frames = in->n_frames; k.n_iter = p->n_iter; k.mode = 0;
-    k.lam_rot = p->lambda_rot; k.lam_tmp = p->lambda_tmp; k.ctmp = 2.f * p->lambda_tmp / 24.f;
-    // torch passes (1-beta) as Python doubles into fp32 tensor ops
-    k.beta2 = p->beta2; k.one_m_b1 = (float)(1.0 - (double)p->beta1); k.one_m_b2 = (float)(1.0 - (double)p->beta2);
-    k.eps = p->eps;
-    k.early_stop = p->early_stop ? 1 : 0;
-    k.stop_eps_pos = p->stop_eps_pos; k.stop_eps_rot = p->stop_eps_rot; k.min_loss_incr = p->min_loss_incr;
-    fill_adam(k, *p);
-    // which kernel (include/dragposer.h: DP_KERNEL_*)
-    const bool w16_can = ctx->d_w16img != nullptr;
-    if (p->kernel != DP_KERNEL_AUTO && p->kernel != DP_KERNEL_W4 && p->kernel != DP_KERNEL_W16)
-        return fail(ctx, DP_ERR_INVALID, w + ": unknown kernel selector");
-    if (sk) {
-        k.skel = sk_off;
-        k.skel_stride = sk_stride;
-        return launch(ctx, k, stream, DP_KERNEL_W4, true);
-    }
-    if (p->kernel == DP_KERNEL_W16 && !w16_can)
+    k.mode = 0;
+    fill_loop(k, p, p.early_stop != 0);
+    fill_adam(k, p);
+    k.skel = sk_off; k.skel_stride = sk_stride;
+    if (sk) return launch(ctx, k, stream, DP_KERNEL_W4, true);
+    if (p.kernel == DP_KERNEL_W16 && !ctx->d_w16img)
         return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize: DP_KERNEL_W16 is laid out for the reference's 22-joint skeleton only");
     // (beyond the argument table of Adam scalars, n_iter > 256, both kernels have LONG instantiations that continue them on the device)
-    const int kernel = p->kernel == DP_KERNEL_AUTO ? dp_auto_kernel(ctx, in->n_frames) : p->kernel;
-    return launch(ctx, k, stream, kernel);
+    return launch(ctx, k, stream, p.kernel == DP_KERNEL_AUTO ? dp_auto_kernel(ctx, in->n_frames) : p.kernel);
 }
 
 // private extension used by the tests: same as dp_optimize, plus an optional debug dump
 // [B][240] = y(104) | dL/dy(104) | dL/dz(24) | pad, all of iteration 0.
 extern "C" int dp_optimize_debug(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_result* out_in, float* dbg, void* stream)
 {
+    if (!ctx) return DP_ERR_INVALID;
     return optimize_impl(ctx, in, p_in, out_in, dbg, stream, nullptr, "dp_optimize");
 }
 
@@ -914,35 +971,32 @@ extern "C" int dp_optimize(dp_ctx* ctx, const dp_batch* in, const dp_params* p, 
     return dp_optimize_debug(ctx, in, p, out, nullptr, stream);
 }
 
-static int forward_impl(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* sk, const dp_result* out, void* stream,
+static int forward_impl(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* sk, const dp_result* out_in, void* stream,
                         const char* who)
 {
-    if (!ctx) return DP_ERR_INVALID;
-    if (n_frames <= 0 || !z || !cur_rot || !out) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": bad arguments");
-    dp_result ov;
-    if (int rc = take_result(ctx, out, ov, who)) return rc;
-    out = &ov;
+    if (n_frames <= 0 || !z || !cur_rot || !out_in) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": bad arguments");
+    dp_result out;
+    if (int rc = take_result(ctx, out_in, out, who)) return rc;
     const float* sk_off = nullptr;
     int sk_stride = 0;
     if (sk) {
         if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
-#ifdef DP_REF8_BUILD
-        return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": not part of the test-only library");
-#endif
-        if (!ctx->d_w4img) return fail(ctx, DP_ERR_DEVICE, std::string(who) + ": the context has no device image");
+        if (REF8_BUILD) return refuse_ref8(ctx, who);
     }
+    if (!ctx->d_w4img) return refuse_no_image(ctx, who);
     KArgs k;
     fill_model_args(ctx, k);
     k.skel = sk_off; k.skel_stride = sk_stride;
     k.z0 = z; k.cur_rot = cur_rot;
-    fill_results(out, k);
-    k.z = nullptr; k.z_pre = nullptr; k.loss = nullptr; k.iters = nullptr; k.clk = nullptr;
+    fill_results(k, out);
+    k.z = nullptr; k.z_pre = nullptr; k.loss = nullptr; k.iters = nullptr;
     k.n_frames = n_frames; k.n_iter = 1; k.mode = 1;
     return launch(ctx, k, stream, DP_KERNEL_W4, sk != nullptr);
 }
 
 extern "C" int dp_forward(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_result* out, void* stream)
 {
+    if (!ctx) return DP_ERR_INVALID;
     return forward_impl(ctx, n_frames, z, cur_rot, nullptr, out, stream, "dp_forward");
 }
 
@@ -955,32 +1009,21 @@ extern "C" int dp_debug_host_ctx(dp_ctx** out)
     return *out ? DP_OK : DP_ERR_DEVICE;
 }
 
-// include/dragposer_grad.h.  dp_grad_in as the caller compiled it: first version = the six pointers, a later caller's struct is read
-// up to what this build knows
-constexpr unsigned GRAD_IN_SIZE_V510 = offsetof(dp_grad_in, rot) + sizeof(void*);
-// dp_forward_vjp (sk = NULL, dp_vjp.hip) and dp_forward_vjp_skeleton (dp_vjp_skel.hip; who names the caller in the messages)
+// include/dragposer_grad.h: dp_forward_vjp (sk = NULL, dp_vjp.hip) and dp_forward_vjp_skeleton (dp_vjp_skel.hip; who names the caller in the messages)
 static int vjp_impl(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* sk, const dp_grad_in* g, float* dz,
                     float* dcur_rot, float* doffsets, int* status, void* stream, const char* who)
 {
     const std::string w = who;
     if (n_frames <= 0) return fail(ctx, DP_ERR_INVALID, w + ": n_frames must be positive");
     if (!z || !cur_rot || !g || !dz) return fail(ctx, DP_ERR_INVALID, w + ": NULL z, cur_rot, g or dz");
-    if (g->struct_size < GRAD_IN_SIZE_V510 || g->struct_size > 4096u || g->reserved0 != 0u)
-        return fail(ctx, DP_ERR_INVALID, w + ": dp_grad_in.struct_size is " + std::to_string(g->struct_size) + " (reserved0 " +
-                                             std::to_string(g->reserved0) + "), this library expects at least " + std::to_string(GRAD_IN_SIZE_V510) +
-                                             " and reserved0 = 0  (dp_grad_in g = DP_GRAD_IN_INIT;)");
     dp_grad_in gv;
-    std::memset(&gv, 0, sizeof(gv));
-    std::memcpy(&gv, g, std::min<size_t>(g->struct_size, sizeof(gv)));
+    if (int rc = take_sized(ctx, g, gv, GRAD_IN_V510, who)) return rc;
     const float* sk_off = nullptr;
     int sk_stride = 0;
     if (sk)
         if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
-#ifdef DP_REF8_BUILD
-    (void)dcur_rot; (void)doffsets; (void)status; (void)stream;
-    return fail(ctx, DP_ERR_UNSUPPORTED, w + ": not part of the test-only library");
-#else
-    if (!ctx->d_vjpimg) return fail(ctx, DP_ERR_DEVICE, w + ": the context has no device image");
+    if (REF8_BUILD) return refuse_ref8(ctx, who);
+    if (!ctx->d_vjpimg) return refuse_no_image(ctx, who);
     DEVICE_GUARD(ctx);
     dpvjp::SkelArgs a;
     a.img = ctx->d_vjpimg;
@@ -992,51 +1035,62 @@ static int vjp_impl(dp_ctx* ctx, int n_frames, const float* z, const float* cur_
     const hipError_t e = sk ? dp_launch_vjp_skel(&a, (hipStream_t)stream) : dp_launch_vjp(&a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(e));
     return DP_OK;
-#endif
 }
 
 extern "C" int dp_forward_vjp(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_grad_in* g, float* dz, float* dcur_rot,
                               int* status, void* stream)
 {
-    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_forward_vjp: ctx is NULL");
-    try {
-        return vjp_impl(ctx, n_frames, z, cur_rot, nullptr, g, dz, dcur_rot, nullptr, status, stream, "dp_forward_vjp");
-    } catch (...) {
-        return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp: host-side failure");
-    }
+    const char* who = "dp_forward_vjp";
+    return entry(ctx, who, [&] { return vjp_impl(ctx, n_frames, z, cur_rot, nullptr, g, dz, dcur_rot, nullptr, status, stream, who); });
 }
 
 extern "C" int dp_forward_vjp_skeleton(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* skel,
                                        const dp_grad_in* g, float* dz, float* dcur_rot, float* doffsets, int* status, void* stream)
 {
-    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_forward_vjp_skeleton: ctx is NULL");
-    try {
-        if (!skel) return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp_skeleton: the skeleton is NULL");
-        return vjp_impl(ctx, n_frames, z, cur_rot, skel, g, dz, dcur_rot, doffsets, status, stream, "dp_forward_vjp_skeleton");
-    } catch (...) {
-        return fail(ctx, DP_ERR_INVALID, "dp_forward_vjp_skeleton: host-side failure");
-    }
+    const char* who = "dp_forward_vjp_skeleton";
+    return entry(ctx, who, [&] {
+        if (!skel) return refuse_null_skeleton(ctx, who);
+        return vjp_impl(ctx, n_frames, z, cur_rot, skel, g, dz, dcur_rot, doffsets, status, stream, who);
+    });
 }
 
-// include/dragposer_constraints.h.  dp_constraints as the caller compiled it (first version: up to loss_extra), checked like dp_grad_in
-constexpr unsigned CONS_SIZE_V510 = offsetof(dp_constraints, loss_extra) + sizeof(void*);
+// dp_optimize_constrained (A = dpcons::Args) and dp_optimize_terms (dpcons::TermArgs), whose callers have refused a NULL argument: everything but
+// the entry point's own struct.  own(a) validates that struct and writes its fields into the zeroed argument block -- between the checks of
+// params / result and those of the batch, which is the order the refusals have.
+static_assert(DP_MAX_TERMS == dpcons::MAX_TERMS, "dp_cons.h's table holds DP_MAX_TERMS terms");
+template <class A, class Own>
+static int constrained_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_result* out_in, void* stream, const char* who, Own own,
+                            hipError_t (*launch_fn)(const A*, hipStream_t))
+{
+    dp_params p; dp_result out;
+    if (int rc = take_params(ctx, p_in, p, who)) return rc;
+    if (int rc = take_result(ctx, out_in, out, who)) return rc;
+    A a;
+    std::memset(&a, 0, sizeof(a));
+    if (int rc = own(a)) return rc;
+    if (int rc = check_batch(ctx, in, who)) return rc;
+    if (int rc = check_adam(ctx, p, who)) return rc;
+    if (REF8_BUILD) return refuse_ref8(ctx, who);
+    if (!ctx->d_vjpimg) return refuse_no_image(ctx, who);
+    DEVICE_GUARD(ctx);
+    a.img = ctx->d_vjpimg;
+    fill_batch(a, *in);
+    fill_results(a, out);
+    fill_loop(a, p, p.early_stop != 0);
+    a.beta1d = p.beta1; a.beta2d = p.beta2; a.lrd = p.lr; // (Adam's bias corrections are Python doubles in torch: fill_adam for dp_optimize)
+    const hipError_t e = launch_fn(&a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
+    return DP_OK;
+}
+
+// include/dragposer_constraints.h
 extern "C" int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_constraints* c_in, const dp_result* out_in,
                                        void* stream)
 {
-    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_optimize_constrained: ctx is NULL");
-    try {
-        const char* who = "dp_optimize_constrained";
-        if (!in || !p_in || !c_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: NULL batch, params, constraints or result");
-        dp_params pv; dp_result ov;
-        if (int rc = take_params(ctx, p_in, pv, who)) return rc;
-        if (int rc = take_result(ctx, out_in, ov, who)) return rc;
-        if (c_in->struct_size < CONS_SIZE_V510 || c_in->struct_size > 4096u || c_in->reserved0 != 0u)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: dp_constraints.struct_size is " + std::to_string(c_in->struct_size) + " (reserved0 " +
-                                                 std::to_string(c_in->reserved0) + "), this library expects at least " + std::to_string(CONS_SIZE_V510) +
-                                                 " and reserved0 = 0  (dp_constraints c = DP_CONSTRAINTS_INIT;)");
+    const char* who = "dp_optimize_constrained";
+    const auto own = [&](dpcons::Args& a) -> int {
         dp_constraints c;
-        std::memset(&c, 0, sizeof(c));
-        std::memcpy(&c, c_in, std::min<size_t>(c_in->struct_size, sizeof(c)));
+        if (int rc = take_sized(ctx, c_in, c, CONS_V510, who)) return rc;
         const float wts[4] = {c.w_feet_floor, c.w_head_hips_forward, c.w_head_hips_colinear, c.w_hips_feet_colinear};
         for (float x : wts)
             if (!(x >= 0.f && x <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: a weight is negative or not finite");
@@ -1048,31 +1102,8 @@ extern "C" int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp
         for (float x : rest)
             if (!(std::fabs(x) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: a constraint parameter is not finite");
         if (c.w_feet_floor != 0.f && !c.global_pos) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: global_pos is NULL while feet_floor is on");
-        if (in->n_frames <= 0) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: n_frames must be positive");
-        if (!in->z0 || !in->z_tgt || !in->cur_rot || !in->tgt_pos || !in->tgt_rot || !in->w || !in->tracked)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: NULL input array");
-        if (!(pv.lr > 0.f) || !(pv.beta1 >= 0.f && pv.beta1 < 1.f) || !(pv.beta2 >= 0.f && pv.beta2 < 1.f))
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: bad Adam hyper-parameters");
-        if (!(pv.eps > 0.f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: Adam eps must be > 0");
-#ifdef DP_REF8_BUILD
-        (void)stream;
-        return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize_constrained: not part of the test-only library");
-#else
-        if (!ctx->d_vjpimg) return fail(ctx, DP_ERR_DEVICE, "dp_optimize_constrained: the context has no device image");
-        DEVICE_GUARD(ctx);
-        dpcons::Args a;
-        std::memset(&a, 0, sizeof(a));
-        a.img = ctx->d_vjpimg;
-        a.z0 = in->z0; a.z_tgt = in->z_tgt; a.cur_rot = in->cur_rot; a.tgt_pos = in->tgt_pos; a.tgt_rot = in->tgt_rot; a.w = in->w; a.tracked = in->tracked;
         a.global_pos = c.global_pos;
-        a.z = ov.z; a.z_pre = ov.z_pre; a.pose = ov.pose; a.disp = ov.disp; a.world_disp = ov.world_disp; a.world_rot = ov.world_rot;
-        a.pos = ov.pos; a.rot = ov.rot; a.loss = ov.loss; a.loss_extra = c.loss_extra; a.iters = ov.iters; a.status = ov.status;
-        a.n_frames = in->n_frames; a.n_iter = pv.n_iter; a.early_stop = pv.early_stop ? 1 : 0;
-        a.stop_eps_pos = pv.stop_eps_pos; a.stop_eps_rot = pv.stop_eps_rot; a.min_loss_incr = pv.min_loss_incr;
-        a.lam_rot = pv.lambda_rot; a.lam_tmp = pv.lambda_tmp; a.ctmp = 2.f * pv.lambda_tmp / 24.f;
-        // torch passes (1-beta) as Python doubles into fp32 tensor ops; its bias corrections are Python doubles (dp_optimize: fill_adam)
-        a.one_m_b1 = (float)(1.0 - (double)pv.beta1); a.beta2 = pv.beta2; a.one_m_b2 = (float)(1.0 - (double)pv.beta2); a.eps = pv.eps;
-        a.beta1d = pv.beta1; a.beta2d = pv.beta2; a.lrd = pv.lr;
+        a.loss_extra = c.loss_extra;
         a.w_floor = c.w_feet_floor; a.w_fwd = c.w_head_hips_forward; a.w_hcol = c.w_head_hips_colinear; a.w_feet = c.w_hips_feet_colinear;
         a.floor_j[0] = c.floor_joints[0]; a.floor_j[1] = c.floor_joints[1]; a.foot_j[0] = c.foot_joints[0]; a.foot_j[1] = c.foot_joints[1];
         a.head = c.head_joint; a.hips = c.hips_joint; a.up = c.up_axis; a.one_sided = c.floor_one_sided ? 1 : 0;
@@ -1080,18 +1111,13 @@ extern "C" int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp
         a.fwd[0] = c.fwd_axis[0]; a.fwd[1] = c.fwd_axis[1]; a.fwd[2] = c.fwd_axis[2];
         a.fwd_thr = c.fwd_threshold; a.fwd_margin = c.fwd_margin;
         a.feet_r2 = c.feet_radius * c.feet_radius; // (the reference: a Python float subtracted from a float32 tensor)
-        const hipError_t e = dp_launch_cons(&a, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("dp_optimize_constrained: kernel launch: ") + hipGetErrorString(e));
         return DP_OK;
-#endif
-    } catch (...) {
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: host-side failure");
-    }
+    };
+    return entry(ctx, who, [&] {
+        if (!in || !p_in || !c_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: NULL batch, params, constraints or result");
+        return constrained_impl<dpcons::Args>(ctx, in, p_in, out_in, stream, who, own, dp_launch_cons);
+    });
 }
-
-// include/dragposer_terms.h.  dp_terms as the caller compiled it (first version: up to loss_terms), checked like dp_constraints
-constexpr unsigned TERMS_SIZE_V510 = offsetof(dp_terms, loss_terms) + sizeof(void*);
-static_assert(DP_MAX_TERMS == dpcons::MAX_TERMS, "dp_cons.h's table holds DP_MAX_TERMS terms");
 
 // one term of the table: "" when it is well-formed, otherwise what is wrong with it
 static std::string check_term(const dp_term& t)
@@ -1121,22 +1147,13 @@ static std::string check_term(const dp_term& t)
     return "";
 }
 
+// include/dragposer_terms.h
 extern "C" int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_terms* t_in, const dp_result* out_in, void* stream)
 {
-    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_optimize_terms: ctx is NULL");
-    try {
-        const char* who = "dp_optimize_terms";
-        if (!in || !p_in || !t_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: NULL batch, params, terms or result");
-        dp_params pv; dp_result ov;
-        if (int rc = take_params(ctx, p_in, pv, who)) return rc;
-        if (int rc = take_result(ctx, out_in, ov, who)) return rc;
-        if (t_in->struct_size < TERMS_SIZE_V510 || t_in->struct_size > 4096u || t_in->reserved0 != 0u)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: dp_terms.struct_size is " + std::to_string(t_in->struct_size) + " (reserved0 " +
-                                                 std::to_string(t_in->reserved0) + "), this library expects at least " + std::to_string(TERMS_SIZE_V510) +
-                                                 " and reserved0 = 0  (dp_terms t = DP_TERMS_INIT;)");
+    const char* who = "dp_optimize_terms";
+    const auto own = [&](dpcons::TermArgs& a) -> int {
         dp_terms ts;
-        std::memset(&ts, 0, sizeof(ts));
-        std::memcpy(&ts, t_in, std::min<size_t>(t_in->struct_size, sizeof(ts)));
+        if (int rc = take_sized(ctx, t_in, ts, TERMS_V510, who)) return rc;
         if (ts.n_terms < 0 || ts.n_terms > DP_MAX_TERMS)
             return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: n_terms " + std::to_string(ts.n_terms) + " outside 0..16");
         if (ts.n_terms > 0 && !ts.terms) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: NULL terms with n_terms > 0");
@@ -1150,30 +1167,7 @@ extern "C" int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_param
         }
         if (need_gp && !ts.global_pos)
             return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: global_pos is NULL while an active PLANE or point-DISTANCE term needs it");
-        if (in->n_frames <= 0) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: n_frames must be positive");
-        if (!in->z0 || !in->z_tgt || !in->cur_rot || !in->tgt_pos || !in->tgt_rot || !in->w || !in->tracked)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: NULL input array");
-        if (!(pv.lr > 0.f) || !(pv.beta1 >= 0.f && pv.beta1 < 1.f) || !(pv.beta2 >= 0.f && pv.beta2 < 1.f))
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: bad Adam hyper-parameters");
-        if (!(pv.eps > 0.f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: Adam eps must be > 0");
-#ifdef DP_REF8_BUILD
-        (void)stream;
-        return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize_terms: not part of the test-only library");
-#else
-        if (!ctx->d_vjpimg) return fail(ctx, DP_ERR_DEVICE, "dp_optimize_terms: the context has no device image");
-        DEVICE_GUARD(ctx);
-        dpcons::TermArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.img = ctx->d_vjpimg;
-        a.z0 = in->z0; a.z_tgt = in->z_tgt; a.cur_rot = in->cur_rot; a.tgt_pos = in->tgt_pos; a.tgt_rot = in->tgt_rot; a.w = in->w; a.tracked = in->tracked;
         a.global_pos = need_gp ? ts.global_pos : nullptr;
-        a.z = ov.z; a.z_pre = ov.z_pre; a.pose = ov.pose; a.disp = ov.disp; a.world_disp = ov.world_disp; a.world_rot = ov.world_rot;
-        a.pos = ov.pos; a.rot = ov.rot; a.loss = ov.loss; a.iters = ov.iters; a.status = ov.status;
-        a.n_frames = in->n_frames; a.n_iter = pv.n_iter; a.early_stop = pv.early_stop ? 1 : 0;
-        a.stop_eps_pos = pv.stop_eps_pos; a.stop_eps_rot = pv.stop_eps_rot; a.min_loss_incr = pv.min_loss_incr;
-        a.lam_rot = pv.lambda_rot; a.lam_tmp = pv.lambda_tmp; a.ctmp = 2.f * pv.lambda_tmp / 24.f;
-        a.one_m_b1 = (float)(1.0 - (double)pv.beta1); a.beta2 = pv.beta2; a.one_m_b2 = (float)(1.0 - (double)pv.beta2); a.eps = pv.eps;
-        a.beta1d = pv.beta1; a.beta2d = pv.beta2; a.lrd = pv.lr;
         a.up = ts.up_axis;
         a.n_terms = ts.n_terms; a.need_gp = need_gp ? 1 : 0; a.loss_terms = ts.loss_terms;
         for (int k = 0; k < ts.n_terms; ++k) { // dp_cons.h's T_* layout
@@ -1193,43 +1187,29 @@ extern "C" int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_param
             const float* pf = t.per_frame;
             std::memcpy(w + dpcons::T_ROW, &pf, sizeof(pf));
         }
-        const hipError_t e = dp_launch_terms(&a, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("dp_optimize_terms: kernel launch: ") + hipGetErrorString(e));
         return DP_OK;
-#endif
-    } catch (...) {
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: host-side failure");
-    }
+    };
+    return entry(ctx, who, [&] {
+        if (!in || !p_in || !t_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: NULL batch, params, terms or result");
+        return constrained_impl<dpcons::TermArgs>(ctx, in, p_in, out_in, stream, who, own, dp_launch_terms);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
 // n_steps frames of S sequences in one launch (+ one for the history buffers), see include/dragposer.h
 static int sequence_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
-                         const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out, void* stream)
+                         const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream)
 {
-    if (!ctx) return DP_ERR_INVALID;
-#ifdef DP_REF8_BUILD
-    (void)n_seq; (void)latent; (void)fr; (void)p_in; (void)sk; (void)st; (void)adj; (void)out; (void)stream;
-    return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize_sequence: not part of the test-only library");
-#else
-    if (n_seq <= 0 || !latent || !fr || !p_in || !st || !out) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: bad arguments");
-    dp_params pv;
-    if (int rc = take_params(ctx, p_in, pv, "dp_optimize_sequence")) return rc;
-    const dp_params* p = &pv;
-    dp_seq_results ov;
-    {
-        constexpr unsigned SEQ_RESULTS_SIZE_V500 = offsetof(dp_seq_results, status) + sizeof(void*);
-        if (out->struct_size < SEQ_RESULTS_SIZE_V500 || out->struct_size > 4096u || out->reserved0 != 0u)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: dp_seq_results.struct_size is " + std::to_string(out->struct_size) + ", this library (DP_VERSION " +
-                                                 std::to_string(DP_VERSION) + ") expects at least " + std::to_string(SEQ_RESULTS_SIZE_V500) +
-                                                 " and reserved0 = 0 -- was the caller compiled against a pre-0.5 dragposer.h?  (dp_seq_results r = DP_SEQ_RESULTS_INIT;)");
-        std::memset(&ov, 0, sizeof(ov));
-        std::memcpy(&ov, out, std::min<size_t>(out->struct_size, sizeof(ov)));
-        out = &ov;
-    }
+    const char* who = "dp_optimize_sequence"; // (in every message but the skeleton's own)
+    if (REF8_BUILD) return refuse_ref8(ctx, who);
+    if (n_seq <= 0 || !latent || !fr || !p_in || !st || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: bad arguments");
+    dp_params p;
+    if (int rc = take_params(ctx, p_in, p, who)) return rc;
+    dp_seq_results out;
+    if (int rc = take_sized(ctx, out_in, out, SEQ_RESULTS_V500, who)) return rc;
     if (fr->n_steps <= 0 || !fr->tgt_pos || !fr->tgt_rot || !fr->w || !fr->tracked || !fr->z_tgt)
         return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: NULL input array / n_steps must be positive");
-    if (!st->global_pos || !st->global_rot || !st->latent_buf || !st->disp_buf || !st->heights_buf || !out->hist_scratch)
+    if (!st->global_pos || !st->global_rot || !st->latent_buf || !st->disp_buf || !st->heights_buf || !out.hist_scratch)
         return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: NULL state array / hist_scratch");
     if (st->history < 1 || st->n_heights < 0 || st->n_heights > DP_MAX_HEIGHT_JOINTS)
         return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: history / n_heights out of range");
@@ -1237,34 +1217,26 @@ static int sequence_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_fra
         if (st->height_joints[h] < 0 || st->height_joints[h] >= NJ) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: bad height joint");
     if (adj && (adj->adjust_joint >= NJ || (adj->adjust_joint >= 0 && (adj->adjust_target_joint < 0 || adj->adjust_target_joint >= NJ))))
         return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: bad joint adjustment");
-    if (p->n_iter < 1 || p->n_iter > DP_MAX_ITERS) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: n_iter out of range [1, DP_MAX_ITERS]");
-    if (!(p->lr > 0.f) || !(p->beta1 >= 0.f && p->beta1 < 1.f) || !(p->beta2 >= 0.f && p->beta2 < 1.f))
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: bad Adam hyper-parameters");
-    if (!(p->eps > 0.f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: Adam eps must be > 0 (include/dragposer.h: dp_params.eps)");
+    if (int rc = check_adam(ctx, p, who)) return rc;
     const float* sk_off = nullptr;
     int sk_stride = 0;
     if (sk) {
-        if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, "dp_optimize_sequence_skeleton")) return rc;
-        if (p->kernel == DP_KERNEL_W16)
-            return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize_sequence_skeleton: DP_KERNEL_W16 keeps the bone offsets in per-slot constants; per-frame "
-                                                 "skeletons run on DP_KERNEL_W4 (DP_KERNEL_AUTO takes it)");
-        if (!ctx->d_w4img) return fail(ctx, DP_ERR_DEVICE, "dp_optimize_sequence_skeleton: the context has no device image");
+        who = "dp_optimize_sequence_skeleton";
+        if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
+        if (p.kernel == DP_KERNEL_W16) return refuse_w16_skeleton(ctx, who);
     }
+    if (!ctx->d_w4img) return refuse_no_image(ctx, who);
     KArgs k;
     fill_model_args(ctx, k);
     k.skel = sk_off; k.skel_stride = sk_stride;
     k.z0 = latent; k.z_tgt = fr->z_tgt; k.cur_rot = st->global_rot; k.tgt_pos = fr->tgt_pos; k.tgt_rot = fr->tgt_rot; k.w = fr->w; k.tracked = fr->tracked;
-    k.z = latent; k.pose = out->pose_ret; k.world_rot = out->world_rot; k.iters = out->iters; k.loss = out->loss; k.status = out->status;
-    k.n_frames = n_seq; k.n_iter = p->n_iter; k.mode = 0;
-    k.lam_rot = p->lambda_rot; k.lam_tmp = p->lambda_tmp; k.ctmp = 2.f * p->lambda_tmp / 24.f;
-    k.beta2 = p->beta2; k.one_m_b1 = (float)(1.0 - (double)p->beta1); k.one_m_b2 = (float)(1.0 - (double)p->beta2);
-    k.eps = p->eps;
-    k.early_stop = 1;
-    k.stop_eps_pos = p->stop_eps_pos; k.stop_eps_rot = p->stop_eps_rot; k.min_loss_incr = p->min_loss_incr;
-    fill_adam(k, *p);
+    k.z = latent; k.pose = out.pose_ret; k.world_rot = out.world_rot; k.iters = out.iters; k.loss = out.loss; k.status = out.status;
+    k.n_frames = n_seq; k.mode = 0;
+    fill_loop(k, p, true);
+    fill_adam(k, p);
     SeqK& q = k.seq;
     q.n_steps = fr->n_steps; q.z_tgt_step = fr->z_tgt_step; q.z_tgt_seq = fr->z_tgt_seq; q.tgt_root = fr->tgt_root;
-    q.global_pos = st->global_pos; q.global_rot = st->global_rot; q.hist = out->hist_scratch; q.pos_ret = out->pos_ret;
+    q.global_pos = st->global_pos; q.global_rot = st->global_rot; q.hist = out.hist_scratch; q.pos_ret = out.pos_ret;
     q.n_heights = st->n_heights;
     for (int h = 0; h < st->n_heights; ++h) q.height_joints[h] = st->height_joints[h];
     q.adjust_joint = adj ? adj->adjust_joint : -1;
@@ -1276,16 +1248,16 @@ static int sequence_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_fra
     DEVICE_GUARD(ctx);
     HistArgs h;
     h.n_seq = n_seq; h.n_steps = fr->n_steps; h.history = st->history; h.n_heights = st->n_heights;
-    h.scratch = out->hist_scratch; h.latent_buf = st->latent_buf; h.disp_buf = st->disp_buf; h.heights_buf = st->heights_buf;
+    h.scratch = out.hist_scratch; h.latent_buf = st->latent_buf; h.disp_buf = st->disp_buf; h.heights_buf = st->heights_buf;
     hipError_t e = dp_launch_sequence_history(&h, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("history launch: ") + hipGetErrorString(e));
     return DP_OK;
-#endif
 }
 
 extern "C" int dp_optimize_sequence(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_seq_state* st,
                                     const dp_seq_step* adj, const dp_seq_results* out, void* stream)
 {
+    if (!ctx) return DP_ERR_INVALID;
     return sequence_impl(ctx, n_seq, latent, fr, p_in, nullptr, st, adj, out, stream);
 }
 
@@ -1293,37 +1265,31 @@ extern "C" int dp_optimize_sequence(dp_ctx* ctx, int n_seq, float* latent, const
 // include/dragposer_skeleton.h: the three calls above with per-frame (per-sequence) bone offsets, on the dp_w4sk units
 extern "C" int dp_optimize_skeleton(dp_ctx* ctx, const dp_batch* in, const dp_params* p, const dp_skeleton_in* skel, const dp_result* out, void* stream)
 {
-    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_optimize_skeleton: ctx is NULL");
-    try {
-        if (!skel) return fail(ctx, DP_ERR_INVALID, "dp_optimize_skeleton: the skeleton is NULL");
-        return optimize_impl(ctx, in, p, out, nullptr, stream, skel, "dp_optimize_skeleton");
-    } catch (...) {
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize_skeleton: host-side failure");
-    }
+    const char* who = "dp_optimize_skeleton";
+    return entry(ctx, who, [&] {
+        if (!skel) return refuse_null_skeleton(ctx, who);
+        return optimize_impl(ctx, in, p, out, nullptr, stream, skel, who);
+    });
 }
 
 extern "C" int dp_forward_skeleton(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_skeleton_in* skel, const dp_result* out,
                                    void* stream)
 {
-    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_forward_skeleton: ctx is NULL");
-    try {
-        if (!skel) return fail(ctx, DP_ERR_INVALID, "dp_forward_skeleton: the skeleton is NULL");
-        return forward_impl(ctx, n_frames, z, cur_rot, skel, out, stream, "dp_forward_skeleton");
-    } catch (...) {
-        return fail(ctx, DP_ERR_INVALID, "dp_forward_skeleton: host-side failure");
-    }
+    const char* who = "dp_forward_skeleton";
+    return entry(ctx, who, [&] {
+        if (!skel) return refuse_null_skeleton(ctx, who);
+        return forward_impl(ctx, n_frames, z, cur_rot, skel, out, stream, who);
+    });
 }
 
 extern "C" int dp_optimize_sequence_skeleton(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p, const dp_skeleton_in* skel,
                                              const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out, void* stream)
 {
-    if (!ctx) return fail(nullptr, DP_ERR_INVALID, "dp_optimize_sequence_skeleton: ctx is NULL");
-    try {
-        if (!skel) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_skeleton: the skeleton is NULL");
+    const char* who = "dp_optimize_sequence_skeleton";
+    return entry(ctx, who, [&] {
+        if (!skel) return refuse_null_skeleton(ctx, who);
         return sequence_impl(ctx, n_seq, latent, fr, p, skel, st, adj, out, stream);
-    } catch (...) {
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_skeleton: host-side failure");
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -55,28 +55,20 @@ class LaunchPlan:
     """A dp_optimize call with its arguments already checked and marshalled (LatentOptimizer.plan).  Holds the input and result
     tensors alive; `plan()` launches on torch's current stream of the optimiser's device and returns the result tensors."""
 
-    __slots__ = ("_opt", "_b", "_p", "_r", "results", "_inputs", "_fn", "_dev", "_s")
+    __slots__ = ("_opt", "_b", "_p", "_r", "results", "_inputs", "_fn", "_args")
 
     def __init__(self, opt, batch, params, res, tensors, inputs, skel=None):
         self._opt, self.results, self._inputs = opt, tensors, inputs
         self._b, self._p, self._r = C.byref(batch), C.byref(params), C.byref(res)  # (byref objects keep their structs alive)
-        self._fn, self._dev = opt.lib.dp_optimize, opt.device
-        self._s = None
+        self._fn, self._args = opt.lib.dp_optimize, (self._b, self._p, self._r)
         if skel is not None:  # per-frame skeletons (include/dragposer_skeleton.h)
-            self._s, self._fn = C.byref(skel), opt.lib.dp_optimize_skeleton
+            self._fn, self._args = opt.lib.dp_optimize_skeleton, (self._b, self._p, C.byref(skel), self._r)
 
     def __call__(self):
-        ctx = self._opt.ctx  # (read per call: after LatentOptimizer.close() it is NULL and the library refuses, instead of a freed context being used)
-        if not ctx.value:
+        # (the context is read per call: after LatentOptimizer.close() it is NULL and the library refuses, instead of a freed context being used)
+        if not self._opt.ctx.value:
             raise _lib.DragPoserError(_lib.DP_ERR_INVALID, "LaunchPlan: the optimiser it was made by has been closed")
-        if self._s is not None:
-            rc = self._fn(ctx, self._b, self._p, self._s, self._r, torch.cuda.current_stream(self._dev).cuda_stream)
-            if rc != _lib.DP_OK:
-                self._opt._fail(rc)
-            return self.results
-        rc = self._fn(ctx, self._b, self._p, self._r, torch.cuda.current_stream(self._dev).cuda_stream)
-        if rc != _lib.DP_OK:
-            self._opt._fail(rc)
+        self._opt._call(self._fn, *self._args)
         return self.results
 
 
@@ -130,6 +122,39 @@ class LatentOptimizer:
     def _fail(self, rc):
         msg = self.lib.dp_last_error(self.ctx)
         raise _lib.DragPoserError(rc, msg.decode() if msg else "")
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _call(self, fn, *args):
+        """fn(ctx, *args, torch's current stream), raising what the library reports"""
+        rc = fn(self.ctx, *args, self._stream())
+        if rc != _lib.DP_OK:
+            self._fail(rc)
+
+    def _batch(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked):
+        B, dev = int(z0.shape[0]), self.device
+        batch = _lib.DpBatch()
+        batch.n_frames = B
+        batch.z0 = _check(z0, "z0", (B, LATENT), torch.float32, dev)
+        batch.z_tgt = _check(z_tgt, "z_tgt", (B, LATENT), torch.float32, dev)
+        batch.cur_rot = _check(cur_rot, "cur_rot", (B, 4), torch.float32, dev)
+        batch.tgt_pos = _check(tgt_pos, "tgt_pos", (B, NJ, 3), torch.float32, dev)
+        batch.tgt_rot = _check(tgt_rot, "tgt_rot", (B, NJ, 9), torch.float32, dev)
+        batch.w = _check(w, "w", (B, NJ, 2), torch.float32, dev)
+        batch.tracked = _check(tracked, "tracked", (B, NJ), torch.uint8, dev)
+        return batch
+
+    @staticmethod
+    def _params(n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, max_trackers=0,
+                kernel=_lib.DP_KERNEL_AUTO, early=None):
+        """`early` None: the while-condition runs when any of its three thresholds is given"""
+        if early is None:
+            early = min_loss_incr is not None or stop_eps_pos > 0 or stop_eps_rot > 0
+        return _lib.DpParams(n_iter=int(n_iter), lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, lambda_rot=lambda_rot,
+                             lambda_tmp=lambda_tmp, early_stop=int(early), stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
+                             min_loss_incr=float("-inf") if min_loss_incr is None else min_loss_incr,
+                             max_trackers=int(max_trackers), kernel=kernel)
 
     def allocate_outputs(self, B, names=None):
         """a reusable set of result tensors for `optimize(..., out=...)`"""
@@ -186,10 +211,7 @@ class LatentOptimizer:
         if _debug is not None:
             if offsets is not None:
                 raise ValueError("optimize: the debug dump has no per-frame-skeleton form (offsets)")
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            rc = self.lib.dp_optimize_debug(self.ctx, plan._b, plan._p, plan._r, C.c_void_p(_debug.data_ptr()), stream)
-            if rc != _lib.DP_OK:
-                self._fail(rc)
+            self._call(self.lib.dp_optimize_debug, plan._b, plan._p, plan._r, C.c_void_p(_debug.data_ptr()))
             return plan.results
         return plan()
 
@@ -201,7 +223,6 @@ class LatentOptimizer:
         tensors (read at launch time: refill them in place between calls) into the same result tensors, on torch's current stream --
         a caller that steps the same buffers every frame pays one ctypes call per launch instead of the checks and struct filling."""
         B = int(z0.shape[0])
-        dev = self.device
         skel = None
         if offsets is not None:
             if kernel == "w16":
@@ -210,26 +231,13 @@ class LatentOptimizer:
             skel = self._skeleton(offsets, B, "optimize")
         if validate_targets:
             check_rotation_targets(tgt_rot, tracked)
-        batch = _lib.DpBatch()
-        batch.n_frames = B
-        batch.z0 = _check(z0, "z0", (B, LATENT), torch.float32, dev)
-        batch.z_tgt = _check(z_tgt, "z_tgt", (B, LATENT), torch.float32, dev)
-        batch.cur_rot = _check(cur_rot, "cur_rot", (B, 4), torch.float32, dev)
-        batch.tgt_pos = _check(tgt_pos, "tgt_pos", (B, NJ, 3), torch.float32, dev)
-        batch.tgt_rot = _check(tgt_rot, "tgt_rot", (B, NJ, 9), torch.float32, dev)
-        batch.w = _check(w, "w", (B, NJ, 2), torch.float32, dev)
-        batch.tracked = _check(tracked, "tracked", (B, NJ), torch.uint8, dev)
-        early = min_loss_incr is not None or stop_eps_pos > 0 or stop_eps_rot > 0
-        p = _lib.DpParams(n_iter=int(n_iter), lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, lambda_rot=lambda_rot,
-                          lambda_tmp=lambda_tmp, early_stop=int(early), stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
-                          min_loss_incr=float("-inf") if min_loss_incr is None else min_loss_incr,
-                          max_trackers=int(max_trackers),
-                          kernel={"auto": _lib.DP_KERNEL_AUTO, "w4": _lib.DP_KERNEL_W4, "w16": _lib.DP_KERNEL_W16}[kernel])
+        batch = self._batch(z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked)
+        p = self._params(n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, max_trackers,
+                         {"auto": _lib.DP_KERNEL_AUTO, "w4": _lib.DP_KERNEL_W4, "w16": _lib.DP_KERNEL_W16}[kernel])
         names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS)
         res, tensors = self._outputs(B, names, out)
-        if skel is not None:
-            return LaunchPlan(self, batch, p, res, tensors, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, offsets), skel=skel)
-        return LaunchPlan(self, batch, p, res, tensors, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked))
+        inputs = (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked)
+        return LaunchPlan(self, batch, p, res, tensors, inputs if skel is None else inputs + (offsets,), skel=skel)
 
     def forward(self, z, cur_rot, outputs=("pose", "disp", "world_disp", "world_rot", "pos", "rot"), out=None, offsets=None):
         """decode + FK of z [B,24] under cur_rot [B,4] (no loss, no update).  `offsets` [22,3] / [B,22,3]: per-frame skeletons as in
@@ -239,15 +247,32 @@ class LatentOptimizer:
         zp = _check(z, "z", (B, LATENT), torch.float32, self.device)
         cp = _check(cur_rot, "cur_rot", (B, 4), torch.float32, self.device)
         res, tensors = self._outputs(B, tuple(outputs), out)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        if skel is not None:
-            rc = self.lib.dp_forward_skeleton(self.ctx, B, C.c_void_p(zp), C.c_void_p(cp), C.byref(skel), C.byref(res), stream)
-            if rc != _lib.DP_OK:
-                self._fail(rc)
-            return tensors
-        rc = self.lib.dp_forward(self.ctx, B, C.c_void_p(zp), C.c_void_p(cp), C.byref(res), stream)
-        if rc != _lib.DP_OK:
-            self._fail(rc)
+        fn, tail = (self.lib.dp_forward, (C.byref(res),)) if skel is None else (self.lib.dp_forward_skeleton, (C.byref(skel), C.byref(res)))
+        self._call(fn, B, C.c_void_p(zp), C.c_void_p(cp), *tail)
+        return tensors
+
+    def _optimize_extra(self, fn, inputs, pargs, global_pos, outputs, out, validate_targets, extra, width, gp_error, to_struct):
+        """What optimize_constrained and optimize_terms share: `optimize`'s batch, parameters and results, the per-frame output of their own
+        (`extra` [B, width]) and the root positions some of their terms need (`gp_error`: what to say when those are missing, or None).
+        to_struct(global_pos pointer, `extra`'s pointer) -> (the extension struct, what it keeps alive)."""
+        z0, tgt_rot, tracked = inputs[0], inputs[4], inputs[6]
+        B, dev = int(z0.shape[0]), self.device
+        if validate_targets:
+            check_rotation_targets(tgt_rot, tracked)
+        batch = self._batch(*inputs)
+        p = self._params(*pargs)
+        names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS)
+        res, tensors = self._outputs(B, [n for n in names if n != extra], out)
+        t = out[extra] if out is not None and extra in out else torch.empty(B, width, dtype=torch.float32, device=dev)
+        tensors[extra] = t
+        gp = None
+        if global_pos is not None:
+            gp = _check(global_pos, "global_pos", (B, 3), torch.float32, dev)
+        elif gp_error:
+            raise ValueError(gp_error)
+        s, keep = to_struct(gp, _check(t, extra, (B, width), torch.float32, dev) if width else None)
+        self._call(fn, C.byref(batch), C.byref(p), C.byref(s), C.byref(res))
+        del keep
         return tensors
 
     def optimize_constrained(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, constraints, global_pos=None, n_iter=50, lr=1e-2,
@@ -258,38 +283,11 @@ class LatentOptimizer:
         fp32): the root position before the frame (the reference's current_global_pos), required when the feet_floor term is on.
         Returns `optimize`'s dict plus `loss_extra` [B,4] (the four weighted terms of the last forward pass).  `kernel` is ignored
         (one kernel implements this operator); `validate_targets` as in `optimize`."""
-        B = int(z0.shape[0])
-        dev = self.device
-        if validate_targets:
-            check_rotation_targets(tgt_rot, tracked)
-        batch = _lib.DpBatch()
-        batch.n_frames = B
-        batch.z0 = _check(z0, "z0", (B, LATENT), torch.float32, dev)
-        batch.z_tgt = _check(z_tgt, "z_tgt", (B, LATENT), torch.float32, dev)
-        batch.cur_rot = _check(cur_rot, "cur_rot", (B, 4), torch.float32, dev)
-        batch.tgt_pos = _check(tgt_pos, "tgt_pos", (B, NJ, 3), torch.float32, dev)
-        batch.tgt_rot = _check(tgt_rot, "tgt_rot", (B, NJ, 9), torch.float32, dev)
-        batch.w = _check(w, "w", (B, NJ, 2), torch.float32, dev)
-        batch.tracked = _check(tracked, "tracked", (B, NJ), torch.uint8, dev)
-        early = min_loss_incr is not None or stop_eps_pos > 0 or stop_eps_rot > 0
-        p = _lib.DpParams(n_iter=int(n_iter), lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, lambda_rot=lambda_rot,
-                          lambda_tmp=lambda_tmp, early_stop=int(early), stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
-                          min_loss_incr=float("-inf") if min_loss_incr is None else min_loss_incr, max_trackers=int(max_trackers))
-        names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS)
-        res, tensors = self._outputs(B, [n for n in names if n != "loss_extra"], out)
-        le = out["loss_extra"] if out is not None and "loss_extra" in out else torch.empty(B, 4, dtype=torch.float32, device=dev)
-        tensors["loss_extra"] = le
-        gp = None
-        if global_pos is not None:
-            gp = _check(global_pos, "global_pos", (B, 3), torch.float32, dev)
-        elif constraints.needs_global_pos:
-            raise ValueError("optimize_constrained: the feet_floor term needs global_pos [B,3]")
-        c = constraints.to_struct(gp, _check(le, "loss_extra", (B, 4), torch.float32, dev))
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = self.lib.dp_optimize_constrained(self.ctx, C.byref(batch), C.byref(p), C.byref(c), C.byref(res), stream)
-        if rc != _lib.DP_OK:
-            self._fail(rc)
-        return tensors
+        return self._optimize_extra(
+            self.lib.dp_optimize_constrained, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked),
+            (n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, max_trackers), global_pos, outputs, out,
+            validate_targets, "loss_extra", 4, "optimize_constrained: the feet_floor term needs global_pos [B,3]" if constraints.needs_global_pos else None,
+            lambda gp, le: (constraints.to_struct(gp, le), None))
 
     def optimize_terms(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, terms, global_pos=None, n_iter=50, lr=1e-2,
                        betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.02, stop_eps_pos=0.0, stop_eps_rot=0.0, min_loss_incr=None,
@@ -299,41 +297,13 @@ class LatentOptimizer:
         the frame, required when an active PLANE or point-DISTANCE term exists.  A term's per-frame rows are its `per_frame` [B,4]
         device tensor.  Returns `optimize`'s dict plus `loss_terms` [B, len(terms)] (each weighted term of the last forward pass).
         `kernel` is ignored; `validate_targets` as in `optimize`."""
-        B = int(z0.shape[0])
-        dev = self.device
         terms.check()
-        if validate_targets:
-            check_rotation_targets(tgt_rot, tracked)
-        batch = _lib.DpBatch()
-        batch.n_frames = B
-        batch.z0 = _check(z0, "z0", (B, LATENT), torch.float32, dev)
-        batch.z_tgt = _check(z_tgt, "z_tgt", (B, LATENT), torch.float32, dev)
-        batch.cur_rot = _check(cur_rot, "cur_rot", (B, 4), torch.float32, dev)
-        batch.tgt_pos = _check(tgt_pos, "tgt_pos", (B, NJ, 3), torch.float32, dev)
-        batch.tgt_rot = _check(tgt_rot, "tgt_rot", (B, NJ, 9), torch.float32, dev)
-        batch.w = _check(w, "w", (B, NJ, 2), torch.float32, dev)
-        batch.tracked = _check(tracked, "tracked", (B, NJ), torch.uint8, dev)
-        early = min_loss_incr is not None or stop_eps_pos > 0 or stop_eps_rot > 0
-        p = _lib.DpParams(n_iter=int(n_iter), lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, lambda_rot=lambda_rot,
-                          lambda_tmp=lambda_tmp, early_stop=int(early), stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
-                          min_loss_incr=float("-inf") if min_loss_incr is None else min_loss_incr, max_trackers=int(max_trackers))
-        names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS)
-        res, tensors = self._outputs(B, [n for n in names if n != "loss_terms"], out)
-        n = len(terms)
-        lt = out["loss_terms"] if out is not None and "loss_terms" in out else torch.empty(B, n, dtype=torch.float32, device=dev)
-        tensors["loss_terms"] = lt
-        gp = None
-        if global_pos is not None:
-            gp = _check(global_pos, "global_pos", (B, 3), torch.float32, dev)
-        elif terms.needs_global_pos:
-            raise ValueError("optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]")
-        s, keep = terms.to_struct(B, dev, gp, _check(lt, "loss_terms", (B, n), torch.float32, dev) if n else None)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = self.lib.dp_optimize_terms(self.ctx, C.byref(batch), C.byref(p), C.byref(s), C.byref(res), stream)
-        del keep
-        if rc != _lib.DP_OK:
-            self._fail(rc)
-        return tensors
+        return self._optimize_extra(
+            self.lib.dp_optimize_terms, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked),
+            (n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, max_trackers), global_pos, outputs, out,
+            validate_targets, "loss_terms", len(terms),
+            "optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]" if terms.needs_global_pos else None,
+            lambda gp, lt: terms.to_struct(int(z0.shape[0]), self.device, gp, lt))
 
     def forward_vjp(self, z, cur_rot, grads, out=None, offsets=None, doffsets=False):
         """dL/dz [B,24] and dL/dcur_rot [B,4] of decode + FK at (z, cur_rot) for upstream gradients `grads` = {output name: dL/d(that
@@ -363,19 +333,12 @@ class LatentOptimizer:
             t = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
             _check(t, name, shape, dtype, dev)
             res[name] = t
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if skel is not None:
-            rc = self.lib.dp_forward_vjp_skeleton(self.ctx, B, C.c_void_p(zp), C.c_void_p(cp), C.byref(skel), C.byref(g),
-                                                  C.c_void_p(res["dz"].data_ptr()), C.c_void_p(res["dcur_rot"].data_ptr()),
-                                                  C.c_void_p(res["doffsets"].data_ptr() if want_doff else None),
-                                                  C.c_void_p(res["status"].data_ptr()), stream)
-            if rc != _lib.DP_OK:
-                self._fail(rc)
-            return res
-        rc = self.lib.dp_forward_vjp(self.ctx, B, C.c_void_p(zp), C.c_void_p(cp), C.byref(g), C.c_void_p(res["dz"].data_ptr()),
-                                     C.c_void_p(res["dcur_rot"].data_ptr()), C.c_void_p(res["status"].data_ptr()), stream)
-        if rc != _lib.DP_OK:
-            self._fail(rc)
+        ptr = {name: C.c_void_p(t.data_ptr()) for name, t in res.items()}
+        if skel is None:
+            fn, args = self.lib.dp_forward_vjp, (C.byref(g), ptr["dz"], ptr["dcur_rot"], ptr["status"])
+        else:
+            fn, args = self.lib.dp_forward_vjp_skeleton, (C.byref(skel), C.byref(g), ptr["dz"], ptr["dcur_rot"], ptr.get("doffsets"), ptr["status"])
+        self._call(fn, B, C.c_void_p(zp), C.c_void_p(cp), *args)
         return res
 
     def sequence_advance(self, frame, global_pos, global_rot, latent_buf, disp_buf, heights_buf, height_joints, pose_ret=None,
@@ -409,80 +372,64 @@ class LatentOptimizer:
             step.pose_ret = _check(pose_ret, "pose_ret", (S, 88), torch.float32, dev)
         if pos_ret is not None:
             step.pos_ret = _check(pos_ret, "pos_ret", (S, 3), torch.float32, dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = self.lib.dp_sequence_advance(self.ctx, S, C.byref(res), C.byref(st), C.byref(step), stream)
-        if rc != _lib.DP_OK:
-            self._fail(rc)
+        self._call(self.lib.dp_sequence_advance, S, C.byref(res), C.byref(st), C.byref(step))
 
-
-def _optimize_sequence(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
-                       heights_buf, height_joints, n_iter=100, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.0,
-                       stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
-                       loss=None, scratch=None, status=None, offsets=None):
-    """T consecutive frames of S sequences in one launch (include/dragposer.h: dp_optimize_sequence): the optimise loop with the
-    reference's while-condition and run()'s epilogue per frame, state carried on the device.  tgt_pos [T,S,22,3] / tgt_rot
-    [T,S,22,9] dense per joint; tgt_root [T,S,3] or None (position targets are then tgt_pos + (tgt_root[t] - running global
-    position), eval_drag.py:186-199); w [S,22,2], tracked [S,22]; z_tgt any fp32 device tensor addressed with `z_tgt_strides` =
-    (floats between steps, floats between sequences).  `latent` [S,24], `global_pos`, `global_rot` and the three history
-    buffers are updated IN PLACE.  Returns dict(pose_ret [T,S,88], pos_ret [T,S,3], iters [T,S], loss [T,S,3], status [T,S]: DP_STATUS_* bits).
-    `offsets` [22,3] / [S,22,3]: one skeleton for every sequence / one per sequence, kept for every step (dp_optimize_sequence_skeleton,
-    include/dragposer_skeleton.h); None = the context's."""
-    T, S = int(tgt_pos.shape[0]), int(tgt_pos.shape[1])
-    dev = self.device
-    skel = self._skeleton(offsets, S, "optimize_sequence") if offsets is not None else None
-    H, NH = int(latent_buf.shape[1]), len(height_joints)
-    fr = _lib.DpSeqFrames()
-    fr.n_steps = T
-    fr.tgt_pos = _check(tgt_pos, "tgt_pos", (T, S, NJ, 3), torch.float32, dev)
-    fr.tgt_rot = _check(tgt_rot, "tgt_rot", (T, S, NJ, 9), torch.float32, dev)
-    fr.tgt_root = _check(tgt_root, "tgt_root", (T, S, 3), torch.float32, dev) if tgt_root is not None else None
-    fr.w = _check(w, "w", (S, NJ, 2), torch.float32, dev)
-    fr.tracked = _check(tracked, "tracked", (S, NJ), torch.uint8, dev)
-    if z_tgt.device != dev or z_tgt.dtype != torch.float32:
-        raise ValueError("z_tgt: expected an fp32 tensor on the optimiser's device")
-    fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = z_tgt.data_ptr(), int(z_tgt_strides[0]), int(z_tgt_strides[1])
-    st = _lib.DpSeqState()
-    st.global_pos = _check(global_pos, "global_pos", (S, 3), torch.float32, dev)
-    st.global_rot = _check(global_rot, "global_rot", (S, 4), torch.float32, dev)
-    st.latent_buf = _check(latent_buf, "latent_buf", (S, H, LATENT), torch.float32, dev)
-    st.disp_buf = _check(disp_buf, "disp_buf", (S, H, 3), torch.float32, dev)
-    st.heights_buf = _check(heights_buf, "heights_buf", (S, H, NH), torch.float32, dev)
-    st.history, st.n_heights = H, NH
-    for i, j in enumerate(height_joints):
-        st.height_joints[i] = int(j)
-    step = _lib.DpSeqStep()
-    step.adjust_joint = -1
-    if adjust is not None:
-        step.adjust_joint, step.adjust_target_joint, step.adjust_weight = int(adjust[0]), int(adjust[1]), float(adjust[2])
-    res = _lib.DpSeqResults()
-    outs = {}
-    res.world_rot = None
-    for name, t, shape, dtype in (("pose_ret", pose_ret, (T, S, 88), torch.float32), ("pos_ret", pos_ret, (T, S, 3), torch.float32),
-                                  ("iters", iters, (T, S), torch.int32), ("loss", loss, (T, S, 3), torch.float32),
-                                  ("status", status, (T, S), torch.int32)):
-        t = t if t is not None else torch.empty(shape, dtype=dtype, device=dev)
-        setattr(res, name, _check(t, name, shape, dtype, dev))
-        outs[name] = t
-    scratch = scratch if scratch is not None else torch.empty(T, S, LATENT + 3 + NH, device=dev)
-    res.hist_scratch = _check(scratch, "scratch", (T, S, LATENT + 3 + NH), torch.float32, dev)
-    p = _lib.DpParams(n_iter=int(n_iter), lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, lambda_rot=lambda_rot, lambda_tmp=lambda_tmp,
-                      early_stop=1, stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
-                      min_loss_incr=float("-inf") if min_loss_incr is None else min_loss_incr, max_trackers=0, kernel=_lib.DP_KERNEL_AUTO)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    if skel is not None:
-        rc = self.lib.dp_optimize_sequence_skeleton(self.ctx, S, C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev)), C.byref(fr),
-                                                    C.byref(p), C.byref(skel), C.byref(st), C.byref(step), C.byref(res), stream)
-        if rc != _lib.DP_OK:
-            self._fail(rc)
+    def optimize_sequence(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
+                          heights_buf, height_joints, n_iter=100, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.0,
+                          stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
+                          loss=None, scratch=None, status=None, offsets=None):
+        """T consecutive frames of S sequences in one launch (include/dragposer.h: dp_optimize_sequence): the optimise loop with the
+        reference's while-condition and run()'s epilogue per frame, state carried on the device.  tgt_pos [T,S,22,3] / tgt_rot
+        [T,S,22,9] dense per joint; tgt_root [T,S,3] or None (position targets are then tgt_pos + (tgt_root[t] - running global
+        position), eval_drag.py:186-199); w [S,22,2], tracked [S,22]; z_tgt any fp32 device tensor addressed with `z_tgt_strides` =
+        (floats between steps, floats between sequences).  `latent` [S,24], `global_pos`, `global_rot` and the three history
+        buffers are updated IN PLACE.  Returns dict(pose_ret [T,S,88], pos_ret [T,S,3], iters [T,S], loss [T,S,3], status [T,S]: DP_STATUS_* bits).
+        `offsets` [22,3] / [S,22,3]: one skeleton for every sequence / one per sequence, kept for every step (dp_optimize_sequence_skeleton,
+        include/dragposer_skeleton.h); None = the context's."""
+        T, S = int(tgt_pos.shape[0]), int(tgt_pos.shape[1])
+        dev = self.device
+        skel = self._skeleton(offsets, S, "optimize_sequence") if offsets is not None else None
+        H, NH = int(latent_buf.shape[1]), len(height_joints)
+        fr = _lib.DpSeqFrames()
+        fr.n_steps = T
+        fr.tgt_pos = _check(tgt_pos, "tgt_pos", (T, S, NJ, 3), torch.float32, dev)
+        fr.tgt_rot = _check(tgt_rot, "tgt_rot", (T, S, NJ, 9), torch.float32, dev)
+        fr.tgt_root = _check(tgt_root, "tgt_root", (T, S, 3), torch.float32, dev) if tgt_root is not None else None
+        fr.w = _check(w, "w", (S, NJ, 2), torch.float32, dev)
+        fr.tracked = _check(tracked, "tracked", (S, NJ), torch.uint8, dev)
+        if z_tgt.device != dev or z_tgt.dtype != torch.float32:
+            raise ValueError("z_tgt: expected an fp32 tensor on the optimiser's device")
+        fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = z_tgt.data_ptr(), int(z_tgt_strides[0]), int(z_tgt_strides[1])
+        st = _lib.DpSeqState()
+        st.global_pos = _check(global_pos, "global_pos", (S, 3), torch.float32, dev)
+        st.global_rot = _check(global_rot, "global_rot", (S, 4), torch.float32, dev)
+        st.latent_buf = _check(latent_buf, "latent_buf", (S, H, LATENT), torch.float32, dev)
+        st.disp_buf = _check(disp_buf, "disp_buf", (S, H, 3), torch.float32, dev)
+        st.heights_buf = _check(heights_buf, "heights_buf", (S, H, NH), torch.float32, dev)
+        st.history, st.n_heights = H, NH
+        for i, j in enumerate(height_joints):
+            st.height_joints[i] = int(j)
+        step = _lib.DpSeqStep()
+        step.adjust_joint = -1
+        if adjust is not None:
+            step.adjust_joint, step.adjust_target_joint, step.adjust_weight = int(adjust[0]), int(adjust[1]), float(adjust[2])
+        res = _lib.DpSeqResults()
+        outs = {}
+        res.world_rot = None
+        for name, t, shape, dtype in (("pose_ret", pose_ret, (T, S, 88), torch.float32), ("pos_ret", pos_ret, (T, S, 3), torch.float32),
+                                      ("iters", iters, (T, S), torch.int32), ("loss", loss, (T, S, 3), torch.float32),
+                                      ("status", status, (T, S), torch.int32)):
+            t = t if t is not None else torch.empty(shape, dtype=dtype, device=dev)
+            setattr(res, name, _check(t, name, shape, dtype, dev))
+            outs[name] = t
+        scratch = scratch if scratch is not None else torch.empty(T, S, LATENT + 3 + NH, device=dev)
+        res.hist_scratch = _check(scratch, "scratch", (T, S, LATENT + 3 + NH), torch.float32, dev)
+        p = self._params(n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, early=True)
+        lp = C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev))
+        tail = (C.byref(st), C.byref(step), C.byref(res))
+        fn, args = (self.lib.dp_optimize_sequence, tail) if skel is None else (self.lib.dp_optimize_sequence_skeleton, (C.byref(skel),) + tail)
+        self._call(fn, S, lp, C.byref(fr), C.byref(p), *args)
         return outs
-    rc = self.lib.dp_optimize_sequence(self.ctx, S, C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev)), C.byref(fr),
-                                       C.byref(p), C.byref(st), C.byref(step), C.byref(res), stream)
-    if rc != _lib.DP_OK:
-        self._fail(rc)
-    return outs
-
-
-LatentOptimizer.optimize_sequence = _optimize_sequence
 
 
 def check_rotation_targets(tgt_rot, tracked, tol=1e-3):

@@ -125,6 +125,33 @@ def test_argument_errors_are_refused_before_any_device_is_touched():
         lib.dp_destroy(ctx)
 
 
+def test_the_plain_entry_points_refuse_a_context_without_a_device_image():
+    """dp_optimize, dp_forward and dp_optimize_sequence, like the calls above: a well-formed call on a context that has no device image is
+    refused with DP_ERR_DEVICE after every argument check (the kernel selector included), before anything of the image is read"""
+    lib = _lib.load()
+    buf = (C.c_float * 4096)()
+    p = C.cast(buf, C.c_void_p).value
+    batch = _lib.DpBatch(n_frames=4, z0=p, z_tgt=p, cur_rot=p, tgt_pos=p, tgt_rot=p, w=p, tracked=p)
+    params = _lib.DpParams(n_iter=10, lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, lambda_rot=1.0)
+    res = _lib.DpResult()
+    fr = _lib.DpSeqFrames(n_steps=2, tgt_pos=p, tgt_rot=p, w=p, tracked=p, z_tgt=p)
+    st = _lib.DpSeqState(global_pos=p, global_rot=p, latent_buf=p, disp_buf=p, heights_buf=p, history=4, n_heights=1)
+    sr = _lib.DpSeqResults(hist_scratch=p)
+    ctx = _host_ctx(lib)
+    try:
+        calls = {"dp_optimize": lambda: lib.dp_optimize(ctx, C.byref(batch), C.byref(params), C.byref(res), None),
+                 "dp_forward": lambda: lib.dp_forward(ctx, 4, p, p, C.byref(res), None),
+                 "dp_optimize_sequence": lambda: lib.dp_optimize_sequence(ctx, 4, p, C.byref(fr), C.byref(params), C.byref(st), None, C.byref(sr), None)}
+        for who, call in calls.items():
+            assert call() == _lib.DP_ERR_DEVICE, who
+            assert lib.dp_last_error(ctx).decode() == who + ": the context has no device image"
+        bad = _lib.DpParams(n_iter=10, lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, lambda_rot=1.0, kernel=7)
+        assert lib.dp_optimize(ctx, C.byref(batch), C.byref(bad), C.byref(res), None) == _lib.DP_ERR_INVALID
+        assert "unknown kernel selector" in lib.dp_last_error(ctx).decode()
+    finally:
+        lib.dp_destroy(ctx)
+
+
 def test_the_test_only_library_declines():
     if not os.path.exists(G.REF8_LIB):
         pytest.skip("test-only library not built")
