@@ -144,7 +144,7 @@ class DpGradIn(_Sized):
 
 
 # every symbol include/dragposer_constraints.h declares (tests/test_constraints_abi.py)
-CONSTRAINT_SYMBOLS = ("dp_optimize_constrained",)
+CONSTRAINT_SYMBOLS = ("dp_optimize_constrained", "dp_optimize_constrained_skeleton")
 
 
 class DpConstraints(_Sized):
@@ -165,7 +165,7 @@ class DpConstraints(_Sized):
 
 
 # every symbol include/dragposer_terms.h declares (tests/test_terms_abi.py)
-TERM_SYMBOLS = ("dp_optimize_terms",)
+TERM_SYMBOLS = ("dp_optimize_terms", "dp_optimize_terms_skeleton")
 DP_MAX_TERMS = 16
 DP_TERM_PLANE, DP_TERM_DISTANCE, DP_TERM_ALIGN = 1, 2, 3
 DP_TERM_ONE_SIDED, DP_TERM_DROP_UP = 1, 2
@@ -245,6 +245,10 @@ def load(path=None):
     lib.dp_optimize_constrained.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpConstraints), C.POINTER(DpResult),
                                             C.c_void_p]
     lib.dp_optimize_terms.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpTerms), C.POINTER(DpResult), C.c_void_p]
+    lib.dp_optimize_constrained_skeleton.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpConstraints),
+                                                     C.POINTER(DpSkeletonIn), C.POINTER(DpResult), C.c_void_p]
+    lib.dp_optimize_terms_skeleton.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpTerms), C.POINTER(DpSkeletonIn),
+                                               C.POINTER(DpResult), C.c_void_p]
     lib.dp_optimize_skeleton.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpSkeletonIn), C.POINTER(DpResult), C.c_void_p]
     lib.dp_forward_skeleton.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpSkeletonIn), C.POINTER(DpResult), C.c_void_p]
     lib.dp_optimize_sequence_skeleton.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSkeletonIn),

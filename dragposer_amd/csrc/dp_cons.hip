@@ -18,6 +18,7 @@
 // the argument block (dp_optimize_constrained); dp_terms_kernel runs a table of up to 16 PLANE / DISTANCE / ALIGN terms
 // (dp_optimize_terms, include/dragposer_terms.h), staged into LDS with the skeleton tables, its per-frame rows read once per launch into
 // the wave's block, evaluated by a loop over the terms with a wave-uniform switch on the type.
+// dp_cons_skel.hip holds both once more with the bones of each frame's own skeleton (DP_CONS_SKEL 1 of the same body).
 // Rotations: the reference takes quat.from_matrix(G) (x) f for the forward axes; G is a rotation matrix (cur_rot a unit quaternion, as
 // every reference caller passes it), so that is G f, which is what is computed.  The rotation loss is the element-wise |G - T|_F^2 of
 // the reference on the matrices themselves: DP_STATUS_TARGET_NOT_ROTATION is never set by this kernel.
@@ -31,55 +32,9 @@
 
 using namespace dpcons;
 
-#define DEV __device__ __forceinline__
+#include "dp_cons_dev.h"
 
-namespace {
-
-constexpr int NJ = dpvjp::NJ, LAT = dpvjp::LAT, H0 = dpvjp::H0, H1 = dpvjp::H1;
-constexpr int NYU = 4 * NJ + 3; // decoder outputs that are used (the 92nd is not)
-#ifndef UNR
-#define UNR 4 // (the dot products' loops: unrolled further, their loads stay in flight in registers and the frame loop spills)
-#endif
-
-DEV void wave_sync()
-{ // orders this wave's LDS writes before its later LDS reads (other lanes' data); no instruction
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-DEV float wsum(float x)
-{ // sum over lanes 0..31 (every lane that contributes is below 32), result in every lane of the half
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) x += __shfl_xor(x, m, 32);
-    return x;
-}
-
-DEV float uni(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); } // lane 0's value, wave-uniform
-
-// component `up` of a 3-vector without indexing registers at run time (no scratch)
-DEV float comp(const float* v, int up) { return up == 0 ? v[0] : up == 1 ? v[1] : v[2]; }
-DEV void flatten(float* v, int up)
-{ // h(v): the up component set to 0
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = c == up ? 0.f : v[c];
-}
-
-// M v with M row-major 3x3
-DEV void mv(const float* M, const float* v, float* o)
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r) o[r] = M[3 * r] * v[0] + M[3 * r + 1] * v[1] + M[3 * r + 2] * v[2];
-}
-
-// global_pos is read: the floor term is on (four terms) / an active PLANE or point-DISTANCE term exists (table)
-DEV bool reads_gp(const Args& a) { return a.w_floor != 0.f; }
-DEV bool reads_gp(const TermArgs& a) { return a.need_gp != 0; }
-
-DEV int uni_i(int x) { return __builtin_amdgcn_readfirstlane(x); } // (an int the wave holds in every lane)
-
-} // namespace
-
+#define DP_CONS_SKEL 0 // (1: dp_cons_skel.hip)
 
 __global__ __launch_bounds__(WPB * 64) void dp_cons_kernel(Args a)
 #define DP_CONS_TABLE 0

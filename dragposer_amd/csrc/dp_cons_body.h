@@ -2,10 +2,19 @@
 // terms, DP_CONS_TABLE 0) and dp_terms_kernel (the term table, DP_CONS_TABLE 1).  A textual body rather than a function both kernels
 // call: passed through a function, even an inlined one, the argument block is loaded whole at entry and the four-term kernel's code
 // changes (78 -> 122 SGPRs parked in VGPR lanes); included, dp_cons_kernel compiles to the same instructions as before the table existed.
-// Everything but the terms is shared; the #if DP_CONS_TABLE blocks are the only difference.  Helpers: dp_cons.hip.
+// Everything but the terms is shared; the #if DP_CONS_TABLE blocks are the only difference.  Helpers: dp_cons_dev.h.
+// dp_cons_skel.hip includes it twice more under DP_CONS_SKEL 1 (dp_cons_skel_kernel, dp_terms_skel_kernel): the bones are then each frame's
+// own (include/dragposer_skeleton.h), read and screened in the prologue and kept in the wave's block (dp_cons_skel.h) instead of L_OFF.  The
+// #if DP_CONS_SKEL blocks are the only difference; with DP_CONS_SKEL 0 the text compiles to the instructions it gave before they existed.
 {
     constexpr bool TBL = DP_CONS_TABLE;
-    __shared__ __attribute__((aligned(16))) float lds[TBL ? LDS_FLOATS_T : LDS_FLOATS];
+#if DP_CONS_SKEL
+    constexpr int N_LDS = TBL ? SK_LDS_FLOATS_T : SK_LDS_FLOATS, W_STRIDE = TBL ? SK_W_FLOATS_T : SK_W_FLOATS;
+    constexpr int W_SK = TBL ? W_SKEL_T : W_SKEL;
+#else
+    constexpr int N_LDS = TBL ? LDS_FLOATS_T : LDS_FLOATS, W_STRIDE = TBL ? W_FLOATS_T : W_FLOATS;
+#endif
+    __shared__ __attribute__((aligned(16))) float lds[N_LDS];
     const float* __restrict__ W = a.img;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int* par = (int*)(lds + L_PAR);
@@ -21,7 +30,9 @@
     if (tid < NJ) par[tid] = Ti[dpvjp::OFF_PARENT + tid];
     if (tid < NJ + 1) ((int*)(lds + L_CST))[tid] = Ti[dpvjp::OFF_CSTART + tid];
     if (tid < NJ) ((int*)(lds + L_CLS))[tid] = Ti[dpvjp::OFF_CLIST + tid];
+#if !DP_CONS_SKEL
     if (tid < 3 * NJ) lds[L_OFF + tid] = W[dpvjp::OFF_BONE + tid];
+#endif
 #if DP_CONS_TABLE
     for (int i = tid; i < a.n_terms * TW; i += WPB * 64) ((unsigned*)lds)[L_TBL + i] = a.tbl[i];
 #endif
@@ -42,7 +53,7 @@
 
     const long long f = (long long)blockIdx.x * WPB + wv;
     if (f >= a.n_frames) return;
-    float* wb = TBL ? lds + L_WAVE0_T + wv * W_FLOATS_T : lds + L_WAVE0 + wv * W_FLOATS;
+    float* wb = lds + (TBL ? L_WAVE0_T : L_WAVE0) + wv * W_STRIDE;
     float *ZB = wb + W_Z, *HB0 = wb + W_H0, *HB1 = wb + W_H1, *QB = wb + W_Q, *DYB = wb + W_DY, *RB = wb + W_R, *BB = wb + W_B,
           *PB = wb + W_P, *GB = wb + W_G, *GPB = wb + W_GP, *FB = wb + W_F;
     const float nan = __builtin_nanf("");
@@ -60,8 +71,25 @@
     const float z0 = lane < LAT ? a.z0[f * LAT + lane] : 0.f;
     const float zt = lane < LAT ? a.z_tgt[f * LAT + lane] : 0.f;
     const bool trk = jl && a.tracked[f * NJ + j] != 0;
+#if DP_CONS_SKEL
+    // lane j: row j of this frame's skeleton (stride 0: the launch's one) -- its bone for the whole loop, and into the wave's block for the
+    // parents' child-bone loop.  Row 0 is never read.  A component out of range refuses the frame (dp_optimize_skeleton's rule).
+    float off[3] = {0.f, 0.f, 0.f};
+    bool bsk = false;
+    if (jl && j != 0) {
+        const float* __restrict__ sk = a.skel + f * (long long)a.skel_stride; // (64-bit: beyond 2^31 / 66 frames a 32-bit product wraps)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { off[c] = sk[3 * j + c]; bsk = bsk || refused(off[c]); }
+    }
+    if (jl)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) wb[W_SK + 3 * j + c] = off[c];
+#endif
     bool bs = refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]) || refused(gp[0]) || refused(gp[1]) ||
               refused(gp[2]);
+#if DP_CONS_SKEL
+    bs = bs || bsk;
+#endif
     bool bt = refused(zt);
     if (trk) {
 #pragma unroll
@@ -134,11 +162,15 @@
                 muB = lane < NYU - 64 ? W[dpvjp::OFF_MU + oB] : 0.f;
     const int pj = jl ? par[j] : 0;
     const unsigned mysubj = jl ? sub[j] : 0u;
+#if !DP_CONS_SKEL
     float off[3] = {0.f, 0.f, 0.f};
+#endif
     float sdj[4] = {1.f, 1.f, 1.f, 1.f}, muj[4] = {0.f, 0.f, 0.f, 0.f};
     if (jl) {
+#if !DP_CONS_SKEL
 #pragma unroll
         for (int c = 0; c < 3; ++c) off[c] = lds[L_OFF + 3 * j + c];
+#endif
 #pragma unroll
         for (int c = 0; c < 4; ++c) { sdj[c] = W[dpvjp::OFF_SD + 4 * j + c]; muj[c] = W[dpvjp::OFF_MU + 4 * j + c]; }
     }
@@ -530,7 +562,11 @@
             for (int k = cst[j]; k < cst[j + 1]; ++k) { // child bones: M += F_c off_c^T
                 const int c = cls[k];
                 const float F0 = FB[4 * c], F1 = FB[4 * c + 1], F2 = FB[4 * c + 2];
+#if DP_CONS_SKEL
+                const float o0 = wb[W_SK + 3 * c], o1 = wb[W_SK + 3 * c + 1], o2 = wb[W_SK + 3 * c + 2];
+#else
                 const float o0 = lds[L_OFF + 3 * c], o1 = lds[L_OFF + 3 * c + 1], o2 = lds[L_OFF + 3 * c + 2];
+#endif
                 M[0] = fmaf(F0, o0, M[0]); M[1] = fmaf(F0, o1, M[1]); M[2] = fmaf(F0, o2, M[2]);
                 M[3] = fmaf(F1, o0, M[3]); M[4] = fmaf(F1, o1, M[4]); M[5] = fmaf(F1, o2, M[5]);
                 M[6] = fmaf(F2, o0, M[6]); M[7] = fmaf(F2, o1, M[7]); M[8] = fmaf(F2, o2, M[8]);

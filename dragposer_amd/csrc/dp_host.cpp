@@ -18,7 +18,7 @@
 #include "../../include/dragposer_constraints.h"
 #include "../../include/dragposer_terms.h"
 #include "../../include/dragposer_skeleton.h"
-#include "dp_cons.h"
+#include "dp_cons_skel.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
 #include "dp_vjp.h"
@@ -1054,8 +1054,8 @@ extern "C" int dp_forward_vjp_skeleton(dp_ctx* ctx, int n_frames, const float* z
     });
 }
 
-// dp_optimize_constrained (A = dpcons::Args) and dp_optimize_terms (dpcons::TermArgs), whose callers have refused a NULL argument: everything but
-// the entry point's own struct.  own(a) validates that struct and writes its fields into the zeroed argument block -- between the checks of
+// dp_optimize_constrained (A = dpcons::Args), dp_optimize_terms (dpcons::TermArgs) and their per-frame-skeleton forms (dpcons::SkelArgs,
+// dpcons::TermSkelArgs: dp_cons_skel.h), whose callers have refused a NULL argument: everything but the entry point's own structs.  own(a) validates that struct and writes its fields into the zeroed argument block -- between the checks of
 // params / result and those of the batch, which is the order the refusals have.
 static_assert(DP_MAX_TERMS == dpcons::MAX_TERMS, "dp_cons.h's table holds DP_MAX_TERMS terms");
 template <class A, class Own>
@@ -1083,25 +1083,25 @@ static int constrained_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_
     return DP_OK;
 }
 
-// include/dragposer_constraints.h
-extern "C" int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_constraints* c_in, const dp_result* out_in,
-                                       void* stream)
+// include/dragposer_constraints.h: dp_constraints validated and written into the argument block (constrained_impl's own(a)), for
+// dp_optimize_constrained and dp_optimize_constrained_skeleton (who names the caller in the messages)
+static int take_constraints(dp_ctx* ctx, const dp_constraints* c_in, dpcons::Args& a, const char* who)
 {
-    const char* who = "dp_optimize_constrained";
-    const auto own = [&](dpcons::Args& a) -> int {
+    const std::string w = who;
+    {
         dp_constraints c;
         if (int rc = take_sized(ctx, c_in, c, CONS_V510, who)) return rc;
         const float wts[4] = {c.w_feet_floor, c.w_head_hips_forward, c.w_head_hips_colinear, c.w_hips_feet_colinear};
         for (float x : wts)
-            if (!(x >= 0.f && x <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: a weight is negative or not finite");
+            if (!(x >= 0.f && x <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": a weight is negative or not finite");
         const int joints[6] = {c.floor_joints[0], c.floor_joints[1], c.foot_joints[0], c.foot_joints[1], c.head_joint, c.hips_joint};
         for (int jj : joints)
-            if (jj < 0 || jj >= NJ) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: joint index " + std::to_string(jj) + " outside 0..21");
-        if (c.up_axis < 0 || c.up_axis > 2) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: up_axis outside 0..2");
+            if (jj < 0 || jj >= NJ) return fail(ctx, DP_ERR_INVALID, w + ": joint index " + std::to_string(jj) + " outside 0..21");
+        if (c.up_axis < 0 || c.up_axis > 2) return fail(ctx, DP_ERR_INVALID, w + ": up_axis outside 0..2");
         const float rest[7] = {c.floor_level, c.fwd_axis[0], c.fwd_axis[1], c.fwd_axis[2], c.fwd_threshold, c.fwd_margin, c.feet_radius};
         for (float x : rest)
-            if (!(std::fabs(x) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: a constraint parameter is not finite");
-        if (c.w_feet_floor != 0.f && !c.global_pos) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: global_pos is NULL while feet_floor is on");
+            if (!(std::fabs(x) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": a constraint parameter is not finite");
+        if (c.w_feet_floor != 0.f && !c.global_pos) return fail(ctx, DP_ERR_INVALID, w + ": global_pos is NULL while feet_floor is on");
         a.global_pos = c.global_pos;
         a.loss_extra = c.loss_extra;
         a.w_floor = c.w_feet_floor; a.w_fwd = c.w_head_hips_forward; a.w_hcol = c.w_head_hips_colinear; a.w_feet = c.w_hips_feet_colinear;
@@ -1112,10 +1112,34 @@ extern "C" int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp
         a.fwd_thr = c.fwd_threshold; a.fwd_margin = c.fwd_margin;
         a.feet_r2 = c.feet_radius * c.feet_radius; // (the reference: a Python float subtracted from a float32 tensor)
         return DP_OK;
-    };
+    }
+}
+
+extern "C" int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_constraints* c_in, const dp_result* out_in,
+                                       void* stream)
+{
+    const char* who = "dp_optimize_constrained";
+    const auto own = [&](dpcons::Args& a) -> int { return take_constraints(ctx, c_in, a, who); };
     return entry(ctx, who, [&] {
         if (!in || !p_in || !c_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained: NULL batch, params, constraints or result");
         return constrained_impl<dpcons::Args>(ctx, in, p_in, out_in, stream, who, own, dp_launch_cons);
+    });
+}
+
+// the same on dp_cons_skel.hip: the skeleton struct is checked after dp_constraints and before the batch
+extern "C" int dp_optimize_constrained_skeleton(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_constraints* c_in,
+                                                const dp_skeleton_in* skel, const dp_result* out_in, void* stream)
+{
+    const char* who = "dp_optimize_constrained_skeleton";
+    const auto own = [&](dpcons::SkelArgs& a) -> int {
+        if (int rc = take_constraints(ctx, c_in, a, who)) return rc;
+        return take_skeleton(ctx, skel, a.skel, a.skel_stride, who);
+    };
+    return entry(ctx, who, [&] {
+        if (!in || !p_in || !c_in || !out_in)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_constrained_skeleton: NULL batch, params, constraints or result");
+        if (!skel) return refuse_null_skeleton(ctx, who);
+        return constrained_impl<dpcons::SkelArgs>(ctx, in, p_in, out_in, stream, who, own, dp_launch_cons_skel);
     });
 }
 
@@ -1147,26 +1171,27 @@ static std::string check_term(const dp_term& t)
     return "";
 }
 
-// include/dragposer_terms.h
-extern "C" int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_terms* t_in, const dp_result* out_in, void* stream)
+// include/dragposer_terms.h: dp_terms validated and written into the argument block (constrained_impl's own(a)), for dp_optimize_terms and
+// dp_optimize_terms_skeleton (who names the caller in the messages)
+static int take_terms(dp_ctx* ctx, const dp_terms* t_in, dpcons::TermArgs& a, const char* who)
 {
-    const char* who = "dp_optimize_terms";
-    const auto own = [&](dpcons::TermArgs& a) -> int {
+    const std::string nm = who;
+    {
         dp_terms ts;
         if (int rc = take_sized(ctx, t_in, ts, TERMS_V510, who)) return rc;
         if (ts.n_terms < 0 || ts.n_terms > DP_MAX_TERMS)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: n_terms " + std::to_string(ts.n_terms) + " outside 0..16");
-        if (ts.n_terms > 0 && !ts.terms) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: NULL terms with n_terms > 0");
-        if (ts.up_axis < 0 || ts.up_axis > 2) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: up_axis outside 0..2");
+            return fail(ctx, DP_ERR_INVALID, nm + ": n_terms " + std::to_string(ts.n_terms) + " outside 0..16");
+        if (ts.n_terms > 0 && !ts.terms) return fail(ctx, DP_ERR_INVALID, nm + ": NULL terms with n_terms > 0");
+        if (ts.up_axis < 0 || ts.up_axis > 2) return fail(ctx, DP_ERR_INVALID, nm + ": up_axis outside 0..2");
         bool need_gp = false;
         for (int k = 0; k < ts.n_terms; ++k) {
             const dp_term& t = ts.terms[k];
             const std::string why = check_term(t);
-            if (!why.empty()) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: term " + std::to_string(k) + ": " + why);
+            if (!why.empty()) return fail(ctx, DP_ERR_INVALID, nm + ": term " + std::to_string(k) + ": " + why);
             need_gp = need_gp || (t.weight != 0.f && (t.type == DP_TERM_PLANE || (t.type == DP_TERM_DISTANCE && t.joint_b < 0)));
         }
         if (need_gp && !ts.global_pos)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: global_pos is NULL while an active PLANE or point-DISTANCE term needs it");
+            return fail(ctx, DP_ERR_INVALID, nm + ": global_pos is NULL while an active PLANE or point-DISTANCE term needs it");
         a.global_pos = need_gp ? ts.global_pos : nullptr;
         a.up = ts.up_axis;
         a.n_terms = ts.n_terms; a.need_gp = need_gp ? 1 : 0; a.loss_terms = ts.loss_terms;
@@ -1188,10 +1213,31 @@ extern "C" int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_param
             std::memcpy(w + dpcons::T_ROW, &pf, sizeof(pf));
         }
         return DP_OK;
-    };
+    }
+}
+
+extern "C" int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_terms* t_in, const dp_result* out_in, void* stream)
+{
+    const char* who = "dp_optimize_terms";
+    const auto own = [&](dpcons::TermArgs& a) -> int { return take_terms(ctx, t_in, a, who); };
     return entry(ctx, who, [&] {
         if (!in || !p_in || !t_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms: NULL batch, params, terms or result");
         return constrained_impl<dpcons::TermArgs>(ctx, in, p_in, out_in, stream, who, own, dp_launch_terms);
+    });
+}
+
+extern "C" int dp_optimize_terms_skeleton(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_terms* t_in, const dp_skeleton_in* skel,
+                                          const dp_result* out_in, void* stream)
+{
+    const char* who = "dp_optimize_terms_skeleton";
+    const auto own = [&](dpcons::TermSkelArgs& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who)) return rc;
+        return take_skeleton(ctx, skel, a.skel, a.skel_stride, who);
+    };
+    return entry(ctx, who, [&] {
+        if (!in || !p_in || !t_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms_skeleton: NULL batch, params, terms or result");
+        if (!skel) return refuse_null_skeleton(ctx, who);
+        return constrained_impl<dpcons::TermSkelArgs>(ctx, in, p_in, out_in, stream, who, own, dp_launch_terms_skel);
     });
 }
 

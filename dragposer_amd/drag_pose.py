@@ -295,15 +295,17 @@ class DragPose:
         this call); not together with `constraints`.
         `offsets`: the performer's bone offsets, as the reference takes them on every call (drag_pose.py:202) -- [22,3] for every sequence
         or [S,22,3] one per sequence.  The context's own skeleton (or None) runs the launches above unchanged; any other runs the same frame
-        with those bones (dp_optimize_sequence_skeleton, include/dragposer_skeleton.h), not together with `constraints` / `terms`.  Passing
+        with those bones (dp_optimize_sequence_skeleton, include/dragposer_skeleton.h), not together with `constraints` / `terms`: this
+        class does not route that combination; LatentOptimizer.optimize_constrained / optimize_terms take `offsets=` themselves.  Passing
         the same object frame after frame costs one host synchronisation in all (DragPose._skeleton)."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
         skel = self._skeleton(offsets)
         if skel is not None and (constraints is not None or terms is not None):
             raise ValueError("DragPose.run: offsets other than the context's skeleton cannot be combined with " +
-                             ("constraints=" if constraints is not None else "terms=") + ": dp_optimize_constrained / dp_optimize_terms have no "
-                             "per-frame-skeleton form (include/dragposer_skeleton.h); create the DragPose from this skeleton instead")
+                             ("constraints=" if constraints is not None else "terms=") + " here: call LatentOptimizer.optimize_constrained / "
+                             "optimize_terms with offsets= (dp_optimize_constrained_skeleton / dp_optimize_terms_skeleton), or create the "
+                             "DragPose from this skeleton")
         dev, S = self.device, self.S
         squeeze = torch.as_tensor(target_ee_pos).dim() == 2
         tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=dev).reshape(S, -1, 3)

@@ -251,10 +251,11 @@ class LatentOptimizer:
         self._call(fn, B, C.c_void_p(zp), C.c_void_p(cp), *tail)
         return tensors
 
-    def _optimize_extra(self, fn, inputs, pargs, global_pos, outputs, out, validate_targets, extra, width, gp_error, to_struct):
+    def _optimize_extra(self, fn, inputs, pargs, global_pos, outputs, out, validate_targets, extra, width, gp_error, to_struct, skel=None):
         """What optimize_constrained and optimize_terms share: `optimize`'s batch, parameters and results, the per-frame output of their own
         (`extra` [B, width]) and the root positions some of their terms need (`gp_error`: what to say when those are missing, or None).
-        to_struct(global_pos pointer, `extra`'s pointer) -> (the extension struct, what it keeps alive)."""
+        to_struct(global_pos pointer, `extra`'s pointer) -> (the extension struct, what it keeps alive).  `skel`: the dp_skeleton_in of the
+        per-frame-skeleton form of `fn`, which takes it after the extension struct."""
         z0, tgt_rot, tracked = inputs[0], inputs[4], inputs[6]
         B, dev = int(z0.shape[0]), self.device
         if validate_targets:
@@ -271,39 +272,44 @@ class LatentOptimizer:
         elif gp_error:
             raise ValueError(gp_error)
         s, keep = to_struct(gp, _check(t, extra, (B, width), torch.float32, dev) if width else None)
-        self._call(fn, C.byref(batch), C.byref(p), C.byref(s), C.byref(res))
+        self._call(fn, C.byref(batch), C.byref(p), C.byref(s), *(() if skel is None else (C.byref(skel),)), C.byref(res))
         del keep
         return tensors
 
     def optimize_constrained(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, constraints, global_pos=None, n_iter=50, lr=1e-2,
                              betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.02, stop_eps_pos=0.0, stop_eps_rot=0.0,
-                             min_loss_incr=None, max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto"):
+                             min_loss_incr=None, max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto", offsets=None):
         """`optimize` with the reference's extra loss terms (`constraints`: a dragposer_amd.Constraints) added to the loss and to the
         while-condition's total: include/dragposer_constraints.h, dp_optimize_constrained (one launch).  `global_pos` [B,3] (device,
         fp32): the root position before the frame (the reference's current_global_pos), required when the feet_floor term is on.
         Returns `optimize`'s dict plus `loss_extra` [B,4] (the four weighted terms of the last forward pass).  `kernel` is ignored
-        (one kernel implements this operator); `validate_targets` as in `optimize`."""
+        (one kernel implements this operator); `validate_targets` as in `optimize`.
+        `offsets`: the performers' bone offsets, [22,3] for every frame or [B,22,3] one per frame (contiguous fp32 on the device; row 0
+        ignored): dp_optimize_constrained_skeleton; None = the context's skeleton (dp_optimize_constrained, unchanged)."""
+        skel = self._skeleton(offsets, int(z0.shape[0]), "optimize_constrained") if offsets is not None else None
         return self._optimize_extra(
-            self.lib.dp_optimize_constrained, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked),
+            self.lib.dp_optimize_constrained if skel is None else self.lib.dp_optimize_constrained_skeleton, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked),
             (n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, max_trackers), global_pos, outputs, out,
             validate_targets, "loss_extra", 4, "optimize_constrained: the feet_floor term needs global_pos [B,3]" if constraints.needs_global_pos else None,
-            lambda gp, le: (constraints.to_struct(gp, le), None))
+            lambda gp, le: (constraints.to_struct(gp, le), None), skel=skel)
 
     def optimize_terms(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, terms, global_pos=None, n_iter=50, lr=1e-2,
                        betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.02, stop_eps_pos=0.0, stop_eps_rot=0.0, min_loss_incr=None,
-                       max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto"):
+                       max_trackers=0, outputs=None, out=None, validate_targets=False, kernel="auto", offsets=None):
         """`optimize` with a table of user-defined terms (`terms`: a dragposer_amd.Terms) added to the loss and to the while-condition's
         total: include/dragposer_terms.h, dp_optimize_terms (one launch).  `global_pos` [B,3] (device, fp32): the root position before
         the frame, required when an active PLANE or point-DISTANCE term exists.  A term's per-frame rows are its `per_frame` [B,4]
         device tensor.  Returns `optimize`'s dict plus `loss_terms` [B, len(terms)] (each weighted term of the last forward pass).
-        `kernel` is ignored; `validate_targets` as in `optimize`."""
+        `kernel` is ignored; `validate_targets` as in `optimize`.  `offsets` [22,3] / [B,22,3]: per-frame skeletons as in
+        `optimize_constrained` (dp_optimize_terms_skeleton); None = the context's skeleton (dp_optimize_terms, unchanged)."""
+        skel = self._skeleton(offsets, int(z0.shape[0]), "optimize_terms") if offsets is not None else None
         terms.check()
         return self._optimize_extra(
-            self.lib.dp_optimize_terms, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked),
+            self.lib.dp_optimize_terms if skel is None else self.lib.dp_optimize_terms_skeleton, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked),
             (n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, max_trackers), global_pos, outputs, out,
             validate_targets, "loss_terms", len(terms),
             "optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]" if terms.needs_global_pos else None,
-            lambda gp, lt: terms.to_struct(int(z0.shape[0]), self.device, gp, lt))
+            lambda gp, lt: terms.to_struct(int(z0.shape[0]), self.device, gp, lt), skel=skel)
 
     def forward_vjp(self, z, cur_rot, grads, out=None, offsets=None, doffsets=False):
         """dL/dz [B,24] and dL/dcur_rot [B,4] of decode + FK at (z, cur_rot) for upstream gradients `grads` = {output name: dL/d(that

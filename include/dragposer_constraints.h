@@ -24,11 +24,22 @@
  * Returns DP_OK or a negative dp_status and never throws; message: dp_last_error(ctx).  DP_ERR_INVALID: NULL ctx / batch / params /
  * result, a bad struct_size or reserved0, a joint index outside 0..21, up_axis outside 0..2, a negative or non-finite weight, a NULL
  * global_pos while the floor term is on, anything dp_optimize refuses.  DP_ERR_UNSUPPORTED from a library built without the kernel.
+ *
+ * Per-frame skeletons.  dp_optimize_constrained_skeleton is the same call with the performer's bone offsets passed as a dp_skeleton_in
+ * (include/dragposer_skeleton.h): stride 66 = frame f uses skeleton f, stride 0 = one skeleton for the launch; the topology stays the
+ * context's and row 0 of every skeleton is never read.  A frame given the context's own offsets gets dp_optimize_constrained's bits.  A row
+ * 1..21 with a component that is not finite or beyond DP_INPUT_LIMIT refuses that frame: every result NaN, loss_extra included, iters as
+ * for a bad z0, status DP_STATUS_NONFINITE_RESULT | DP_STATUS_BAD_STATE; a frame is a wave that shares nothing, so the other frames are
+ * bit-identical to a launch without the fault.  Refusals, in this order: NULL ctx; NULL batch / params / constraints / result; a NULL
+ * skeleton; what dp_params and dp_result refuse; what dp_constraints refuses (above); the skeleton struct -- a bad struct_size, a non-zero
+ * reserved0, NULL `offsets`, a stride other than 0 or 66 (checked like dp_optimize_skeleton's); what the batch and Adam's parameters
+ * refuse (all DP_ERR_INVALID); then DP_ERR_UNSUPPORTED from a library built without the kernel.
  */
 #ifndef DRAGPOSER_CONSTRAINTS_H
 #define DRAGPOSER_CONSTRAINTS_H
 
 #include "dragposer.h"
+#include "dragposer_skeleton.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -58,6 +69,10 @@ typedef struct dp_constraints {
 
 int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp_params* params, const dp_constraints* cons, const dp_result* out,
                             void* hip_stream);
+
+/* dp_optimize_constrained with per-frame skeletons: frame f uses skeleton f (stride 66) or the single one (stride 0). */
+int dp_optimize_constrained_skeleton(dp_ctx* ctx, const dp_batch* in, const dp_params* params, const dp_constraints* cons,
+                                     const dp_skeleton_in* skel, const dp_result* out, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -22,8 +22,9 @@
  * rounds of 16 frames per CU on a 256-CU device) plain dp_optimize would switch to DP_KERNEL_W16, so such batches run extra rounds
  * of the 4-frames-per-wave kernel (about 1.3x the time of dp_w16 from three rounds on).  DP_KERNEL_W16 is refused
  * (DP_ERR_UNSUPPORTED): its slot map keeps the offsets in per-slot constants.  dp_forward_vjp's per-frame form, with the gradient of the
- * offsets, is dp_forward_vjp_skeleton (include/dragposer_grad.h).  dp_optimize_constrained and dp_optimize_terms read the bones from the
- * context's own image and have no per-frame form.
+ * offsets, is dp_forward_vjp_skeleton (include/dragposer_grad.h).  The per-frame forms of dp_optimize_constrained and dp_optimize_terms are
+ * dp_optimize_constrained_skeleton (include/dragposer_constraints.h) and dp_optimize_terms_skeleton (include/dragposer_terms.h): one frame
+ * per wave there, the frame's bones read in the set-up into the wave's own block; a refused row makes every result of that frame NaN.
  *
  * Returns DP_OK or a negative dp_status and never throws; message: dp_last_error(ctx).  DP_ERR_INVALID: a NULL skeleton or NULL
  * `offsets`, a `stride` other than 0 or 66, a bad struct_size or a non-zero reserved0 (checked like dp_grad_in's), and anything the

@@ -38,11 +38,22 @@
  * within 1e-4 where it is read (a PLANE's normal; a world ALIGN's direction unless a per-frame row replaces it); a zero axis_a (ALIGN) or
  * axis_b (joint-to-joint ALIGN); a NULL global_pos while an active PLANE or point-DISTANCE term exists; anything dp_optimize refuses.
  * DP_ERR_UNSUPPORTED from a library built without the kernel.
+ *
+ * Per-frame skeletons.  dp_optimize_terms_skeleton is the same call with the performer's bone offsets passed as a dp_skeleton_in
+ * (include/dragposer_skeleton.h): stride 66 = frame f uses skeleton f, stride 0 = one skeleton for the launch; the topology stays the
+ * context's and row 0 of every skeleton is never read.  A frame given the context's own offsets gets dp_optimize_terms' bits.  A row 1..21
+ * with a component that is not finite or beyond DP_INPUT_LIMIT refuses that frame: every result NaN, loss_terms included, iters as for a
+ * bad z0, status DP_STATUS_NONFINITE_RESULT | DP_STATUS_BAD_STATE; the other frames are bit-identical to a launch without the fault.
+ * Refusals, in this order: NULL ctx; NULL batch / params / terms / result; a NULL skeleton; what dp_params and dp_result refuse; what
+ * dp_terms and its table refuse (above); the skeleton struct -- a bad struct_size, a non-zero reserved0, NULL `offsets`, a stride other than
+ * 0 or 66 (checked like dp_optimize_skeleton's); what the batch and Adam's parameters refuse (all DP_ERR_INVALID); then
+ * DP_ERR_UNSUPPORTED from a library built without the kernel.
  */
 #ifndef DRAGPOSER_TERMS_H
 #define DRAGPOSER_TERMS_H
 
 #include "dragposer.h"
+#include "dragposer_skeleton.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -81,6 +92,10 @@ typedef struct dp_terms {
 
 int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_params* params, const dp_terms* terms, const dp_result* out,
                       void* hip_stream);
+
+/* dp_optimize_terms with per-frame skeletons: frame f uses skeleton f (stride 66) or the single one (stride 0). */
+int dp_optimize_terms_skeleton(dp_ctx* ctx, const dp_batch* in, const dp_params* params, const dp_terms* terms, const dp_skeleton_in* skel,
+                               const dp_result* out, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,10 @@ integer forward axis in the quaternion's dtype.
 
   tests/golden/cons_s1.npz   256 frames, 6 trackers, 50 iterations at a fixed count
   tests/golden/cons_es.npz   128 frames, 6 trackers, the reference's early stop (eval_drag.py:210-214), at most 100 iterations
+  tests/golden/cons_skel.npz     cons_s1's recipe and draws; frame b on make_goldens.skeleton_set(offsets, B)[b] (stored as `offsets`)
+  tests/golden/cons_skel_es.npz  cons_es's recipe and draws, likewise
+
+Names on the command line choose which files are written; none writes all four.
 """
 import hashlib
 import json
@@ -111,7 +115,8 @@ def build(mod, parents):
     return td, Rec(gm, stub, torch.zeros(24), torch.ones(24), "cpu", "cpu"), stub
 
 
-def run(name, B, n_iter, early_stop, mod, parents, offsets_t):
+def run(name, B, n_iter, early_stop, mod, parents, offsets_t, offsets_frames=None):
+    """offsets_frames [B,22,3]: frame b's skeleton -- its targets are the FK of that skeleton and DragPose.run gets it as `offsets`"""
     td, drag, stub = build(mod, parents)
     Zs, Z0, ZT, CR, _ = MG.draw_recipe(B, False)
     g = torch.Generator().manual_seed(4321)
@@ -125,8 +130,11 @@ def run(name, B, n_iter, early_stop, mod, parents, offsets_t):
                pos=np.zeros((B, MG.NJ, 3), np.float32), rot=np.zeros((B, MG.NJ, 9), np.float32), z_final=np.zeros((B, 24), np.float32),
                z_pre=np.zeros((B, 24), np.float32), iters=np.zeros(B, np.int32), loss_hist=np.full((B, n_iter, 3), np.nan, np.float32),
                extra_hist=np.full((B, n_iter), np.nan, np.float32))
+    if offsets_frames is not None:
+        out["offsets"] = offsets_frames.numpy()
     for b in range(B):
-        pos_t, rot_t, _, _ = MG.forward_fk(drag, td, Zs[b], CR[b], offsets_t)
+        off_b = offsets_t if offsets_frames is None else offsets_frames[b]
+        pos_t, rot_t, _, _ = MG.forward_fk(drag, td, Zs[b], CR[b], off_b)
         tp, tR = pos_t[idx].clone(), rot_t[idx].clone()
         out["w"][b, track] = wtab.numpy()
         out["tracked"][b, track] = 1
@@ -139,7 +147,7 @@ def run(name, B, n_iter, early_stop, mod, parents, offsets_t):
             kw = dict(stop_eps_pos=0.01 * 0.01, stop_eps_rot=0.01, max_iter=n_iter, min_loss_incr=0.00001)
         else:
             kw = dict(stop_eps_pos=0.0, stop_eps_rot=0.0, max_iter=n_iter, min_loss_incr=-float("inf"))
-        drag.run(target_ee_pos=tp, target_ee_rot=tR, mask_joints=idx, weights_joints=wtab, offsets=offsets_t, learning_rate=1e-2,
+        drag.run(target_ee_pos=tp, target_ee_rot=tR, mask_joints=idx, weights_joints=wtab, offsets=off_b, learning_rate=1e-2,
                  lambda_rot=1, lambda_temporal=0.02, temporal_future_window=0, height_indices=[0, 4, 8, 13, 17, 21],
                  joint_adjustment_indices=None, joint_adjustment_weight=0.0, verbose=False, **kw)
         last = drag.rec[-1]
@@ -164,8 +172,16 @@ def main():
     offsets_t = torch.tensor(offsets)
     mod = constrained_module()
     dst = os.path.join(MG.REPO, "tests", "golden")
-    for name, B, n_iter, es in (("cons_s1", 256, 50, False), ("cons_es", 128, 100, True)):
-        np.savez_compressed(os.path.join(dst, name + ".npz"), **run(name, B, n_iter, es, mod, parents, offsets_t))
+    recipes = (("cons_s1", 256, 50, False, False), ("cons_es", 128, 100, True, False),
+               ("cons_skel", 256, 50, False, True), ("cons_skel_es", 128, 100, True, True))
+    unknown = set(sys.argv[1:]) - {r[0] for r in recipes}
+    if unknown:
+        raise SystemExit(f"unknown golden {sorted(unknown)}")
+    for name, B, n_iter, es, skel in recipes:
+        if sys.argv[1:] and name not in sys.argv[1:]:
+            continue
+        frames = MG.skeleton_set(offsets_t, B) if skel else None
+        np.savez_compressed(os.path.join(dst, name + ".npz"), **run(name, B, n_iter, es, mod, parents, offsets_t, frames))
 
 
 if __name__ == "__main__":
