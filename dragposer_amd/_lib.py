@@ -207,6 +207,45 @@ class DpSkeletonIn(_Sized):
     _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("offsets", C.c_void_p), ("stride", C.c_int)]
 
 
+# every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
+ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
+                   "dp_sequence_begin", "dp_debug_encoder_image")
+DP_ENCODER_IN = 176
+
+
+class DpEncoderModel(_Sized):
+    """include/dragposer_encoder.h: dp_encoder_model (host pointers to the checkpoint's encoder tensors)"""
+    _fields_ = [("struct_size", C.c_uint), ("conv_w", _f * 3), ("conv_mask", _f * 3), ("conv_b", _f * 3), ("pool_w", _f * 3),
+                ("f_mu_w", _f), ("f_mu_b", _f), ("f_logvar_w", _f), ("f_logvar_b", _f)]
+
+
+class DpEncoderFolded(C.Structure):
+    _fields_ = [("A0", C.c_float * (112 * 176)), ("c0", C.c_float * 112), ("A1", C.c_float * (72 * 112)), ("c1", C.c_float * 72),
+                ("A2", C.c_float * (48 * 72)), ("c2", C.c_float * 48), ("Ah", C.c_float * (48 * 48)), ("ch", C.c_float * 48)]
+
+
+def encoder_model(arrays):
+    """the checkpoint's encoder tensors (the keys of data/model_dancedb.npz) -> (DpEncoderModel, the arrays its pointers refer to:
+    keep them alive as long as the struct is used)"""
+    import numpy as np
+
+    keep = []
+
+    def arr(key, squeeze=False):
+        a = np.asarray(arrays[key], dtype=np.float32)
+        a = np.ascontiguousarray(a[..., 0] if squeeze else a)
+        keep.append(a)
+        return a.ctypes.data_as(_f)
+
+    m = DpEncoderModel()
+    for l in range(3):
+        m.conv_w[l], m.conv_mask[l] = arr(f"encoder.layers.{l}.0.weight", True), arr(f"encoder.layers.{l}.0.mask", True)
+        m.conv_b[l], m.pool_w[l] = arr(f"encoder.layers.{l}.0.bias"), arr(f"encoder.layers.{l}.1.weight")
+    m.f_mu_w, m.f_mu_b = arr("encoder.f_mu.weight"), arr("encoder.f_mu.bias")
+    m.f_logvar_w, m.f_logvar_b = arr("encoder.f_logvar.weight"), arr("encoder.f_logvar.bias")
+    return m, keep
+
+
 _libs = {}
 
 
@@ -266,6 +305,15 @@ def load(path=None):
     lib.dp_temporal_last_error.restype = C.c_char_p
     lib.dp_temporal_last_error.argtypes = [C.c_void_p]
     lib.dp_temporal_predict.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpSeqState), C.c_int, C.c_void_p, C.c_void_p]
+    lib.dp_fold_encoder.argtypes = [C.POINTER(DpEncoderModel), C.POINTER(DpEncoderFolded)]
+    lib.dp_encoder_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(DpEncoderModel), C.c_int]
+    lib.dp_encoder_destroy.argtypes = [C.c_void_p]
+    lib.dp_encoder_last_error.restype = C.c_char_p
+    lib.dp_encoder_last_error.argtypes = [C.c_void_p]
+    lib.dp_encoder_geometry.argtypes = [C.c_void_p, _i, _i, _i]
+    lib.dp_encode.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    lib.dp_sequence_begin.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(DpSeqState), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dp_debug_encoder_image.argtypes = [C.POINTER(DpEncoderFolded), _f, _i, C.c_int]
     # private test hooks (not part of include/dragposer.h)
     lib.dp_optimize_debug.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpResult),
                                       C.c_void_p, C.c_void_p]

@@ -46,14 +46,15 @@ _RUN_OUTPUTS = ("z", "z_pre", "pose", "disp", "world_disp", "world_rot", "pos", 
 
 class DragPose:
     def __init__(self, generator_model, temporal_model, means_latent, stds_latent, device=None, device_gpu=None, n_sequences=1,
-                 offsets=None, native_temporal=False):
+                 offsets=None, native_temporal=False, native_encoder=False):
         """Argument order of the reference (drag_pose.py:13).  `generator_model` is one of
           * a `LatentOptimizer` (an existing kernel context; `device` arguments are then ignored),
           * None / a path to a model .npz / a dict of its arrays (dragposer_amd.model) -- a context is created on
             `device_gpu` (or `device` if that names a GPU, else cuda:0),
           * the reference's own Generator_Model object, with `offsets` [22,3] (see arrays_from_generator_model).
         `n_sequences`: sequences advancing in lock-step (the reference: 1).  `native_temporal`: run the temporal target
-        block (drag_pose.py:248-292) in one HIP launch (dp_temporal_predict) instead of PyTorch ops around nn.Transformer."""
+        block (drag_pose.py:248-292) in one HIP launch (dp_temporal_predict) instead of PyTorch ops around nn.Transformer.
+        `native_encoder`: set_initial_pose is one HIP launch (dp_sequence_begin, include/dragposer_encoder.h) instead of the PyTorch encoder."""
         if isinstance(generator_model, LatentOptimizer) or hasattr(generator_model, "host_model"):
             optimizer, arrays = generator_model, None
         else:
@@ -72,6 +73,7 @@ class DragPose:
         self.opt = optimizer
         self._arrays = arrays
         self._encoder = None
+        self._native_encoder = bool(native_encoder)
         self.device = optimizer.device
         self.temporal = temporal_model.to(self.device).eval() if temporal_model is not None else None
         self.S = int(n_sequences)
@@ -131,6 +133,8 @@ class DragPose:
         set_initial_state.  `eps` [S,24]: the normal draw to use (the reference takes it from torch's global generator);
         `generator`: a torch.Generator for the draw otherwise."""
         S = self.S
+        if self._native_encoder:
+            return self._begin_native(initial_pose, init_global_pos, initial_global_rot, initial_heights, eps, generator)
         if self._encoder is None:
             self._encoder = (PoseEncoder(arrays=self._arrays) if self._arrays is not None else PoseEncoder()).to(self.device)
         pose = torch.as_tensor(initial_pose, dtype=torch.float32, device=self.device).reshape(S, 176)
@@ -140,6 +144,23 @@ class DragPose:
                 eps = torch.randn((S, LATENT), generator=generator)
             latent = mu + torch.as_tensor(eps, dtype=torch.float32).reshape(S, LATENT).to(self.device) * torch.exp(0.5 * logvar)
         self.set_initial_state(latent, init_global_pos, initial_global_rot, initial_heights)
+
+    def _begin_native(self, initial_pose, init_global_pos, initial_global_rot, initial_heights, eps, generator):
+        """set_initial_pose with native_encoder=True: eps drawn as above, then ONE launch that encodes and fills freshly allocated state"""
+        from .encoder import NativePoseEncoder
+
+        S = self.S
+        if not isinstance(self._encoder, NativePoseEncoder):
+            self._encoder = NativePoseEncoder(arrays=self._arrays, device=self.device) if self._arrays is not None else NativePoseEncoder(device=self.device)
+        if eps is None:
+            eps = torch.randn((S, LATENT), generator=generator)
+        f = lambda t, width: torch.as_tensor(t, dtype=torch.float32, device=self.device).reshape(S, width)
+        o = self._encoder.begin(f(initial_pose, 176), f(eps, LATENT), f(init_global_pos, 3), f(initial_global_rot, 4), f(initial_heights, -1), HISTORY)
+        self.latent, self.current_global_pos, self.current_global_rot = o["latent"], o["global_pos"], o["global_rot"]
+        self.latent_buffer, self.displacement_buffer, self.heights_buffer = o["latent_buf"], o["disp_buf"], o["heights_buf"]
+        self.begin_status = o["status"]  # [S] DP_STATUS_* bits: non-zero where a sequence's initial pose / state was refused
+        self.current_index = 0
+        self.target_latent_buffer = None
 
     def set_initial_state(self, latent, init_global_pos, initial_global_rot, initial_heights):
         """What set_initial_pose leaves behind, with the initial latent given instead of encoded."""
