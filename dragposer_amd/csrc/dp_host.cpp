@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -19,33 +20,35 @@
 #include "../../include/dragposer_terms.h"
 #include "../../include/dragposer_skeleton.h"
 #include "dp_cons_skel.h"
+#include "dp_host_rt.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
 #include "dp_vjp.h"
 #include "dp_w4.h"
 
 using namespace dpl;
+using dprt::DeviceBuf;
+using dprt::DeviceGuard;
+using dprt::fail;
 
 struct dp_ctx {
     int device = -1;
     int n_cu = 256;
-    float* d_wfrag = nullptr;
-    float* d_bias = nullptr;
-    float* d_w4img = nullptr;
-    float* d_w4bias = nullptr;
-    dpw4::Pair* d_w4pairs = nullptr;
+    std::string err;
+    // device memory (DeviceBuf: get() is NULL until uploaded -- a dp_debug_host_ctx context has none)
+    DeviceBuf<float> d_wfrag, d_bias, d_w4img, d_w4bias;
+    DeviceBuf<dpw4::Pair> d_w4pairs;
     bool w4_bp = false; // the w4 image / pairs are in the body-part layout (dp_w4_bp.hip), not the dense one (dp_w4.hip)
     std::vector<float> w4img_h[2], w4bias_h[2]; // host copies of both layouts [dense, body-part] (empty: the model does not fit it),
     std::vector<dpw4::Pair> w4pairs_h[2];       // for dp_debug_set_w4_layout
-    unsigned* d_w16img = nullptr; // 16-frames-per-wave kernel (dp_w16.hip); NULL when the skeleton is not the one its slot map is for
-    float* d_w16bias = nullptr;
-    dpw16::SlotConst* d_w16slots = nullptr;
-    float* d_vjpimg = nullptr; // dp_forward_vjp's image (dp_vjp.h): folded decoder, de-normalisation, bones, skeleton walk
+    DeviceBuf<unsigned> d_w16img; // 16-frames-per-wave kernel (dp_w16.hip); NULL when the skeleton is not the one its slot map is for
+    DeviceBuf<float> d_w16bias;
+    DeviceBuf<dpw16::SlotConst> d_w16slots;
+    DeviceBuf<float> d_vjpimg; // dp_forward_vjp's image (dp_vjp.h): folded decoder, de-normalisation, bones, skeleton walk
     int weight_dtype = DP_WEIGHTS_FP32;
-    ItemConst* d_items = nullptr;
+    DeviceBuf<ItemConst> d_items;
     dp_folded folded;
     std::vector<unsigned> smask;
-    std::string err;
     float mean_q0[4] = {0, 0, 0, 0}, std_q0[4] = {1, 1, 1, 1}; // root quaternion channels (sequence epilogue)
     int last_kernel = 0;   // what the last launch used: 4 = dp_w4.hip (8 in the test-only library, below)
     LaunchPick last_pick{}; // the instantiation the last launch ran, as its launcher recorded it (dp_debug_last_launch)
@@ -61,37 +64,15 @@ constexpr int KERNEL_CHOICE = 8;
 constexpr int KERNEL_CHOICE = 4;
 #endif
 
-static thread_local std::string g_create_err;
+constexpr dp_ctx* NO_HANDLE = nullptr; // (its messages go to the thread-local slot: dp_last_error(NULL))
 
-// Every entry point that touches the device runs on the context's device, whatever the calling thread's current device
-// is, and leaves the caller's current device as it found it (a NULL stream would otherwise launch on the wrong GPU).
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int device)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) ok = hipSetDevice(device) == hipSuccess;
-        else prev = -1; // nothing to restore
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 #define DEVICE_GUARD(ctx)                                                                        \
     DeviceGuard guard_((ctx)->device);                                                           \
     if (!guard_.ok) return fail(ctx, DP_ERR_DEVICE, "cannot select the context's device")
 
-static int fail(dp_ctx* ctx, int code, const std::string& msg)
-{
-    if (ctx) ctx->err = msg; else g_create_err = msg;
-    return code;
-}
-
 extern "C" int dp_version(void) { return DP_VERSION; }
 
-extern "C" const char* dp_last_error(const dp_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
+extern "C" const char* dp_last_error(const dp_ctx* ctx) { return dprt::last_error(ctx); }
 
 // ------------------------------------------------------------------------------------------------
 static float round_bf16(float x)
@@ -115,12 +96,12 @@ static bool model_ptrs_ok(const dp_model* m)
 
 // A0 = (W0*M0) U0 Wf, c0 = (W0*M0) U0 bf + b0, A1 = (W1*M1) U1, A2 = (W2*M2) U2
 // (reference: autoencoder.py:228-234, skeleton.py:120,245 -- no non-linearity between these steps)
-extern "C" int dp_fold_decoder(const dp_model* m, dp_folded* out)
+static int fold_decoder(const dp_model* m, dp_folded* out)
 {
-    if (!model_ptrs_ok(m) || !out) return fail(nullptr, DP_ERR_INVALID, "dp_fold_decoder: NULL pointer in model");
+    if (!model_ptrs_ok(m) || !out) return fail(NO_HANDLE, DP_ERR_INVALID, "dp_fold_decoder: NULL pointer in model");
     const int dims[4] = {24, 40, 60, 92};
     const bool bf = m->weight_dtype == DP_WEIGHTS_BF16;
-    if (m->weight_dtype != DP_WEIGHTS_FP32 && !bf) return fail(nullptr, DP_ERR_INVALID, "dp_fold_decoder: unknown weight_dtype");
+    if (m->weight_dtype != DP_WEIGHTS_FP32 && !bf) return fail(NO_HANDLE, DP_ERR_INVALID, "dp_fold_decoder: unknown weight_dtype");
     auto wq = [&](float x) { return bf ? round_bf16(x) : x; };
     // T = U0 Wf (40x24), tb = U0 bf
     std::vector<double> T(40 * 24), tb(40);
@@ -163,6 +144,8 @@ extern "C" int dp_fold_decoder(const dp_model* m, dp_folded* out)
     }
     return DP_OK;
 }
+// (every exported function whose body can allocate runs inside dprt::shell: nothing is thrown across the C ABI)
+extern "C" int dp_fold_decoder(const dp_model* m, dp_folded* out) { return dprt::shell(NO_HANDLE, "dp_fold_decoder", [&] { return fold_decoder(m, out); }); }
 
 // ------------------------------------------------------------------------------------------------
 // Skeleton-derived layout of the P3 items (see dp_layout.h)
@@ -233,13 +216,13 @@ static float gemm_bias(const dp_folded& f, int g, int row)
 // host-only, exported for the CPU tests: per-wave/per-lane MFMA operand images
 //   wfrag [NWAVE][W_REGS][64], bias [2][64] (rows of c0 / b1, zero padded; b1 row 60 = 1 feeds the
 //   constant-1 column that carries b2), smask [NWAVE][NGEMM] (bit i: step i of the wave's chain is non-zero)
-extern "C" int dp_debug_pack(const dp_folded* f, const int* parents, float* wfrag, float* bias, unsigned* smask)
+static int pack_frags(const dp_folded* f, const int* parents, float* wfrag, float* bias, unsigned* smask)
 {
     if (!f || !parents || !wfrag || !bias || !smask) return DP_ERR_INVALID;
     ItemPlan pl;
     std::string err;
     int rc = plan_items(parents, pl, err);
-    if (rc != DP_OK) return fail(nullptr, rc, err);
+    if (rc != DP_OK) return fail(NO_HANDLE, rc, err);
     std::memset(wfrag, 0, sizeof(float) * NWAVE * W_REGS * 64);
     std::memset(smask, 0, sizeof(unsigned) * NWAVE * NGEMM);
     for (int r = 0; r < 64; ++r) { bias[r] = gemm_bias(*f, G_L0, r); bias[64 + r] = gemm_bias(*f, G_L1, r); }
@@ -262,6 +245,7 @@ extern "C" int dp_debug_pack(const dp_folded* f, const int* parents, float* wfra
     }
     return DP_OK;
 }
+extern "C" int dp_debug_pack(const dp_folded* f, const int* parents, float* wfrag, float* bias, unsigned* smask) { return dprt::shell(NO_HANDLE, "dp_debug_pack", [&] { return pack_frags(f, parents, wfrag, bias, smask); }); }
 
 // host-only, exported for the CPU tests: weight image of the wave-private kernel (dp_w4.h)
 //   img [N_GROUPS][64][4]: step s = 4 g + m of lane l at img[(g * 64 + l) * 4 + m];  bias [4][64]
@@ -285,7 +269,7 @@ static int pack_w4(const dp_folded* f, const dp_model* m, float* img, float* bia
     ItemPlan pl;
     std::string err;
     int rc = plan_items(m->parents, pl, err);
-    if (rc != DP_OK) return fail(nullptr, rc, err);
+    if (rc != DP_OK) return fail(NO_HANDLE, rc, err);
     std::memset(img, 0, sizeof(float) * dpw4::IMG_FLOATS);
     std::memset(bias, 0, sizeof(float) * dpw4::BIAS_FLOATS);
     auto put = [&](int step, int lane, float v) { img[((step >> 2) * 64 + lane) * 4 + (step & 3)] = v; };
@@ -323,7 +307,7 @@ static int pack_w4(const dp_folded* f, const dp_model* m, float* img, float* bia
                 for (int g = 0; g < (blk ? dpw4::BP_NG_B : dpw4::BP_NG_A); ++g) run = run || (blk ? dpw4::BP_GROUPS_B[g] : dpw4::BP_GROUPS_A[g]) == k / 4;
                 if (run) put(s0 + kept++, l, v);
                 else if (v != 0.f)
-                    return fail(nullptr, DP_ERR_UNSUPPORTED, "w4 body-part layout: K-group " + std::to_string(k / 4) + " of item " +
+                    return fail(NO_HANDLE, DP_ERR_UNSUPPORTED, "w4 body-part layout: K-group " + std::to_string(k / 4) + " of item " +
                                                                  std::to_string(it2b[blk]) + " is not zero");
             }
         }
@@ -343,8 +327,8 @@ static int pack_w4(const dp_folded* f, const dp_model* m, float* img, float* bia
     return DP_OK;
 }
 
-extern "C" int dp_debug_pack_w4(const dp_folded* f, const dp_model* m, float* img, float* bias) { return pack_w4(f, m, img, bias, false); }
-extern "C" int dp_debug_pack_w4_bp(const dp_folded* f, const dp_model* m, float* img, float* bias) { return pack_w4(f, m, img, bias, true); }
+extern "C" int dp_debug_pack_w4(const dp_folded* f, const dp_model* m, float* img, float* bias) { return dprt::shell(NO_HANDLE, "dp_debug_pack_w4", [&] { return pack_w4(f, m, img, bias, false); }); }
+extern "C" int dp_debug_pack_w4_bp(const dp_folded* f, const dp_model* m, float* img, float* bias) { return dprt::shell(NO_HANDLE, "dp_debug_pack_w4_bp", [&] { return pack_w4(f, m, img, bias, true); }); }
 
 // host-only, exported for the CPU tests: the body-part placement (dp_w4.h) -- items [2][16] (side, quad; -1 idle), the K-groups of layer 2
 // each block runs [2][15] (-1 beyond BP_NG_A / BP_NG_B)
@@ -360,14 +344,14 @@ extern "C" int dp_debug_w4_bp_layout(int* items, int* groups)
     return DP_OK;
 }
 
-extern "C" int dp_debug_items(const dp_model* m, void* out_items);
+static int items_of(const dp_model* m, void* out_items);
 
 // host-only, exported for the CPU tests: kinematics constants of the wave-private kernel, one dpw4::Pair per lane quad
 static int pairs_w4(const dp_model* m, void* out_pairs, bool bp)
 {
-    if (!model_ptrs_ok(m) || !out_pairs) return fail(nullptr, DP_ERR_INVALID, "dp_debug_pairs_w4: NULL pointer");
+    if (!model_ptrs_ok(m) || !out_pairs) return fail(NO_HANDLE, DP_ERR_INVALID, "dp_debug_pairs_w4: NULL pointer");
     std::vector<ItemConst> items(32);
-    int rc = dp_debug_items(m, items.data());
+    int rc = items_of(m, items.data());
     if (rc != DP_OK) return rc;
     dpw4::Pair* pr = (dpw4::Pair*)out_pairs;
     std::memset(pr, 0, sizeof(dpw4::Pair) * 16);
@@ -392,20 +376,20 @@ static int pairs_w4(const dp_model* m, void* out_pairs, bool bp)
         }
     return DP_OK;
 }
-extern "C" int dp_debug_pairs_w4(const dp_model* m, void* out_pairs /* 16 x 144 B */) { return pairs_w4(m, out_pairs, false); }
-extern "C" int dp_debug_pairs_w4_bp(const dp_model* m, void* out_pairs /* 16 x 144 B */) { return pairs_w4(m, out_pairs, true); }
+extern "C" int dp_debug_pairs_w4(const dp_model* m, void* out_pairs /* 16 x 144 B */) { return dprt::shell(NO_HANDLE, "dp_debug_pairs_w4", [&] { return pairs_w4(m, out_pairs, false); }); }
+extern "C" int dp_debug_pairs_w4_bp(const dp_model* m, void* out_pairs /* 16 x 144 B */) { return dprt::shell(NO_HANDLE, "dp_debug_pairs_w4_bp", [&] { return pairs_w4(m, out_pairs, true); }); }
 
 // host-only, exported for the CPU tests: P3 per-item constants [32]
-extern "C" int dp_debug_items(const dp_model* m, void* out_items /* 32 x 128 B */)
+static int items_of(const dp_model* m, void* out_items /* 32 x 128 B */)
 {
-    if (!model_ptrs_ok(m) || !out_items) return fail(nullptr, DP_ERR_INVALID, "dp_debug_items: NULL pointer");
+    if (!model_ptrs_ok(m) || !out_items) return fail(NO_HANDLE, DP_ERR_INVALID, "dp_debug_items: NULL pointer");
     ItemConst* it = (ItemConst*)out_items;
     std::memset(it, 0, sizeof(ItemConst) * 32);
     const int* par = m->parents;
     ItemPlan pl;
     std::string err;
     int rc = plan_items(par, pl, err);
-    if (rc != DP_OK) return fail(nullptr, rc, err);
+    if (rc != DP_OK) return fail(NO_HANDLE, rc, err);
     unsigned sub[NJ]; // subtree masks
     for (int j = 0; j < NJ; ++j) sub[j] = 1u << j;
     for (int j = NJ - 1; j >= 1; --j) sub[par[j]] |= sub[j];
@@ -430,7 +414,7 @@ extern "C" int dp_debug_items(const dp_model* m, void* out_items /* 32 x 128 B *
             if (id > 0 && pl.first_child[id] >= 0) set_child(c, pl.first_child[id]);
             int chain[NJ], n = 0; // bones on the path root -> id (joint ids, root excluded)
             for (int k = id; k != 0; k = par[k]) chain[n++] = k;
-            if (n > MAX_PATH) return fail(nullptr, DP_ERR_UNSUPPORTED, "kinematic chain deeper than 7 bones");
+            if (n > MAX_PATH) return fail(NO_HANDLE, DP_ERR_UNSUPPORTED, "kinematic chain deeper than 7 bones");
             path = 0;
             for (int i = 0; i < MAX_PATH; ++i) path |= (unsigned long long)(i < n ? chain[i] : SLOT_ZERO) << (5 * i);
         } else if (id == ITEM_DISP) {
@@ -454,6 +438,7 @@ extern "C" int dp_debug_items(const dp_model* m, void* out_items /* 32 x 128 B *
     }
     return DP_OK;
 }
+extern "C" int dp_debug_items(const dp_model* m, void* out_items) { return dprt::shell(NO_HANDLE, "dp_debug_items", [&] { return items_of(m, out_items); }); }
 
 // dp_forward_vjp's image (dp_vjp.h), from the context's folded decoder
 static void pack_vjp(const dp_folded& fd, const dp_model* m, std::vector<float>& img)
@@ -495,166 +480,118 @@ static void pack_vjp(const dp_folded& fd, const dp_model* m, std::vector<float>&
         if (e_ != hipSuccess) return fail(ctx, DP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-extern "C" int dp_create(dp_ctx** out, const dp_model* model, int device)
+// dp_create behind the exception shell.  Order: the arguments, the device (queries only), everything built on the host -- all that can throw --,
+// and only then the device's memory: a flat list of uploads into a context that a unique_ptr owns until *out has it.
+static int create_impl(dp_ctx** out, const dp_model* model, int device)
 {
-    if (!out) return fail(nullptr, DP_ERR_INVALID, "dp_create: out is NULL");
-    *out = nullptr;
-    if (!model_ptrs_ok(model)) return fail(nullptr, DP_ERR_INVALID, "dp_create: NULL pointer in model");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, DP_ERR_DEVICE, "dp_create: no HIP device (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(nullptr, DP_ERR_INVALID, "dp_create: bad device index");
-    hipDeviceProp_t prop;
-    HIP_TRY(nullptr, hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(nullptr, DP_ERR_DEVICE, std::string("dp_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
-
-    dp_ctx* ctx = new dp_ctx();
-    ctx->device = device;
-    ctx->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (!model_ptrs_ok(model)) return fail(NO_HANDLE, DP_ERR_INVALID, "dp_create: NULL pointer in model");
+    int n_cu = 256;
+    if (int rc = dprt::open_device<dp_ctx>("dp_create", device, &n_cu)) return rc;
+    std::unique_ptr<dp_ctx> ctx(new dp_ctx());
+    ctx->n_cu = n_cu;
     for (int k = 0; k < 4; ++k) { ctx->mean_q0[k] = model->mean_q[k]; ctx->std_q0[k] = model->std_q[k]; }
-    int rc = dp_fold_decoder(model, &ctx->folded);
+    int rc = fold_decoder(model, &ctx->folded);
     std::vector<float> wfrag(NWAVE * W_REGS * 64), bfrag(128);
     ctx->smask.assign(NWAVE * NGEMM, 0u);
     std::vector<ItemConst> items(32);
-    if (rc == DP_OK) rc = dp_debug_pack(&ctx->folded, model->parents, wfrag.data(), bfrag.data(), ctx->smask.data());
+    if (rc == DP_OK) rc = pack_frags(&ctx->folded, model->parents, wfrag.data(), bfrag.data(), ctx->smask.data());
     // the w4 family: the body-part layout when the decoder's block sparsity fits it (every K-group it leaves out exactly zero), else dense.
     // Both are packed and kept on the host (dp_debug_set_w4_layout switches between them).
     for (int bp = 0; bp < 2 && rc == DP_OK; ++bp) {
         std::vector<float> img(dpw4::IMG_FLOATS), bias(dpw4::BIAS_FLOATS);
-        const std::string prev_err = g_create_err; // (a model the body-part layout does not fit is no error)
+        const std::string prev_err = dprt::null_slot<dp_ctx>(); // (a model the body-part layout does not fit is no error)
         const int prc = pack_w4(&ctx->folded, model, img.data(), bias.data(), bp == 1);
-        if (prc != DP_OK && bp == 1) { g_create_err = prev_err; continue; }
+        if (prc != DP_OK && bp == 1) { dprt::null_slot<dp_ctx>() = prev_err; continue; }
         rc = prc;
         std::vector<dpw4::Pair> pairs(16);
         if (rc == DP_OK) rc = pairs_w4(model, pairs.data(), bp == 1);
         ctx->w4img_h[bp].swap(img); ctx->w4bias_h[bp].swap(bias); ctx->w4pairs_h[bp].swap(pairs);
     }
     ctx->w4_bp = rc == DP_OK && !ctx->w4img_h[1].empty();
-    const std::vector<float>& w4img = ctx->w4img_h[ctx->w4_bp], &w4bias = ctx->w4bias_h[ctx->w4_bp];
-    const std::vector<dpw4::Pair>& pairs = ctx->w4pairs_h[ctx->w4_bp];
-    if (rc == DP_OK) rc = dp_debug_items(model, items.data());
+    if (rc == DP_OK) rc = items_of(model, items.data());
     const bool w16 = rc == DP_OK && dp_w16_supported(model);
     std::vector<unsigned> w16img(w16 ? dpw16::IMG_U32 : 0);
     std::vector<float> w16bias(dpw16::BIAS_FLOATS);
     std::vector<dpw16::SlotConst> w16slots(dpw16::NTY * 4);
     if (w16) rc = dp_debug_pack_w16(&ctx->folded, model, w16img.data(), w16bias.data(), w16slots.data());
     ctx->weight_dtype = model->weight_dtype;
-    if (rc != DP_OK) { delete ctx; return rc; }
+    if (rc != DP_OK) return rc;
     std::vector<float> vjpimg;
     pack_vjp(ctx->folded, model, vjpimg); // (the skeleton passed plan_items' checks above: parents[j] < j)
-    int prev = 0;
-    hipGetDevice(&prev);
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_wfrag, wfrag.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_bias, bfrag.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_items, items.size() * sizeof(ItemConst));
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w4img, w4img.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w4bias, w4bias.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w4pairs, pairs.size() * sizeof(dpw4::Pair));
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_w4pairs, pairs.data(), pairs.size() * sizeof(dpw4::Pair), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_vjpimg, vjpimg.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_vjpimg, vjpimg.data(), vjpimg.size() * sizeof(float), hipMemcpyHostToDevice);
+
+    ctx->device = device;
+    DeviceGuard guard(device); // (declared before nothing that owns device memory but `ctx`, which a failure below frees first)
+    hipError_t e = guard.ok ? hipSuccess : hipErrorInvalidDevice;
+    const auto up = [&e](auto& buf, const auto& v) { if (e == hipSuccess) e = buf.upload(v); };
+    up(ctx->d_wfrag, wfrag);
+    up(ctx->d_bias, bfrag);
+    up(ctx->d_items, items);
+    up(ctx->d_w4img, ctx->w4img_h[ctx->w4_bp]);
+    up(ctx->d_w4bias, ctx->w4bias_h[ctx->w4_bp]);
+    up(ctx->d_w4pairs, ctx->w4pairs_h[ctx->w4_bp]);
+    up(ctx->d_vjpimg, vjpimg);
     if (w16) {
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w16img, w16img.size() * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w16bias, w16bias.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_w16slots, w16slots.size() * sizeof(dpw16::SlotConst));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_w16img, w16img.data(), w16img.size() * sizeof(unsigned), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_w16bias, w16bias.data(), w16bias.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_w16slots, w16slots.data(), w16slots.size() * sizeof(dpw16::SlotConst), hipMemcpyHostToDevice);
+        up(ctx->d_w16img, w16img);
+        up(ctx->d_w16bias, w16bias);
+        up(ctx->d_w16slots, w16slots);
     }
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_w4img, w4img.data(), w4img.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_w4bias, w4bias.data(), w4bias.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_wfrag, wfrag.data(), wfrag.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_bias, bfrag.data(), bfrag.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_items, items.data(), items.size() * sizeof(ItemConst), hipMemcpyHostToDevice);
-    hipSetDevice(prev);
     if (e != hipSuccess) {
-        std::string msg = std::string("dp_create: ") + hipGetErrorString(e);
-        hipFree(ctx->d_wfrag); hipFree(ctx->d_bias); hipFree(ctx->d_items); hipFree(ctx->d_w4img); hipFree(ctx->d_w4bias); hipFree(ctx->d_w4pairs);
-        hipFree(ctx->d_w16img); hipFree(ctx->d_w16bias); hipFree(ctx->d_w16slots); hipFree(ctx->d_vjpimg);
-        delete ctx;
-        return fail(nullptr, DP_ERR_DEVICE, msg);
+        ctx.reset(); // (under the guard)
+        return fail(NO_HANDLE, DP_ERR_DEVICE, std::string("dp_create: ") + hipGetErrorString(e));
     }
-    *out = ctx;
+    *out = ctx.release();
     return DP_OK;
+}
+
+extern "C" int dp_create(dp_ctx** out, const dp_model* model, int device)
+{
+    if (!out) return fail(NO_HANDLE, DP_ERR_INVALID, "dp_create: out is NULL");
+    *out = nullptr;
+    return dprt::shell(NO_HANDLE, "dp_create", [&] { return create_impl(out, model, device); });
 }
 
 extern "C" int dp_destroy(dp_ctx* ctx)
 {
     if (!ctx) return DP_ERR_INVALID;
-    DeviceGuard guard_(ctx->device);
-    hipFree(ctx->d_wfrag);
-    hipFree(ctx->d_bias);
-    hipFree(ctx->d_items);
-    hipFree(ctx->d_w4img);
-    hipFree(ctx->d_w4bias);
-    hipFree(ctx->d_w4pairs);
-    hipFree(ctx->d_w16img);
-    hipFree(ctx->d_w16bias);
-    hipFree(ctx->d_w16slots);
-    hipFree(ctx->d_vjpimg);
+    DeviceGuard guard(ctx->device);
     delete ctx;
     return DP_OK;
 }
 
+// The dp_io_* helpers: one runtime call each, on the context's device
+template <class Call>
+static int io_call(dp_ctx* ctx, bool args_ok, const char* who, Call call)
+{
+    if (!ctx || !args_ok) return DP_ERR_INVALID;
+    return dprt::shell(ctx, who, [&] {
+        DEVICE_GUARD(ctx);
+        const hipError_t e = call();
+        return e == hipSuccess ? (int)DP_OK : fail(ctx, DP_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    });
+}
 extern "C" int dp_io_alloc(dp_ctx* ctx, unsigned long long bytes, void** dev_ptr)
 {
-    if (!ctx || !dev_ptr) return DP_ERR_INVALID;
-    DEVICE_GUARD(ctx);
-    HIP_TRY(ctx, hipMalloc(dev_ptr, bytes));
-    HIP_TRY(ctx, hipMemset(*dev_ptr, 0, bytes));
-    return DP_OK;
+    return io_call(ctx, dev_ptr, "dp_io_alloc", [&] { const hipError_t e = dprt::device_alloc(dev_ptr, bytes); return e != hipSuccess ? e : hipMemset(*dev_ptr, 0, bytes); });
 }
-
-extern "C" int dp_io_free(dp_ctx* ctx, void* dev_ptr)
-{
-    if (!ctx) return DP_ERR_INVALID;
-    DEVICE_GUARD(ctx);
-    HIP_TRY(ctx, hipFree(dev_ptr));
-    return DP_OK;
-}
-
+extern "C" int dp_io_free(dp_ctx* ctx, void* dev_ptr) { return io_call(ctx, true, "dp_io_free", [&] { return dprt::device_free(dev_ptr); }); }
 extern "C" int dp_io_upload(dp_ctx* ctx, void* dev_dst, const void* host_src, unsigned long long bytes, void* stream)
 {
-    if (!ctx || !dev_dst || !host_src) return DP_ERR_INVALID;
-    DEVICE_GUARD(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(dev_dst, host_src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-    return DP_OK;
+    return io_call(ctx, dev_dst && host_src, "dp_io_upload", [&] { return hipMemcpyAsync(dev_dst, host_src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream); });
 }
-
 extern "C" int dp_io_download(dp_ctx* ctx, void* host_dst, const void* dev_src, unsigned long long bytes, void* stream)
 {
-    if (!ctx || !host_dst || !dev_src) return DP_ERR_INVALID;
-    DEVICE_GUARD(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    return DP_OK;
+    return io_call(ctx, host_dst && dev_src, "dp_io_download", [&] { return hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream); });
 }
-
 extern "C" int dp_io_alloc_host(dp_ctx* ctx, unsigned long long bytes, void** host_ptr)
 {
-    if (!ctx || !host_ptr) return DP_ERR_INVALID;
-    DEVICE_GUARD(ctx);
-    HIP_TRY(ctx, hipHostMalloc(host_ptr, bytes, hipHostMallocDefault));
-    std::memset(*host_ptr, 0, bytes);
-    return DP_OK;
+    return io_call(ctx, host_ptr, "dp_io_alloc_host", [&] {
+        const hipError_t e = dprt::pinned_alloc(host_ptr, bytes);
+        if (e == hipSuccess) std::memset(*host_ptr, 0, bytes);
+        return e;
+    });
 }
-
-extern "C" int dp_io_free_host(dp_ctx* ctx, void* host_ptr)
-{
-    if (!ctx) return DP_ERR_INVALID;
-    DEVICE_GUARD(ctx);
-    HIP_TRY(ctx, hipHostFree(host_ptr));
-    return DP_OK;
-}
-
-extern "C" int dp_stream_sync(dp_ctx* ctx, void* stream)
-{
-    if (!ctx) return DP_ERR_INVALID;
-    DEVICE_GUARD(ctx);
-    HIP_TRY(ctx, hipStreamSynchronize((hipStream_t)stream));
-    return DP_OK;
-}
+extern "C" int dp_io_free_host(dp_ctx* ctx, void* host_ptr) { return io_call(ctx, true, "dp_io_free_host", [&] { return dprt::pinned_free(host_ptr); }); }
+extern "C" int dp_stream_sync(dp_ctx* ctx, void* stream) { return io_call(ctx, true, "dp_stream_sync", [&] { return hipStreamSynchronize((hipStream_t)stream); }); }
 
 extern "C" int dp_kernel_geometry(const dp_ctx* ctx, int* frames_per_block, int* threads_per_block, int* lds_bytes)
 { // of the kernel the context's launches use
@@ -676,15 +613,15 @@ extern "C" int dp_kernel_geometry(const dp_ctx* ctx, int* frames_per_block, int*
 static void fill_model_args(const dp_ctx* ctx, KArgs& k)
 {
     std::memset(&k, 0, sizeof(k));
-    k.wfrag = ctx->d_wfrag;
-    k.bias = ctx->d_bias;
-    k.items = ctx->d_items;
-    k.w4img = ctx->d_w4img;
-    k.w4bias = ctx->d_w4bias;
-    k.w4pairs = ctx->d_w4pairs;
-    k.w16img = ctx->d_w16img;
-    k.w16bias = ctx->d_w16bias;
-    k.w16slots = ctx->d_w16slots;
+    k.wfrag = ctx->d_wfrag.get();
+    k.bias = ctx->d_bias.get();
+    k.items = ctx->d_items.get();
+    k.w4img = ctx->d_w4img.get();
+    k.w4bias = ctx->d_w4bias.get();
+    k.w4pairs = ctx->d_w4pairs.get();
+    k.w16img = ctx->d_w16img.get();
+    k.w16bias = ctx->d_w16bias.get();
+    k.w16slots = ctx->d_w16slots.get();
     std::memcpy(k.smask, ctx->smask.data(), sizeof(k.smask));
 }
 
@@ -811,16 +748,18 @@ static int check_adam(dp_ctx* ctx, const dp_params& p, const char* who)
     return DP_OK;
 }
 
-// The shell of an entry point that reports a NULL context in words: the refusal, and no C++ exception (std::string, std::vector) crosses the C ABI
+// The shell of an entry point that reports a NULL context in words: the refusal, then dprt::shell
 template <class Body>
 static int entry(dp_ctx* ctx, const char* who, Body body)
 {
-    if (!ctx) return fail(nullptr, DP_ERR_INVALID, std::string(who) + ": ctx is NULL");
-    try {
-        return body();
-    } catch (...) {
-        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": host-side failure");
-    }
+    if (!ctx) return dprt::shell(NO_HANDLE, who, [&] { return fail(NO_HANDLE, DP_ERR_INVALID, std::string(who) + ": ctx is NULL"); });
+    return dprt::shell(ctx, who, body);
+}
+// ... and of the entry points older than that, which refuse a NULL context by the code alone
+template <class Body>
+static int entry_quiet(dp_ctx* ctx, const char* who, Body body)
+{
+    return ctx ? dprt::shell(ctx, who, body) : (int)DP_ERR_INVALID;
 }
 
 // The test-only library (DP_REF8_BUILD) has the round-1 kernel behind dp_optimize and dp_forward only: every other launch is refused, after its
@@ -875,14 +814,16 @@ extern "C" int dp_debug_set_w4_layout(dp_ctx* ctx, int bp)
 {
     if (!ctx || bp < -1 || bp > 1) return DP_ERR_INVALID;
     if (bp < 0) return ctx->w4_bp ? 1 : 0;
-    if (ctx->w4img_h[bp].empty()) return fail(ctx, DP_ERR_UNSUPPORTED, "dp_debug_set_w4_layout: the model does not fit the body-part layout");
-    DEVICE_GUARD(ctx);
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(ctx->d_w4img, ctx->w4img_h[bp].data(), ctx->w4img_h[bp].size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_w4bias, ctx->w4bias_h[bp].data(), ctx->w4bias_h[bp].size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_w4pairs, ctx->w4pairs_h[bp].data(), ctx->w4pairs_h[bp].size() * sizeof(dpw4::Pair), hipMemcpyHostToDevice));
-    ctx->w4_bp = bp == 1;
-    return bp;
+    return dprt::shell(ctx, "dp_debug_set_w4_layout", [&] {
+        if (ctx->w4img_h[bp].empty()) return fail(ctx, DP_ERR_UNSUPPORTED, "dp_debug_set_w4_layout: the model does not fit the body-part layout");
+        DEVICE_GUARD(ctx);
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        HIP_TRY(ctx, hipMemcpy(ctx->d_w4img.get(), ctx->w4img_h[bp].data(), ctx->w4img_h[bp].size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(ctx->d_w4bias.get(), ctx->w4bias_h[bp].data(), ctx->w4bias_h[bp].size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(ctx->d_w4pairs.get(), ctx->w4pairs_h[bp].data(), ctx->w4pairs_h[bp].size() * sizeof(dpw4::Pair), hipMemcpyHostToDevice));
+        ctx->w4_bp = bp == 1;
+        return bp;
+    });
 }
 
 // include/dragposer_skeleton.h: dp_skeleton_in as the caller compiled it (the entry point has refused a NULL one) -> what goes into
@@ -927,7 +868,7 @@ static int optimize_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in,
         return fail(ctx, DP_ERR_INVALID, std::string(who) + ": unknown kernel selector");
     if (sk && p.kernel == DP_KERNEL_W16) return refuse_w16_skeleton(ctx, who);
     if (sk && REF8_BUILD) return refuse_ref8(ctx, who);
-    if (!ctx->d_w4img) return refuse_no_image(ctx, who);
+    if (!ctx->d_w4img.get()) return refuse_no_image(ctx, who);
     KArgs k;
     fill_model_args(ctx, k);
     fill_batch(k, *in);
@@ -939,7 +880,7 @@ static int optimize_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in,
     fill_adam(k, p);
     k.skel = sk_off; k.skel_stride = sk_stride;
     if (sk) return launch(ctx, k, stream, DP_KERNEL_W4, true);
-    if (p.kernel == DP_KERNEL_W16 && !ctx->d_w16img)
+    if (p.kernel == DP_KERNEL_W16 && !ctx->d_w16img.get())
         return fail(ctx, DP_ERR_UNSUPPORTED, "dp_optimize: DP_KERNEL_W16 is laid out for the reference's 22-joint skeleton only");
     // (beyond the argument table of Adam scalars, n_iter > 256, both kernels have LONG instantiations that continue them on the device)
     return launch(ctx, k, stream, p.kernel == DP_KERNEL_AUTO ? dp_auto_kernel(ctx, in->n_frames) : p.kernel);
@@ -949,8 +890,7 @@ static int optimize_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in,
 // [B][240] = y(104) | dL/dy(104) | dL/dz(24) | pad, all of iteration 0.
 extern "C" int dp_optimize_debug(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_result* out_in, float* dbg, void* stream)
 {
-    if (!ctx) return DP_ERR_INVALID;
-    return optimize_impl(ctx, in, p_in, out_in, dbg, stream, nullptr, "dp_optimize");
+    return entry_quiet(ctx, "dp_optimize", [&] { return optimize_impl(ctx, in, p_in, out_in, dbg, stream, nullptr, "dp_optimize"); });
 }
 
 extern "C" int dp_auto_kernel(const dp_ctx* ctx, int n_frames)
@@ -962,7 +902,7 @@ extern "C" int dp_auto_kernel(const dp_ctx* ctx, int n_frames)
     // more than TWO rounds of dp_w4's 16 frames per CU: dp_w16 (where its slot map fits the skeleton).  Up to two rounds dp_w4 is the faster one
     // since round 5 (its waves' staggered start: 0.252 ms for 8192 frames against dp_w16's 0.273 at the steady clock, 0.251 against 0.274 at 6144,
     // profiles/r05_batch_sweep.txt; equal from an idle GPU); from three rounds on dp_w16 wins by 1.3x and more
-    return ctx->d_w16img != nullptr && n_frames > ctx->n_cu * 32 ? DP_KERNEL_W16 : DP_KERNEL_W4;
+    return ctx->d_w16img.get() != nullptr && n_frames > ctx->n_cu * 32 ? DP_KERNEL_W16 : DP_KERNEL_W4;
 #endif
 }
 
@@ -983,7 +923,7 @@ static int forward_impl(dp_ctx* ctx, int n_frames, const float* z, const float* 
         if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
         if (REF8_BUILD) return refuse_ref8(ctx, who);
     }
-    if (!ctx->d_w4img) return refuse_no_image(ctx, who);
+    if (!ctx->d_w4img.get()) return refuse_no_image(ctx, who);
     KArgs k;
     fill_model_args(ctx, k);
     k.skel = sk_off; k.skel_stride = sk_stride;
@@ -996,8 +936,7 @@ static int forward_impl(dp_ctx* ctx, int n_frames, const float* z, const float* 
 
 extern "C" int dp_forward(dp_ctx* ctx, int n_frames, const float* z, const float* cur_rot, const dp_result* out, void* stream)
 {
-    if (!ctx) return DP_ERR_INVALID;
-    return forward_impl(ctx, n_frames, z, cur_rot, nullptr, out, stream, "dp_forward");
+    return entry_quiet(ctx, "dp_forward", [&] { return forward_impl(ctx, n_frames, z, cur_rot, nullptr, out, stream, "dp_forward"); });
 }
 
 // host-only, exported for the CPU tests: a context with no device and no device memory -- argument checks run on it, every launch is
@@ -1023,10 +962,10 @@ static int vjp_impl(dp_ctx* ctx, int n_frames, const float* z, const float* cur_
     if (sk)
         if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
     if (REF8_BUILD) return refuse_ref8(ctx, who);
-    if (!ctx->d_vjpimg) return refuse_no_image(ctx, who);
+    if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
     DEVICE_GUARD(ctx);
     dpvjp::SkelArgs a;
-    a.img = ctx->d_vjpimg;
+    a.img = ctx->d_vjpimg.get();
     a.z = z; a.cur_rot = cur_rot;
     a.g_pose = gv.pose; a.g_disp = gv.disp; a.g_wdisp = gv.world_disp; a.g_wrot = gv.world_rot; a.g_pos = gv.pos; a.g_rot = gv.rot;
     a.dz = dz; a.dcur = dcur_rot; a.status = status;
@@ -1071,9 +1010,9 @@ static int constrained_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_
     if (int rc = check_batch(ctx, in, who)) return rc;
     if (int rc = check_adam(ctx, p, who)) return rc;
     if (REF8_BUILD) return refuse_ref8(ctx, who);
-    if (!ctx->d_vjpimg) return refuse_no_image(ctx, who);
+    if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
     DEVICE_GUARD(ctx);
-    a.img = ctx->d_vjpimg;
+    a.img = ctx->d_vjpimg.get();
     fill_batch(a, *in);
     fill_results(a, out);
     fill_loop(a, p, p.early_stop != 0);
@@ -1088,31 +1027,29 @@ static int constrained_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_
 static int take_constraints(dp_ctx* ctx, const dp_constraints* c_in, dpcons::Args& a, const char* who)
 {
     const std::string w = who;
-    {
-        dp_constraints c;
-        if (int rc = take_sized(ctx, c_in, c, CONS_V510, who)) return rc;
-        const float wts[4] = {c.w_feet_floor, c.w_head_hips_forward, c.w_head_hips_colinear, c.w_hips_feet_colinear};
-        for (float x : wts)
-            if (!(x >= 0.f && x <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": a weight is negative or not finite");
-        const int joints[6] = {c.floor_joints[0], c.floor_joints[1], c.foot_joints[0], c.foot_joints[1], c.head_joint, c.hips_joint};
-        for (int jj : joints)
-            if (jj < 0 || jj >= NJ) return fail(ctx, DP_ERR_INVALID, w + ": joint index " + std::to_string(jj) + " outside 0..21");
-        if (c.up_axis < 0 || c.up_axis > 2) return fail(ctx, DP_ERR_INVALID, w + ": up_axis outside 0..2");
-        const float rest[7] = {c.floor_level, c.fwd_axis[0], c.fwd_axis[1], c.fwd_axis[2], c.fwd_threshold, c.fwd_margin, c.feet_radius};
-        for (float x : rest)
-            if (!(std::fabs(x) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": a constraint parameter is not finite");
-        if (c.w_feet_floor != 0.f && !c.global_pos) return fail(ctx, DP_ERR_INVALID, w + ": global_pos is NULL while feet_floor is on");
-        a.global_pos = c.global_pos;
-        a.loss_extra = c.loss_extra;
-        a.w_floor = c.w_feet_floor; a.w_fwd = c.w_head_hips_forward; a.w_hcol = c.w_head_hips_colinear; a.w_feet = c.w_hips_feet_colinear;
-        a.floor_j[0] = c.floor_joints[0]; a.floor_j[1] = c.floor_joints[1]; a.foot_j[0] = c.foot_joints[0]; a.foot_j[1] = c.foot_joints[1];
-        a.head = c.head_joint; a.hips = c.hips_joint; a.up = c.up_axis; a.one_sided = c.floor_one_sided ? 1 : 0;
-        a.floor_level = c.floor_level;
-        a.fwd[0] = c.fwd_axis[0]; a.fwd[1] = c.fwd_axis[1]; a.fwd[2] = c.fwd_axis[2];
-        a.fwd_thr = c.fwd_threshold; a.fwd_margin = c.fwd_margin;
-        a.feet_r2 = c.feet_radius * c.feet_radius; // (the reference: a Python float subtracted from a float32 tensor)
-        return DP_OK;
-    }
+    dp_constraints c;
+    if (int rc = take_sized(ctx, c_in, c, CONS_V510, who)) return rc;
+    const float wts[4] = {c.w_feet_floor, c.w_head_hips_forward, c.w_head_hips_colinear, c.w_hips_feet_colinear};
+    for (float x : wts)
+        if (!(x >= 0.f && x <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": a weight is negative or not finite");
+    const int joints[6] = {c.floor_joints[0], c.floor_joints[1], c.foot_joints[0], c.foot_joints[1], c.head_joint, c.hips_joint};
+    for (int jj : joints)
+        if (jj < 0 || jj >= NJ) return fail(ctx, DP_ERR_INVALID, w + ": joint index " + std::to_string(jj) + " outside 0..21");
+    if (c.up_axis < 0 || c.up_axis > 2) return fail(ctx, DP_ERR_INVALID, w + ": up_axis outside 0..2");
+    const float rest[7] = {c.floor_level, c.fwd_axis[0], c.fwd_axis[1], c.fwd_axis[2], c.fwd_threshold, c.fwd_margin, c.feet_radius};
+    for (float x : rest)
+        if (!(std::fabs(x) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": a constraint parameter is not finite");
+    if (c.w_feet_floor != 0.f && !c.global_pos) return fail(ctx, DP_ERR_INVALID, w + ": global_pos is NULL while feet_floor is on");
+    a.global_pos = c.global_pos;
+    a.loss_extra = c.loss_extra;
+    a.w_floor = c.w_feet_floor; a.w_fwd = c.w_head_hips_forward; a.w_hcol = c.w_head_hips_colinear; a.w_feet = c.w_hips_feet_colinear;
+    a.floor_j[0] = c.floor_joints[0]; a.floor_j[1] = c.floor_joints[1]; a.foot_j[0] = c.foot_joints[0]; a.foot_j[1] = c.foot_joints[1];
+    a.head = c.head_joint; a.hips = c.hips_joint; a.up = c.up_axis; a.one_sided = c.floor_one_sided ? 1 : 0;
+    a.floor_level = c.floor_level;
+    a.fwd[0] = c.fwd_axis[0]; a.fwd[1] = c.fwd_axis[1]; a.fwd[2] = c.fwd_axis[2];
+    a.fwd_thr = c.fwd_threshold; a.fwd_margin = c.fwd_margin;
+    a.feet_r2 = c.feet_radius * c.feet_radius; // (the reference: a Python float subtracted from a float32 tensor)
+    return DP_OK;
 }
 
 extern "C" int dp_optimize_constrained(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_constraints* c_in, const dp_result* out_in,
@@ -1176,44 +1113,42 @@ static std::string check_term(const dp_term& t)
 static int take_terms(dp_ctx* ctx, const dp_terms* t_in, dpcons::TermArgs& a, const char* who)
 {
     const std::string nm = who;
-    {
-        dp_terms ts;
-        if (int rc = take_sized(ctx, t_in, ts, TERMS_V510, who)) return rc;
-        if (ts.n_terms < 0 || ts.n_terms > DP_MAX_TERMS)
-            return fail(ctx, DP_ERR_INVALID, nm + ": n_terms " + std::to_string(ts.n_terms) + " outside 0..16");
-        if (ts.n_terms > 0 && !ts.terms) return fail(ctx, DP_ERR_INVALID, nm + ": NULL terms with n_terms > 0");
-        if (ts.up_axis < 0 || ts.up_axis > 2) return fail(ctx, DP_ERR_INVALID, nm + ": up_axis outside 0..2");
-        bool need_gp = false;
-        for (int k = 0; k < ts.n_terms; ++k) {
-            const dp_term& t = ts.terms[k];
-            const std::string why = check_term(t);
-            if (!why.empty()) return fail(ctx, DP_ERR_INVALID, nm + ": term " + std::to_string(k) + ": " + why);
-            need_gp = need_gp || (t.weight != 0.f && (t.type == DP_TERM_PLANE || (t.type == DP_TERM_DISTANCE && t.joint_b < 0)));
-        }
-        if (need_gp && !ts.global_pos)
-            return fail(ctx, DP_ERR_INVALID, nm + ": global_pos is NULL while an active PLANE or point-DISTANCE term needs it");
-        a.global_pos = need_gp ? ts.global_pos : nullptr;
-        a.up = ts.up_axis;
-        a.n_terms = ts.n_terms; a.need_gp = need_gp ? 1 : 0; a.loss_terms = ts.loss_terms;
-        for (int k = 0; k < ts.n_terms; ++k) { // dp_cons.h's T_* layout
-            const dp_term& t = ts.terms[k];
-            unsigned* w = a.tbl + k * dpcons::TW;
-            float* wf = (float*)w;
-            w[dpcons::T_TYPE] = (unsigned)t.type; w[dpcons::T_JA] = (unsigned)t.joint_a; w[dpcons::T_JB] = (unsigned)t.joint_b;
-            w[dpcons::T_FLAGS] = (unsigned)t.flags;
-            wf[dpcons::T_W] = t.weight;
-            for (int c = 0; c < 3; ++c) {
-                wf[dpcons::T_PT + c] = t.point[c]; wf[dpcons::T_DIR + c] = t.dir[c];
-                wf[dpcons::T_AXA + c] = t.axis_a[c]; wf[dpcons::T_AXB + c] = t.axis_b[c];
-            }
-            // DISTANCE: lo^2, hi^2 (float products, as the reference's feet_radius ** 2 meets a float32 tensor)
-            wf[dpcons::T_P0] = t.type == DP_TERM_DISTANCE ? t.p0 * t.p0 : t.p0;
-            wf[dpcons::T_P1] = t.type == DP_TERM_DISTANCE ? t.p1 * t.p1 : t.p1;
-            const float* pf = t.per_frame;
-            std::memcpy(w + dpcons::T_ROW, &pf, sizeof(pf));
-        }
-        return DP_OK;
+    dp_terms ts;
+    if (int rc = take_sized(ctx, t_in, ts, TERMS_V510, who)) return rc;
+    if (ts.n_terms < 0 || ts.n_terms > DP_MAX_TERMS)
+        return fail(ctx, DP_ERR_INVALID, nm + ": n_terms " + std::to_string(ts.n_terms) + " outside 0..16");
+    if (ts.n_terms > 0 && !ts.terms) return fail(ctx, DP_ERR_INVALID, nm + ": NULL terms with n_terms > 0");
+    if (ts.up_axis < 0 || ts.up_axis > 2) return fail(ctx, DP_ERR_INVALID, nm + ": up_axis outside 0..2");
+    bool need_gp = false;
+    for (int k = 0; k < ts.n_terms; ++k) {
+        const dp_term& t = ts.terms[k];
+        const std::string why = check_term(t);
+        if (!why.empty()) return fail(ctx, DP_ERR_INVALID, nm + ": term " + std::to_string(k) + ": " + why);
+        need_gp = need_gp || (t.weight != 0.f && (t.type == DP_TERM_PLANE || (t.type == DP_TERM_DISTANCE && t.joint_b < 0)));
     }
+    if (need_gp && !ts.global_pos)
+        return fail(ctx, DP_ERR_INVALID, nm + ": global_pos is NULL while an active PLANE or point-DISTANCE term needs it");
+    a.global_pos = need_gp ? ts.global_pos : nullptr;
+    a.up = ts.up_axis;
+    a.n_terms = ts.n_terms; a.need_gp = need_gp ? 1 : 0; a.loss_terms = ts.loss_terms;
+    for (int k = 0; k < ts.n_terms; ++k) { // dp_cons.h's T_* layout
+        const dp_term& t = ts.terms[k];
+        unsigned* w = a.tbl + k * dpcons::TW;
+        float* wf = (float*)w;
+        w[dpcons::T_TYPE] = (unsigned)t.type; w[dpcons::T_JA] = (unsigned)t.joint_a; w[dpcons::T_JB] = (unsigned)t.joint_b;
+        w[dpcons::T_FLAGS] = (unsigned)t.flags;
+        wf[dpcons::T_W] = t.weight;
+        for (int c = 0; c < 3; ++c) {
+            wf[dpcons::T_PT + c] = t.point[c]; wf[dpcons::T_DIR + c] = t.dir[c];
+            wf[dpcons::T_AXA + c] = t.axis_a[c]; wf[dpcons::T_AXB + c] = t.axis_b[c];
+        }
+        // DISTANCE: lo^2, hi^2 (float products, as the reference's feet_radius ** 2 meets a float32 tensor)
+        wf[dpcons::T_P0] = t.type == DP_TERM_DISTANCE ? t.p0 * t.p0 : t.p0;
+        wf[dpcons::T_P1] = t.type == DP_TERM_DISTANCE ? t.p1 * t.p1 : t.p1;
+        const float* pf = t.per_frame;
+        std::memcpy(w + dpcons::T_ROW, &pf, sizeof(pf));
+    }
+    return DP_OK;
 }
 
 extern "C" int dp_optimize_terms(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_terms* t_in, const dp_result* out_in, void* stream)
@@ -1271,7 +1206,7 @@ static int sequence_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_fra
         if (int rc = take_skeleton(ctx, sk, sk_off, sk_stride, who)) return rc;
         if (p.kernel == DP_KERNEL_W16) return refuse_w16_skeleton(ctx, who);
     }
-    if (!ctx->d_w4img) return refuse_no_image(ctx, who);
+    if (!ctx->d_w4img.get()) return refuse_no_image(ctx, who);
     KArgs k;
     fill_model_args(ctx, k);
     k.skel = sk_off; k.skel_stride = sk_stride;
@@ -1303,8 +1238,7 @@ static int sequence_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_fra
 extern "C" int dp_optimize_sequence(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_seq_state* st,
                                     const dp_seq_step* adj, const dp_seq_results* out, void* stream)
 {
-    if (!ctx) return DP_ERR_INVALID;
-    return sequence_impl(ctx, n_seq, latent, fr, p_in, nullptr, st, adj, out, stream);
+    return entry_quiet(ctx, "dp_optimize_sequence", [&] { return sequence_impl(ctx, n_seq, latent, fr, p_in, nullptr, st, adj, out, stream); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1340,9 +1274,8 @@ extern "C" int dp_optimize_sequence_skeleton(dp_ctx* ctx, int n_seq, float* late
 
 // ------------------------------------------------------------------------------------------------
 // per-frame epilogue of S sequences (reference drag_pose.py:369-402), see include/dragposer.h
-extern "C" int dp_sequence_advance(dp_ctx* ctx, int n_seq, const dp_result* res, const dp_seq_state* st, const dp_seq_step* step, void* stream)
+static int advance_impl(dp_ctx* ctx, int n_seq, const dp_result* res, const dp_seq_state* st, const dp_seq_step* step, void* stream)
 {
-    if (!ctx) return DP_ERR_INVALID;
     if (n_seq <= 0 || !res || !st || !step) return fail(ctx, DP_ERR_INVALID, "dp_sequence_advance: bad arguments");
     dp_result rv;
     if (int rc = take_result(ctx, res, rv, "dp_sequence_advance")) return rc;
@@ -1372,4 +1305,9 @@ extern "C" int dp_sequence_advance(dp_ctx* ctx, int n_seq, const dp_result* res,
     hipError_t e = dp_launch_sequence_advance(&a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("sequence kernel launch: ") + hipGetErrorString(e));
     return DP_OK;
+}
+
+extern "C" int dp_sequence_advance(dp_ctx* ctx, int n_seq, const dp_result* res, const dp_seq_state* st, const dp_seq_step* step, void* stream)
+{
+    return entry_quiet(ctx, "dp_sequence_advance", [&] { return advance_impl(ctx, n_seq, res, st, step, stream); });
 }

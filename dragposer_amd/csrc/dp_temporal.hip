@@ -17,53 +17,20 @@
 //     product's result AS the second's A operand (a lane's eight hidden units are its eight K-slots by the host's packing of W2: no LDS, no
 //     transposition).  The tiles are dealt to the 8 waves, a tile's image (weights already split: 21 + 2 sixteen-byte words per lane) passes
 //     through the registers in three parts, the waves' partial outputs are summed through LDS (see the comment above ffn_p1).
+// The handle, the packer of the weight image and the choice of the variant are host code: dp_temporal_host.cpp (shared: dp_temporal.h).
 #include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-#include "../../include/dragposer.h"
+#include "dp_temporal.h"
 
 namespace {
 
-constexpr int D = DP_TEMPORAL_D_MODEL, NHD = DP_TEMPORAL_HEADS, HD = D / NHD, LAT = 24;
-constexpr int MAXT = DP_TEMPORAL_MAX_TOKENS, MAXL = DP_TEMPORAL_MAX_LAYERS;
-constexpr int NT = 512, NWV = NT / 64;              // threads / waves per workgroup (two waves per SIMD)
+using namespace dpt;
+constexpr int NHD = DP_TEMPORAL_HEADS, HD = D / NHD;
 constexpr int LN_MAX = (MAXL * 4 + MAXL * 6 + 4) * D;  // floats of the LayerNorm block at the largest architecture
-constexpr int MAX_IN = 36;                          // 24 + 3 + 8 heights, padded to a multiple of 4 (K-steps)
-constexpr int FT = 32;                              // hidden units per feed-forward tile (the K of one v_mfma_f32_16x16x32_bf16)
-constexpr int FFN_IMG_V = 12 + 9 + 2;               // 16-byte words per lane of a tile's image: W1 [2 M-tiles][2 K-blocks][3 terms], W2 [3 column tiles][3 terms], bias1 [2]
-constexpr int FFN_TILE_FLOATS = FFN_IMG_V * 64 * 4; // ... in 32-bit words
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-
-struct TLayer { // offsets (in floats) into the device weight buffer
-    int sa_in_wT, sa_in_b, sa_out_wT, sa_out_b, ca_in_wT, ca_in_b, ca_out_wT, ca_out_b;
-    int ffn_pack, lin2_b, n1w, n1b, n2w, n2b, n3w, n3b; // ffn_pack: [ceil(F / 16)][7][64 lanes][4] (dp_temporal_create)
-};
-struct TArgs {
-    const float* w;
-    int enc_tab, dec_tab; // offsets of the TLayer tables inside the weight buffer (a kernel-argument array indexed by the
-                          // layer loop would be copied into registers: 288 SGPRs)
-    int n_enc, n_dec, ff, n_in, nh, max_len, step;
-    int ipe_wT, ipe_b, ipd_wT, ipd_b, op_wT, op_b, pe, encn_w, encn_b, decn_w, decn_b, mean, stdv;
-    int ln0, ln_len; // all LayerNorm rows (the layers' and the two final ones) are one block: the TEAM kernel keeps it in LDS
-    // per call
-    const float *latent_buf, *disp_buf, *heights_buf;
-    float* target;
-    int H, n_seq, window;
-    // a TEAM of G workgroups per sequence (few sequences: latency; below): the exchange area of the handle, the tag base of this launch
-    float* xch;
-    unsigned* epochs; // one word per team: the tag of the team's last exchange (device-resident, so that a captured launch can be replayed)
-    int* tstatus;     // the handle's status word in DEVICE memory: what every team launch checks at entry and while it waits
-    int* hstatus;     // ... and its mirror in page-locked HOST memory: what dp_temporal_status / the next dp_temporal_predict read without a synchronise
-    int G;
-    int poll_limit;   // re-reads of a granule set before a member gives up (XCH_POLL_LIMIT; the debug hook shortens it)
-    int dbg_skip_team, dbg_skip_member; // private test hook: that member of that team never publishes (-1: nobody)
-};
 
 #define DEV __device__ __forceinline__
 // PAIR (round 6, many sequences): ONE workgroup of 2 NT threads per CU instead of two of NT -- two HALVES, each the NS = 2 workgroup it was (its own
@@ -427,9 +394,7 @@ DEV void mha(float* o, const float* xq, int Tq, const float* xkv, int Tk, const 
 // back by the first at exit -- which it reaches only after every member has entered); a slot (team, granule, member) is only ever written by that
 // member of that team, whatever the team size of the launch (the layout is that of the largest team), so what a slot holds is always an OLDER tag of
 // the same counter: never the awaited one.  Nothing of this lives in kernel arguments: a launch captured into a graph can be replayed.
-constexpr int XCH_GRANULES = 2 * 16 * D / 3;          // two token tiles of 16 x 48 partial sums, three per granule
-constexpr int XCH_GMAX = 16;                          // the largest team; slots per granule in the layout
-constexpr int XCH_POLL_LIMIT = 1 << 19;               // (~1 s: then the member gives up -- see "time-out" below)
+// (XCH_GRANULES, XCH_GMAX, XCH_POLL_LIMIT: dp_temporal.h -- the host sizes the exchange area by them)
 // Time-out.  A team waits for its members, so all of them must be resident.  The host sizes teams so that they are (one workgroup per CU by the
 // occupancy query, at most HALF the CUs the stream may use: dp_temporal_predict) -- against its own launch; another stream's long kernel, a CU mask
 // set behind the library's back or a second process can still keep a member off the device.  What happens then is never silent:
@@ -1004,248 +969,35 @@ __global__ __launch_bounds__(PAIR ? 2 * NT : NT, PAIR ? 1 : OCC) void dp_tempora
     STAMP(15);
 }
 
-thread_local std::string g_terr;
-
 } // namespace
 
-struct dp_temporal {
-    int device = -1, n_cu = 256;
-    int forced_variant = 0; // dp_temporal_debug_force_variant (private test hook, below): 21, 41 or 42 (waves per SIMD, sequences
-                            // per workgroup) = that kernel variant whatever the batch; 0 = chosen from the batch (the product)
-    float* d_w = nullptr;
-    float* d_xch = nullptr;  // the teams' exchange area: [n_cu / 2 teams][2][XCH_GRANULES][XCH_GMAX] granules, the teams' tag counters, the status word
-    size_t xch_granule_bytes = 0;
-    int* h_status = nullptr; // page-locked host mirror of the status word (written by the device on a team time-out, read here without a synchronise)
-    int status_seen = 0;     // DP_TEMPORAL_* bits ever seen in it (sticky)
-    bool teams_off = false;  // no team launches any more: a time-out was reported, or the TEAM kernel does not fit a CU of this device
-    int poll_limit = XCH_POLL_LIMIT, dbg_skip_team = -1, dbg_skip_member = -1; // dp_temporal_debug_team_fault (private test hook)
-    TArgs args{};
-    std::string err;
-};
-
-static int tfail(dp_temporal* t, int code, const std::string& msg)
+hipError_t dpt::dp_launch_temporal(int variant, int n_seq, int G, const TArgs& a, hipStream_t stream)
 {
-    if (t) t->err = msg;
-    else g_terr = msg;
-    return code;
+    if (variant >= 100) hipLaunchKernelGGL((dp_temporal_kernel<2, 1, true>), dim3(n_seq * G), dim3(NT), 0, stream, a);
+    else if (variant == 21) hipLaunchKernelGGL((dp_temporal_kernel<2, 1>), dim3(n_seq), dim3(NT), 0, stream, a);
+    else if (variant == 41) hipLaunchKernelGGL((dp_temporal_kernel<4, 1>), dim3(n_seq), dim3(NT), 0, stream, a);
+    else if (variant == 44) hipLaunchKernelGGL((dp_temporal_kernel<4, 2, false, true>), dim3((n_seq + 3) / 4), dim3(2 * NT), 0, stream, a);
+    else hipLaunchKernelGGL((dp_temporal_kernel<4, 2>), dim3((n_seq + 1) / 2), dim3(NT), 0, stream, a);
+    return hipGetLastError();
 }
 
-// float -> three bf16 terms with x = t0 + t1 + t2 exactly: the host's copy of the device's split_pair (round to nearest even at every stage, what
-// v_cvt_pk_bf16_f32 does; the remainders are exact fp32 differences).  Weights are finite.
-static unsigned host_bf16_rne(float x)
+// a team member needs a CU's worth of LDS and registers: co-residency is sized from what the RUNTIME says fits, not from this file's arithmetic
+int dpt::dp_temporal_team_blocks_per_cu()
 {
-    unsigned u;
-    std::memcpy(&u, &x, 4);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-static float host_bf16_val(unsigned h)
-{
-    const unsigned u = h << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-static void host_split3(float x, unsigned (&t)[3])
-{
-    t[0] = host_bf16_rne(x);
-    const float r = x - host_bf16_val(t[0]);
-    t[1] = host_bf16_rne(r);
-    const float q = r - host_bf16_val(t[1]);
-    t[2] = host_bf16_rne(q);
-}
-// private test hook (host arithmetic only; a CPU test holds it to numpy): the three bf16 terms of x as 16-bit patterns
-extern "C" void dp_temporal_debug_split3(float x, unsigned short* out3)
-{
-    unsigned t[3];
-    host_split3(x, t);
-    for (int k = 0; k < 3; ++k) out3[k] = (unsigned short)t[k];
+    int per_cu = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dp_temporal_kernel<2, 1, true>, NT, 0) == hipSuccess ? per_cu : 0;
 }
 
-extern "C" const char* dp_temporal_last_error(const dp_temporal* t) { return t ? t->err.c_str() : g_terr.c_str(); }
-
-extern "C" int dp_temporal_create(dp_temporal** out, const dp_temporal_model* m, int device)
+// (the device's CUs, or the stream's CU mask when it has one -- hipExtStreamGetCUMask reports the effective mask)
+int dpt::dp_temporal_stream_cus(hipStream_t stream, int n_cu)
 {
-    if (!out) return tfail(nullptr, DP_ERR_INVALID, "dp_temporal_create: out is NULL");
-    *out = nullptr;
-    if (!m) return tfail(nullptr, DP_ERR_INVALID, "dp_temporal_create: model is NULL");
-    if (m->n_heights < 0 || m->n_heights > DP_MAX_HEIGHT_JOINTS || m->dim_feedforward < 1 || m->sample_step < 1 || m->max_len < 1 ||
-        m->n_encoder_layers < 1 || m->n_encoder_layers > MAXL || m->n_decoder_layers < 1 || m->n_decoder_layers > MAXL)
-        return tfail(nullptr, DP_ERR_INVALID, "dp_temporal_create: architecture out of range (layers 1..8, heights <= 8)");
-    const int n_in = LAT + 3 + m->n_heights, F = m->dim_feedforward;
-    std::vector<float> buf;
-    bool null_seen = false;
-    auto put = [&](const float* p, size_t n) { // plain copy
-        const int off = (int)buf.size();
-        if (!p) { null_seen = true; buf.resize(buf.size() + n, 0.f); return off; }
-        buf.insert(buf.end(), p, p + n);
-        return off;
-    };
-    auto putT = [&](const float* p, int rows_out, int cols_in, int ldk = 0) { // Linear.weight [out][in] as it is, rows padded with zeros to a multiple of 4 (or to ldk)
-        while (buf.size() % 4) buf.push_back(0.f);               // floats and 16-byte aligned (lin: a lane reads KS consecutive floats of a row)
-        const int off = (int)buf.size();
-        if (ldk == 0) ldk = (cols_in + 3) / 4 * 4;
-        buf.resize(buf.size() + (size_t)rows_out * ldk, 0.f);
-        if (!p) { null_seen = true; return off; }
-        for (int r = 0; r < rows_out; ++r)
-            for (int c = 0; c < cols_in; ++c) buf[off + (size_t)r * ldk + c] = p[(size_t)r * cols_in + c];
-        return off;
-    };
-    // feed-forward image (split precision: the comment above ffn_tile), per tile of 32 hidden units and lane (l16 = lane & 15, g = lane >> 4),
-    // FFN_IMG_V 16-byte words of eight bf16 each (element j in bits 16 (j & 1) of word j >> 1), three words per operand = its hi / mid / lo terms:
-    //   v = (t 2) 3 + term:           W1[32 nt + 16 t + l16][8 g + j]                                  (A of product 1: M-tile t, channels 0 .. 31)
-    //   v = (t 2 + 1) 3 + {0, 1, 2}:  [hi | hi], [mid | mid], [lo | hi] of W1[32 nt + 16 t + l16][32 + 8 (g & 1) + j]: the first term in lanes g < 2,
-    //                                 the second in lanes g >= 2                                       (channels 32 .. 47: two term pairs per MFMA)
-    //   v = 12 + ct 3 + term:         W2[16 ct + l16][32 nt + 16 (j >> 2) + 4 g + (j & 3)]             (B of product 2: column tile ct)
-    //   v = 21 + t (four floats):     bias1[32 nt + 16 t + 4 g + r]
-    // hidden units beyond F and input channels beyond 47 are zeros (ReLU(0) = 0 contributes nothing)
-    auto split3 = [&](float x, unsigned (&t)[3]) { host_split3(x, t); };
-    auto pack_ffn = [&](const float* w1, const float* b1, const float* w2) {
-        while (buf.size() % 4) buf.push_back(0.f); // 16-byte alignment of the image
-        const int off = (int)buf.size(), ntiles = (F + FT - 1) / FT;
-        buf.resize(buf.size() + (size_t)ntiles * FFN_TILE_FLOATS, 0.f);
-        if (!w1 || !b1 || !w2) { null_seen = true; return off; }
-        for (int nt = 0; nt < ntiles; ++nt)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int l16 = lane & 15, g = lane >> 4;
-                float* dst = buf.data() + off + (size_t)nt * FFN_TILE_FLOATS;
-                auto put8 = [&](int v0, const float (&val)[8]) { // eight values -> the words v0 (hi), v0 + 1 (mid), v0 + 2 (lo) of this lane
-                    unsigned words[3][4] = {};
-                    for (int j = 0; j < 8; ++j) {
-                        unsigned t[3];
-                        split3(val[j], t);
-                        for (int k = 0; k < 3; ++k) words[k][j >> 1] |= t[k] << (16 * (j & 1));
-                    }
-                    for (int k = 0; k < 3; ++k) std::memcpy(dst + ((v0 + k) * 64 + lane) * 4, words[k], 16);
-                };
-                for (int t = 0; t < 2; ++t) {
-                    float val[8];
-                    const int h = FT * nt + 16 * t + l16;
-                    for (int j = 0; j < 8; ++j) val[j] = h < F ? w1[(size_t)h * D + 8 * g + j] : 0.f;
-                    put8((t * 2) * 3, val);
-                    // channels 32 .. 47: which TERM a lane holds depends on its half of the K-block
-                    unsigned words[3][4] = {};
-                    for (int j = 0; j < 8; ++j) {
-                        unsigned tm[3];
-                        split3(h < F ? w1[(size_t)h * D + 32 + 8 * (g & 1) + j] : 0.f, tm);
-                        const unsigned pick[3] = {tm[0], tm[1], g < 2 ? tm[2] : tm[0]}; // [hi | hi], [mid | mid], [lo | hi]
-                        for (int k = 0; k < 3; ++k) words[k][j >> 1] |= pick[k] << (16 * (j & 1));
-                    }
-                    for (int k = 0; k < 3; ++k) std::memcpy(dst + (((t * 2 + 1) * 3 + k) * 64 + lane) * 4, words[k], 16);
-                }
-                for (int ct = 0; ct < 3; ++ct) {
-                    float val[8];
-                    for (int j = 0; j < 8; ++j) {
-                        const int h = FT * nt + 16 * (j >> 2) + 4 * g + (j & 3);
-                        val[j] = h < F ? w2[(size_t)(16 * ct + l16) * F + h] : 0.f;
-                    }
-                    put8(12 + ct * 3, val);
-                }
-                for (int t = 0; t < 2; ++t)
-                    for (int r = 0; r < 4; ++r) {
-                        const int h = FT * nt + 16 * t + 4 * g + r;
-                        dst[((21 + t) * 64 + lane) * 4 + r] = h < F ? b1[h] : 0.f;
-                    }
-            }
-        return off;
-    };
-    std::vector<float> lnbuf; // the LayerNorm rows, appended to buf as one block below (offsets are relative until then)
-    auto put_ln = [&](const float* p) {
-        const int off = (int)lnbuf.size();
-        if (!p) { null_seen = true; lnbuf.resize(lnbuf.size() + D, 0.f); return off; }
-        lnbuf.insert(lnbuf.end(), p, p + D);
-        return off;
-    };
-    TArgs a{};
-    a.n_enc = m->n_encoder_layers; a.n_dec = m->n_decoder_layers; a.ff = F; a.n_in = n_in; a.nh = m->n_heights;
-    a.max_len = m->max_len; a.step = m->sample_step;
-    a.ipe_wT = putT(m->in_proj_encoder_w, D, n_in, MAX_IN); a.ipe_b = put(m->in_proj_encoder_b, D); // (the kernel's K-steps cover MAX_IN inputs)
-    a.ipd_wT = putT(m->in_proj_decoder_w, D, LAT); a.ipd_b = put(m->in_proj_decoder_b, D);
-    a.op_wT = putT(m->out_proj_w, LAT, D); a.op_b = put(m->out_proj_b, LAT);
-    a.pe = put(m->pos_encoding, (size_t)m->max_len * D);
-    a.encn_w = put_ln(m->enc_norm_w); a.encn_b = put_ln(m->enc_norm_b);
-    a.decn_w = put_ln(m->dec_norm_w); a.decn_b = put_ln(m->dec_norm_b);
-    a.mean = put(m->means_latent, LAT); a.stdv = put(m->stds_latent, LAT);
-    if (!m->enc || !m->dec) return tfail(nullptr, DP_ERR_INVALID, "dp_temporal_create: NULL layer array");
-    auto layer = [&](const dp_temporal_layer& L, bool dec) {
-        TLayer o{};
-        o.sa_in_wT = putT(L.sa_in_w, 3 * D, D); o.sa_in_b = put(L.sa_in_b, 3 * D);
-        o.sa_out_wT = putT(L.sa_out_w, D, D); o.sa_out_b = put(L.sa_out_b, D);
-        if (dec) {
-            o.ca_in_wT = putT(L.ca_in_w, 3 * D, D); o.ca_in_b = put(L.ca_in_b, 3 * D);
-            o.ca_out_wT = putT(L.ca_out_w, D, D); o.ca_out_b = put(L.ca_out_b, D);
-        }
-        o.ffn_pack = pack_ffn(L.lin1_w, L.lin1_b, L.lin2_w);
-        o.lin2_b = put(L.lin2_b, D);
-        o.n1w = put_ln(L.norm1_w); o.n1b = put_ln(L.norm1_b);
-        o.n2w = put_ln(L.norm2_w); o.n2b = put_ln(L.norm2_b);
-        if (dec) { o.n3w = put_ln(L.norm3_w); o.n3b = put_ln(L.norm3_b); }
-        return o;
-    };
-    std::vector<TLayer> tabs;
-    for (int l = 0; l < a.n_enc; ++l) tabs.push_back(layer(m->enc[l], false));
-    for (int l = 0; l < a.n_dec; ++l) tabs.push_back(layer(m->dec[l], true));
-    while (buf.size() % 4) buf.push_back(0.f);
-    a.ln0 = (int)buf.size(); a.ln_len = (int)lnbuf.size();
-    buf.insert(buf.end(), lnbuf.begin(), lnbuf.end());
-    for (TLayer& t : tabs) { t.n1w += a.ln0; t.n1b += a.ln0; t.n2w += a.ln0; t.n2b += a.ln0; t.n3w += a.ln0; t.n3b += a.ln0; } // (n3*: decoder layers only; unused otherwise)
-    a.encn_w += a.ln0; a.encn_b += a.ln0; a.decn_w += a.ln0; a.decn_b += a.ln0;
-    static_assert(sizeof(TLayer) % sizeof(float) == 0, "layer tables live in the float buffer");
-    a.enc_tab = (int)buf.size();
-    a.dec_tab = a.enc_tab + a.n_enc * (int)(sizeof(TLayer) / sizeof(float));
-    buf.resize(buf.size() + tabs.size() * sizeof(TLayer) / sizeof(float));
-    std::memcpy(buf.data() + a.enc_tab, tabs.data(), tabs.size() * sizeof(TLayer));
-    if (null_seen) return tfail(nullptr, DP_ERR_INVALID, "dp_temporal_create: NULL tensor pointer in model");
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return tfail(nullptr, DP_ERR_DEVICE, "dp_temporal_create: no HIP device (there is no CPU fallback)");
-    if (device < 0 || device >= ndev) return tfail(nullptr, DP_ERR_INVALID, "dp_temporal_create: bad device index");
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    if (hipSetDevice(device) != hipSuccess) return tfail(nullptr, DP_ERR_DEVICE, "dp_temporal_create: hipSetDevice failed");
-    dp_temporal* t = new dp_temporal;
-    t->device = device;
-    { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) t->n_cu = cu; }
-    hipError_t e = hipMalloc((void**)&t->d_w, buf.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(t->d_w, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice);
-    const int max_teams = t->n_cu / 2 > 0 ? t->n_cu / 2 : 1;
-    t->xch_granule_bytes = (size_t)max_teams * 2 * XCH_GRANULES * XCH_GMAX * sizeof(f4);
-    const size_t xch_bytes = t->xch_granule_bytes + (size_t)max_teams * sizeof(unsigned) + 16;
-    if (e == hipSuccess) e = hipMalloc((void**)&t->d_xch, xch_bytes);
-    if (e == hipSuccess) e = hipMemset(t->d_xch, 0, xch_bytes); // (tag 0 = never written; a team's first exchange carries tag 1)
-    if (e == hipSuccess) e = hipHostMalloc((void**)&t->h_status, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) {
-        *t->h_status = 0;
-        // a team member needs a CU's worth of LDS and registers: co-residency is sized from what the RUNTIME says fits, not from this file's arithmetic
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dp_temporal_kernel<2, 1, true>, NT, 0) != hipSuccess || per_cu < 1) t->teams_off = true;
-    }
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) {
-        if (t->d_w) (void)hipFree(t->d_w);
-        if (t->d_xch) (void)hipFree(t->d_xch);
-        if (t->h_status) (void)hipHostFree(t->h_status);
-        delete t;
-        return tfail(nullptr, DP_ERR_DEVICE, std::string("dp_temporal_create: ") + hipGetErrorString(e));
-    }
-    a.w = t->d_w;
-    t->args = a;
-    *out = t;
-    return DP_OK;
-}
-
-extern "C" int dp_temporal_destroy(dp_temporal* t)
-{
-    if (!t) return DP_ERR_INVALID;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(t->device);
-    if (t->d_w) (void)hipFree(t->d_w);
-    if (t->d_xch) (void)hipFree(t->d_xch);
-    if (t->h_status) (void)hipHostFree(t->h_status);
-    if (prev >= 0 && prev != t->device) (void)hipSetDevice(prev);
-    delete t;
-    return DP_OK;
+    uint32_t mask[16] = {};
+    if (hipExtStreamGetCUMask(stream, 16, mask) == hipSuccess) {
+        int bits = 0;
+        for (uint32_t w : mask) bits += __builtin_popcount(w);
+        if (bits > 0 && bits < n_cu) n_cu = bits;
+    } else (void)hipGetLastError(); // (not an error of this call)
+    return n_cu;
 }
 
 #ifdef DPT_STAMPS
@@ -1261,126 +1013,3 @@ extern "C" int dp_temporal_debug_read_stamps(unsigned long long* out, int cap)
     return n;
 }
 #endif
-
-// private test hook (not in include/dragposer.h; the product reads no environment variable): pin the kernel variant of later predictions
-extern "C" int dp_temporal_debug_force_variant(dp_temporal* t, int variant)
-{
-    // (102, 104, 108, 116: a team of 2 / 4 / 8 / 16 workgroups per sequence where the launch fits the device, else as 0)
-    if (!t || (variant != 0 && variant != 21 && variant != 41 && variant != 42 && variant != 44 && variant != 102 && variant != 104 && variant != 108 && variant != 116)) return DP_ERR_INVALID;
-    t->forced_variant = variant;
-    return DP_OK;
-}
-
-// The team size the library picks for n_seq sequences on a device of n_cu usable CUs (1: no teams).  Host arithmetic only (a CPU test holds it): the
-// largest power of two up to 16 with every workgroup on a CU of its own (team members wait for each other: all of them must be resident, and the
-// TEAM kernel's 86 KB of LDS allow one workgroup per CU), ALL TEAMS TOGETHER ON AT MOST HALF THE CUs (round 6: the other half is what keeps a second
-// handle's teams, or another stream's kernel, from starving a member -- a launch that filled the device left no slack at all) and at least one
-// feed-forward tile per wave; 16 pays with a quarter of the device at most (profiles/r05_team_latency.txt), 8 beyond.
-extern "C" int dp_temporal_debug_team_size(int n_cu, int n_seq, int dim_feedforward)
-{
-    if (n_cu <= 0 || n_seq <= 0 || dim_feedforward <= 0) return 1;
-    int G = 1;
-    while (G < 16 && n_seq * (2 * G) <= n_cu / 2 && (dim_feedforward + FT - 1) / FT >= 2 * G * NWV) G *= 2;
-    if (G == 16 && n_seq * 64 > n_cu) G = 8;
-    return G;
-}
-
-// private test hook: make the team exchange fail on purpose -- member `member` of sequence `team`'s team never publishes its partial sums (-1: nobody),
-// and a member gives up after `poll_limit` re-reads instead of ~1 s (0: the default).  What the product promises then is in "time-out" above.
-extern "C" int dp_temporal_debug_team_fault(dp_temporal* t, int team, int member, int poll_limit)
-{
-    if (!t) return DP_ERR_INVALID;
-    t->dbg_skip_team = team; t->dbg_skip_member = member;
-    t->poll_limit = poll_limit > 0 ? poll_limit : XCH_POLL_LIMIT;
-    return DP_OK;
-}
-
-// Health of the handle, WITHOUT a synchronise: DP_TEMPORAL_TEAM_TIMEOUT once a team member of an earlier launch has given up waiting (the device
-// writes the word into page-locked host memory the moment it happens; sticky).  The targets of that launch's affected sequences are NaN.
-extern "C" int dp_temporal_status(const dp_temporal* t)
-{
-    if (!t) return DP_ERR_INVALID;
-    int v = t->status_seen;
-    if (t->h_status && *(volatile const int*)t->h_status != 0) v |= DP_TEMPORAL_TEAM_TIMEOUT;
-    return v;
-}
-
-// private test hook: the teams' status word (0: every exchange completed; 1: a workgroup waited XCH_POLL_LIMIT reads for its team -- the launch's
-// predictions are garbage); synchronises the device
-extern "C" int dp_temporal_debug_team_status(dp_temporal* t)
-{
-    if (!t || !t->d_xch) return -1;
-    int v = -1;
-    if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(&v, (char*)t->d_xch + t->xch_granule_bytes + (size_t)(t->n_cu / 2 > 0 ? t->n_cu / 2 : 1) * sizeof(unsigned), sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return v;
-}
-
-extern "C" int dp_temporal_predict(dp_temporal* t, int n_seq, const dp_seq_state* st, int window, float* target_buf, void* stream)
-{
-    if (!t) return DP_ERR_INVALID;
-    if (n_seq <= 0 || !st || !target_buf) return tfail(t, DP_ERR_INVALID, "dp_temporal_predict: bad arguments");
-    if (!st->latent_buf || !st->disp_buf || !st->heights_buf) return tfail(t, DP_ERR_INVALID, "dp_temporal_predict: NULL history buffer");
-    const TArgs& m = t->args;
-    if (st->n_heights != m.nh) return tfail(t, DP_ERR_INVALID, "dp_temporal_predict: state.n_heights differs from the model's");
-    if (window < 0 || window % m.step != 0) return tfail(t, DP_ERR_INVALID, "dp_temporal_predict: window must be a non-negative multiple of sample_step");
-    const int n_past = (st->history + m.step - 1) / m.step, n_steps = window / m.step + 1;
-    if (st->history < 2 * m.step || n_past - 1 > MAXT || n_steps > MAXT || n_past - 1 > m.max_len || n_steps > m.max_len)
-        return tfail(t, DP_ERR_UNSUPPORTED, "dp_temporal_predict: more than 32 encoder or decoder tokens (or more than max_len positions)");
-    if (!t->teams_off && *(volatile const int*)t->h_status != 0) { // a team member of an EARLIER launch gave up waiting (see "time-out")
-        t->teams_off = true;
-        t->status_seen |= DP_TEMPORAL_TEAM_TIMEOUT;
-        return tfail(t, DP_ERR_TIMEOUT, "dp_temporal_predict: a team of workgroups of an earlier launch of this handle timed out waiting for a member that was not "
-                                        "resident (another stream's kernel or a CU mask held its CUs?); that launch wrote NaN into the targets of the affected "
-                                        "sequences.  Nothing was launched now; the handle runs one workgroup per sequence from here on -- call again");
-    }
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    if (prev != t->device && hipSetDevice(t->device) != hipSuccess) return tfail(t, DP_ERR_DEVICE, "cannot select the predictor's device");
-    TArgs a = m;
-    a.latent_buf = st->latent_buf; a.disp_buf = st->disp_buf; a.heights_buf = st->heights_buf;
-    a.H = st->history; a.n_seq = n_seq; a.window = window; a.target = target_buf;
-    // variant: few sequences -> latency (one workgroup per CU, prefetch); many -> two workgroups per CU, and two sequences per
-    // workgroup when each has at most 16 tokens (every weight fetch then serves both)
-    const bool pair_ok = n_past - 1 <= 16 && n_steps <= 16;
-    // (44 = PAIR, one 1024-thread workgroup of two NS = 2 halves per CU that share the weight fetches of the feed-forward layers in calls over at
-    //  most 8 tokens.  Measured at 1024 / 4096 sequences, profiles/r06_temporal_pair_ab.txt: window 16 (five decoder calls of 1 .. 5 tokens) -12.8 %
-    //  / -12.8 %; window 0 -3.1 % / -1.2 %; window 60 -2.7 % / -2.4 % -- there most of what the shared fetches save is given back by the halves'
-    //  lock-step: two independent workgroups on a CU drift apart and run one's small phases under the other's tile loop.  Taken wherever variant 42
-    //  would put two workgroups on a CU anyway.)
-    int variant = n_seq <= t->n_cu ? 21 : (pair_ok ? (n_seq > 2 * t->n_cu ? 44 : 42) : 41);
-    // few sequences: a TEAM of G workgroups per sequence (the largest power of two up to 16 with every workgroup on a CU of its own -- they wait for
-    // each other, so all of them must be resident -- and at least one feed-forward tile per wave)
-    // (the CUs this launch may use: the device's, or the stream's CU mask when it has one -- hipExtStreamGetCUMask reports the effective mask)
-    int n_cu = t->n_cu;
-    {
-        uint32_t mask[16] = {};
-        if (hipExtStreamGetCUMask((hipStream_t)stream, 16, mask) == hipSuccess) {
-            int bits = 0;
-            for (uint32_t w : mask) bits += __builtin_popcount(w);
-            if (bits > 0 && bits < n_cu) n_cu = bits;
-        } else (void)hipGetLastError(); // (not an error of this call)
-    }
-    int G = t->teams_off ? 1 : dp_temporal_debug_team_size(n_cu, n_seq, m.ff);
-    if (t->forced_variant >= 100 && !t->teams_off) { // (a forced size: the largest the launch fits -- here the whole device may be used --, whatever pays)
-        G = 1;
-        while (G < 16 && n_seq * (2 * G) <= n_cu && (m.ff + FT - 1) / FT >= 2 * G * NWV) G *= 2;
-        const int want = t->forced_variant - 100;
-        G = G >= want ? want : 1;
-    }
-    if (G >= 2 && (t->forced_variant == 0 || t->forced_variant >= 100)) variant = 100 + G;
-    if (t->forced_variant == 21 || t->forced_variant == 41 || ((t->forced_variant == 42 || t->forced_variant == 44) && pair_ok)) variant = t->forced_variant;
-    if (variant >= 100) {
-        const int max_teams = t->n_cu / 2 > 0 ? t->n_cu / 2 : 1;
-        a.G = G; a.xch = t->d_xch; a.epochs = (unsigned*)((char*)t->d_xch + t->xch_granule_bytes); a.tstatus = (int*)(a.epochs + max_teams);
-        a.hstatus = t->h_status; a.poll_limit = t->poll_limit; a.dbg_skip_team = t->dbg_skip_team; a.dbg_skip_member = t->dbg_skip_member;
-        hipLaunchKernelGGL((dp_temporal_kernel<2, 1, true>), dim3(n_seq * G), dim3(NT), 0, (hipStream_t)stream, a);
-    } else if (variant == 21) hipLaunchKernelGGL((dp_temporal_kernel<2, 1>), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream, a);
-    else if (variant == 41) hipLaunchKernelGGL((dp_temporal_kernel<4, 1>), dim3(n_seq), dim3(NT), 0, (hipStream_t)stream, a);
-    else if (variant == 44) hipLaunchKernelGGL((dp_temporal_kernel<4, 2, false, true>), dim3((n_seq + 3) / 4), dim3(2 * NT), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((dp_temporal_kernel<4, 2>), dim3((n_seq + 1) / 2), dim3(NT), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != t->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return tfail(t, DP_ERR_LAUNCH, std::string("dp_temporal_predict: ") + hipGetErrorString(e));
-    return DP_OK;
-}

@@ -1,7 +1,7 @@
 // dp_unity.cpp -- libDragPoserDLL.so: the reference's ten-function Unity plugin ABI (DragPoserDLL/exportFunc.h:61-70)
 // implemented natively on top of the dp_* library.  What the reference does in python/src/run_drag.py (RunDrag) and in
 // DragPose.set_initial_pose / the epilogue of DragPose.run is restated here in C++; the optimise loop itself is
-// dp_optimize on the GPU.  No HIP headers in this file: device buffers go through the dp_io_* helpers.
+// dp_optimize on the GPU.  No HIP calls in this file: device buffers go through the dp_io_* helpers.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -14,6 +14,7 @@
 
 #include "../../include/dragposer.h"
 #include "../../include/dragposer_unity.h"
+#include "dp_host_rt.h"
 
 namespace {
 
@@ -257,20 +258,15 @@ bool load_temporal(DragPoser* d, const std::string& path, std::string& err)
 
 } // namespace
 
-extern "C" {
+namespace impl { // the bodies of the exported functions (below: each behind the exception shell)
 
-DragPoser* init_drag_poser(void) { return new DragPoser(); }
 
-const char* drag_poser_last_error(const DragPoser* d) { return d ? d->err.c_str() : "null handle"; }
-int drag_poser_last_iterations(const DragPoser* d) { return d ? d->last_iters : 0; }
-void drag_poser_get_latent(const DragPoser* d, float* z) { if (d && z) std::memcpy(z, d->latent, sizeof(d->latent)); }
-void drag_poser_set_latent(DragPoser* d, const float* z)
+void set_latent(DragPoser* d, const float* z)
 { // replaces the latent and re-initialises the history with it, as set_initial_pose does with the encoder's (drag_pose.py:50-55)
     if (!d || !z) return;
     std::memcpy(d->latent, z, sizeof(d->latent));
     if (d->ctx && d->d_state && !reset_device_state(d)) d->fail(std::string("drag_poser_set_latent: ") + dp_last_error(d->ctx));
 }
-int drag_poser_has_temporal(const DragPoser* d) { return d && d->temporal ? 1 : 0; }
 
 void set_reference_skeleton(DragPoser* d, char* bvhPath)
 { // run_drag.py:30-38
@@ -522,5 +518,38 @@ void destroy_drag_poser(DragPoser* d)
     }
     delete d;
 }
+
+} // namespace impl
+
+// The reference ABI has no return codes and its callers are C#: no exception leaves an exported function.  One thrown inside `body` is recorded
+// as "<who>: host-side failure" (drag_poser_last_error, stderr).
+template <class Body>
+static void guarded(DragPoser* d, const char* who, Body body)
+{
+    if (dprt::shell(d, who, [&] { body(); return (int)DP_OK; }) != DP_OK) std::fprintf(stderr, "[DragPoserDLL] %s\n", dprt::last_error(d));
+}
+
+extern "C" {
+
+DragPoser* init_drag_poser(void)
+{
+    DragPoser* d = nullptr;
+    guarded(d, "init_drag_poser", [&] { d = new DragPoser(); });
+    return d;
+}
+const char* drag_poser_last_error(const DragPoser* d) { return d ? d->err.c_str() : "null handle"; }
+int drag_poser_last_iterations(const DragPoser* d) { return d ? d->last_iters : 0; }
+void drag_poser_get_latent(const DragPoser* d, float* z) { if (d && z) std::memcpy(z, d->latent, sizeof(d->latent)); }
+int drag_poser_has_temporal(const DragPoser* d) { return d && d->temporal ? 1 : 0; }
+void drag_poser_set_latent(DragPoser* d, const float* z) { guarded(d, "drag_poser_set_latent", [&] { impl::set_latent(d, z); }); }
+void set_reference_skeleton(DragPoser* d, char* bvhPath) { guarded(d, "set_reference_skeleton", [&] { impl::set_reference_skeleton(d, bvhPath); }); }
+void load_models(DragPoser* d, char* modelPath) { guarded(d, "load_models", [&] { impl::load_models(d, modelPath); }); }
+void set_mask_and_weights(DragPoser* d, float* mask, dp_float2* weights) { guarded(d, "set_mask_and_weights", [&] { impl::set_mask_and_weights(d, mask, weights); }); }
+void init_drag_model(DragPoser* d, dp_float3 pos, dp_quaternion rot) { guarded(d, "init_drag_model", [&] { impl::init_drag_model(d, pos, rot); }); }
+void set_optim_params(DragPoser* d, float stopEpsPos, float stopEpsRot, int maxIter, float lr) { guarded(d, "set_optim_params", [&] { impl::set_optim_params(d, stopEpsPos, stopEpsRot, maxIter, lr); }); }
+void set_lambdas(DragPoser* d, float lambdaRot, float lambdaTemporal, int temporalFutureWindow) { guarded(d, "set_lambdas", [&] { impl::set_lambdas(d, lambdaRot, lambdaTemporal, temporalFutureWindow); }); }
+void set_global_pos(DragPoser* d, dp_float3 p) { guarded(d, "set_global_pos", [&] { impl::set_global_pos(d, p); }); }
+void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quaternion* resultPose, dp_float3* resultGlobalPos) { guarded(d, "drag_pose", [&] { impl::drag_pose(d, nEE, tp, tq, resultPose, resultGlobalPos); }); }
+void destroy_drag_poser(DragPoser* d) { guarded(d, "destroy_drag_poser", [&] { impl::destroy_drag_poser(d); }); }
 
 } // extern "C"

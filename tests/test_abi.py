@@ -173,7 +173,7 @@ def test_temporal_predictor_argument_checks_and_no_cpu_fallback():
 
 
 def test_temporal_team_size_rule():
-    """host arithmetic of dp_temporal_predict's kernel choice (dp_temporal.hip: teams of workgroups per sequence when there are few): every member on a
+    """host arithmetic of dp_temporal_predict's kernel choice (dp_temporal_host.cpp: teams of workgroups per sequence when there are few): every member on a
     CU of its own, at least one feed-forward tile per wave, 16 up to a quarter of the device"""
     lib = _lib.load()
     size = lambda n_seq, n_cu=256, ff=2048: lib.dp_temporal_debug_team_size(n_cu, n_seq, ff)
@@ -189,7 +189,7 @@ def test_temporal_team_size_rule():
 
 
 def test_host_split_into_three_bf16_terms_is_exact():
-    """the feed-forward weights of the temporal predictor reach the bf16 matrix pipe as three bf16 terms each (dp_temporal.hip: split precision).
+    """the feed-forward weights of the temporal predictor reach the bf16 matrix pipe as three bf16 terms each (dp_temporal_host.cpp: host_split3; dp_temporal.hip: split precision).
     The host's split: every term the round-to-nearest-even bf16 of what is left, the three summing to the weight EXACTLY in fp32 arithmetic"""
     import numpy as np
 
