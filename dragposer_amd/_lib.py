@@ -207,6 +207,16 @@ class DpSkeletonIn(_Sized):
     _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("offsets", C.c_void_p), ("stride", C.c_int)]
 
 
+# every symbol include/dragposer_sequence_constraints.h declares (tests/test_sequence_constraints_abi.py)
+SEQUENCE_CONSTRAINT_SYMBOLS = ("dp_optimize_sequence_constrained", "dp_optimize_sequence_terms")
+
+
+class DpSeqExtra(_Sized):
+    """include/dragposer_sequence_constraints.h: dp_seq_extra (per-step outputs of the terms and the per-term row steps; all optional)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("loss_extra", C.c_void_p), ("loss_terms", C.c_void_p),
+                ("joint_pos", C.c_void_p), ("row_step", C.c_int * DP_MAX_TERMS)]
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -292,6 +302,10 @@ def load(path=None):
     lib.dp_forward_skeleton.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DpSkeletonIn), C.POINTER(DpResult), C.c_void_p]
     lib.dp_optimize_sequence_skeleton.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSkeletonIn),
                                                   C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]
+    _seq_tail = [C.POINTER(DpSkeletonIn), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.POINTER(DpSeqExtra), C.c_void_p]
+    lib.dp_optimize_sequence_constrained.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams),
+                                                     C.POINTER(DpConstraints)] + _seq_tail
+    lib.dp_optimize_sequence_terms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms)] + _seq_tail
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

@@ -35,6 +35,7 @@ using namespace dpcons;
 #include "dp_cons_dev.h"
 
 #define DP_CONS_SKEL 0 // (1: dp_cons_skel.hip)
+#define DP_CONS_SEQ 0  // (1: dp_cons_seq.hip)
 
 __global__ __launch_bounds__(WPB * 64) void dp_cons_kernel(Args a)
 #define DP_CONS_TABLE 0

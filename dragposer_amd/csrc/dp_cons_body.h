@@ -6,6 +6,10 @@
 // dp_cons_skel.hip includes it twice more under DP_CONS_SKEL 1 (dp_cons_skel_kernel, dp_terms_skel_kernel): the bones are then each frame's
 // own (include/dragposer_skeleton.h), read and screened in the prologue and kept in the wave's block (dp_cons_skel.h) instead of L_OFF.  The
 // #if DP_CONS_SKEL blocks are the only difference; with DP_CONS_SKEL 0 the text compiles to the instructions it gave before they existed.
+// dp_cons_seq.hip includes it twice more under DP_CONS_SKEL 1 and DP_CONS_SEQ 1 (dp_cons_seq_kernel, dp_terms_seq_kernel): a wave is then a
+// SEQUENCE and runs a.q.n_steps frames of it -- the screening, the iteration loop and the results below once per step, run()'s epilogue
+// (dp_sequence_advance_kernel's arithmetic) at each step's `stop`, the latent, global position and global rotation carried in registers
+// (dp_cons_seq.h).  The #if DP_CONS_SEQ blocks are the only difference; with DP_CONS_SEQ 0 the four kernels above keep their instructions.
 {
     constexpr bool TBL = DP_CONS_TABLE;
 #if DP_CONS_SKEL
@@ -61,6 +65,7 @@
     const bool jl = lane < NJ;
 
     // ---- screening (include/dragposer.h: DP_STATUS_*)
+#if !DP_CONS_SEQ // (a sequence: per step, below the skeleton)
     float cr[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) cr[k] = a.cur_rot[f * 4 + k];
@@ -70,6 +75,7 @@
         for (int k = 0; k < 3; ++k) gp[k] = a.global_pos[f * 3 + k];
     const float z0 = lane < LAT ? a.z0[f * LAT + lane] : 0.f;
     const float zt = lane < LAT ? a.z_tgt[f * LAT + lane] : 0.f;
+#endif
     const bool trk = jl && a.tracked[f * NJ + j] != 0;
 #if DP_CONS_SKEL
     // lane j: row j of this frame's skeleton (stride 0: the launch's one) -- its bone for the whole loop, and into the wave's block for the
@@ -85,6 +91,35 @@
 #pragma unroll
         for (int c = 0; c < 3; ++c) wb[W_SK + 3 * j + c] = off[c];
 #endif
+#if DP_CONS_SEQ
+    // what the sequence carries from step to step: the latent (lane k: component k), the global rotation and position (every lane)
+    float zc = lane < LAT ? a.z0[f * LAT + lane] : 0.f, crc[4], gpc[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) crc[k] = a.cur_rot[f * 4 + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gpc[k] = a.q.global_pos[f * 3 + k]; // (the state's array, never NULL; Args::global_pos is NULL when no term reads it)
+    const int NS = a.n_frames, NH = a.q.n_heights;
+    for (int stp = 0; stp < a.q.n_steps; ++stp) { // ---- the step loop: frame stp of this sequence, row ft of every per-step array
+    const long long ft = (long long)stp * NS + f;
+    float cr[4] = {crc[0], crc[1], crc[2], crc[3]};
+    float gp[3] = {0.f, 0.f, 0.f}; // (what the terms read and the screening sees: as in a per-frame launch, only when a term needs it)
+    if (reads_gp(a))
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gp[k] = gpc[k];
+    const float z0 = zc;
+    const float zt = lane < LAT ? a.z_tgt[(long long)stp * a.q.z_tgt_step + f * a.q.z_tgt_seq + lane] : 0.f;
+    float sh[3] = {0.f, 0.f, 0.f}; // this step's target shift: tgt_root[stp] - the global position before the step
+    if (a.q.tgt_root)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sh[k] = a.q.tgt_root[ft * 3 + k] - gpc[k];
+    float tpe[3] = {0.f, 0.f, 0.f}; // lane j: joint j's effective position target of this step
+    if (trk)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float tk = a.tgt_pos[(ft * NJ + j) * 3 + k];
+            tpe[k] = a.q.tgt_root ? tk + sh[k] : tk;
+        }
+#endif
     bool bs = refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]) || refused(gp[0]) || refused(gp[1]) ||
               refused(gp[2]);
 #if DP_CONS_SKEL
@@ -93,9 +128,15 @@
     bool bt = refused(zt);
     if (trk) {
 #pragma unroll
+#if DP_CONS_SEQ
+        for (int k = 0; k < 3; ++k) bt = bt || refused(tpe[k]);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) bt = bt || refused(a.tgt_rot[(ft * NJ + j) * 9 + k]);
+#else
         for (int k = 0; k < 3; ++k) bt = bt || refused(a.tgt_pos[(f * NJ + j) * 3 + k]);
 #pragma unroll
         for (int k = 0; k < 9; ++k) bt = bt || refused(a.tgt_rot[(f * NJ + j) * 9 + k]);
+#endif
         bt = bt || refused(a.w[(f * NJ + j) * 2]) || refused(a.w[(f * NJ + j) * 2 + 1]);
     }
 #if DP_CONS_TABLE
@@ -109,7 +150,11 @@
         r[3] = 1.f;
         if (pf && tb[T_W] != 0.f) {
 #pragma unroll
+#if DP_CONS_SEQ // (the term's rows of this step: T_STEP floats further per step, 0 = one row held)
+            for (int c = 0; c < 4; ++c) r[c] = pf[(long long)stp * __float_as_int(tb[T_STEP]) + f * 4 + c];
+#else
             for (int c = 0; c < 4; ++c) r[c] = pf[f * 4 + c];
+#endif
             bt = bt || refused(r[0]) || refused(r[1]) || refused(r[2]) || refused(r[3]) || r[3] < 0.f;
         }
 #pragma unroll
@@ -119,6 +164,41 @@
     const bool bad_state = __ballot(bs) != 0ull;
     const bool bad_tgt = !bad_state && __ballot(bt) != 0ull;
     const int E = __popcll(__ballot(trk));
+#if DP_CONS_SEQ
+    if (bad_state) { // this step's results NaN and, as the per-frame epilogue makes them from such a frame, the carried state: every later step too
+        float* const o = a.q.hist + ft * (LAT + 3 + NH);
+        if (lane < LAT + 3 + NH) o[lane] = nan;
+        if (jl) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) if (a.pose) a.pose[ft * 88 + 4 * j + c] = nan;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) if (a.pos) a.pos[(ft * NJ + j) * 3 + c] = nan;
+        }
+        if (lane < 4) {
+            if (a.world_rot) a.world_rot[ft * 4 + lane] = nan;
+#if !DP_CONS_TABLE
+            if (a.loss_extra) a.loss_extra[ft * 4 + lane] = nan;
+#endif
+        }
+#if DP_CONS_TABLE
+        if (lane < a.n_terms && a.loss_terms) a.loss_terms[ft * a.n_terms + lane] = nan;
+#endif
+        if (lane < 3) {
+            if (a.q.pos_ret) a.q.pos_ret[ft * 3 + lane] = nan;
+            if (a.loss) a.loss[ft * 3 + lane] = nan;
+        }
+        if (lane == 0) {
+            if (a.iters) a.iters[ft] = a.early_stop ? 1 : a.n_iter;
+            if (a.status) a.status[ft] = DP_STATUS_NONFINITE_RESULT | DP_STATUS_BAD_STATE;
+        }
+        zc = nan;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) crc[k] = nan;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gpc[k] = nan;
+        continue;
+    }
+#else
     if (bad_state) { // every result NaN (the reference's latent is NaN from here on); the reference's loop ends after one pass
         if (lane < LAT) {
             if (a.z) a.z[f * LAT + lane] = nan;
@@ -152,6 +232,7 @@
         }
         return;
     }
+#endif
 
     // per-lane constants of the frame loop
     const float c0 = lane < H0 ? W[dpvjp::OFF_C0 + lane] : 0.f;
@@ -278,13 +359,21 @@
             const float wp = a.w[(f * NJ + j) * 2], wrr = a.w[(f * NJ + j) * 2 + 1];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
+#if DP_CONS_SEQ
+                const float e = P[c] - tpe[c];
+#else
                 const float e = P[c] - a.tgt_pos[(f * NJ + j) * 3 + c];
+#endif
                 dpj = fmaf(e, e, dpj);
                 gPj[c] = cp * wp * e;
             }
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
+#if DP_CONS_SEQ
+                const float e = G[k] - a.tgt_rot[(ft * NJ + j) * 9 + k];
+#else
                 const float e = G[k] - a.tgt_rot[(f * NJ + j) * 9 + k];
+#endif
                 drj = fmaf(e, e, drj);
                 gGj[k] = crt * wrr * e;
             }
@@ -508,6 +597,70 @@
         const bool last = it + 1 >= n_iter;
         const bool stop = last || (a.early_stop && !((lp > a.stop_eps_pos || lr > a.stop_eps_rot) && (prev - tot > a.min_loss_incr)));
         prev = tot;
+#if DP_CONS_SEQ
+        if (stop) { // results of this, the step's last, forward pass, and run()'s epilogue (drag_pose.py:369-402) on them: the arithmetic and
+                    // order of dp_sequence_advance_kernel, which reads them from the per-frame kernel's result arrays.  Every lane holds the
+                    // same wd, d and carried gpc and computes the same new position.  (A bad target: the warm start's pose, as per frame.)
+            long long fo = ft; // (opaque: the step's store addresses are formed here, not hoisted into registers that live across the iteration loop)
+            asm volatile("" : "+v"(fo));
+            float gpn[3], dsp[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                gpn[k] = gpc[k] + wd[k]; // drag_pose.py:370
+                dsp[k] = d[k];
+            }
+            if (a.q.adjust_joint >= 0) { // drag_pose.py:377-384
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    float tk = a.tgt_pos[(fo * NJ + a.q.adjust_target_joint) * 3 + k]; // (that joint's effective target: its lane's tpe)
+                    if (a.q.tgt_root) tk = tk + sh[k];
+                    // a difference, a product and two sums, none fused: dp_sequence_advance_kernel's v_sub, v_mul, v_add, v_add
+                    const float adj = __fmul_rn(__fsub_rn(tk, PB[4 * a.q.adjust_joint + k]), a.q.adjust_weight);
+                    gpn[k] = __fadd_rn(gpn[k], adj);
+                    dsp[k] = __fadd_rn(dsp[k], adj);
+                }
+            }
+            float* const o = a.q.hist + fo * (LAT + 3 + NH);
+            if (lane < LAT) o[lane] = z;
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    o[LAT + k] = dsp[k];
+                    if (a.q.pos_ret) a.q.pos_ret[fo * 3 + k] = gpn[k];
+                }
+                for (int h = 0; h < NH; ++h) o[LAT + 3 + h] = PB[4 * a.q.height_joints[h] + 1] + gpn[1]; // y of (pos + the new global position)
+            }
+            if (jl) {
+                if (a.pose)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) // the returned pose: root channels = the normalised world rotation (drag_pose.py:399-402)
+                        a.pose[fo * 88 + 4 * j + c] = j == 0 ? (wr[c] - a.q.mean_q0[c]) / a.q.std_q0[c] : (qn[c] - muj[c]) / sdj[c];
+                if (a.pos)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) a.pos[(fo * NJ + j) * 3 + c] = P[c];
+            }
+            if (lane == 0) {
+                if (a.world_rot)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) a.world_rot[fo * 4 + c] = wr[c];
+                if (a.loss) {
+                    a.loss[fo * 3] = bad_tgt ? nan : lp; a.loss[fo * 3 + 1] = bad_tgt ? nan : lr; a.loss[fo * 3 + 2] = bad_tgt ? nan : lt;
+                }
+#if !DP_CONS_TABLE
+                if (a.loss_extra)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) a.loss_extra[fo * 4 + c] = bad_tgt ? nan : ext[c];
+#endif
+            }
+#if DP_CONS_TABLE
+            if (lane < a.n_terms && a.loss_terms) a.loss_terms[fo * a.n_terms + lane] = bad_tgt ? nan : mine;
+#endif
+#pragma unroll
+            for (int k = 0; k < 3; ++k) gpc[k] = gpn[k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) crc[k] = uni(wr[k]); // lane 0 holds the world root rotation (drag_pose.py:371)
+        }
+#else
         if (stop) { // results of this, the last, forward pass (drag_pose.py:309-312)
             const bool pz = bad_tgt && !(a.early_stop || a.n_iter == 1); // (fixed count: the reference would decode the NaN latent)
             if (lane < LAT && a.z_pre) a.z_pre[f * LAT + lane] = pz ? nan : z;
@@ -544,6 +697,7 @@
             if (lane < a.n_terms && a.loss_terms) a.loss_terms[f * a.n_terms + lane] = bad_tgt ? nan : mine;
 #endif
         }
+#endif
         wave_sync();
 
         // ---- backward: subtree sums, per-joint rotations, root
@@ -633,10 +787,24 @@
         if (stop) break;
     }
     const bool pz = bad_tgt;
+#if DP_CONS_SEQ
+    zc = pz ? nan : z; // the next step's warm start (a bad target: NaN, which that step's screening finds)
+    const bool nonfin = pz || __ballot(lane < LAT && !(fabsf(z) <= 3.0e38f)) != 0ull;
+    if (lane == 0) {
+        if (a.iters) a.iters[ft] = bad_tgt && !a.early_stop ? a.n_iter : it + 1;
+        if (a.status) a.status[ft] = (nonfin ? DP_STATUS_NONFINITE_RESULT : 0) | (bad_tgt ? DP_STATUS_BAD_TARGETS : 0);
+    }
+    wave_sync(); // (the next step's first writes into the wave's block follow this step's last reads)
+    } // the step loop
+    if (lane < LAT) a.z[f * LAT + lane] = zc;
+    if (lane < 3) a.q.global_pos[f * 3 + lane] = lane == 0 ? gpc[0] : lane == 1 ? gpc[1] : gpc[2];
+    if (lane < 4) a.q.global_rot[f * 4 + lane] = lane == 0 ? crc[0] : lane == 1 ? crc[1] : lane == 2 ? crc[2] : crc[3];
+#else
     if (lane < LAT && a.z) a.z[f * LAT + lane] = pz ? nan : z;
     const bool nonfin = pz || __ballot(lane < LAT && !(fabsf(z) <= 3.0e38f)) != 0ull;
     if (lane == 0) {
         if (a.iters) a.iters[f] = bad_tgt && !a.early_stop ? a.n_iter : it + 1;
         if (a.status) a.status[f] = (nonfin ? DP_STATUS_NONFINITE_RESULT : 0) | (bad_tgt ? DP_STATUS_BAD_TARGETS : 0);
     }
+#endif
 }

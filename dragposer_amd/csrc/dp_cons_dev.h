@@ -1,5 +1,5 @@
-// dp_cons_dev.h -- device helpers of dp_cons_body.h, shared by its two units: dp_cons.hip (the context's skeleton) and dp_cons_skel.hip
-// (per-frame skeletons).  Included after dp_cons.h, dp_math.h and dp_vjp.h, inside a unit that says `using namespace dpcons;`.
+// dp_cons_dev.h -- device helpers of dp_cons_body.h, shared by its units: dp_cons.hip (the context's skeleton), dp_cons_skel.hip
+// (per-frame skeletons) and dp_cons_seq.hip (the frame loop of a sequence in the launch).  Included after dp_cons.h, dp_math.h and dp_vjp.h, inside a unit that says `using namespace dpcons;`.
 #pragma once
 
 #define DEV __device__ __forceinline__

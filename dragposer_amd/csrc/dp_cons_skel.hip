@@ -18,6 +18,7 @@ using namespace dpcons;
 #include "dp_cons_dev.h"
 
 #define DP_CONS_SKEL 1
+#define DP_CONS_SEQ 0 // (1: dp_cons_seq.hip)
 
 __global__ __launch_bounds__(WPB * 64) void dp_cons_skel_kernel(SkelArgs a)
 #define DP_CONS_TABLE 0

@@ -19,7 +19,8 @@
 #include "../../include/dragposer_constraints.h"
 #include "../../include/dragposer_terms.h"
 #include "../../include/dragposer_skeleton.h"
-#include "dp_cons_skel.h"
+#include "../../include/dragposer_sequence_constraints.h"
+#include "dp_cons_seq.h"
 #include "dp_host_rt.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -670,6 +671,7 @@ constexpr Sized SKEL_IN_V510 = {"dp_skeleton_in", "dp_skeleton_in s = DP_SKELETO
 constexpr Sized GRAD_IN_V510 = {"dp_grad_in", "dp_grad_in g = DP_GRAD_IN_INIT;", offsetof(dp_grad_in, rot) + sizeof(void*), false};
 constexpr Sized CONS_V510 = {"dp_constraints", "dp_constraints c = DP_CONSTRAINTS_INIT;", offsetof(dp_constraints, loss_extra) + sizeof(void*), false};
 constexpr Sized TERMS_V510 = {"dp_terms", "dp_terms t = DP_TERMS_INIT;", offsetof(dp_terms, loss_terms) + sizeof(void*), false};
+constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
 {
@@ -1022,13 +1024,29 @@ static int constrained_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_
     return DP_OK;
 }
 
+// What a sequence launch (include/dragposer_sequence_constraints.h) asks of the two per-frame pointers of dp_constraints / dp_terms: the terms
+// read the state's own global position step after step, so `global_pos` is NULL or that array, and the per-frame output is dp_seq_extra's
+static int seq_pointers(dp_ctx* ctx, const float*& global_pos, const float* per_frame_out, const dp_seq_state* seq, const std::string& w, const char* strct,
+                        const char* out_name)
+{
+    if (global_pos && global_pos != seq->global_pos)
+        return fail(ctx, DP_ERR_INVALID, w + ": " + strct + ".global_pos must be NULL or dp_seq_state.global_pos (the terms read the sequence's own position)");
+    if (per_frame_out)
+        return fail(ctx, DP_ERR_INVALID, w + ": " + strct + "." + out_name + " is one row per frame; a sequence launch writes dp_seq_extra." + out_name);
+    global_pos = seq->global_pos;
+    return DP_OK;
+}
+
 // include/dragposer_constraints.h: dp_constraints validated and written into the argument block (constrained_impl's own(a)), for
-// dp_optimize_constrained and dp_optimize_constrained_skeleton (who names the caller in the messages)
-static int take_constraints(dp_ctx* ctx, const dp_constraints* c_in, dpcons::Args& a, const char* who)
+// dp_optimize_constrained, dp_optimize_constrained_skeleton and, with `seq` (the launch's state), dp_optimize_sequence_constrained (who names
+// the caller in the messages)
+static int take_constraints(dp_ctx* ctx, const dp_constraints* c_in, dpcons::Args& a, const char* who, const dp_seq_state* seq = nullptr)
 {
     const std::string w = who;
     dp_constraints c;
     if (int rc = take_sized(ctx, c_in, c, CONS_V510, who)) return rc;
+    if (seq)
+        if (int rc = seq_pointers(ctx, c.global_pos, c.loss_extra, seq, w, "dp_constraints", "loss_extra")) return rc;
     const float wts[4] = {c.w_feet_floor, c.w_head_hips_forward, c.w_head_hips_colinear, c.w_hips_feet_colinear};
     for (float x : wts)
         if (!(x >= 0.f && x <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": a weight is negative or not finite");
@@ -1039,7 +1057,7 @@ static int take_constraints(dp_ctx* ctx, const dp_constraints* c_in, dpcons::Arg
     const float rest[7] = {c.floor_level, c.fwd_axis[0], c.fwd_axis[1], c.fwd_axis[2], c.fwd_threshold, c.fwd_margin, c.feet_radius};
     for (float x : rest)
         if (!(std::fabs(x) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": a constraint parameter is not finite");
-    if (c.w_feet_floor != 0.f && !c.global_pos) return fail(ctx, DP_ERR_INVALID, w + ": global_pos is NULL while feet_floor is on");
+    if (!seq && c.w_feet_floor != 0.f && !c.global_pos) return fail(ctx, DP_ERR_INVALID, w + ": global_pos is NULL while feet_floor is on");
     a.global_pos = c.global_pos;
     a.loss_extra = c.loss_extra;
     a.w_floor = c.w_feet_floor; a.w_fwd = c.w_head_hips_forward; a.w_hcol = c.w_head_hips_colinear; a.w_feet = c.w_hips_feet_colinear;
@@ -1108,13 +1126,15 @@ static std::string check_term(const dp_term& t)
     return "";
 }
 
-// include/dragposer_terms.h: dp_terms validated and written into the argument block (constrained_impl's own(a)), for dp_optimize_terms and
-// dp_optimize_terms_skeleton (who names the caller in the messages)
-static int take_terms(dp_ctx* ctx, const dp_terms* t_in, dpcons::TermArgs& a, const char* who)
+// include/dragposer_terms.h: dp_terms validated and written into the argument block (constrained_impl's own(a)), for dp_optimize_terms,
+// dp_optimize_terms_skeleton and, with `seq` (the launch's state), dp_optimize_sequence_terms (who names the caller in the messages)
+static int take_terms(dp_ctx* ctx, const dp_terms* t_in, dpcons::TermArgs& a, const char* who, const dp_seq_state* seq = nullptr)
 {
     const std::string nm = who;
     dp_terms ts;
     if (int rc = take_sized(ctx, t_in, ts, TERMS_V510, who)) return rc;
+    if (seq)
+        if (int rc = seq_pointers(ctx, ts.global_pos, ts.loss_terms, seq, nm, "dp_terms", "loss_terms")) return rc;
     if (ts.n_terms < 0 || ts.n_terms > DP_MAX_TERMS)
         return fail(ctx, DP_ERR_INVALID, nm + ": n_terms " + std::to_string(ts.n_terms) + " outside 0..16");
     if (ts.n_terms > 0 && !ts.terms) return fail(ctx, DP_ERR_INVALID, nm + ": NULL terms with n_terms > 0");
@@ -1126,7 +1146,7 @@ static int take_terms(dp_ctx* ctx, const dp_terms* t_in, dpcons::TermArgs& a, co
         if (!why.empty()) return fail(ctx, DP_ERR_INVALID, nm + ": term " + std::to_string(k) + ": " + why);
         need_gp = need_gp || (t.weight != 0.f && (t.type == DP_TERM_PLANE || (t.type == DP_TERM_DISTANCE && t.joint_b < 0)));
     }
-    if (need_gp && !ts.global_pos)
+    if (!seq && need_gp && !ts.global_pos)
         return fail(ctx, DP_ERR_INVALID, nm + ": global_pos is NULL while an active PLANE or point-DISTANCE term needs it");
     a.global_pos = need_gp ? ts.global_pos : nullptr;
     a.up = ts.up_axis;
@@ -1177,6 +1197,48 @@ extern "C" int dp_optimize_terms_skeleton(dp_ctx* ctx, const dp_batch* in, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// What every whole-sequence launch asks of its frames, state, scratch and joint adjustment (who names the caller in the messages)
+static int check_sequence(dp_ctx* ctx, const dp_seq_frames* fr, const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results& out, const std::string& who)
+{
+    if (fr->n_steps <= 0 || !fr->tgt_pos || !fr->tgt_rot || !fr->w || !fr->tracked || !fr->z_tgt)
+        return fail(ctx, DP_ERR_INVALID, who + ": NULL input array / n_steps must be positive");
+    if (!st->global_pos || !st->global_rot || !st->latent_buf || !st->disp_buf || !st->heights_buf || !out.hist_scratch)
+        return fail(ctx, DP_ERR_INVALID, who + ": NULL state array / hist_scratch");
+    if (st->history < 1 || st->n_heights < 0 || st->n_heights > DP_MAX_HEIGHT_JOINTS)
+        return fail(ctx, DP_ERR_INVALID, who + ": history / n_heights out of range");
+    for (int h = 0; h < st->n_heights; ++h)
+        if (st->height_joints[h] < 0 || st->height_joints[h] >= NJ) return fail(ctx, DP_ERR_INVALID, who + ": bad height joint");
+    if (adj && (adj->adjust_joint >= NJ || (adj->adjust_joint >= 0 && (adj->adjust_target_joint < 0 || adj->adjust_target_joint >= NJ))))
+        return fail(ctx, DP_ERR_INVALID, who + ": bad joint adjustment");
+    return DP_OK;
+}
+
+// ... the step loop's part of the argument block (Q: dp_kernel.h's SeqK, dp_cons_seq.h's SeqFields -- the same field names)
+template <class Q>
+static void fill_sequence(Q& q, const dp_ctx* ctx, const dp_seq_frames* fr, const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results& out)
+{
+    q.n_steps = fr->n_steps; q.z_tgt_step = fr->z_tgt_step; q.z_tgt_seq = fr->z_tgt_seq; q.tgt_root = fr->tgt_root;
+    q.global_pos = st->global_pos; q.global_rot = st->global_rot; q.hist = out.hist_scratch; q.pos_ret = out.pos_ret;
+    q.n_heights = st->n_heights;
+    for (int h = 0; h < st->n_heights; ++h) q.height_joints[h] = st->height_joints[h];
+    q.adjust_joint = adj ? adj->adjust_joint : -1;
+    q.adjust_target_joint = adj ? adj->adjust_target_joint : -1;
+    q.adjust_weight = adj ? adj->adjust_weight : 0.f;
+    for (int c = 0; c < 4; ++c) { q.mean_q0[c] = ctx->mean_q0[c]; q.std_q0[c] = ctx->std_q0[c]; }
+}
+
+// ... and its second launch: the steps' rows appended to the three history buffers
+static int append_history(dp_ctx* ctx, int n_seq, const dp_seq_frames* fr, const dp_seq_state* st, const dp_seq_results& out, void* stream)
+{
+    DEVICE_GUARD(ctx);
+    HistArgs h;
+    h.n_seq = n_seq; h.n_steps = fr->n_steps; h.history = st->history; h.n_heights = st->n_heights;
+    h.scratch = out.hist_scratch; h.latent_buf = st->latent_buf; h.disp_buf = st->disp_buf; h.heights_buf = st->heights_buf;
+    hipError_t e = dp_launch_sequence_history(&h, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("history launch: ") + hipGetErrorString(e));
+    return DP_OK;
+}
+
 // n_steps frames of S sequences in one launch (+ one for the history buffers), see include/dragposer.h
 static int sequence_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
                          const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream)
@@ -1188,16 +1250,7 @@ static int sequence_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_fra
     if (int rc = take_params(ctx, p_in, p, who)) return rc;
     dp_seq_results out;
     if (int rc = take_sized(ctx, out_in, out, SEQ_RESULTS_V500, who)) return rc;
-    if (fr->n_steps <= 0 || !fr->tgt_pos || !fr->tgt_rot || !fr->w || !fr->tracked || !fr->z_tgt)
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: NULL input array / n_steps must be positive");
-    if (!st->global_pos || !st->global_rot || !st->latent_buf || !st->disp_buf || !st->heights_buf || !out.hist_scratch)
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: NULL state array / hist_scratch");
-    if (st->history < 1 || st->n_heights < 0 || st->n_heights > DP_MAX_HEIGHT_JOINTS)
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: history / n_heights out of range");
-    for (int h = 0; h < st->n_heights; ++h)
-        if (st->height_joints[h] < 0 || st->height_joints[h] >= NJ) return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: bad height joint");
-    if (adj && (adj->adjust_joint >= NJ || (adj->adjust_joint >= 0 && (adj->adjust_target_joint < 0 || adj->adjust_target_joint >= NJ))))
-        return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence: bad joint adjustment");
+    if (int rc = check_sequence(ctx, fr, st, adj, out, who)) return rc;
     if (int rc = check_adam(ctx, p, who)) return rc;
     const float* sk_off = nullptr;
     int sk_stride = 0;
@@ -1215,24 +1268,10 @@ static int sequence_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_fra
     k.n_frames = n_seq; k.mode = 0;
     fill_loop(k, p, true);
     fill_adam(k, p);
-    SeqK& q = k.seq;
-    q.n_steps = fr->n_steps; q.z_tgt_step = fr->z_tgt_step; q.z_tgt_seq = fr->z_tgt_seq; q.tgt_root = fr->tgt_root;
-    q.global_pos = st->global_pos; q.global_rot = st->global_rot; q.hist = out.hist_scratch; q.pos_ret = out.pos_ret;
-    q.n_heights = st->n_heights;
-    for (int h = 0; h < st->n_heights; ++h) q.height_joints[h] = st->height_joints[h];
-    q.adjust_joint = adj ? adj->adjust_joint : -1;
-    q.adjust_target_joint = adj ? adj->adjust_target_joint : -1;
-    q.adjust_weight = adj ? adj->adjust_weight : 0.f;
-    for (int c = 0; c < 4; ++c) { q.mean_q0[c] = ctx->mean_q0[c]; q.std_q0[c] = ctx->std_q0[c]; }
+    fill_sequence(k.seq, ctx, fr, st, adj, out);
     int rc = launch(ctx, k, stream, DP_KERNEL_W4, sk != nullptr);
     if (rc != DP_OK) return rc;
-    DEVICE_GUARD(ctx);
-    HistArgs h;
-    h.n_seq = n_seq; h.n_steps = fr->n_steps; h.history = st->history; h.n_heights = st->n_heights;
-    h.scratch = out.hist_scratch; h.latent_buf = st->latent_buf; h.disp_buf = st->disp_buf; h.heights_buf = st->heights_buf;
-    hipError_t e = dp_launch_sequence_history(&h, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string("history launch: ") + hipGetErrorString(e));
-    return DP_OK;
+    return append_history(ctx, n_seq, fr, st, out, stream);
 }
 
 extern "C" int dp_optimize_sequence(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_seq_state* st,
@@ -1269,6 +1308,107 @@ extern "C" int dp_optimize_sequence_skeleton(dp_ctx* ctx, int n_seq, float* late
     return entry(ctx, who, [&] {
         if (!skel) return refuse_null_skeleton(ctx, who);
         return sequence_impl(ctx, n_seq, latent, fr, p, skel, st, adj, out, stream);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// include/dragposer_sequence_constraints.h: dp_optimize_sequence_constrained (A = dpcons::SeqConsArgs) and dp_optimize_sequence_terms
+// (dpcons::SeqTermArgs), whose callers have refused a NULL argument -- constrained_impl's order of refusals with sequence_impl's frames and
+// state in the batch's place: params, results, own(a) (dp_constraints / dp_terms, then dp_seq_extra), the skeleton (NULL: the context's own
+// bones, one for the launch), frames / state, Adam.
+static int take_seq_extra(dp_ctx* ctx, const dp_seq_extra* e_in, dp_seq_extra& e, const char* who)
+{
+    std::memset(&e, 0, sizeof(e)); // (NULL: no per-step output of the terms, every per_frame array one row per sequence)
+    if (!e_in) return DP_OK;
+    if (int rc = take_sized(ctx, e_in, e, SEQ_EXTRA_V520, who)) return rc;
+    for (int k = 0; k < DP_MAX_TERMS; ++k)
+        if (e.row_step[k] < 0) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_seq_extra.row_step[" + std::to_string(k) + "] is negative");
+    return DP_OK;
+}
+
+// dp_cons_seq.hip is a unit a link of the host code may leave out (a host-only program without the kernel units): its two launchers are weak
+// references here, and a library without them refuses the calls with DP_ERR_UNSUPPORTED, as the header states.
+#ifndef DP_REF8_BUILD
+hipError_t dp_launch_cons_seq(const dpcons::SeqConsArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_terms_seq(const dpcons::SeqTermArgs* args, hipStream_t stream) __attribute__((weak));
+#endif
+
+template <class A, class Own>
+static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
+                                     const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream, const char* who, Own own)
+{
+    dp_params p;
+    if (int rc = take_params(ctx, p_in, p, who)) return rc;
+    dp_seq_results out;
+    if (int rc = take_sized(ctx, out_in, out, SEQ_RESULTS_V500, who)) return rc;
+    A a;
+    std::memset(&a, 0, sizeof(a));
+    if (int rc = own(a)) return rc;
+    if (sk)
+        if (int rc = take_skeleton(ctx, sk, a.skel, a.skel_stride, who)) return rc;
+    if (int rc = check_sequence(ctx, fr, st, adj, out, who)) return rc;
+    if (int rc = check_adam(ctx, p, who)) return rc;
+#ifdef DP_REF8_BUILD
+    (void)n_seq; (void)latent; (void)stream;
+    return refuse_ref8(ctx, who);
+#else
+    if (!dp_launch_cons_seq || !dp_launch_terms_seq) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_seq.hip");
+    if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+    a.img = ctx->d_vjpimg.get();
+    if (!sk) { a.skel = ctx->d_vjpimg.get() + dpvjp::OFF_BONE; a.skel_stride = 0; } // (the image's bone rows: what the per-frame kernels stage)
+    a.z0 = latent; a.z = latent; a.z_tgt = fr->z_tgt; a.cur_rot = st->global_rot; a.tgt_pos = fr->tgt_pos; a.tgt_rot = fr->tgt_rot; a.w = fr->w;
+    a.tracked = fr->tracked; a.n_frames = n_seq;
+    a.pose = out.pose_ret; a.world_rot = out.world_rot; a.iters = out.iters; a.loss = out.loss; a.status = out.status;
+    fill_loop(a, p, true);
+    a.beta1d = p.beta1; a.beta2d = p.beta2; a.lrd = p.lr;
+    fill_sequence(a.q, ctx, fr, st, adj, out);
+    {
+        DEVICE_GUARD(ctx);
+        hipError_t e;
+        if constexpr (std::is_same<A, dpcons::SeqConsArgs>::value) e = dp_launch_cons_seq(&a, (hipStream_t)stream);
+        else e = dp_launch_terms_seq(&a, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
+    }
+    return append_history(ctx, n_seq, fr, st, out, stream);
+#endif
+}
+
+extern "C" int dp_optimize_sequence_constrained(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in,
+                                                const dp_constraints* c_in, const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj,
+                                                const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_constrained";
+    const auto own = [&](dpcons::SeqConsArgs& a) -> int {
+        if (int rc = take_constraints(ctx, c_in, a, who, st)) return rc;
+        dp_seq_extra e;
+        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
+        a.loss_extra = e.loss_extra; a.pos = e.joint_pos;
+        return DP_OK;
+    };
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !c_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_constrained: n_sequences must be positive; NULL latent, frames, params, constraints, state or results");
+        return sequence_constrained_impl<dpcons::SeqConsArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own);
+    });
+}
+
+extern "C" int dp_optimize_sequence_terms(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                          const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out,
+                                          const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_terms";
+    const auto own = [&](dpcons::SeqTermArgs& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
+        dp_seq_extra e;
+        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
+        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
+        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
+        return DP_OK;
+    };
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_terms: n_sequences must be positive; NULL latent, frames, params, terms, state or results");
+        return sequence_constrained_impl<dpcons::SeqTermArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own);
     });
 }
 

@@ -247,13 +247,20 @@ class DragPose:
 
     def run_frames(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, target_root=None, stop_eps_pos=1e-2, stop_eps_rot=1e-2,
                    max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1, temporal_future_window=60,
-                   height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01, offsets=None):
+                   height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01, offsets=None,
+                   constraints=None, terms=None):
         """T consecutive frames of every sequence -- T calls of run() -- with the frame loop on the device: one kernel launch per
         stretch of frames between two temporal predictions (all T of them when there is no predictor or lambda_temporal is 0).
         target_ee_pos [T,S,E,3], target_ee_rot [T,S,E,3,3]; `target_root` [T,S,3] or None: given, the position targets of frame t
         are target_ee_pos[t] + (target_root[t] - current_global_pos) as eval_drag builds them (eval_drag.py:186-199), which no
         caller can do ahead of time.  `offsets`: the performers' bone offsets as in run() -- [22,3] or [S,22,3], kept for all T frames.
+        `constraints` (a dragposer_amd.Constraints) or `terms` (a dragposer_amd.Terms): the extra loss terms of run(constraints= / terms=)
+        in every frame's loss, the frame loop still on the device (dp_optimize_sequence_constrained / dp_optimize_sequence_terms), cut
+        into the same stretches and, unlike run(), together with `offsets`; a term's `per_frame` is [S,4], held for all T frames, or
+        [T,S,4].  `last_terms` then holds the weighted terms of every frame ([T,S,4] / [T,S,len(terms)]) and `last_joint_pos` [T,S,22,3].
         Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
+        if constraints is not None and terms is not None:
+            raise ValueError("DragPose.run_frames: pass constraints or terms, not both")
         dev, S = self.device, self.S
         skel = self._skeleton(offsets)
         tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=dev)
@@ -277,6 +284,23 @@ class DragPose:
         gpos = torch.empty(T, S, 3, device=dev)
         iters = torch.empty(T, S, dtype=torch.int32, device=dev)
         status = torch.empty(T, S, dtype=torch.int32, device=dev)
+        with_terms = constraints is not None or terms is not None
+        if with_terms:
+            if terms is not None:
+                for i, term in enumerate(terms.terms):
+                    if term.per_frame is not None and term.per_frame.dim() == 3 and int(term.per_frame.shape[0]) != T:
+                        raise ValueError(f"Terms: term {i}: per_frame must be [{S},4] or [{T},{S},4], got {tuple(term.per_frame.shape)}")
+            key, width = ("loss_extra", 4) if terms is None else ("loss_terms", len(terms))
+            self.last_terms = torch.empty(T, S, width, device=dev)
+            self.last_joint_pos = torch.empty(T, S, NJ, 3, device=dev)
+
+        def extra(t0, n):
+            """the stretch's share of the terms' arguments: the table's rows and the per-step outputs of frames t0 .. t0 + n"""
+            if not with_terms:
+                return {}
+            return {"constraints": constraints, "terms": terms.frames(t0, t0 + n) if terms is not None else None,
+                    key: self.last_terms[t0:t0 + n], "joint_pos": self.last_joint_pos[t0:t0 + n]}
+
         # The reference predicts at current_index == 0 whatever lambda_temporal is (drag_pose.py:235-291), so the stretches between two
         # predictions are cut the same way with the pull term on or off; without a predictor there is nothing to pull towards and the
         # term is off in run() and here alike (the reference cannot run without one).
@@ -297,7 +321,8 @@ class DragPose:
                                        self.latent_buffer, self.displacement_buffer, self.heights_buffer, tuple(int(h) for h in height_indices),
                                        n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_temporal) if pull else 0.0,
                                        stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, adjust=adjust,
-                                       pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n], offsets=skel)
+                                       pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n], offsets=skel,
+                                       **extra(t, n))
             t += n
             self.current_index = 0 if window == 0 else (self.current_index + n) % window
         self.last_status = status  # [T,S] DP_STATUS_* bits (include/dragposer.h): non-zero where a frame's inputs were not finite

@@ -21,6 +21,7 @@ import torch
 
 from . import quat_np as Q
 from .bvh import BVH
+from .constraints import Constraints
 from .drag_pose import DragPose
 from .encoder import PoseEncoder
 from .model import DEFAULT_MODEL, NJ, load_model_arrays
@@ -127,6 +128,9 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
     drag.set_initial_state(torch.cat([q["z0"] for q in seqs], dim=0), np.stack([q["m"]["global_pos"][0] for q in seqs]),
                            np.stack([q["m"]["global_rot"][0] for q in seqs]), np.stack([q["m"]["heights"][0] for q in seqs]))
     ja = tuple(cfg["joint_adjustment_indices"]) if cfg["enable_joint_adjustment"] else None
+    cons = None
+    if getattr(args, "constraints", None) == "reference":  # the reference's `# Additional Losses` block (drag_pose.py:129-183), un-commented
+        cons = Constraints.reference()
     poses = torch.zeros(T, S, 88, device=dev)
     out_pos = torch.zeros(T, S, 3, device=dev)
     iters = torch.zeros(T, S, dtype=torch.int32, device=dev)
@@ -138,7 +142,7 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
         poses, out_pos, iters = drag.run_frames(tp_rel, tR.reshape(T, S, -1, 3, 3), mask_idx, weights, target_root=gpos, stop_eps_pos=0.01 * 0.01,
                                                 stop_eps_rot=0.01, max_iter=args.max_iter, min_loss_incr=0.00001, learning_rate=1e-2, lambda_rot=1,
                                                 lambda_temporal=lam_tmp, temporal_future_window=window, height_indices=HEIGHT_INDICES,
-                                                joint_adjustment_indices=ja, joint_adjustment_weight=cfg["joint_adjustment_weight"], offsets=offsets)
+                                                joint_adjustment_indices=ja, joint_adjustment_weight=cfg["joint_adjustment_weight"], offsets=offsets, constraints=cons)
     for i in range(T if getattr(args, "per_frame", False) else 0):
         if i % 1000 == 0:
             print(f"Frame: {i + 1} out of {T}", flush=True)
@@ -146,7 +150,7 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
         drag.run(tp, tR[i], mask_idx, weights, offsets=offsets, stop_eps_pos=0.01 * 0.01, stop_eps_rot=0.01, max_iter=args.max_iter,
                  min_loss_incr=0.00001, learning_rate=1e-2, lambda_rot=1, lambda_temporal=lam_tmp,
                  temporal_future_window=window, height_indices=HEIGHT_INDICES, joint_adjustment_indices=ja,
-                 joint_adjustment_weight=cfg["joint_adjustment_weight"], verbose=args.verbose, out_pose=poses[i], out_pos=out_pos[i])
+                 joint_adjustment_weight=cfg["joint_adjustment_weight"], verbose=args.verbose, out_pose=poses[i], out_pos=out_pos[i], constraints=cons)
         iters[i] = drag.last["iters"]
     torch.cuda.synchronize()
     elapsed = time.time() - t0
@@ -210,6 +214,11 @@ def main(argv=None):
     ap.add_argument("--per-frame", action="store_true",
                     help="drive the frame loop from the host, one DragPose.run (two launches) per frame, as the reference does (default: the "
                          "frame loop runs on the device, DragPose.run_frames; same results)")
+    ap.add_argument("--constraints", choices=("reference",), default=None,
+                    help="add the reference's extra loss terms (the `# Additional Losses` block of DragPose.loss, every weight 1) to every frame's "
+                         "loss: DragPose.run_frames(constraints=Constraints.reference()) -- the frame loop still in one launch per stretch --, or "
+                         "with --per-frame DragPose.run(constraints=...), two launches per frame; same results -- for a BVH with the model's own skeleton: "
+                         "run() does not route other bones together with constraints and raises, run_frames() takes them")
     ap.add_argument("--lockstep", action="store_true",
                     help="directory input: advance all files together, one kernel launch per frame index for all of them "
                          "(same per-file results; the reference evaluates them one after the other)")

@@ -383,7 +383,8 @@ class LatentOptimizer:
     def optimize_sequence(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
                           heights_buf, height_joints, n_iter=100, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.0,
                           stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
-                          loss=None, scratch=None, status=None, offsets=None):
+                          loss=None, scratch=None, status=None, offsets=None, constraints=None, terms=None, loss_extra=None, loss_terms=None,
+                          joint_pos=None):
         """T consecutive frames of S sequences in one launch (include/dragposer.h: dp_optimize_sequence): the optimise loop with the
         reference's while-condition and run()'s epilogue per frame, state carried on the device.  tgt_pos [T,S,22,3] / tgt_rot
         [T,S,22,9] dense per joint; tgt_root [T,S,3] or None (position targets are then tgt_pos + (tgt_root[t] - running global
@@ -391,7 +392,17 @@ class LatentOptimizer:
         (floats between steps, floats between sequences).  `latent` [S,24], `global_pos`, `global_rot` and the three history
         buffers are updated IN PLACE.  Returns dict(pose_ret [T,S,88], pos_ret [T,S,3], iters [T,S], loss [T,S,3], status [T,S]: DP_STATUS_* bits).
         `offsets` [22,3] / [S,22,3]: one skeleton for every sequence / one per sequence, kept for every step (dp_optimize_sequence_skeleton,
-        include/dragposer_skeleton.h); None = the context's."""
+        include/dragposer_skeleton.h); None = the context's.
+        `constraints` (a dragposer_amd.Constraints) or `terms` (a dragposer_amd.Terms; a term's `per_frame` [S,4] held for all frames or
+        [T,S,4]): the extra loss terms in every frame's loss, the frame loop still in one launch -- dp_optimize_sequence_constrained /
+        dp_optimize_sequence_terms (include/dragposer_sequence_constraints.h), bit for bit what optimize_constrained / optimize_terms,
+        sequence_advance and a copy of the latent give frame by frame; the floor, PLANE and point-DISTANCE terms read `global_pos` as it
+        runs.  The dict then also holds `loss_extra` [T,S,4] / `loss_terms` [T,S,len(terms)] and `joint_pos` [T,S,22,3] (storage for them
+        may be passed).  Both None: dp_optimize_sequence, unchanged."""
+        if constraints is not None and terms is not None:
+            raise ValueError("optimize_sequence: pass constraints or terms, not both")
+        if constraints is None and terms is None and (loss_extra is not None or loss_terms is not None or joint_pos is not None):
+            raise ValueError("optimize_sequence: loss_extra / loss_terms / joint_pos are outputs of constraints= / terms=")
         T, S = int(tgt_pos.shape[0]), int(tgt_pos.shape[1])
         dev = self.device
         skel = self._skeleton(offsets, S, "optimize_sequence") if offsets is not None else None
@@ -433,6 +444,22 @@ class LatentOptimizer:
         p = self._params(n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, early=True)
         lp = C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev))
         tail = (C.byref(st), C.byref(step), C.byref(res))
+        if constraints is not None or terms is not None:
+            ex = _lib.DpSeqExtra()
+            per_step = ("loss_extra", loss_extra, (T, S, 4)) if terms is None else ("loss_terms", loss_terms, (T, S, len(terms)))
+            for field, given, shape in (per_step, ("joint_pos", joint_pos, (T, S, NJ, 3))):
+                buf = given if given is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+                setattr(ex, field, _check(buf, field, shape, torch.float32, dev) if buf.numel() else None)
+                outs[field] = buf
+            if terms is None:
+                own, keep, fn = constraints.to_struct(), None, self.lib.dp_optimize_sequence_constrained
+            else:
+                own, keep = terms.to_struct(S, dev, steps=T)
+                ex.row_step[:len(terms)] = terms.row_steps(S)
+                fn = self.lib.dp_optimize_sequence_terms
+            self._call(fn, S, lp, C.byref(fr), C.byref(p), C.byref(own), C.byref(skel) if skel is not None else None, *tail, C.byref(ex))
+            del keep
+            return outs
         fn, args = (self.lib.dp_optimize_sequence, tail) if skel is None else (self.lib.dp_optimize_sequence_skeleton, (C.byref(skel),) + tail)
         self._call(fn, S, lp, C.byref(fr), C.byref(p), *args)
         return outs

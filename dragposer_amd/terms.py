@@ -1,7 +1,9 @@
 """User-defined constraint terms for the per-frame latent optimisation: include/dragposer_terms.h, dp_optimize_terms.  A `Terms` table
 of up to 16 `Term`s, each a PLANE on a joint, a DISTANCE band between a joint and a joint or a point, or the ALIGNment of a joint axis
 with a joint axis or a world direction, optionally scaled (and its point / direction replaced) per frame.  Used by
-`LatentOptimizer.optimize_terms` and `DragPose.run(terms=...)`; semantics in the header's comment."""
+`LatentOptimizer.optimize_terms` and `DragPose.run(terms=...)`; semantics in the header's comment.  Whole-sequence launches
+(`LatentOptimizer.optimize_sequence(terms=...)`, `DragPose.run_frames(terms=...)`: include/dragposer_sequence_constraints.h) take a
+`per_frame` of [S,4], held for all frames, or [T,S,4], one row per frame."""
 import math
 from dataclasses import dataclass, field
 from typing import Optional
@@ -109,7 +111,8 @@ class Term:
             if self.joint_b < 0 and self.per_frame is None and not unit(self.dir):
                 bad("ALIGN's world direction is not unit length")
 
-    def to_struct(self, B=None, device=None):
+    def to_struct(self, B=None, device=None, steps=None):
+        """`steps` (a whole-sequence launch of that many frames): per_frame may also be [steps,B,4]"""
         t = _lib.DpTerm(type=int(self.type), joint_a=int(self.joint_a), joint_b=int(self.joint_b), flags=int(self.flags),
                         weight=float(self.weight), p0=float(self.p0), p1=float(self.p1))
         t.point[:], t.dir[:] = list(self.point), list(self.dir)
@@ -119,7 +122,8 @@ class Term:
 
             from .optimizer import _check
 
-            t.per_frame = _check(self.per_frame, "per_frame", (B, 4), torch.float32, device)
+            shape = (steps, B, 4) if steps is not None and getattr(self.per_frame, "dim", lambda: 2)() == 3 else (B, 4)
+            t.per_frame = _check(self.per_frame, "per_frame", shape, torch.float32, device)
         return t
 
 
@@ -165,11 +169,22 @@ class Terms:
         for i, t in enumerate(self.terms):
             t.check(i)
 
-    def to_struct(self, B, device, global_pos_ptr=None, loss_terms_ptr=None):
-        """-> (_lib.DpTerms, the DpTerm array it points to: keep both alive for the call)"""
+    def row_steps(self, B):
+        """dp_seq_extra.row_step of a whole-sequence launch: floats between two frames' rows of each term's per_frame (0: [B,4], held)"""
+        return [4 * B if t.per_frame is not None and t.per_frame.dim() == 3 else 0 for t in self.terms]
+
+    def frames(self, t0, t1):
+        """the table of frames t0..t1 of a clip: every [T,S,4] per_frame cut to those rows (a view), the rest shared"""
+        from dataclasses import replace
+
+        cut = lambda t: replace(t, per_frame=t.per_frame[t0:t1]) if t.per_frame is not None and t.per_frame.dim() == 3 else t
+        return Terms([cut(t) for t in self.terms], self.up_axis)
+
+    def to_struct(self, B, device, global_pos_ptr=None, loss_terms_ptr=None, steps=None):
+        """-> (_lib.DpTerms, the DpTerm array it points to: keep both alive for the call).  `steps`: as Term.to_struct"""
         self.check()
         n = len(self.terms)
-        arr = (_lib.DpTerm * max(n, 1))(*[t.to_struct(B, device) for t in self.terms])
+        arr = (_lib.DpTerm * max(n, 1))(*[t.to_struct(B, device, steps) for t in self.terms])
         s = _lib.DpTerms(n_terms=n, up_axis=int(self.up_axis))
         s.terms = _lib.C.cast(arr, _lib.C.c_void_p) if n else None
         s.global_pos = global_pos_ptr
