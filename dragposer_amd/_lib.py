@@ -217,6 +217,22 @@ class DpSeqExtra(_Sized):
                 ("joint_pos", C.c_void_p), ("row_step", C.c_int * DP_MAX_TERMS)]
 
 
+# every symbol include/dragposer_holds.h declares (tests/test_holds_abi.py)
+HOLD_SYMBOLS = ("dp_optimize_sequence_holds",)
+DP_MAX_HOLDS = 4
+
+
+class DpHold(C.Structure):
+    """include/dragposer_holds.h: dp_hold"""
+    _fields_ = [("term", C.c_int), ("level", C.c_float), ("contact_lo", C.c_float), ("contact_hi", C.c_float)]
+
+
+class DpHolds(_Sized):
+    """include/dragposer_holds.h: dp_holds (holds: a HOST array of DpHold; state / trace: device pointers)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("n_holds", C.c_int), ("holds", C.c_void_p), ("state", C.c_void_p),
+                ("trace", C.c_void_p)]
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -306,6 +322,8 @@ def load(path=None):
     lib.dp_optimize_sequence_constrained.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams),
                                                      C.POINTER(DpConstraints)] + _seq_tail
     lib.dp_optimize_sequence_terms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms)] + _seq_tail
+    lib.dp_optimize_sequence_holds.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
+                                               C.POINTER(DpHolds)] + _seq_tail
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

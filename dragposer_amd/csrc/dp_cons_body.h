@@ -10,6 +10,9 @@
 // SEQUENCE and runs a.q.n_steps frames of it -- the screening, the iteration loop and the results below once per step, run()'s epilogue
 // (dp_sequence_advance_kernel's arithmetic) at each step's `stop`, the latent, global position and global rotation carried in registers
 // (dp_cons_seq.h).  The #if DP_CONS_SEQ blocks are the only difference; with DP_CONS_SEQ 0 the four kernels above keep their instructions.
+// dp_cons_hold.hip includes it once more under DP_CONS_TABLE 1, DP_CONS_SKEL 1, DP_CONS_SEQ 1 and DP_CONS_HOLD 1 (dp_terms_hold_seq_kernel,
+// include/dragposer_holds.h): a held term's row of the wave's block is its hold's state, updated by run()'s epilogue (dp_cons_hold.h).  The
+// #if DP_CONS_HOLD blocks are the only difference; without DP_CONS_HOLD the six kernels above keep their instructions.
 {
     constexpr bool TBL = DP_CONS_TABLE;
 #if DP_CONS_SKEL
@@ -99,6 +102,14 @@
 #pragma unroll
     for (int k = 0; k < 3; ++k) gpc[k] = a.q.global_pos[f * 3 + k]; // (the state's array, never NULL; Args::global_pos is NULL when no term reads it)
     const int NS = a.n_frames, NH = a.q.n_heights;
+#if DP_CONS_HOLD // lane t, term t held and active: its row of the wave's block is the hold's state from here to the end of the launch
+    if (lane < a.n_terms) {
+        const int hd = hold_of(a.h.n_holds, a.h.terms, lane);
+        if (hd >= 0 && lds[L_TBL + lane * TW + T_W] != 0.f)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) wb[W_ROW + 4 * lane + c] = a.h.state[(f * a.h.n_holds + hd) * 4 + c];
+    }
+#endif
     for (int stp = 0; stp < a.q.n_steps; ++stp) { // ---- the step loop: frame stp of this sequence, row ft of every per-step array
     const long long ft = (long long)stp * NS + f;
     float cr[4] = {crc[0], crc[1], crc[2], crc[3]};
@@ -157,6 +168,13 @@
 #endif
             bt = bt || refused(r[0]) || refused(r[1]) || refused(r[2]) || refused(r[3]) || r[3] < 0.f;
         }
+#if DP_CONS_HOLD // (a held term has no per_frame array: its row is the state as the step before left it, screened as a per_frame row)
+        if (tb[T_W] != 0.f && hold_of(a.h.n_holds, a.h.terms, lane) >= 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) r[c] = wb[W_ROW + 4 * lane + c];
+            bt = bt || refused(r[0]) || refused(r[1]) || refused(r[2]) || refused(r[3]) || r[3] < 0.f;
+        }
+#endif
 #pragma unroll
         for (int c = 0; c < 4; ++c) wb[W_ROW + 4 * lane + c] = r[c];
     }
@@ -182,6 +200,14 @@
         }
 #if DP_CONS_TABLE
         if (lane < a.n_terms && a.loss_terms) a.loss_terms[ft * a.n_terms + lane] = nan;
+#endif
+#if DP_CONS_HOLD // (the hold's state stays as it is: the trace repeats it)
+        if (lane < a.n_terms && a.h.trace) {
+            const int hd = hold_of(a.h.n_holds, a.h.terms, lane);
+            if (hd >= 0 && lds[L_TBL + lane * TW + T_W] != 0.f)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) a.h.trace[(ft * a.h.n_holds + hd) * 4 + c] = wb[W_ROW + 4 * lane + c];
+        }
 #endif
         if (lane < 3) {
             if (a.q.pos_ret) a.q.pos_ret[ft * 3 + lane] = nan;
@@ -620,6 +646,26 @@
                     dsp[k] = __fadd_rn(dsp[k], adj);
                 }
             }
+#if DP_CONS_HOLD // include/dragposer_holds.h, "The update": lane t on its own row, which no lane reads again before the step's closing wave_sync()
+            if (lane < a.n_terms) {
+                const int hd = hold_of(a.h.n_holds, a.h.terms, lane);
+                const float* tb = lds + L_TBL + lane * TW;
+                if (hd >= 0 && tb[T_W] != 0.f) {
+                    const int ja = __float_as_int(tb[T_JA]);
+                    float* const row = wb + W_ROW + 4 * lane;
+                    float wp[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) wp[k] = __fadd_rn(gpn[k], __fsub_rn(PB[4 * ja + k], PB[k])); // where a renderer puts joint a
+                    const float hgt = __fsub_rn(comp(wp, up), tb[T_HLEVEL]);
+                    if (row[3] == 0.f) {
+                        if (hgt <= tb[T_HLO]) { row[0] = wp[0]; row[1] = wp[1]; row[2] = wp[2]; row[3] = 1.f; }
+                    } else if (hgt > tb[T_HHI]) row[3] = 0.f;
+                    if (a.h.trace)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) a.h.trace[(fo * a.h.n_holds + hd) * 4 + c] = row[c];
+                }
+            }
+#endif
             float* const o = a.q.hist + fo * (LAT + 3 + NH);
             if (lane < LAT) o[lane] = z;
             if (lane == 0) {
@@ -796,6 +842,14 @@
     }
     wave_sync(); // (the next step's first writes into the wave's block follow this step's last reads)
     } // the step loop
+#if DP_CONS_HOLD
+    if (lane < a.n_terms) {
+        const int hd = hold_of(a.h.n_holds, a.h.terms, lane);
+        if (hd >= 0 && lds[L_TBL + lane * TW + T_W] != 0.f)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) a.h.state[(f * a.h.n_holds + hd) * 4 + c] = wb[W_ROW + 4 * lane + c];
+    }
+#endif
     if (lane < LAT) a.z[f * LAT + lane] = zc;
     if (lane < 3) a.q.global_pos[f * 3 + lane] = lane == 0 ? gpc[0] : lane == 1 ? gpc[1] : gpc[2];
     if (lane < 4) a.q.global_rot[f * 4 + lane] = lane == 0 ? crc[0] : lane == 1 ? crc[1] : lane == 2 ? crc[2] : crc[3];

@@ -20,7 +20,8 @@
 #include "../../include/dragposer_terms.h"
 #include "../../include/dragposer_skeleton.h"
 #include "../../include/dragposer_sequence_constraints.h"
-#include "dp_cons_seq.h"
+#include "../../include/dragposer_holds.h"
+#include "dp_cons_hold.h"
 #include "dp_host_rt.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -671,6 +672,7 @@ constexpr Sized SKEL_IN_V510 = {"dp_skeleton_in", "dp_skeleton_in s = DP_SKELETO
 constexpr Sized GRAD_IN_V510 = {"dp_grad_in", "dp_grad_in g = DP_GRAD_IN_INIT;", offsetof(dp_grad_in, rot) + sizeof(void*), false};
 constexpr Sized CONS_V510 = {"dp_constraints", "dp_constraints c = DP_CONSTRAINTS_INIT;", offsetof(dp_constraints, loss_extra) + sizeof(void*), false};
 constexpr Sized TERMS_V510 = {"dp_terms", "dp_terms t = DP_TERMS_INIT;", offsetof(dp_terms, loss_terms) + sizeof(void*), false};
+constexpr Sized HOLDS_V530 = {"dp_holds", "dp_holds h = DP_HOLDS_INIT;", offsetof(dp_holds, trace) + sizeof(void*), false};
 constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
@@ -1331,6 +1333,7 @@ static int take_seq_extra(dp_ctx* ctx, const dp_seq_extra* e_in, dp_seq_extra& e
 #ifndef DP_REF8_BUILD
 hipError_t dp_launch_cons_seq(const dpcons::SeqConsArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_terms_seq(const dpcons::SeqTermArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_terms_hold_seq(const dpcons::HoldSeqArgs* args, hipStream_t stream) __attribute__((weak)); // (dp_cons_hold.hip, likewise)
 #endif
 
 template <class A, class Own>
@@ -1352,7 +1355,9 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
     (void)n_seq; (void)latent; (void)stream;
     return refuse_ref8(ctx, who);
 #else
-    if (!dp_launch_cons_seq || !dp_launch_terms_seq) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_seq.hip");
+    constexpr bool HOLDS = std::is_same<A, dpcons::HoldSeqArgs>::value;
+    if (HOLDS ? !dp_launch_terms_hold_seq : (!dp_launch_cons_seq || !dp_launch_terms_seq))
+        return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without " + (HOLDS ? "dp_cons_hold.hip" : "dp_cons_seq.hip"));
     if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
     a.img = ctx->d_vjpimg.get();
     if (!sk) { a.skel = ctx->d_vjpimg.get() + dpvjp::OFF_BONE; a.skel_stride = 0; } // (the image's bone rows: what the per-frame kernels stage)
@@ -1366,6 +1371,7 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
         DEVICE_GUARD(ctx);
         hipError_t e;
         if constexpr (std::is_same<A, dpcons::SeqConsArgs>::value) e = dp_launch_cons_seq(&a, (hipStream_t)stream);
+        else if constexpr (HOLDS) e = dp_launch_terms_hold_seq(&a, (hipStream_t)stream);
         else e = dp_launch_terms_seq(&a, (hipStream_t)stream);
         if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
     }
@@ -1409,6 +1415,64 @@ extern "C" int dp_optimize_sequence_terms(dp_ctx* ctx, int n_seq, float* latent,
         if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !st || !out)
             return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_terms: n_sequences must be positive; NULL latent, frames, params, terms, state or results");
         return sequence_constrained_impl<dpcons::SeqTermArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own);
+    });
+}
+
+// include/dragposer_holds.h: dp_optimize_sequence_terms with holds (A = dpcons::HoldSeqArgs).  take_holds runs after take_terms has accepted
+// the table t_in: it checks dp_holds against it, puts each hold's level and thresholds into its term's staged axis_a words (a point-DISTANCE
+// term never reads them) and fills the hold-to-term map (dp_cons_hold.h).
+static int take_holds(dp_ctx* ctx, const dp_holds* h_in, const dp_terms* t_in, dpcons::HoldSeqArgs& a, const char* who)
+{
+    const std::string nm = who;
+    dp_holds hs;
+    if (int rc = take_sized(ctx, h_in, hs, HOLDS_V530, who)) return rc;
+    dp_terms ts;
+    copy_sized(t_in, ts);
+    if (hs.n_holds < 0 || hs.n_holds > DP_MAX_HOLDS)
+        return fail(ctx, DP_ERR_INVALID, nm + ": dp_holds.n_holds " + std::to_string(hs.n_holds) + " outside 0.." + std::to_string(DP_MAX_HOLDS));
+    if (hs.n_holds > 0 && !hs.holds) return fail(ctx, DP_ERR_INVALID, nm + ": dp_holds.holds is NULL with n_holds > 0");
+    if (hs.n_holds > 0 && !hs.state) return fail(ctx, DP_ERR_INVALID, nm + ": dp_holds.state is NULL with n_holds > 0");
+    a.h.state = hs.state; a.h.trace = hs.trace; a.h.n_holds = hs.n_holds; a.h.terms = 0u;
+    for (int h = 0; h < hs.n_holds; ++h) {
+        const dp_hold& hd = hs.holds[h];
+        const std::string hn = nm + ": hold " + std::to_string(h) + ": ";
+        if (hd.term < 0 || hd.term >= ts.n_terms)
+            return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " outside the table of " + std::to_string(ts.n_terms));
+        const dp_term& t = ts.terms[hd.term];
+        if (t.type != DP_TERM_DISTANCE) return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " is not a DP_TERM_DISTANCE term");
+        if (t.joint_b != -1) return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " has a joint_b (a hold needs a point-DISTANCE term)");
+        if (t.per_frame) return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " has a per_frame array (the hold's state is its row)");
+        for (int g = 0; g < h; ++g)
+            if (hs.holds[g].term == hd.term)
+                return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " is already held by hold " + std::to_string(g));
+        if (!std::isfinite(hd.level) || !std::isfinite(hd.contact_lo) || !std::isfinite(hd.contact_hi))
+            return fail(ctx, DP_ERR_INVALID, hn + "non-finite level, contact_lo or contact_hi");
+        if (hd.contact_lo > hd.contact_hi) return fail(ctx, DP_ERR_INVALID, hn + "contact_lo is above contact_hi");
+        float* wf = (float*)(a.tbl + hd.term * dpcons::TW);
+        wf[dpcons::T_HLEVEL] = hd.level; wf[dpcons::T_HLO] = hd.contact_lo; wf[dpcons::T_HHI] = hd.contact_hi;
+        a.h.terms |= (unsigned)hd.term << (8 * h);
+    }
+    return DP_OK;
+}
+
+extern "C" int dp_optimize_sequence_holds(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                          const dp_holds* h_in, const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj,
+                                          const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_holds";
+    const auto own = [&](dpcons::HoldSeqArgs& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
+        if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
+        dp_seq_extra e;
+        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
+        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
+        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
+        return DP_OK;
+    };
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !h_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_holds: n_sequences must be positive; NULL latent, frames, params, terms, holds, state or results");
+        return sequence_constrained_impl<dpcons::HoldSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own);
     });
 }
 

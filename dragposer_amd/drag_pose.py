@@ -97,7 +97,18 @@ class DragPose:
         self._trk_cache = {}
         self._out = [None, None]
         self._flip = 0
+        self.hold_state = None  # [S,len(holds),4] (x, y, z, held) of run(holds=) / run_frames(holds=); zeroed when a sequence begins
         self._skel_obj, self._skel_dev = None, None  # the last `offsets` object run() / run_frames() was given, and what it decided (_skeleton)
+
+    def _holds(self, holds, terms, constraints, who):
+        """run()'s / run_frames()'s `holds`: checked against the table, `hold_state` allocated (zeros: nothing held) on first use"""
+        if holds is None:
+            return
+        if terms is None or constraints is not None:
+            raise ValueError(f"DragPose.{who}: holds= refer to a table, pass terms= (Terms.from_constraints turns constraints into one)")
+        holds.check(terms)
+        if self.hold_state is None or tuple(self.hold_state.shape) != (self.S, len(holds), 4):
+            self.hold_state = holds.new_state(self.S, self.device)
 
     def _index(self, values):
         """device index tensor for a Python list, created once (no host->device copy inside a captured step)"""
@@ -161,6 +172,7 @@ class DragPose:
         self.begin_status = o["status"]  # [S] DP_STATUS_* bits: non-zero where a sequence's initial pose / state was refused
         self.current_index = 0
         self.target_latent_buffer = None
+        self.hold_state = None
 
     def set_initial_state(self, latent, init_global_pos, initial_global_rot, initial_heights):
         """What set_initial_pose leaves behind, with the initial latent given instead of encoded."""
@@ -174,6 +186,7 @@ class DragPose:
         self.heights_buffer = f(initial_heights, (S, 1, -1)).repeat(1, HISTORY, 1)
         self.current_index = 0
         self.target_latent_buffer = None
+        self.hold_state = None
 
     # ------------------------------------------------------------------ temporal target (drag_pose.py:234-294)
     def _temporal_targets(self, window):
@@ -248,7 +261,7 @@ class DragPose:
     def run_frames(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, target_root=None, stop_eps_pos=1e-2, stop_eps_rot=1e-2,
                    max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1, temporal_future_window=60,
                    height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01, offsets=None,
-                   constraints=None, terms=None):
+                   constraints=None, terms=None, holds=None):
         """T consecutive frames of every sequence -- T calls of run() -- with the frame loop on the device: one kernel launch per
         stretch of frames between two temporal predictions (all T of them when there is no predictor or lambda_temporal is 0).
         target_ee_pos [T,S,E,3], target_ee_rot [T,S,E,3,3]; `target_root` [T,S,3] or None: given, the position targets of frame t
@@ -258,9 +271,13 @@ class DragPose:
         in every frame's loss, the frame loop still on the device (dp_optimize_sequence_constrained / dp_optimize_sequence_terms), cut
         into the same stretches and, unlike run(), together with `offsets`; a term's `per_frame` is [S,4], held for all T frames, or
         [T,S,4].  `last_terms` then holds the weighted terms of every frame ([T,S,4] / [T,S,len(terms)]) and `last_joint_pos` [T,S,22,3].
+        `holds` (a dragposer_amd.Holds, with `terms`): joints held where they touched down (dp_optimize_sequence_holds,
+        include/dragposer_holds.h); the state lives in `hold_state` [S,len(holds),4], zeroed when a sequence begins and passed through
+        every stretch, and `last_hold_trace` [T,S,len(holds),4] holds it after every frame.
         Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run_frames: pass constraints or terms, not both")
+        self._holds(holds, terms, constraints, "run_frames")
         dev, S = self.device, self.S
         skel = self._skeleton(offsets)
         tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=dev)
@@ -293,13 +310,18 @@ class DragPose:
             key, width = ("loss_extra", 4) if terms is None else ("loss_terms", len(terms))
             self.last_terms = torch.empty(T, S, width, device=dev)
             self.last_joint_pos = torch.empty(T, S, NJ, 3, device=dev)
+        if holds is not None:
+            self.last_hold_trace = torch.zeros(T, S, len(holds), 4, device=dev)
 
         def extra(t0, n):
             """the stretch's share of the terms' arguments: the table's rows and the per-step outputs of frames t0 .. t0 + n"""
             if not with_terms:
                 return {}
-            return {"constraints": constraints, "terms": terms.frames(t0, t0 + n) if terms is not None else None,
-                    key: self.last_terms[t0:t0 + n], "joint_pos": self.last_joint_pos[t0:t0 + n]}
+            kw = {"constraints": constraints, "terms": terms.frames(t0, t0 + n) if terms is not None else None,
+                  key: self.last_terms[t0:t0 + n], "joint_pos": self.last_joint_pos[t0:t0 + n]}
+            if holds is not None:
+                kw.update(holds=holds, hold_state=self.hold_state, hold_trace=self.last_hold_trace[t0:t0 + n])
+            return kw
 
         # The reference predicts at current_index == 0 whatever lambda_temporal is (drag_pose.py:235-291), so the stretches between two
         # predictions are cut the same way with the pull term on or off; without a predictor there is nothing to pull towards and the
@@ -331,14 +353,16 @@ class DragPose:
     def run(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, offsets=None, stop_eps_pos=1e-2,
             stop_eps_rot=1e-2, max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1,
             temporal_future_window=60, height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None,
-            joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None):
+            joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None, holds=None):
         """One frame for every sequence: one launch for the optimise loop and the epilogue, one for the history buffers, plus two
         row scatters of the targets.  `out_pose` [S,88] / `out_pos` [S,3]: optional caller storage for the returned tensors.
         `constraints` (a dragposer_amd.Constraints): the reference's extra loss terms (drag_pose.py:129-183) join the loss -- the frame
         is then dp_optimize_constrained followed by dp_sequence_advance (two launches), with this frame's current_global_pos as the
         floor term's global position; None runs the path above unchanged.  `terms` (a dragposer_amd.Terms): a table of user-defined
         terms instead, the same two launches with dp_optimize_terms (a term's per-frame rows: its [S,4] `per_frame` tensor, read at
-        this call); not together with `constraints`.
+        this call); not together with `constraints`.  `holds` (a dragposer_amd.Holds, with `terms`): each held term reads its row from
+        `hold_state`, and the state is updated after the frame with include/dragposer_holds.h's arithmetic in torch on the device, no
+        synchronisation -- frame by frame the bits of run_frames(terms=, holds=).
         `offsets`: the performer's bone offsets, as the reference takes them on every call (drag_pose.py:202) -- [22,3] for every sequence
         or [S,22,3] one per sequence.  The context's own skeleton (or None) runs the launches above unchanged; any other runs the same frame
         with those bones (dp_optimize_sequence_skeleton, include/dragposer_skeleton.h), not together with `constraints` / `terms`: this
@@ -346,6 +370,7 @@ class DragPose:
         the same object frame after frame costs one host synchronisation in all (DragPose._skeleton)."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
+        self._holds(holds, terms, constraints, "run")
         skel = self._skeleton(offsets)
         if skel is not None and (constraints is not None or terms is not None):
             raise ValueError("DragPose.run: offsets other than the context's skeleton cannot be combined with " +
@@ -385,7 +410,7 @@ class DragPose:
         if constraints is not None or terms is not None:
             return self._run_constrained(constraints if terms is None else terms, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot,
                                          lambda_temporal if pull else 0.0, stop_eps_pos, stop_eps_rot, min_loss_incr, temporal_future_window,
-                                         verbose, squeeze)
+                                         verbose, squeeze, holds)
         self.opt.optimize_sequence(self.latent, trk["tgt_pos"].unsqueeze(0), trk["tgt_rot"].unsqueeze(0), None, trk["w"], trk["tracked"], z_tgt,
                                    (0, (int(temporal_future_window) + 1) * LATENT), self.current_global_pos, self.current_global_rot,
                                    self.latent_buffer, self.displacement_buffer, self.heights_buffer, tuple(int(h) for h in height_indices),
@@ -405,7 +430,7 @@ class DragPose:
         return pose, gpos
 
     def _run_constrained(self, constraints, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot, lambda_tmp,
-                         stop_eps_pos, stop_eps_rot, min_loss_incr, window, verbose, squeeze):
+                         stop_eps_pos, stop_eps_rot, min_loss_incr, window, verbose, squeeze, holds=None):
         """run()'s frame with extra loss terms: the optimise loop (dp_optimize_constrained for a Constraints, dp_optimize_terms for a
         Terms table) and run()'s epilogue (dp_sequence_advance)"""
         from .terms import Terms
@@ -421,6 +446,9 @@ class DragPose:
             fr[key] = torch.empty(S, width, device=self.device)
         z_tgt = self.target_latent_buffer[:, self.current_index].contiguous()
         run = self.opt.optimize_terms if table else self.opt.optimize_constrained
+        table_in = constraints
+        if holds is not None:  # (held terms read this frame's state rows; the update follows the epilogue)
+            constraints = holds.frame_terms(table_in, self.hold_state)
         run(self.latent, z_tgt, self.current_global_rot, trk["tgt_pos"], trk["tgt_rot"], trk["w"], trk["tracked"], constraints,
             global_pos=self.current_global_pos, n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_tmp),
             stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, out=fr, outputs=tuple(fr))
@@ -428,6 +456,8 @@ class DragPose:
                                   self.heights_buffer, tuple(int(h) for h in height_indices), pose_ret=pose, pos_ret=gpos, adjust=adjust,
                                   tgt_pos=trk["tgt_pos"] if adjust is not None else None)
         self.latent.copy_(fr["z"])
+        if holds is not None:
+            holds.update(table_in, self.hold_state, fr["pos"], self.current_global_pos)
         o["z"].copy_(self.latent)
         self.last = dict(iters=fr["iters"], loss=fr["loss"], z=o["z"], pose=pose, pos=gpos, status=fr["status"])
         self.last[key] = fr[key]

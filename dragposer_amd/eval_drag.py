@@ -24,13 +24,16 @@ from .bvh import BVH
 from .constraints import Constraints
 from .drag_pose import DragPose
 from .encoder import PoseEncoder
+from .holds import Hold, Holds
 from .model import DEFAULT_MODEL, NJ, load_model_arrays
 from .motion import local_quats_from_bvh, prepare_motion
 from .optimizer import LatentOptimizer
 from .temporal import load_reference_checkpoint
+from .terms import Term, Terms
 
 SPARSE_JOINTS = [0, 4, 8, 13, 17, 21]  # train.py:32-39 (evaluation only)
 HEIGHT_INDICES = [0, 4, 8, 13, 17, 21]
+FOOT_LOCK_JOINTS = (4, 8)  # --foot-lock: the two joints Constraints.reference() keeps on the floor
 
 DEFAULT_CONFIG = dict(  # eval_drag.py:68-131
     mask=[1, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1],
@@ -49,6 +52,34 @@ def eval_pos_error(gt_bvh, eval_bvh):
     ep, _ = Q.fk(eq[:n], np.zeros((n, 3)), offsets, parents)
     err = np.linalg.norm(ep - gp, axis=-1)
     return float(err.mean()), float(err[:, SPARSE_JOINTS[1:]].mean())
+
+
+def foot_skate(gt_bvh, eval_bvh, contact_lo, floor_level=0.0, up=1, joints=FOOT_LOCK_JOINTS):
+    """--foot-lock's extra line: the mean horizontal displacement per frame of `joints` in the result, over the frames on which the
+    ground-truth joint is at or below `contact_lo` above the floor.  World positions by eval_pos_error's FK, each file's own root
+    trajectory.  -> (the mean, or nan when no frame qualifies; the number of (frame, joint) pairs)"""
+    gq, gpos, parents, offsets = local_quats_from_bvh(gt_bvh)
+    eq, epos, _, _ = local_quats_from_bvh(eval_bvh)
+    n = min(len(gq), len(eq))
+    root = lambda p: np.asarray(p)[:n].reshape(n, -1, 3)[:, 0]
+    gp, _ = Q.fk(gq[:n], root(gpos), offsets, parents)
+    ep, _ = Q.fk(eq[:n], root(epos), offsets, parents)
+    j = list(joints)
+    contact = (gp[1:, j, up] - floor_level) <= contact_lo
+    step = ep[1:, j] - ep[:-1, j]
+    step[..., up] = 0.0
+    d = np.linalg.norm(step, axis=-1)[contact]
+    return (float(d.mean()) if d.size else float("nan")), int(d.size)
+
+
+def foot_lock_terms(args, cons):
+    """--foot-lock: two horizontal soft pins on FOOT_LOCK_JOINTS and their holds, appended to the reference's terms as a table when
+    --constraints reference is given -> (Terms, Holds)"""
+    base = Terms.from_constraints(cons) if cons is not None else Terms(up_axis=args.up_axis)  # (a table has one up axis: the constraints' own)
+    lo, hi = args.contact_height
+    pins = [Term.distance(j, point=(0.0, 0.0, 0.0), lo=0.0, hi=0.0, weight=args.foot_lock_weight, drop_up=True) for j in FOOT_LOCK_JOINTS]
+    holds = Holds([Hold(len(base) + i, lo, hi, level=args.floor_level) for i in range(len(pins))])
+    return Terms(base.terms + pins, base.up_axis), holds
 
 
 def result_to_bvh(poses, global_pos, means, stds, bvh, out_path):
@@ -131,6 +162,10 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
     cons = None
     if getattr(args, "constraints", None) == "reference":  # the reference's `# Additional Losses` block (drag_pose.py:129-183), un-commented
         cons = Constraints.reference()
+    extra = dict(constraints=cons)
+    if getattr(args, "foot_lock", False):
+        terms, holds = foot_lock_terms(args, cons)
+        extra = dict(terms=terms, holds=holds)
     poses = torch.zeros(T, S, 88, device=dev)
     out_pos = torch.zeros(T, S, 3, device=dev)
     iters = torch.zeros(T, S, dtype=torch.int32, device=dev)
@@ -142,7 +177,7 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
         poses, out_pos, iters = drag.run_frames(tp_rel, tR.reshape(T, S, -1, 3, 3), mask_idx, weights, target_root=gpos, stop_eps_pos=0.01 * 0.01,
                                                 stop_eps_rot=0.01, max_iter=args.max_iter, min_loss_incr=0.00001, learning_rate=1e-2, lambda_rot=1,
                                                 lambda_temporal=lam_tmp, temporal_future_window=window, height_indices=HEIGHT_INDICES,
-                                                joint_adjustment_indices=ja, joint_adjustment_weight=cfg["joint_adjustment_weight"], offsets=offsets, constraints=cons)
+                                                joint_adjustment_indices=ja, joint_adjustment_weight=cfg["joint_adjustment_weight"], offsets=offsets, **extra)
     for i in range(T if getattr(args, "per_frame", False) else 0):
         if i % 1000 == 0:
             print(f"Frame: {i + 1} out of {T}", flush=True)
@@ -150,7 +185,7 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
         drag.run(tp, tR[i], mask_idx, weights, offsets=offsets, stop_eps_pos=0.01 * 0.01, stop_eps_rot=0.01, max_iter=args.max_iter,
                  min_loss_incr=0.00001, learning_rate=1e-2, lambda_rot=1, lambda_temporal=lam_tmp,
                  temporal_future_window=window, height_indices=HEIGHT_INDICES, joint_adjustment_indices=ja,
-                 joint_adjustment_weight=cfg["joint_adjustment_weight"], verbose=args.verbose, out_pose=poses[i], out_pos=out_pos[i], constraints=cons)
+                 joint_adjustment_weight=cfg["joint_adjustment_weight"], verbose=args.verbose, out_pose=poses[i], out_pos=out_pos[i], **extra)
         iters[i] = drag.last["iters"]
     torch.cuda.synchronize()
     elapsed = time.time() - t0
@@ -172,6 +207,12 @@ def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
     print(f"Frames: {n}  ({n / elapsed:.1f} frames/s, mean iterations/frame {res['iters'].mean():.1f}, "
           f"lambda_temporal {lam_tmp}{'' if has_temporal else ' -- no temporal checkpoint given: pull term off'})")
     out = dict(mpjpe=mpjpe, mpeepe=mpeepe, time=elapsed, frames=n, out=out_path, mean_iters=float(res["iters"].mean()))
+    if getattr(args, "foot_lock", False):
+        up = Constraints.reference().up_axis if getattr(args, "constraints", None) == "reference" else args.up_axis
+        skate, pairs = foot_skate(BVH().load(q["path"]), BVH().load(out_path), args.contact_height[0], args.floor_level, up)
+        print(f"Foot skate: {skate} (mean horizontal displacement per frame of joints {FOOT_LOCK_JOINTS[0]} and {FOOT_LOCK_JOINTS[1]} over "
+              f"{pairs} ground-truth contact frames)")
+        out.update(foot_skate=skate, contact_frames=pairs)
     if getattr(args, "keep_frames", False):
         out.update(poses=res["poses"], pos=res["pos"], iters=res["iters"])
     return out
@@ -219,6 +260,21 @@ def main(argv=None):
                          "loss: DragPose.run_frames(constraints=Constraints.reference()) -- the frame loop still in one launch per stretch --, or "
                          "with --per-frame DragPose.run(constraints=...), two launches per frame; same results -- for a BVH with the model's own skeleton: "
                          "run() does not route other bones together with constraints and raises, run_frames() takes them")
+    ap.add_argument("--foot-lock", action="store_true",
+                    help="hold joints 4 and 8 where they touched down: two horizontal soft pins (point-DISTANCE terms, lo = hi = 0, the up "
+                         "component dropped) whose points are latched from the reconstruction itself (DragPose.run_frames(terms=, holds=), "
+                         "include/dragposer_holds.h; with --per-frame DragPose.run(terms=, holds=), same results); with --constraints reference "
+                         "they are appended to Terms.from_constraints(Constraints.reference()).  Prints one extra line, the foot skate.  The "
+                         "defaults of the four options below are placeholders nobody has tuned: the best of the few settings tried on the "
+                         "shipped example clips (DESIGN.md section 13d), where they do not lower the skate without raising the position error")
+    ap.add_argument("--foot-lock-weight", type=float, default=1.0, help="weight of each of the two pins (placeholder default, untuned)")
+    ap.add_argument("--contact-height", type=float, nargs=2, default=(0.03, 0.06), metavar=("LO", "HI"),
+                    help="touch-down at or below LO, release above HI, heights above --floor-level (placeholder defaults, untuned)")
+    ap.add_argument("--floor-level", type=float, default=-1.0,
+                    help="the floor along the up axis (placeholder default, untuned: the shipped example clips' toes rest near -1.0)")
+    ap.add_argument("--up-axis", type=int, choices=(0, 1, 2), default=2,
+                    help="the axis heights are measured along and the pins drop (default z, the shipped example clips' up; --constraints "
+                         "reference keeps its own, y)")
     ap.add_argument("--lockstep", action="store_true",
                     help="directory input: advance all files together, one kernel launch per frame index for all of them "
                          "(same per-file results; the reference evaluates them one after the other)")

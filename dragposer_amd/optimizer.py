@@ -384,7 +384,7 @@ class LatentOptimizer:
                           heights_buf, height_joints, n_iter=100, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.0,
                           stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
                           loss=None, scratch=None, status=None, offsets=None, constraints=None, terms=None, loss_extra=None, loss_terms=None,
-                          joint_pos=None):
+                          joint_pos=None, holds=None, hold_state=None, hold_trace=None):
         """T consecutive frames of S sequences in one launch (include/dragposer.h: dp_optimize_sequence): the optimise loop with the
         reference's while-condition and run()'s epilogue per frame, state carried on the device.  tgt_pos [T,S,22,3] / tgt_rot
         [T,S,22,9] dense per joint; tgt_root [T,S,3] or None (position targets are then tgt_pos + (tgt_root[t] - running global
@@ -398,7 +398,16 @@ class LatentOptimizer:
         dp_optimize_sequence_terms (include/dragposer_sequence_constraints.h), bit for bit what optimize_constrained / optimize_terms,
         sequence_advance and a copy of the latent give frame by frame; the floor, PLANE and point-DISTANCE terms read `global_pos` as it
         runs.  The dict then also holds `loss_extra` [T,S,4] / `loss_terms` [T,S,len(terms)] and `joint_pos` [T,S,22,3] (storage for them
-        may be passed).  Both None: dp_optimize_sequence, unchanged."""
+        may be passed).  Both None: dp_optimize_sequence, unchanged.
+        `holds` (a dragposer_amd.Holds, with `terms`): joints held where they touched down, dp_optimize_sequence_holds
+        (include/dragposer_holds.h).  `hold_state` [S,len(holds),4] is updated IN PLACE (required); `hold_trace` [T,S,len(holds),4] or True
+        (allocated here) receives the state after every step and is returned as `hold_trace`."""
+        if holds is not None and (terms is None or constraints is not None):
+            raise ValueError("optimize_sequence: holds= refer to a table, pass terms= (Terms.from_constraints turns constraints into one)")
+        if holds is None and (hold_state is not None or hold_trace is not None):
+            raise ValueError("optimize_sequence: hold_state / hold_trace belong to holds=")
+        if holds is not None and hold_state is None:
+            raise ValueError("optimize_sequence: holds= needs hold_state [S,len(holds),4]")
         if constraints is not None and terms is not None:
             raise ValueError("optimize_sequence: pass constraints or terms, not both")
         if constraints is None and terms is None and (loss_extra is not None or loss_terms is not None or joint_pos is not None):
@@ -457,7 +466,15 @@ class LatentOptimizer:
                 own, keep = terms.to_struct(S, dev, steps=T)
                 ex.row_step[:len(terms)] = terms.row_steps(S)
                 fn = self.lib.dp_optimize_sequence_terms
-            self._call(fn, S, lp, C.byref(fr), C.byref(p), C.byref(own), C.byref(skel) if skel is not None else None, *tail, C.byref(ex))
+            mid = ()
+            if holds is not None:
+                if hold_trace is True:
+                    hold_trace = torch.zeros(T, S, len(holds), 4, dtype=torch.float32, device=dev)
+                hs, keep_h = holds.to_struct(terms, S, dev, hold_state, hold_trace, steps=T)
+                fn, mid = self.lib.dp_optimize_sequence_holds, (C.byref(hs),)
+                if hold_trace is not None:
+                    outs["hold_trace"] = hold_trace
+            self._call(fn, S, lp, C.byref(fr), C.byref(p), C.byref(own), *mid, C.byref(skel) if skel is not None else None, *tail, C.byref(ex))
             del keep
             return outs
         fn, args = (self.lib.dp_optimize_sequence, tail) if skel is None else (self.lib.dp_optimize_sequence_skeleton, (C.byref(skel),) + tail)
