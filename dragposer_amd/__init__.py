@@ -3,3 +3,13 @@ from .constraints import Constraints  # noqa: F401  (the reference's extra loss 
 from .terms import Term, Terms  # noqa: F401  (user-defined constraint terms: include/dragposer_terms.h)
 from .holds import Hold, Holds  # noqa: F401  (joints held where they touched down: include/dragposer_holds.h)
 from .encoder import NativePoseEncoder  # noqa: F401  (the pose encoder in one HIP launch: include/dragposer_encoder.h)
+
+
+def __getattr__(name):
+    """LatentAR (a training-free predictor for the pull term: include/dragposer_latent_ar.h), imported on first use so that
+    `python -m dragposer_amd.ar` runs the module once"""
+    if name == "LatentAR":
+        from .ar import LatentAR
+
+        return LatentAR
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -233,6 +233,17 @@ class DpHolds(_Sized):
                 ("trace", C.c_void_p)]
 
 
+# every symbol include/dragposer_latent_ar.h declares (tests/test_latent_ar_abi.py)
+LATENT_AR_SYMBOLS = ("dp_optimize_sequence_ar",)
+DP_MAX_AR_ORDER = 4
+
+
+class DpLatentAR(_Sized):
+    """include/dragposer_latent_ar.h: dp_latent_ar (coeffs / bias / trace: device pointers)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("order", C.c_int), ("coeffs", C.c_void_p), ("bias", C.c_void_p),
+                ("trace", C.c_void_p)]
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -324,6 +335,8 @@ def load(path=None):
     lib.dp_optimize_sequence_terms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms)] + _seq_tail
     lib.dp_optimize_sequence_holds.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
                                                C.POINTER(DpHolds)] + _seq_tail
+    lib.dp_optimize_sequence_ar.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
+                                            C.POINTER(DpHolds), C.POINTER(DpLatentAR)] + _seq_tail
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

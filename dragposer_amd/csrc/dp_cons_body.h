@@ -13,6 +13,9 @@
 // dp_cons_hold.hip includes it once more under DP_CONS_TABLE 1, DP_CONS_SKEL 1, DP_CONS_SEQ 1 and DP_CONS_HOLD 1 (dp_terms_hold_seq_kernel,
 // include/dragposer_holds.h): a held term's row of the wave's block is its hold's state, updated by run()'s epilogue (dp_cons_hold.h).  The
 // #if DP_CONS_HOLD blocks are the only difference; without DP_CONS_HOLD the six kernels above keep their instructions.
+// dp_cons_ar.hip includes it once more with DP_CONS_AR 1 on top of those four (dp_terms_ar_seq_kernel, include/dragposer_latent_ar.h): a
+// step's z_tgt row is formed from the sequence's last history rows, kept in a second LDS array (dp_cons_ar.h).  The #if DP_CONS_AR blocks are
+// the only difference; without DP_CONS_AR the seven kernels above keep their instructions.
 {
     constexpr bool TBL = DP_CONS_TABLE;
 #if DP_CONS_SKEL
@@ -22,6 +25,9 @@
     constexpr int N_LDS = TBL ? LDS_FLOATS_T : LDS_FLOATS, W_STRIDE = TBL ? W_FLOATS_T : W_FLOATS;
 #endif
     __shared__ __attribute__((aligned(16))) float lds[N_LDS];
+#if DP_CONS_AR
+    __shared__ float arh[WPB * AR_W_FLOATS];
+#endif
     const float* __restrict__ W = a.img;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int* par = (int*)(lds + L_PAR);
@@ -110,6 +116,14 @@
             for (int c = 0; c < 4; ++c) wb[W_ROW + 4 * lane + c] = a.h.state[(f * a.h.n_holds + hd) * 4 + c];
     }
 #endif
+#if DP_CONS_AR // lane i: column i of the sequence's last `order` history rows, the newest (h_1) first
+    float* const hb = arh + wv * AR_W_FLOATS;
+    if (lane < LAT)
+#pragma unroll
+        for (int k = 0; k < MAX_AR_ORDER; ++k)
+            if (k < a.r.order) hb[k * LAT + lane] = a.r.latent_buf[(f * a.r.history + (a.r.history - 1 - k)) * LAT + lane];
+    wave_sync();
+#endif
     for (int stp = 0; stp < a.q.n_steps; ++stp) { // ---- the step loop: frame stp of this sequence, row ft of every per-step array
     const long long ft = (long long)stp * NS + f;
     float cr[4] = {crc[0], crc[1], crc[2], crc[3]};
@@ -118,7 +132,19 @@
 #pragma unroll
         for (int k = 0; k < 3; ++k) gp[k] = gpc[k];
     const float z0 = zc;
+#if DP_CONS_AR // include/dragposer_latent_ar.h, "The predictor": lane i forms component i, unfused, in the stated order
+    float zt = 0.f;
+    if (lane < LAT) {
+        zt = a.r.bias[lane];
+        for (int k = 0; k < a.r.order; ++k) {
+            const float* __restrict__ Ak = a.r.coeffs + (k * LAT + lane) * LAT;
+#pragma unroll
+            for (int c = 0; c < LAT; ++c) zt = __fadd_rn(zt, __fmul_rn(Ak[c], hb[k * LAT + c]));
+        }
+    }
+#else
     const float zt = lane < LAT ? a.z_tgt[(long long)stp * a.q.z_tgt_step + f * a.q.z_tgt_seq + lane] : 0.f;
+#endif
     float sh[3] = {0.f, 0.f, 0.f}; // this step's target shift: tgt_root[stp] - the global position before the step
     if (a.q.tgt_root)
 #pragma unroll
@@ -209,6 +235,9 @@
                 for (int c = 0; c < 4; ++c) a.h.trace[(ft * a.h.n_holds + hd) * 4 + c] = wb[W_ROW + 4 * lane + c];
         }
 #endif
+#if DP_CONS_AR // (the history stays as it is; the step used no target)
+        if (lane < LAT && a.r.trace) a.r.trace[ft * LAT + lane] = nan;
+#endif
         if (lane < 3) {
             if (a.q.pos_ret) a.q.pos_ret[ft * 3 + lane] = nan;
             if (a.loss) a.loss[ft * 3 + lane] = nan;
@@ -260,6 +289,9 @@
     }
 #endif
 
+#if DP_CONS_AR
+    if (lane < LAT && a.r.trace) a.r.trace[ft * LAT + lane] = zt;
+#endif
     // per-lane constants of the frame loop
     const float c0 = lane < H0 ? W[dpvjp::OFF_C0 + lane] : 0.f;
     const float b1 = lane < H1 ? W[dpvjp::OFF_B1 + lane] : 0.f;
@@ -668,6 +700,15 @@
 #endif
             float* const o = a.q.hist + fo * (LAT + 3 + NH);
             if (lane < LAT) o[lane] = z;
+#if DP_CONS_AR // the step's history row becomes h_1, the older rows shift: lane i on column i, read again behind the step's closing wave_sync()
+            if (lane < LAT) {
+                float* const hs = arh + wv * AR_W_FLOATS + lane;
+#pragma unroll
+                for (int k = MAX_AR_ORDER - 1; k > 0; --k)
+                    if (k < a.r.order) hs[k * LAT] = hs[(k - 1) * LAT];
+                hs[0] = z;
+            }
+#endif
             if (lane == 0) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {

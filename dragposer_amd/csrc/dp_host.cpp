@@ -21,7 +21,8 @@
 #include "../../include/dragposer_skeleton.h"
 #include "../../include/dragposer_sequence_constraints.h"
 #include "../../include/dragposer_holds.h"
-#include "dp_cons_hold.h"
+#include "../../include/dragposer_latent_ar.h"
+#include "dp_cons_ar.h"
 #include "dp_host_rt.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -673,6 +674,7 @@ constexpr Sized GRAD_IN_V510 = {"dp_grad_in", "dp_grad_in g = DP_GRAD_IN_INIT;",
 constexpr Sized CONS_V510 = {"dp_constraints", "dp_constraints c = DP_CONSTRAINTS_INIT;", offsetof(dp_constraints, loss_extra) + sizeof(void*), false};
 constexpr Sized TERMS_V510 = {"dp_terms", "dp_terms t = DP_TERMS_INIT;", offsetof(dp_terms, loss_terms) + sizeof(void*), false};
 constexpr Sized HOLDS_V530 = {"dp_holds", "dp_holds h = DP_HOLDS_INIT;", offsetof(dp_holds, trace) + sizeof(void*), false};
+constexpr Sized LATENT_AR_V540 = {"dp_latent_ar", "dp_latent_ar r = DP_LATENT_AR_INIT;", offsetof(dp_latent_ar, trace) + sizeof(void*), false};
 constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
@@ -1200,9 +1202,11 @@ extern "C" int dp_optimize_terms_skeleton(dp_ctx* ctx, const dp_batch* in, const
 
 // ------------------------------------------------------------------------------------------------
 // What every whole-sequence launch asks of its frames, state, scratch and joint adjustment (who names the caller in the messages)
-static int check_sequence(dp_ctx* ctx, const dp_seq_frames* fr, const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results& out, const std::string& who)
+// (own_z_tgt: the launch forms its targets itself, include/dragposer_latent_ar.h, and frames->z_tgt is its own check's business)
+static int check_sequence(dp_ctx* ctx, const dp_seq_frames* fr, const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results& out, const std::string& who,
+                          bool own_z_tgt = false)
 {
-    if (fr->n_steps <= 0 || !fr->tgt_pos || !fr->tgt_rot || !fr->w || !fr->tracked || !fr->z_tgt)
+    if (fr->n_steps <= 0 || !fr->tgt_pos || !fr->tgt_rot || !fr->w || !fr->tracked || (!own_z_tgt && !fr->z_tgt))
         return fail(ctx, DP_ERR_INVALID, who + ": NULL input array / n_steps must be positive");
     if (!st->global_pos || !st->global_rot || !st->latent_buf || !st->disp_buf || !st->heights_buf || !out.hist_scratch)
         return fail(ctx, DP_ERR_INVALID, who + ": NULL state array / hist_scratch");
@@ -1334,12 +1338,33 @@ static int take_seq_extra(dp_ctx* ctx, const dp_seq_extra* e_in, dp_seq_extra& e
 hipError_t dp_launch_cons_seq(const dpcons::SeqConsArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_terms_seq(const dpcons::SeqTermArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_terms_hold_seq(const dpcons::HoldSeqArgs* args, hipStream_t stream) __attribute__((weak)); // (dp_cons_hold.hip, likewise)
+hipError_t dp_launch_terms_ar_seq(const dpcons::ArSeqArgs* args, hipStream_t stream) __attribute__((weak));     // (dp_cons_ar.hip, likewise)
 #endif
+
+// include/dragposer_latent_ar.h: dp_latent_ar checked, after everything dp_optimize_sequence_holds checks, against the launch's frames and
+// state, and written into the argument block
+static int take_latent_ar(dp_ctx* ctx, const dp_latent_ar* r_in, const dp_seq_frames* fr, const dp_seq_state* st, dpcons::ArFields& r, const char* who)
+{
+    const std::string nm = who;
+    dp_latent_ar ar;
+    if (int rc = take_sized(ctx, r_in, ar, LATENT_AR_V540, who)) return rc;
+    if (ar.order < 1 || ar.order > DP_MAX_AR_ORDER)
+        return fail(ctx, DP_ERR_INVALID, nm + ": dp_latent_ar.order " + std::to_string(ar.order) + " outside 1.." + std::to_string(DP_MAX_AR_ORDER));
+    if (!ar.coeffs || !ar.bias) return fail(ctx, DP_ERR_INVALID, nm + ": dp_latent_ar.coeffs or bias is NULL");
+    if (st->history < ar.order)
+        return fail(ctx, DP_ERR_INVALID, nm + ": the state's history of " + std::to_string(st->history) + " rows is shorter than dp_latent_ar.order " +
+                                             std::to_string(ar.order));
+    if (fr->z_tgt) return fail(ctx, DP_ERR_INVALID, nm + ": frames->z_tgt must be NULL (the predictor is the targets' one source)");
+    r.coeffs = ar.coeffs; r.bias = ar.bias; r.trace = ar.trace; r.latent_buf = st->latent_buf; r.order = ar.order; r.history = st->history;
+    return DP_OK;
+}
 
 template <class A, class Own>
 static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
-                                     const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream, const char* who, Own own)
+                                     const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream, const char* who, Own own,
+                                     const dp_latent_ar* ar = nullptr)
 {
+    constexpr bool HOLDS = std::is_same<A, dpcons::HoldSeqArgs>::value, AR = std::is_same<A, dpcons::ArSeqArgs>::value;
     dp_params p;
     if (int rc = take_params(ctx, p_in, p, who)) return rc;
     dp_seq_results out;
@@ -1349,15 +1374,17 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
     if (int rc = own(a)) return rc;
     if (sk)
         if (int rc = take_skeleton(ctx, sk, a.skel, a.skel_stride, who)) return rc;
-    if (int rc = check_sequence(ctx, fr, st, adj, out, who)) return rc;
+    if (int rc = check_sequence(ctx, fr, st, adj, out, who, AR)) return rc;
     if (int rc = check_adam(ctx, p, who)) return rc;
+    if constexpr (AR)
+        if (int rc = take_latent_ar(ctx, ar, fr, st, a.r, who)) return rc;
 #ifdef DP_REF8_BUILD
     (void)n_seq; (void)latent; (void)stream;
     return refuse_ref8(ctx, who);
 #else
-    constexpr bool HOLDS = std::is_same<A, dpcons::HoldSeqArgs>::value;
-    if (HOLDS ? !dp_launch_terms_hold_seq : (!dp_launch_cons_seq || !dp_launch_terms_seq))
-        return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without " + (HOLDS ? "dp_cons_hold.hip" : "dp_cons_seq.hip"));
+    if (AR ? !dp_launch_terms_ar_seq : HOLDS ? !dp_launch_terms_hold_seq : (!dp_launch_cons_seq || !dp_launch_terms_seq))
+        return fail(ctx, DP_ERR_UNSUPPORTED,
+                    std::string(who) + ": this library was linked without " + (AR ? "dp_cons_ar.hip" : HOLDS ? "dp_cons_hold.hip" : "dp_cons_seq.hip"));
     if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
     a.img = ctx->d_vjpimg.get();
     if (!sk) { a.skel = ctx->d_vjpimg.get() + dpvjp::OFF_BONE; a.skel_stride = 0; } // (the image's bone rows: what the per-frame kernels stage)
@@ -1372,6 +1399,7 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
         hipError_t e;
         if constexpr (std::is_same<A, dpcons::SeqConsArgs>::value) e = dp_launch_cons_seq(&a, (hipStream_t)stream);
         else if constexpr (HOLDS) e = dp_launch_terms_hold_seq(&a, (hipStream_t)stream);
+        else if constexpr (AR) e = dp_launch_terms_ar_seq(&a, (hipStream_t)stream);
         else e = dp_launch_terms_seq(&a, (hipStream_t)stream);
         if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
     }
@@ -1473,6 +1501,30 @@ extern "C" int dp_optimize_sequence_holds(dp_ctx* ctx, int n_seq, float* latent,
         if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !h_in || !st || !out)
             return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_holds: n_sequences must be positive; NULL latent, frames, params, terms, holds, state or results");
         return sequence_constrained_impl<dpcons::HoldSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own);
+    });
+}
+
+// include/dragposer_latent_ar.h: dp_optimize_sequence_holds with the step's z_tgt formed in the launch (A = dpcons::ArSeqArgs); `holds` may be
+// NULL, and dp_latent_ar is checked last (take_latent_ar, from sequence_constrained_impl)
+extern "C" int dp_optimize_sequence_ar(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                       const dp_holds* h_in, const dp_latent_ar* r_in, const dp_skeleton_in* skel, const dp_seq_state* st,
+                                       const dp_seq_step* adj, const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_ar";
+    const auto own = [&](dpcons::ArSeqArgs& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
+        if (h_in)
+            if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
+        dp_seq_extra e;
+        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
+        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
+        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
+        return DP_OK;
+    };
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !r_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_ar: n_sequences must be positive; NULL latent, frames, params, terms, ar, state or results");
+        return sequence_constrained_impl<dpcons::ArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in);
     });
 }
 

@@ -44,6 +44,14 @@ def arrays_from_generator_model(generator_model, offsets):
 _RUN_OUTPUTS = ("z", "z_pre", "pose", "disp", "world_disp", "world_rot", "pos", "loss", "iters")
 
 
+def _check_ar(temporal, ar, who):
+    """what run(ar=) / run_frames(ar=) refuse before anything else"""
+    if temporal is not None:
+        raise ValueError(f"DragPose.{who}: ar= and a temporal model are two sources of the pull term's target; create the DragPose without one")
+    if ar.order > HISTORY:
+        raise ValueError(f"DragPose.{who}: ar.order {ar.order} exceeds the history of {HISTORY} frames")
+
+
 class DragPose:
     def __init__(self, generator_model, temporal_model, means_latent, stds_latent, device=None, device_gpu=None, n_sequences=1,
                  offsets=None, native_temporal=False, native_encoder=False):
@@ -261,7 +269,7 @@ class DragPose:
     def run_frames(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, target_root=None, stop_eps_pos=1e-2, stop_eps_rot=1e-2,
                    max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1, temporal_future_window=60,
                    height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01, offsets=None,
-                   constraints=None, terms=None, holds=None):
+                   constraints=None, terms=None, holds=None, ar=None):
         """T consecutive frames of every sequence -- T calls of run() -- with the frame loop on the device: one kernel launch per
         stretch of frames between two temporal predictions (all T of them when there is no predictor or lambda_temporal is 0).
         target_ee_pos [T,S,E,3], target_ee_rot [T,S,E,3,3]; `target_root` [T,S,3] or None: given, the position targets of frame t
@@ -274,9 +282,20 @@ class DragPose:
         `holds` (a dragposer_amd.Holds, with `terms`): joints held where they touched down (dp_optimize_sequence_holds,
         include/dragposer_holds.h); the state lives in `hold_state` [S,len(holds),4], zeroed when a sequence begins and passed through
         every stretch, and `last_hold_trace` [T,S,len(holds),4] holds it after every frame.
+        `ar` (a dragposer_amd.LatentAR, for a DragPose without a temporal model): the pull term's target of every frame is the
+        predictor's, formed from the sequence's own last latents inside ONE launch for all T frames (dp_optimize_sequence_ar,
+        include/dragposer_latent_ar.h), weighed by `lambda_temporal`; with or without `terms`, `holds` and `offsets`, and `constraints`
+        go through Terms.from_constraints (`last_terms` is then [T,S,len of that table]).  `last_z_tgt` [T,S,24] holds the targets used,
+        `last_loss` [T,S,3] every frame's three loss parts.
         Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run_frames: pass constraints or terms, not both")
+        if ar is not None:
+            _check_ar(self.temporal, ar, "run_frames")
+            if constraints is not None:
+                from .terms import Terms
+
+                terms, constraints = Terms.from_constraints(constraints), None
         self._holds(holds, terms, constraints, "run_frames")
         dev, S = self.device, self.S
         skel = self._skeleton(offsets)
@@ -312,6 +331,8 @@ class DragPose:
             self.last_joint_pos = torch.empty(T, S, NJ, 3, device=dev)
         if holds is not None:
             self.last_hold_trace = torch.zeros(T, S, len(holds), 4, device=dev)
+        if ar is not None:
+            self.last_z_tgt = torch.zeros(T, S, LATENT, device=dev)
 
         def extra(t0, n):
             """the stretch's share of the terms' arguments: the table's rows and the per-step outputs of frames t0 .. t0 + n"""
@@ -322,6 +343,19 @@ class DragPose:
             if holds is not None:
                 kw.update(holds=holds, hold_state=self.hold_state, hold_trace=self.last_hold_trace[t0:t0 + n])
             return kw
+
+        if ar is not None:  # one launch, no stretches: the targets come from inside it
+            kw = extra(0, T)
+            kw.pop("constraints", None)
+            o = self.opt.optimize_sequence(self.latent, dense_p, dense_r, root, trk["w"], trk["tracked"], None, (0, 0), self.current_global_pos,
+                                       self.current_global_rot, self.latent_buffer, self.displacement_buffer, self.heights_buffer,
+                                       tuple(int(h) for h in height_indices), n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot),
+                                       lambda_tmp=float(lambda_temporal), stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
+                                       min_loss_incr=min_loss_incr, adjust=adjust, pose_ret=poses, pos_ret=gpos, iters=iters, status=status,
+                                       offsets=skel, ar=ar, z_tgt_trace=self.last_z_tgt, **kw)
+            self.last_loss = o["loss"]  # [T,S,3] (the third: lambda_temporal times the pull towards last_z_tgt)
+            self.last_status = status
+            return poses, gpos, iters
 
         # The reference predicts at current_index == 0 whatever lambda_temporal is (drag_pose.py:235-291), so the stretches between two
         # predictions are cut the same way with the pull term on or off; without a predictor there is nothing to pull towards and the
@@ -353,7 +387,7 @@ class DragPose:
     def run(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, offsets=None, stop_eps_pos=1e-2,
             stop_eps_rot=1e-2, max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1,
             temporal_future_window=60, height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None,
-            joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None, holds=None):
+            joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None, holds=None, ar=None):
         """One frame for every sequence: one launch for the optimise loop and the epilogue, one for the history buffers, plus two
         row scatters of the targets.  `out_pose` [S,88] / `out_pos` [S,3]: optional caller storage for the returned tensors.
         `constraints` (a dragposer_amd.Constraints): the reference's extra loss terms (drag_pose.py:129-183) join the loss -- the frame
@@ -362,7 +396,8 @@ class DragPose:
         terms instead, the same two launches with dp_optimize_terms (a term's per-frame rows: its [S,4] `per_frame` tensor, read at
         this call); not together with `constraints`.  `holds` (a dragposer_amd.Holds, with `terms`): each held term reads its row from
         `hold_state`, and the state is updated after the frame with include/dragposer_holds.h's arithmetic in torch on the device, no
-        synchronisation -- frame by frame the bits of run_frames(terms=, holds=).
+        synchronisation -- frame by frame the bits of run_frames(terms=, holds=).  `ar` (a dragposer_amd.LatentAR): the frame is a one-step
+        launch of run_frames(ar=), with everything that call takes (`offsets` together with `terms` included); frame by frame its bits.
         `offsets`: the performer's bone offsets, as the reference takes them on every call (drag_pose.py:202) -- [22,3] for every sequence
         or [S,22,3] one per sequence.  The context's own skeleton (or None) runs the launches above unchanged; any other runs the same frame
         with those bones (dp_optimize_sequence_skeleton, include/dragposer_skeleton.h), not together with `constraints` / `terms`: this
@@ -370,6 +405,14 @@ class DragPose:
         the same object frame after frame costs one host synchronisation in all (DragPose._skeleton)."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
+        if ar is not None:
+            _check_ar(self.temporal, ar, "run")
+            return self._run_ar(target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose,
+                                dict(offsets=offsets, stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, max_iter=max_iter,
+                                     min_loss_incr=min_loss_incr, learning_rate=learning_rate, lambda_rot=lambda_rot, lambda_temporal=lambda_temporal,
+                                     temporal_future_window=temporal_future_window, height_indices=height_indices,
+                                     joint_adjustment_indices=joint_adjustment_indices, joint_adjustment_weight=joint_adjustment_weight,
+                                     constraints=constraints, terms=terms, holds=holds, ar=ar))
         self._holds(holds, terms, constraints, "run")
         skel = self._skeleton(offsets)
         if skel is not None and (constraints is not None or terms is not None):
@@ -425,6 +468,28 @@ class DragPose:
             print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "
                   f"Loss Temporal: {l[:, 2].mean():.5f} // Iter: {it.float().mean():.1f}")
         self.current_index = 0 if temporal_future_window == 0 else (self.current_index + 1) % temporal_future_window
+        if squeeze and S == 1:
+            return pose[0], gpos[0]
+        return pose, gpos
+
+    def _run_ar(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose, kw):
+        """run(ar=): run_frames(ar=) on this one frame"""
+        S = self.S
+        squeeze = torch.as_tensor(target_ee_pos).dim() == 2
+        tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=self.device).reshape(1, S, -1, 3)
+        tR = torch.as_tensor(target_ee_rot, dtype=torch.float32, device=self.device).reshape(1, S, -1, 3, 3)
+        poses, gposs, iters = self.run_frames(tp, tR, mask_joints, weights_joints, **kw)
+        pose, gpos = poses[0], gposs[0]
+        if out_pose is not None:
+            pose = out_pose.copy_(pose)
+        if out_pos is not None:
+            gpos = out_pos.copy_(gpos)
+        self.last = dict(iters=iters[0], loss=self.last_loss[0], z=self.latent.clone(), pose=pose, pos=gpos, status=self.last_status[0],
+                         z_tgt=self.last_z_tgt[0])
+        if verbose:
+            l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
+            print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "
+                  f"Loss Temporal: {l[:, 2].mean():.5f} // Iter: {it.float().mean():.1f}")
         if squeeze and S == 1:
             return pose[0], gpos[0]
         return pose, gpos

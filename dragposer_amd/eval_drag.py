@@ -9,7 +9,8 @@ result written to data/eval_<name> relative to the working directory, and the re
 verbatim (eval_drag.py:249-252).  Also accepted as `model_path`: this package's flat .npz fixture (default: the shipped
 model_dancedb).  Stated in the output: because the reference's temporal.pt is not distributed with it the temporal
 predictor is optional -- without one (no temporal.pt in the folder, no --temporal-checkpoint) the pull term is switched off
-(lambda_temporal = 0) instead of pulling towards the predictions of an untrained network.
+(lambda_temporal = 0) instead of pulling towards the predictions of an untrained network, unless --latent-ar names a predictor that
+needs no training (dragposer_amd.ar, include/dragposer_latent_ar.h): then the configuration's lambda_temporal pulls towards its targets.
 """
 import argparse
 import json
@@ -147,7 +148,8 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
     mask_idx = np.nonzero(np.asarray(cfg["mask"]))[0]
     weights = np.asarray(cfg["weights"], np.float32)[mask_idx]
     temporal, means_latent, stds_latent = temporal_pack
-    lam_tmp = cfg["lambda_temporal"] if temporal is not None else 0.0
+    ar = getattr(args, "latent_ar_model", None)  # (main: --latent-ar; not together with a temporal checkpoint)
+    lam_tmp = cfg["lambda_temporal"] if temporal is not None or ar is not None else 0.0
     window = cfg["temporal_future_window"] if temporal is not None else 0
     pad = lambda t: torch.cat((t, t[-1:].expand(T - t.shape[0], *t.shape[1:])), dim=0) if t.shape[0] < T else t
     tp_rel = torch.stack([pad(q["tp_rel"]) for q in seqs], dim=1).contiguous()  # [T, S, E, 3]
@@ -166,6 +168,8 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
     if getattr(args, "foot_lock", False):
         terms, holds = foot_lock_terms(args, cons)
         extra = dict(terms=terms, holds=holds)
+    if ar is not None:
+        extra["ar"] = ar
     poses = torch.zeros(T, S, 88, device=dev)
     out_pos = torch.zeros(T, S, 3, device=dev)
     iters = torch.zeros(T, S, dtype=torch.int32, device=dev)
@@ -190,7 +194,7 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
     torch.cuda.synchronize()
     elapsed = time.time() - t0
     poses, out_pos, iters = poses.cpu().numpy(), out_pos.cpu().numpy(), iters.cpu().numpy()
-    return [dict(poses=poses[:q["n_frames"], k], pos=out_pos[:q["n_frames"], k], iters=iters[:q["n_frames"], k]) for k, q in enumerate(seqs)], elapsed, lam_tmp, temporal is not None
+    return [dict(poses=poses[:q["n_frames"], k], pos=out_pos[:q["n_frames"], k], iters=iters[:q["n_frames"], k]) for k, q in enumerate(seqs)], elapsed, lam_tmp, temporal is not None or ar is not None
 
 
 def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
@@ -204,6 +208,8 @@ def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
     print(f"Mean Per Joint Position Error: {mpjpe}")
     print(f"Mean End Effector Position Error: {mpeepe}")
     print(f"Time: {elapsed}" + (f"  (shared by {shared} sequences in lock-step)" if shared > 1 else ""))
+    if getattr(args, "latent_ar_model", None) is not None:
+        print(f"Latent predictor: {args.latent_ar_text} (DragPose.run_frames(ar=), include/dragposer_latent_ar.h)")
     print(f"Frames: {n}  ({n / elapsed:.1f} frames/s, mean iterations/frame {res['iters'].mean():.1f}, "
           f"lambda_temporal {lam_tmp}{'' if has_temporal else ' -- no temporal checkpoint given: pull term off'})")
     out = dict(mpjpe=mpjpe, mpeepe=mpeepe, time=elapsed, frames=n, out=out_path, mean_iters=float(res["iters"].mean()))
@@ -232,6 +238,23 @@ def evaluate_files(args, paths, opt, encoder, temporal_pack, cfg, raw):
 
 def evaluate_file(args, input_path, opt, encoder, temporal_pack, cfg, raw):
     return evaluate_files(args, [input_path], opt, encoder, temporal_pack, cfg, raw)[0]
+
+
+def latent_tracks(clips, model_path=None, device="cuda:0", max_frames=None):
+    """[T_i,24] latent tracks of .bvh clips for LatentAR.fit: the pose encoder's mu (dp_encode) of every frame, prepared as above"""
+    from .encoder import NativePoseEncoder
+
+    model_path = model_path if model_path is not None else DEFAULT_MODEL
+    raw = load_model_arrays(model_path, skeleton_bvh=clips[0])
+    means = {"dqs": raw["means.dqs"], "displacement": raw["means.displacement"]}
+    stds = {"dqs": raw["stds.dqs"], "displacement": raw["stds.displacement"]}
+    enc = NativePoseEncoder(arrays=raw, device=device)
+    tracks = []
+    for path in clips:
+        m = prepare_motion(BVH().load(path), means, stds, HEIGHT_INDICES)
+        dqs = torch.tensor(np.asarray(m["dqs"][:max_frames], np.float32), device=device)
+        tracks.append(enc.encode(dqs, outputs=("mu",))["mu"].cpu().numpy())
+    return tracks
 
 
 def main(argv=None):
@@ -275,6 +298,11 @@ def main(argv=None):
     ap.add_argument("--up-axis", type=int, choices=(0, 1, 2), default=2,
                     help="the axis heights are measured along and the pins drop (default z, the shipped example clips' up; --constraints "
                          "reference keeps its own, y)")
+    ap.add_argument("--latent-ar", default=None, metavar="hold | cv[:DAMPING] | FILE.npz",
+                    help="without a temporal checkpoint: pull the latent towards a linear autoregressive prediction from the sequence's own "
+                         "recent latents, with the configuration's lambda_temporal instead of 0 (DragPose.run_frames(ar=), "
+                         "include/dragposer_latent_ar.h; with --per-frame DragPose.run(ar=), same results).  hold: the last latent; cv: constant "
+                         "velocity, optionally damped; FILE.npz: a model fitted by `python -m dragposer_amd.ar fit`")
     ap.add_argument("--lockstep", action="store_true",
                     help="directory input: advance all files together, one kernel launch per frame index for all of them "
                          "(same per-file results; the reference evaluates them one after the other)")
@@ -301,6 +329,12 @@ def main(argv=None):
         temporal_pack = load_reference_checkpoint(tck, opt.device)
     else:
         temporal_pack = (None, np.zeros(24, np.float32), np.ones(24, np.float32))
+    if args.latent_ar is not None:
+        if tck is not None:
+            raise SystemExit("--latent-ar and a temporal checkpoint are two sources of the pull term's target: give one")
+        from .ar import parse
+
+        args.latent_ar_model, args.latent_ar_text = parse(args.latent_ar)
     if args.lockstep and len(files) > 1:
         print(f"Evaluate {len(files)} files in lock-step ------------------------")
         return evaluate_files(args, files, opt, encoder, temporal_pack, cfg, raw)

@@ -384,7 +384,7 @@ class LatentOptimizer:
                           heights_buf, height_joints, n_iter=100, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.0,
                           stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
                           loss=None, scratch=None, status=None, offsets=None, constraints=None, terms=None, loss_extra=None, loss_terms=None,
-                          joint_pos=None, holds=None, hold_state=None, hold_trace=None):
+                          joint_pos=None, holds=None, hold_state=None, hold_trace=None, ar=None, z_tgt_trace=None):
         """T consecutive frames of S sequences in one launch (include/dragposer.h: dp_optimize_sequence): the optimise loop with the
         reference's while-condition and run()'s epilogue per frame, state carried on the device.  tgt_pos [T,S,22,3] / tgt_rot
         [T,S,22,9] dense per joint; tgt_root [T,S,3] or None (position targets are then tgt_pos + (tgt_root[t] - running global
@@ -401,7 +401,24 @@ class LatentOptimizer:
         may be passed).  Both None: dp_optimize_sequence, unchanged.
         `holds` (a dragposer_amd.Holds, with `terms`): joints held where they touched down, dp_optimize_sequence_holds
         (include/dragposer_holds.h).  `hold_state` [S,len(holds),4] is updated IN PLACE (required); `hold_trace` [T,S,len(holds),4] or True
-        (allocated here) receives the state after every step and is returned as `hold_trace`."""
+        (allocated here) receives the state after every step and is returned as `hold_trace`.
+        `ar` (a dragposer_amd.LatentAR): every step's z_tgt row is formed in the launch from the sequence's last history rows,
+        dp_optimize_sequence_ar (include/dragposer_latent_ar.h) -- `z_tgt` must then be None (`z_tgt_strides` is ignored), `terms` / `holds`
+        are optional (`constraints` is not taken: Terms.from_constraints turns them into a table) and `latent_buf` holds at least
+        `ar.order` rows.  `z_tgt_trace` [T,S,24] or True (allocated here) receives the row every step used and is returned as `z_tgt_trace`."""
+        if ar is None and z_tgt_trace is not None:
+            raise ValueError("optimize_sequence: z_tgt_trace belongs to ar=")
+        if ar is not None:
+            if z_tgt is not None:
+                raise ValueError("optimize_sequence: ar= forms the targets itself, pass z_tgt=None")
+            if constraints is not None:
+                raise ValueError("optimize_sequence: ar= takes a table, pass terms= (Terms.from_constraints turns constraints into one)")
+            if ar.order > int(latent_buf.shape[1]):
+                raise ValueError(f"optimize_sequence: latent_buf holds {int(latent_buf.shape[1])} rows, fewer than ar.order = {ar.order}")
+            if terms is None:
+                from .terms import Terms
+
+                terms = Terms()
         if holds is not None and (terms is None or constraints is not None):
             raise ValueError("optimize_sequence: holds= refer to a table, pass terms= (Terms.from_constraints turns constraints into one)")
         if holds is None and (hold_state is not None or hold_trace is not None):
@@ -423,9 +440,12 @@ class LatentOptimizer:
         fr.tgt_root = _check(tgt_root, "tgt_root", (T, S, 3), torch.float32, dev) if tgt_root is not None else None
         fr.w = _check(w, "w", (S, NJ, 2), torch.float32, dev)
         fr.tracked = _check(tracked, "tracked", (S, NJ), torch.uint8, dev)
-        if z_tgt.device != dev or z_tgt.dtype != torch.float32:
-            raise ValueError("z_tgt: expected an fp32 tensor on the optimiser's device")
-        fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = z_tgt.data_ptr(), int(z_tgt_strides[0]), int(z_tgt_strides[1])
+        if ar is not None:
+            fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = None, 0, 0
+        else:
+            if z_tgt.device != dev or z_tgt.dtype != torch.float32:
+                raise ValueError("z_tgt: expected an fp32 tensor on the optimiser's device")
+            fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = z_tgt.data_ptr(), int(z_tgt_strides[0]), int(z_tgt_strides[1])
         st = _lib.DpSeqState()
         st.global_pos = _check(global_pos, "global_pos", (S, 3), torch.float32, dev)
         st.global_rot = _check(global_rot, "global_rot", (S, 4), torch.float32, dev)
@@ -474,6 +494,13 @@ class LatentOptimizer:
                 fn, mid = self.lib.dp_optimize_sequence_holds, (C.byref(hs),)
                 if hold_trace is not None:
                     outs["hold_trace"] = hold_trace
+            if ar is not None:
+                if z_tgt_trace is True:
+                    z_tgt_trace = torch.zeros(T, S, LATENT, dtype=torch.float32, device=dev)
+                rs, keep_r = ar.to_struct(dev, z_tgt_trace, (T, S, LATENT))
+                fn, mid = self.lib.dp_optimize_sequence_ar, (mid[0] if mid else None, C.byref(rs))
+                if z_tgt_trace is not None:
+                    outs["z_tgt_trace"] = z_tgt_trace
             self._call(fn, S, lp, C.byref(fr), C.byref(p), C.byref(own), *mid, C.byref(skel) if skel is not None else None, *tail, C.byref(ex))
             del keep
             return outs
