@@ -2,6 +2,7 @@ from .autograd import decode_fk  # noqa: F401  (differentiable decode + FK: incl
 from .constraints import Constraints  # noqa: F401  (the reference's extra loss terms: include/dragposer_constraints.h)
 from .terms import Term, Terms  # noqa: F401  (user-defined constraint terms: include/dragposer_terms.h)
 from .holds import Hold, Holds  # noqa: F401  (joints held where they touched down: include/dragposer_holds.h)
+from .gaps import Gaps  # noqa: F401  (trackers that drop out and come back: include/dragposer_gaps.h)
 from .encoder import NativePoseEncoder  # noqa: F401  (the pose encoder in one HIP launch: include/dragposer_encoder.h)
 
 

@@ -244,6 +244,19 @@ class DpLatentAR(_Sized):
                 ("trace", C.c_void_p)]
 
 
+# every symbol include/dragposer_gaps.h declares (tests/test_gaps_abi.py)
+GAP_SYMBOLS = ("dp_optimize_sequence_gaps",)
+DP_GAP_STATE_FLOATS = 16
+DP_GAP_MAX_HOLD = 65535
+DP_STATUS_TRACKER_HELD, DP_STATUS_TRACKER_LOST, DP_STATUS_NO_TRACKER = 16, 32, 64
+
+
+class DpGaps(_Sized):
+    """include/dragposer_gaps.h: dp_gaps (state / present / trace: device pointers)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("max_hold", C.c_int), ("decay", C.c_float), ("state", C.c_void_p),
+                ("present", C.c_void_p), ("trace", C.c_void_p)]
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -337,6 +350,8 @@ def load(path=None):
                                                C.POINTER(DpHolds)] + _seq_tail
     lib.dp_optimize_sequence_ar.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
                                             C.POINTER(DpHolds), C.POINTER(DpLatentAR)] + _seq_tail
+    lib.dp_optimize_sequence_gaps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
+                                              C.POINTER(DpHolds), C.POINTER(DpLatentAR), C.POINTER(DpGaps)] + _seq_tail
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

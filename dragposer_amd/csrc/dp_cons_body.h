@@ -16,6 +16,10 @@
 // dp_cons_ar.hip includes it once more with DP_CONS_AR 1 on top of those four (dp_terms_ar_seq_kernel, include/dragposer_latent_ar.h): a
 // step's z_tgt row is formed from the sequence's last history rows, kept in a second LDS array (dp_cons_ar.h).  The #if DP_CONS_AR blocks are
 // the only difference; without DP_CONS_AR the seven kernels above keep their instructions.
+// dp_cons_gap.hip includes it twice more with DP_CONS_GAP 1 on top of DP_CONS_HOLD's four, without and with DP_CONS_AR
+// (dp_terms_gap_seq_kernel, dp_terms_gap_ar_seq_kernel, include/dragposer_gaps.h): `trk` is then a per-step value, the lane's code of the
+// step, decided from the joint's row of dp_gaps.state in global memory (dp_cons_gap.h).  The #if DP_CONS_GAP blocks are the only difference;
+// without DP_CONS_GAP the nine kernels above keep their instructions.
 {
     constexpr bool TBL = DP_CONS_TABLE;
 #if DP_CONS_SKEL
@@ -150,7 +154,12 @@
 #pragma unroll
         for (int k = 0; k < 3; ++k) sh[k] = a.q.tgt_root[ft * 3 + k] - gpc[k];
     float tpe[3] = {0.f, 0.f, 0.f}; // lane j: joint j's effective position target of this step
+#if DP_CONS_GAP // (a sample marked absent is not read)
+    const bool smp = trk && !(a.g.present && a.g.present[ft * NJ + j] == 0);
+    if (smp)
+#else
     if (trk)
+#endif
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float tk = a.tgt_pos[(ft * NJ + j) * 3 + k];
@@ -162,10 +171,57 @@
 #if DP_CONS_SKEL
     bs = bs || bsk;
 #endif
+#if DP_CONS_GAP
+    // include/dragposer_gaps.h, "The rule": lane j decides joint j's code of this step and advances its row of the state, unless the step is
+    // refused as bad state (which leaves the state as it is).  From here to the end of the step `trk` is the step's: code 1 or 2.
+    const bool cfg = trk;
+    float* const grow = a.g.state + (f * NJ + j) * GAP_ROW; // (dereferenced by lanes with cfg only: j < NJ)
+    int code = 0;
+    const bool gbad = __ballot(bs) != 0ull;
+    if (cfg && !gbad) {
+        bool absent = !smp;
+        if (smp) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) absent = absent || refused(tpe[k]);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) absent = absent || refused(a.tgt_rot[(ft * NJ + j) * 9 + k]);
+        }
+        if (!absent) {
+            code = GAP_PRESENT;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) grow[G_P + k] = __fadd_rn(tpe[k], gpc[k]);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) grow[G_R + k] = a.tgt_rot[(ft * NJ + j) * 9 + k];
+            grow[G_VALID] = 1.f; grow[G_AGE] = 0.f; grow[G_FACTOR] = 1.f;
+        } else {
+            const float age = __fadd_rn(grow[G_AGE], 1.f);
+            if (grow[G_VALID] != 0.f && age <= a.g.max_hold) {
+                code = GAP_HELD;
+                grow[G_AGE] = age;
+                grow[G_FACTOR] = __fmul_rn(grow[G_FACTOR], a.g.decay);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) tpe[k] = __fsub_rn(grow[G_P + k], gpc[k]);
+            } else {
+                code = GAP_LOST;
+                grow[G_VALID] = 0.f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) tpe[k] = 0.f;
+            }
+        }
+    }
+    if (jl && a.g.trace) a.g.trace[ft * NJ + j] = gbad ? 0xFF : (unsigned char)code; // (0: not tracked by configuration)
+    const bool trk = code == GAP_PRESENT || code == GAP_HELD;
+    const int gbits = (__ballot(code == GAP_HELD) != 0ull ? DP_STATUS_TRACKER_HELD : 0) | (__ballot(code == GAP_LOST) != 0ull ? DP_STATUS_TRACKER_LOST : 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the row's stores have left before the iteration loop reads the row
+#endif
     bool bt = refused(zt);
     if (trk) {
 #pragma unroll
-#if DP_CONS_SEQ
+#if DP_CONS_GAP // (the effective targets and weights: what the per-frame composition hands dp_optimize_terms)
+        for (int k = 0; k < 3; ++k) bt = bt || refused(tpe[k]);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) bt = bt || refused(grow[G_R + k]);
+#elif DP_CONS_SEQ
         for (int k = 0; k < 3; ++k) bt = bt || refused(tpe[k]);
 #pragma unroll
         for (int k = 0; k < 9; ++k) bt = bt || refused(a.tgt_rot[(ft * NJ + j) * 9 + k]);
@@ -174,7 +230,11 @@
 #pragma unroll
         for (int k = 0; k < 9; ++k) bt = bt || refused(a.tgt_rot[(f * NJ + j) * 9 + k]);
 #endif
+#if DP_CONS_GAP
+        bt = bt || refused(__fmul_rn(a.w[(f * NJ + j) * 2], grow[G_FACTOR])) || refused(__fmul_rn(a.w[(f * NJ + j) * 2 + 1], grow[G_FACTOR]));
+#else
         bt = bt || refused(a.w[(f * NJ + j) * 2]) || refused(a.w[(f * NJ + j) * 2 + 1]);
+#endif
     }
 #if DP_CONS_TABLE
     if (lane < a.n_terms) { // lane t: term t's row of this frame (the term's own vector and s_f = 1 without one) into the wave's block
@@ -207,7 +267,12 @@
 #endif
     const bool bad_state = __ballot(bs) != 0ull;
     const bool bad_tgt = !bad_state && __ballot(bt) != 0ull;
+#if DP_CONS_GAP // (a step without a tracker: max(E, 1), both tracker losses exactly 0, the pull and the table's terms act alone)
+    const int En = __popcll(__ballot(trk));
+    const int E = En > 0 ? En : 1;
+#else
     const int E = __popcll(__ballot(trk));
+#endif
 #if DP_CONS_SEQ
     if (bad_state) { // this step's results NaN and, as the per-frame epilogue makes them from such a frame, the carried state: every later step too
         float* const o = a.q.hist + ft * (LAT + 3 + NH);
@@ -414,7 +479,11 @@
 #pragma unroll
         for (int k = 0; k < 9; ++k) gGj[k] = 0.f;
         if (trk) { // (targets re-read every iteration: not held in registers)
+#if DP_CONS_GAP // (the row's factor: 1 for a present sample, and w * 1 is w)
+            const float wp = __fmul_rn(a.w[(f * NJ + j) * 2], grow[G_FACTOR]), wrr = __fmul_rn(a.w[(f * NJ + j) * 2 + 1], grow[G_FACTOR]);
+#else
             const float wp = a.w[(f * NJ + j) * 2], wrr = a.w[(f * NJ + j) * 2 + 1];
+#endif
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
 #if DP_CONS_SEQ
@@ -427,7 +496,9 @@
             }
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
-#if DP_CONS_SEQ
+#if DP_CONS_GAP // (the row's rotation: the sample's own when present, the held one otherwise)
+                const float e = G[k] - grow[G_R + k];
+#elif DP_CONS_SEQ
                 const float e = G[k] - a.tgt_rot[(ft * NJ + j) * 9 + k];
 #else
                 const float e = G[k] - a.tgt_rot[(f * NJ + j) * 9 + k];
@@ -670,8 +741,13 @@
             if (a.q.adjust_joint >= 0) { // drag_pose.py:377-384
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
+#if DP_CONS_GAP // that joint's effective target from its lane; lost or not tracked in this step: the adjusted joint's own position, adj = +0
+                    float tk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tpe[k]), a.q.adjust_target_joint));
+                    if (((__ballot(trk) >> a.q.adjust_target_joint) & 1ull) == 0ull) tk = PB[4 * a.q.adjust_joint + k];
+#else
                     float tk = a.tgt_pos[(fo * NJ + a.q.adjust_target_joint) * 3 + k]; // (that joint's effective target: its lane's tpe)
                     if (a.q.tgt_root) tk = tk + sh[k];
+#endif
                     // a difference, a product and two sums, none fused: dp_sequence_advance_kernel's v_sub, v_mul, v_add, v_add
                     const float adj = __fmul_rn(__fsub_rn(tk, PB[4 * a.q.adjust_joint + k]), a.q.adjust_weight);
                     gpn[k] = __fadd_rn(gpn[k], adj);
@@ -879,7 +955,12 @@
     const bool nonfin = pz || __ballot(lane < LAT && !(fabsf(z) <= 3.0e38f)) != 0ull;
     if (lane == 0) {
         if (a.iters) a.iters[ft] = bad_tgt && !a.early_stop ? a.n_iter : it + 1;
+#if DP_CONS_GAP
+        if (a.status)
+            a.status[ft] = (nonfin ? DP_STATUS_NONFINITE_RESULT : 0) | (bad_tgt ? DP_STATUS_BAD_TARGETS : 0) | gbits | (En == 0 ? DP_STATUS_NO_TRACKER : 0);
+#else
         if (a.status) a.status[ft] = (nonfin ? DP_STATUS_NONFINITE_RESULT : 0) | (bad_tgt ? DP_STATUS_BAD_TARGETS : 0);
+#endif
     }
     wave_sync(); // (the next step's first writes into the wave's block follow this step's last reads)
     } // the step loop

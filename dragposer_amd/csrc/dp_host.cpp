@@ -22,7 +22,8 @@
 #include "../../include/dragposer_sequence_constraints.h"
 #include "../../include/dragposer_holds.h"
 #include "../../include/dragposer_latent_ar.h"
-#include "dp_cons_ar.h"
+#include "../../include/dragposer_gaps.h"
+#include "dp_cons_gap.h"
 #include "dp_host_rt.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -675,6 +676,7 @@ constexpr Sized CONS_V510 = {"dp_constraints", "dp_constraints c = DP_CONSTRAINT
 constexpr Sized TERMS_V510 = {"dp_terms", "dp_terms t = DP_TERMS_INIT;", offsetof(dp_terms, loss_terms) + sizeof(void*), false};
 constexpr Sized HOLDS_V530 = {"dp_holds", "dp_holds h = DP_HOLDS_INIT;", offsetof(dp_holds, trace) + sizeof(void*), false};
 constexpr Sized LATENT_AR_V540 = {"dp_latent_ar", "dp_latent_ar r = DP_LATENT_AR_INIT;", offsetof(dp_latent_ar, trace) + sizeof(void*), false};
+constexpr Sized GAPS_V550 = {"dp_gaps", "dp_gaps g = DP_GAPS_INIT;", offsetof(dp_gaps, trace) + sizeof(void*), false};
 constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
@@ -1339,6 +1341,8 @@ hipError_t dp_launch_cons_seq(const dpcons::SeqConsArgs* args, hipStream_t strea
 hipError_t dp_launch_terms_seq(const dpcons::SeqTermArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_terms_hold_seq(const dpcons::HoldSeqArgs* args, hipStream_t stream) __attribute__((weak)); // (dp_cons_hold.hip, likewise)
 hipError_t dp_launch_terms_ar_seq(const dpcons::ArSeqArgs* args, hipStream_t stream) __attribute__((weak));     // (dp_cons_ar.hip, likewise)
+hipError_t dp_launch_terms_gap_seq(const dpcons::GapSeqArgs* args, hipStream_t stream) __attribute__((weak));    // (dp_cons_gap.hip, likewise)
+hipError_t dp_launch_terms_gap_ar_seq(const dpcons::GapArSeqArgs* args, hipStream_t stream) __attribute__((weak));
 #endif
 
 // include/dragposer_latent_ar.h: dp_latent_ar checked, after everything dp_optimize_sequence_holds checks, against the launch's frames and
@@ -1359,12 +1363,27 @@ static int take_latent_ar(dp_ctx* ctx, const dp_latent_ar* r_in, const dp_seq_fr
     return DP_OK;
 }
 
+// include/dragposer_gaps.h: dp_gaps checked, after everything dp_optimize_sequence_ar checks, and written into the argument block
+static int take_gaps(dp_ctx* ctx, const dp_gaps* g_in, dpcons::GapFields& g, const char* who)
+{
+    const std::string nm = who;
+    dp_gaps gs;
+    if (int rc = take_sized(ctx, g_in, gs, GAPS_V550, who)) return rc;
+    if (gs.max_hold < 0 || gs.max_hold > DP_GAP_MAX_HOLD)
+        return fail(ctx, DP_ERR_INVALID, nm + ": dp_gaps.max_hold " + std::to_string(gs.max_hold) + " outside 0.." + std::to_string(DP_GAP_MAX_HOLD));
+    if (!(gs.decay > 0.f && gs.decay <= 1.f)) return fail(ctx, DP_ERR_INVALID, nm + ": dp_gaps.decay must be a finite number in (0, 1]");
+    if (!gs.state) return fail(ctx, DP_ERR_INVALID, nm + ": dp_gaps.state is NULL");
+    g.state = gs.state; g.present = gs.present; g.trace = gs.trace; g.decay = gs.decay; g.max_hold = (float)gs.max_hold;
+    return DP_OK;
+}
+
 template <class A, class Own>
 static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
                                      const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream, const char* who, Own own,
-                                     const dp_latent_ar* ar = nullptr)
+                                     const dp_latent_ar* ar = nullptr, const dp_gaps* gaps = nullptr)
 {
-    constexpr bool HOLDS = std::is_same<A, dpcons::HoldSeqArgs>::value, AR = std::is_same<A, dpcons::ArSeqArgs>::value;
+    constexpr bool GAP = std::is_same<A, dpcons::GapSeqArgs>::value, GAP_AR = std::is_same<A, dpcons::GapArSeqArgs>::value;
+    constexpr bool HOLDS = std::is_same<A, dpcons::HoldSeqArgs>::value, AR = std::is_same<A, dpcons::ArSeqArgs>::value || GAP_AR;
     dp_params p;
     if (int rc = take_params(ctx, p_in, p, who)) return rc;
     dp_seq_results out;
@@ -1378,11 +1397,16 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
     if (int rc = check_adam(ctx, p, who)) return rc;
     if constexpr (AR)
         if (int rc = take_latent_ar(ctx, ar, fr, st, a.r, who)) return rc;
+    if constexpr (GAP || GAP_AR)
+        if (int rc = take_gaps(ctx, gaps, a.g, who)) return rc;
 #ifdef DP_REF8_BUILD
     (void)n_seq; (void)latent; (void)stream;
     return refuse_ref8(ctx, who);
 #else
-    if (AR ? !dp_launch_terms_ar_seq : HOLDS ? !dp_launch_terms_hold_seq : (!dp_launch_cons_seq || !dp_launch_terms_seq))
+    if (GAP || GAP_AR) {
+        if (!dp_launch_terms_gap_seq || !dp_launch_terms_gap_ar_seq)
+            return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_gap.hip");
+    } else if (AR ? !dp_launch_terms_ar_seq : HOLDS ? !dp_launch_terms_hold_seq : (!dp_launch_cons_seq || !dp_launch_terms_seq))
         return fail(ctx, DP_ERR_UNSUPPORTED,
                     std::string(who) + ": this library was linked without " + (AR ? "dp_cons_ar.hip" : HOLDS ? "dp_cons_hold.hip" : "dp_cons_seq.hip"));
     if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
@@ -1398,6 +1422,8 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
         DEVICE_GUARD(ctx);
         hipError_t e;
         if constexpr (std::is_same<A, dpcons::SeqConsArgs>::value) e = dp_launch_cons_seq(&a, (hipStream_t)stream);
+        else if constexpr (GAP) e = dp_launch_terms_gap_seq(&a, (hipStream_t)stream);
+        else if constexpr (GAP_AR) e = dp_launch_terms_gap_ar_seq(&a, (hipStream_t)stream);
         else if constexpr (HOLDS) e = dp_launch_terms_hold_seq(&a, (hipStream_t)stream);
         else if constexpr (AR) e = dp_launch_terms_ar_seq(&a, (hipStream_t)stream);
         else e = dp_launch_terms_seq(&a, (hipStream_t)stream);
@@ -1525,6 +1551,31 @@ extern "C" int dp_optimize_sequence_ar(dp_ctx* ctx, int n_seq, float* latent, co
         if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !r_in || !st || !out)
             return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_ar: n_sequences must be positive; NULL latent, frames, params, terms, ar, state or results");
         return sequence_constrained_impl<dpcons::ArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in);
+    });
+}
+
+// include/dragposer_gaps.h: dp_optimize_sequence_ar with a tracker set decided per step (A = dpcons::GapArSeqArgs; `ar` NULL:
+// dpcons::GapSeqArgs, dp_optimize_sequence_holds' frames->z_tgt); dp_gaps is checked last (take_gaps, from sequence_constrained_impl)
+extern "C" int dp_optimize_sequence_gaps(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                         const dp_holds* h_in, const dp_latent_ar* r_in, const dp_gaps* g_in, const dp_skeleton_in* skel,
+                                         const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_gaps";
+    const auto own = [&](auto& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
+        if (h_in)
+            if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
+        dp_seq_extra e;
+        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
+        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
+        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
+        return DP_OK;
+    };
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !g_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_gaps: n_sequences must be positive; NULL latent, frames, params, terms, gaps, state or results");
+        if (r_in) return sequence_constrained_impl<dpcons::GapArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in, g_in);
+        return sequence_constrained_impl<dpcons::GapSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, nullptr, g_in);
     });
 }
 

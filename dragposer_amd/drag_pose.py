@@ -106,6 +106,7 @@ class DragPose:
         self._out = [None, None]
         self._flip = 0
         self.hold_state = None  # [S,len(holds),4] (x, y, z, held) of run(holds=) / run_frames(holds=); zeroed when a sequence begins
+        self.gap_state = None  # [S,22,16] of run(gaps=) / run_frames(gaps=) (include/dragposer_gaps.h); zeroed when a sequence begins
         self._skel_obj, self._skel_dev = None, None  # the last `offsets` object run() / run_frames() was given, and what it decided (_skeleton)
 
     def _holds(self, holds, terms, constraints, who):
@@ -181,6 +182,7 @@ class DragPose:
         self.current_index = 0
         self.target_latent_buffer = None
         self.hold_state = None
+        self.gap_state = torch.zeros(self.S, NJ, 16, device=self.device)
 
     def set_initial_state(self, latent, init_global_pos, initial_global_rot, initial_heights):
         """What set_initial_pose leaves behind, with the initial latent given instead of encoded."""
@@ -195,6 +197,7 @@ class DragPose:
         self.current_index = 0
         self.target_latent_buffer = None
         self.hold_state = None
+        self.gap_state = torch.zeros(self.S, NJ, 16, device=self.device)
 
     # ------------------------------------------------------------------ temporal target (drag_pose.py:234-294)
     def _temporal_targets(self, window):
@@ -269,7 +272,7 @@ class DragPose:
     def run_frames(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, target_root=None, stop_eps_pos=1e-2, stop_eps_rot=1e-2,
                    max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1, temporal_future_window=60,
                    height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01, offsets=None,
-                   constraints=None, terms=None, holds=None, ar=None):
+                   constraints=None, terms=None, holds=None, ar=None, gaps=None, present=None):
         """T consecutive frames of every sequence -- T calls of run() -- with the frame loop on the device: one kernel launch per
         stretch of frames between two temporal predictions (all T of them when there is no predictor or lambda_temporal is 0).
         target_ee_pos [T,S,E,3], target_ee_rot [T,S,E,3,3]; `target_root` [T,S,3] or None: given, the position targets of frame t
@@ -287,15 +290,25 @@ class DragPose:
         include/dragposer_latent_ar.h), weighed by `lambda_temporal`; with or without `terms`, `holds` and `offsets`, and `constraints`
         go through Terms.from_constraints (`last_terms` is then [T,S,len of that table]).  `last_z_tgt` [T,S,24] holds the targets used,
         `last_loss` [T,S,3] every frame's three loss parts.
+        `gaps` (a dragposer_amd.Gaps): trackers that drop out and come back (dp_optimize_sequence_gaps, include/dragposer_gaps.h) -- a
+        sample that is NaN, or whose entry of `present` [T,S,E] (tracker-list order; None: NaN samples alone mark gaps) is 0, is held at the
+        joint's last good one for up to gaps.max_hold frames and leaves the loss after that.  With `ar` it is one launch, without it the
+        usual stretches; the state lives in `gap_state` [S,22,16], zeroed when a sequence begins, and `last_gap_trace` [T,S,22] holds every
+        joint's code of every frame (1 present, 2 held, 3 lost, 0 not a tracker).  Without `terms` it runs with an empty table, and
+        `constraints` go through Terms.from_constraints, as with `ar`.
         Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run_frames: pass constraints or terms, not both")
         if ar is not None:
             _check_ar(self.temporal, ar, "run_frames")
-            if constraints is not None:
-                from .terms import Terms
+        if gaps is None and present is not None:
+            raise ValueError("DragPose.run_frames: present belongs to gaps=")
+        if gaps is not None:
+            gaps.check()
+        if (ar is not None or gaps is not None) and constraints is not None:
+            from .terms import Terms
 
-                terms, constraints = Terms.from_constraints(constraints), None
+            terms, constraints = Terms.from_constraints(constraints), None
         self._holds(holds, terms, constraints, "run_frames")
         dev, S = self.device, self.S
         skel = self._skeleton(offsets)
@@ -333,15 +346,34 @@ class DragPose:
             self.last_hold_trace = torch.zeros(T, S, len(holds), 4, device=dev)
         if ar is not None:
             self.last_z_tgt = torch.zeros(T, S, LATENT, device=dev)
+        dense_here = None
+        if gaps is not None:
+            if self.gap_state is None:
+                self.gap_state = gaps.new_state(S, dev)
+            self.last_gap_trace = torch.zeros(T, S, NJ, dtype=torch.uint8, device=dev)
+            if present is not None:
+                here = torch.as_tensor(present, device=dev).reshape(T, S, -1)
+                if here.shape[2] != E:
+                    raise ValueError("present must have one entry per entry of mask_joints")
+                dense_here = torch.ones(T, S, NJ, dtype=torch.uint8, device=dev)
+                dense_here.index_copy_(2, trk["mj"], (here != 0).to(torch.uint8))
+
+        def gap_kw(t0, n):
+            """the stretch's share of the gaps' arguments"""
+            if gaps is None:
+                return {}
+            return dict(gaps=gaps, gap_state=self.gap_state, present=dense_here[t0:t0 + n] if dense_here is not None else None,
+                        gap_trace=self.last_gap_trace[t0:t0 + n])
 
         def extra(t0, n):
             """the stretch's share of the terms' arguments: the table's rows and the per-step outputs of frames t0 .. t0 + n"""
             if not with_terms:
-                return {}
+                return gap_kw(t0, n)
             kw = {"constraints": constraints, "terms": terms.frames(t0, t0 + n) if terms is not None else None,
                   key: self.last_terms[t0:t0 + n], "joint_pos": self.last_joint_pos[t0:t0 + n]}
             if holds is not None:
                 kw.update(holds=holds, hold_state=self.hold_state, hold_trace=self.last_hold_trace[t0:t0 + n])
+            kw.update(gap_kw(t0, n))
             return kw
 
         if ar is not None:  # one launch, no stretches: the targets come from inside it
@@ -364,6 +396,7 @@ class DragPose:
         pull = have and float(lambda_temporal) != 0.0
         window = int(temporal_future_window)
         zero_tgt = torch.zeros(S, LATENT, device=dev)
+        loss = torch.empty(T, S, 3, device=dev) if gaps is not None else None  # (last_loss of run_frames(gaps=), as of run_frames(ar=))
         t = 0
         while t < T:
             if have:  # frames up to the next prediction (a prediction every `window` frames; every frame when window = 0)
@@ -378,16 +411,19 @@ class DragPose:
                                        n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_temporal) if pull else 0.0,
                                        stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, adjust=adjust,
                                        pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n], offsets=skel,
-                                       **extra(t, n))
+                                       loss=loss[t:t + n] if loss is not None else None, **extra(t, n))
             t += n
             self.current_index = 0 if window == 0 else (self.current_index + n) % window
         self.last_status = status  # [T,S] DP_STATUS_* bits (include/dragposer.h): non-zero where a frame's inputs were not finite
+        if gaps is not None:
+            self.last_loss = loss
         return poses, gpos, iters
 
     def run(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, offsets=None, stop_eps_pos=1e-2,
             stop_eps_rot=1e-2, max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1,
             temporal_future_window=60, height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None,
-            joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None, holds=None, ar=None):
+            joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None, holds=None, ar=None,
+            gaps=None, present=None):
         """One frame for every sequence: one launch for the optimise loop and the epilogue, one for the history buffers, plus two
         row scatters of the targets.  `out_pose` [S,88] / `out_pos` [S,3]: optional caller storage for the returned tensors.
         `constraints` (a dragposer_amd.Constraints): the reference's extra loss terms (drag_pose.py:129-183) join the loss -- the frame
@@ -398,6 +434,8 @@ class DragPose:
         `hold_state`, and the state is updated after the frame with include/dragposer_holds.h's arithmetic in torch on the device, no
         synchronisation -- frame by frame the bits of run_frames(terms=, holds=).  `ar` (a dragposer_amd.LatentAR): the frame is a one-step
         launch of run_frames(ar=), with everything that call takes (`offsets` together with `terms` included); frame by frame its bits.
+        `gaps` (a dragposer_amd.Gaps) with `present` [S,E] or None: likewise a one-step run_frames(gaps=), with or without `ar`; `last`
+        then holds the frame's `gap_trace` [S,22].
         `offsets`: the performer's bone offsets, as the reference takes them on every call (drag_pose.py:202) -- [22,3] for every sequence
         or [S,22,3] one per sequence.  The context's own skeleton (or None) runs the launches above unchanged; any other runs the same frame
         with those bones (dp_optimize_sequence_skeleton, include/dragposer_skeleton.h), not together with `constraints` / `terms`: this
@@ -405,14 +443,20 @@ class DragPose:
         the same object frame after frame costs one host synchronisation in all (DragPose._skeleton)."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
-        if ar is not None:
-            _check_ar(self.temporal, ar, "run")
+        if gaps is None and present is not None:
+            raise ValueError("DragPose.run: present belongs to gaps=")
+        if ar is not None or gaps is not None:
+            if ar is not None:
+                _check_ar(self.temporal, ar, "run")
+            if gaps is not None:
+                gaps.check()
+                present = torch.as_tensor(present, device=self.device).reshape(1, self.S, -1) if present is not None else None
             return self._run_ar(target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose,
                                 dict(offsets=offsets, stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, max_iter=max_iter,
                                      min_loss_incr=min_loss_incr, learning_rate=learning_rate, lambda_rot=lambda_rot, lambda_temporal=lambda_temporal,
                                      temporal_future_window=temporal_future_window, height_indices=height_indices,
                                      joint_adjustment_indices=joint_adjustment_indices, joint_adjustment_weight=joint_adjustment_weight,
-                                     constraints=constraints, terms=terms, holds=holds, ar=ar))
+                                     constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, present=present))
         self._holds(holds, terms, constraints, "run")
         skel = self._skeleton(offsets)
         if skel is not None and (constraints is not None or terms is not None):
@@ -473,7 +517,7 @@ class DragPose:
         return pose, gpos
 
     def _run_ar(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose, kw):
-        """run(ar=): run_frames(ar=) on this one frame"""
+        """run(ar=) / run(gaps=): run_frames(ar= / gaps=) on this one frame"""
         S = self.S
         squeeze = torch.as_tensor(target_ee_pos).dim() == 2
         tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=self.device).reshape(1, S, -1, 3)
@@ -484,8 +528,11 @@ class DragPose:
             pose = out_pose.copy_(pose)
         if out_pos is not None:
             gpos = out_pos.copy_(gpos)
-        self.last = dict(iters=iters[0], loss=self.last_loss[0], z=self.latent.clone(), pose=pose, pos=gpos, status=self.last_status[0],
-                         z_tgt=self.last_z_tgt[0])
+        self.last = dict(iters=iters[0], loss=self.last_loss[0], z=self.latent.clone(), pose=pose, pos=gpos, status=self.last_status[0])
+        if kw.get("ar") is not None:
+            self.last["z_tgt"] = self.last_z_tgt[0]
+        if kw.get("gaps") is not None:
+            self.last["gap_trace"] = self.last_gap_trace[0]
         if verbose:
             l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
             print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "

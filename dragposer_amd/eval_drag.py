@@ -44,14 +44,17 @@ DEFAULT_CONFIG = dict(  # eval_drag.py:68-131
     lambda_temporal=0.02, temporal_future_window=0)
 
 
-def eval_pos_error(gt_bvh, eval_bvh):
-    """eval_metrics.eval_pos_error (eval_metrics.py:6-32): FK of both files with the root at the origin."""
+def eval_pos_error(gt_bvh, eval_bvh, frames=None):
+    """eval_metrics.eval_pos_error (eval_metrics.py:6-32): FK of both files with the root at the origin.  `frames`: a boolean mask, the
+    means are then over those frames alone (--drop's second line)."""
     gq, _, parents, offsets = local_quats_from_bvh(gt_bvh)
     eq, _, _, _ = local_quats_from_bvh(eval_bvh)
     n = min(len(gq), len(eq))
     gp, _ = Q.fk(gq[:n], np.zeros((n, 3)), offsets, parents)
     ep, _ = Q.fk(eq[:n], np.zeros((n, 3)), offsets, parents)
     err = np.linalg.norm(ep - gp, axis=-1)
+    if frames is not None:
+        err = err[np.asarray(frames, bool)[:n]]
     return float(err.mean()), float(err[:, SPARSE_JOINTS[1:]].mean())
 
 
@@ -81,6 +84,24 @@ def foot_lock_terms(args, cons):
     pins = [Term.distance(j, point=(0.0, 0.0, 0.0), lo=0.0, hi=0.0, weight=args.foot_lock_weight, drop_up=True) for j in FOOT_LOCK_JOINTS]
     holds = Holds([Hold(len(base) + i, lo, hi, level=args.floor_level) for i in range(len(pins))])
     return Terms(base.terms + pins, base.up_axis), holds
+
+
+def parse_drop(text, mask_idx, n_frames):
+    """--drop J:START:LEN[,...] -> (a boolean [n_frames, E] array in tracker-list order: the samples of joint J that are blanked; a boolean
+    [n_frames]: the frames named).  A joint that is not among the configuration's trackers has no sample to blank: its frames are still
+    named, so that a configuration without that tracker is scored on the same frames."""
+    drop, rows = np.zeros((n_frames, len(mask_idx)), bool), np.zeros(n_frames, bool)
+    for item in text.split(","):
+        try:
+            j, start, length = (int(x) for x in item.split(":"))
+        except ValueError:
+            raise SystemExit(f"--drop: expected J:START:LEN[,...], got {item!r}")
+        if not 0 <= j < NJ or start < 0 or length <= 0:
+            raise SystemExit(f"--drop: {item!r}: J must be a joint, START must not be negative and LEN must be positive")
+        rows[start:start + length] = True
+        if j in list(mask_idx):
+            drop[start:start + length, list(mask_idx).index(j)] = True
+    return drop, rows
 
 
 def result_to_bvh(poses, global_pos, means, stds, bvh, out_path):
@@ -126,6 +147,11 @@ def prepare_file(args, input_path, opt, encoder, cfg, raw):
     # targets (eval_drag.py:164-202): FK of the ground-truth pose with the root at the origin, per frame; the
     # root translation relative to the running estimate is added inside the loop, on the device
     p_rel, r_mats = synthesize_targets(m, n_frames, mask_idx)
+    dropped, rows = None, None
+    if getattr(args, "drop", None):  # the blanked samples arrive as NaN, as a tracker out of view sends them
+        dropped, rows = parse_drop(args.drop, mask_idx, n_frames)
+        p_rel, r_mats = p_rel.copy(), r_mats.copy()
+        p_rel[dropped], r_mats[dropped] = np.nan, np.nan
     if getattr(args, "initial_latent", None):
         # (parity runs: the reference draws the encoder's noise from torch's GLOBAL generator after its model constructors have
         #  consumed an implementation-defined amount of it -- eval_drag.py:23,49-51,152 -- so its latent is handed over instead)
@@ -133,7 +159,7 @@ def prepare_file(args, input_path, opt, encoder, cfg, raw):
     else:
         gen = torch.Generator(device="cpu").manual_seed(2222)  # train.param["seed"]
         z0 = encoder.sample(torch.tensor(m["dqs"][0:1], device=dev), generator=gen)  # drag_pose.py:50
-    return dict(path=input_path, bvh=bvh, m=m, n_frames=n_frames, means=means, stds=stds, z0=z0,
+    return dict(path=input_path, bvh=bvh, m=m, n_frames=n_frames, means=means, stds=stds, z0=z0, dropped_rows=rows,
                 offsets=torch.tensor(np.asarray(m["offsets"], np.float32).reshape(NJ, 3), device=dev),
                 tp_rel=torch.tensor(p_rel, dtype=torch.float32, device=dev), tR=torch.tensor(r_mats, dtype=torch.float32, device=dev),
                 gpos=torch.tensor(m["global_pos"][:n_frames], dtype=torch.float32, device=dev))
@@ -170,6 +196,10 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
         extra = dict(terms=terms, holds=holds)
     if ar is not None:
         extra["ar"] = ar
+    if getattr(args, "gaps_model", None) is not None:
+        if extra.get("constraints") is None:
+            extra.pop("constraints", None)
+        extra["gaps"] = args.gaps_model
     poses = torch.zeros(T, S, 88, device=dev)
     out_pos = torch.zeros(T, S, 3, device=dev)
     iters = torch.zeros(T, S, dtype=torch.int32, device=dev)
@@ -207,12 +237,23 @@ def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
     print(f"Evaluate Loss: {mpjpe + mpeepe}")
     print(f"Mean Per Joint Position Error: {mpjpe}")
     print(f"Mean End Effector Position Error: {mpeepe}")
+    blank = None
+    if q.get("dropped_rows") is not None and q["dropped_rows"].any():
+        rows = q["dropped_rows"]
+        blank = eval_pos_error(BVH().load(q["path"]), BVH().load(out_path), frames=rows)
+        print(f"Blanked frames ({int(rows.sum())} of {len(rows)}, --drop {args.drop}): Mean Per Joint Position Error: {blank[0]} // "
+              f"Mean End Effector Position Error: {blank[1]}")
+    if getattr(args, "gaps_model", None) is not None:
+        g = args.gaps_model
+        print(f"Gaps: max_hold {g.max_hold}, decay {g.decay} (DragPose.run_frames(gaps=), include/dragposer_gaps.h)")
     print(f"Time: {elapsed}" + (f"  (shared by {shared} sequences in lock-step)" if shared > 1 else ""))
     if getattr(args, "latent_ar_model", None) is not None:
         print(f"Latent predictor: {args.latent_ar_text} (DragPose.run_frames(ar=), include/dragposer_latent_ar.h)")
     print(f"Frames: {n}  ({n / elapsed:.1f} frames/s, mean iterations/frame {res['iters'].mean():.1f}, "
           f"lambda_temporal {lam_tmp}{'' if has_temporal else ' -- no temporal checkpoint given: pull term off'})")
     out = dict(mpjpe=mpjpe, mpeepe=mpeepe, time=elapsed, frames=n, out=out_path, mean_iters=float(res["iters"].mean()))
+    if blank is not None:
+        out.update(mpjpe_blanked=blank[0], mpeepe_blanked=blank[1])
     if getattr(args, "foot_lock", False):
         up = Constraints.reference().up_axis if getattr(args, "constraints", None) == "reference" else args.up_axis
         skate, pairs = foot_skate(BVH().load(q["path"]), BVH().load(out_path), args.contact_height[0], args.floor_level, up)
@@ -303,6 +344,15 @@ def main(argv=None):
                          "recent latents, with the configuration's lambda_temporal instead of 0 (DragPose.run_frames(ar=), "
                          "include/dragposer_latent_ar.h; with --per-frame DragPose.run(ar=), same results).  hold: the last latent; cv: constant "
                          "velocity, optionally damped; FILE.npz: a model fitted by `python -m dragposer_amd.ar fit`")
+    ap.add_argument("--drop", default=None, metavar="J:START:LEN[,...]",
+                    help="blank the samples of tracker joint J on frames START .. START + LEN of the synthesised targets (NaN, as a tracker out of "
+                         "view sends them); the position errors are then also printed over the blanked frames alone.  Without --gaps the clip ends "
+                         "at the first blanked frame: every later result is NaN (DP_STATUS_BAD_STATE)")
+    ap.add_argument("--gaps", default=None, metavar="MAX_HOLD:DECAY",
+                    help="keep going through missing samples: a tracker whose sample is NaN is held at its last good sample for up to MAX_HOLD "
+                         "frames at a weight that decays by DECAY per frame, and leaves the loss after that until it returns "
+                         "(DragPose.run_frames(gaps=), include/dragposer_gaps.h; with --per-frame DragPose.run(gaps=), same results).  No default: "
+                         "nobody has tuned one")
     ap.add_argument("--lockstep", action="store_true",
                     help="directory input: advance all files together, one kernel launch per frame index for all of them "
                          "(same per-file results; the reference evaluates them one after the other)")
@@ -335,6 +385,16 @@ def main(argv=None):
         from .ar import parse
 
         args.latent_ar_model, args.latent_ar_text = parse(args.latent_ar)
+    args.gaps_model = None
+    if args.gaps is not None:
+        from .gaps import Gaps
+
+        try:
+            hold, decay = args.gaps.split(":")
+            args.gaps_model = Gaps(int(hold), float(decay))
+            args.gaps_model.check()
+        except ValueError as e:
+            raise SystemExit(f"--gaps: expected MAX_HOLD:DECAY with 0 <= MAX_HOLD <= 65535 and 0 < DECAY <= 1 ({e})")
     if args.lockstep and len(files) > 1:
         print(f"Evaluate {len(files)} files in lock-step ------------------------")
         return evaluate_files(args, files, opt, encoder, temporal_pack, cfg, raw)

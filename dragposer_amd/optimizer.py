@@ -384,7 +384,8 @@ class LatentOptimizer:
                           heights_buf, height_joints, n_iter=100, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.0,
                           stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
                           loss=None, scratch=None, status=None, offsets=None, constraints=None, terms=None, loss_extra=None, loss_terms=None,
-                          joint_pos=None, holds=None, hold_state=None, hold_trace=None, ar=None, z_tgt_trace=None):
+                          joint_pos=None, holds=None, hold_state=None, hold_trace=None, ar=None, z_tgt_trace=None, gaps=None, gap_state=None,
+                          present=None, gap_trace=None):
         """T consecutive frames of S sequences in one launch (include/dragposer.h: dp_optimize_sequence): the optimise loop with the
         reference's while-condition and run()'s epilogue per frame, state carried on the device.  tgt_pos [T,S,22,3] / tgt_rot
         [T,S,22,9] dense per joint; tgt_root [T,S,3] or None (position targets are then tgt_pos + (tgt_root[t] - running global
@@ -405,7 +406,24 @@ class LatentOptimizer:
         `ar` (a dragposer_amd.LatentAR): every step's z_tgt row is formed in the launch from the sequence's last history rows,
         dp_optimize_sequence_ar (include/dragposer_latent_ar.h) -- `z_tgt` must then be None (`z_tgt_strides` is ignored), `terms` / `holds`
         are optional (`constraints` is not taken: Terms.from_constraints turns them into a table) and `latent_buf` holds at least
-        `ar.order` rows.  `z_tgt_trace` [T,S,24] or True (allocated here) receives the row every step used and is returned as `z_tgt_trace`."""
+        `ar.order` rows.  `z_tgt_trace` [T,S,24] or True (allocated here) receives the row every step used and is returned as `z_tgt_trace`.
+        `gaps` (a dragposer_amd.Gaps): trackers that drop out and come back, dp_optimize_sequence_gaps (include/dragposer_gaps.h), with or
+        without `ar` (without: `z_tgt` as usual); `terms` / `holds` are optional, `constraints` is not taken.  `gap_state` [S,22,16] is
+        updated IN PLACE (required); `present` [T,S,22] uint8 or None (NaN samples alone mark gaps); `gap_trace` [T,S,22] uint8 or True
+        (allocated here) receives every joint's code of every step and is returned as `gap_trace`.  `status` then also carries
+        DP_STATUS_TRACKER_HELD / _LOST / DP_STATUS_NO_TRACKER."""
+        if gaps is None and (gap_state is not None or present is not None or gap_trace is not None):
+            raise ValueError("optimize_sequence: gap_state / present / gap_trace belong to gaps=")
+        if gaps is not None:
+            gaps.check()
+            if gap_state is None:
+                raise ValueError("optimize_sequence: gaps= needs gap_state [S,22,16]")
+            if constraints is not None:
+                raise ValueError("optimize_sequence: gaps= takes a table, pass terms= (Terms.from_constraints turns constraints into one)")
+            if terms is None:
+                from .terms import Terms
+
+                terms = Terms()
         if ar is None and z_tgt_trace is not None:
             raise ValueError("optimize_sequence: z_tgt_trace belongs to ar=")
         if ar is not None:
@@ -501,6 +519,14 @@ class LatentOptimizer:
                 fn, mid = self.lib.dp_optimize_sequence_ar, (mid[0] if mid else None, C.byref(rs))
                 if z_tgt_trace is not None:
                     outs["z_tgt_trace"] = z_tgt_trace
+            if gaps is not None:
+                if gap_trace is True:
+                    gap_trace = torch.zeros(T, S, NJ, dtype=torch.uint8, device=dev)
+                gs = gaps.to_struct(S, dev, gap_state, present, gap_trace, steps=T)
+                hold_ref, ar_ref = (mid[0] if mid else None), (mid[1] if len(mid) > 1 else None)
+                fn, mid = self.lib.dp_optimize_sequence_gaps, (hold_ref, ar_ref, C.byref(gs))
+                if gap_trace is not None:
+                    outs["gap_trace"] = gap_trace
             self._call(fn, S, lp, C.byref(fr), C.byref(p), C.byref(own), *mid, C.byref(skel) if skel is not None else None, *tail, C.byref(ex))
             del keep
             return outs

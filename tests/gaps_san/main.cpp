@@ -1,0 +1,179 @@
+// tests/gaps_san/main.cpp -- dp_optimize_sequence_gaps (include/dragposer_gaps.h) under AddressSanitizer and
+// UndefinedBehaviorSanitizer: a stand-alone program that links dp_host.cpp against tests/host_san/fake_hip.cpp (no HIP runtime, no kernel
+// unit) and walks the call's refusals, in the header's order, on a context without a device.  Every sized struct is handed over in a heap
+// block of exactly struct_size bytes, the term table in one of exactly n_terms entries and the holds array in one of exactly n_holds entries,
+// so a read past what the caller owns is an error here.  Device pointers are a constant that is never dereferenced.  Built and run by
+// tests/test_gaps_san.py; every condition is exact.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dragposer_gaps.h"
+
+extern "C" int dp_debug_host_ctx(dp_ctx**); // the library's private hook: a context with no device behind it
+
+#define CHECK(cond)                                                                      \
+    do {                                                                                 \
+        if (!(cond)) {                                                                   \
+            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
+            std::exit(1);                                                                \
+        }                                                                                \
+    } while (0)
+
+namespace {
+
+float* const PTR = (float*)0x10000; // stands for a device pointer
+
+// a T in a heap block of exactly `size` bytes (default: sizeof(T))
+template <class T>
+struct Exact {
+    void* block;
+    explicit Exact(const T& init, size_t size = sizeof(T)) : block(std::malloc(size)) { std::memcpy(block, &init, size < sizeof(T) ? size : sizeof(T)); }
+    ~Exact() { std::free(block); }
+    Exact(const Exact&) = delete;
+    const T* get() const { return (const T*)block; }
+};
+template <class T>
+struct Array { // exactly n entries (n = 0: a NULL pointer)
+    T* p;
+    explicit Array(const std::vector<T>& v) : p(v.empty() ? nullptr : (T*)std::malloc(v.size() * sizeof(T)))
+    {
+        if (p) std::memcpy(p, v.data(), v.size() * sizeof(T));
+    }
+    ~Array() { std::free(p); }
+    Array(const Array&) = delete;
+};
+
+std::vector<dp_term> good_terms()
+{
+    dp_term plane = DP_TERM_INIT;
+    plane.type = DP_TERM_PLANE; plane.joint_a = 4; plane.weight = 1.f;
+    dp_term pin = DP_TERM_INIT;
+    pin.type = DP_TERM_DISTANCE; pin.joint_a = 8; pin.weight = 0.8f; pin.flags = DP_TERM_DROP_UP;
+    return {plane, pin};
+}
+
+struct Case { // what one call is made of; the defaults are well-formed
+    std::vector<dp_term> terms = good_terms();
+    std::vector<dp_hold> holds = {{1, 0.f, 0.02f, 0.05f}};
+    bool null_holds_struct = false, null_ar = false, with_trace = true, with_extra = true, with_skeleton = true;
+    unsigned holds_size = sizeof(dp_holds), ar_size = sizeof(dp_latent_ar), ar_reserved0 = 0u;
+    int order = 2, history = 60, n_steps = 3, row_step1 = 0;
+    bool null_coeffs = false, null_bias = false, z_tgt = false;
+    float lr = 1e-2f;
+    bool null_gaps = false, null_gap_state = false, with_present = true, with_gap_trace = true;
+    unsigned gaps_size = sizeof(dp_gaps), gaps_reserved0 = 0u;
+    int max_hold = 3;
+    float decay = 0.7f;
+};
+
+int run(dp_ctx* ctx, const Case& c)
+{
+    dp_seq_frames fr0{};
+    fr0.n_steps = c.n_steps; fr0.tgt_pos = fr0.tgt_rot = fr0.w = PTR; fr0.tracked = (const unsigned char*)PTR;
+    fr0.z_tgt = c.z_tgt ? PTR : nullptr;
+    dp_params p0 = DP_PARAMS_INIT;
+    p0.n_iter = 10; p0.lr = c.lr; p0.beta1 = 0.9f; p0.beta2 = 0.999f; p0.eps = 1e-8f; p0.lambda_rot = 1.f; p0.lambda_tmp = 0.02f;
+    dp_seq_state st0{};
+    st0.global_pos = st0.global_rot = st0.latent_buf = st0.disp_buf = st0.heights_buf = PTR; st0.history = c.history; st0.n_heights = 2;
+    st0.height_joints[0] = 4; st0.height_joints[1] = 8;
+    dp_seq_step adj0{};
+    adj0.adjust_joint = 0; adj0.adjust_target_joint = 13; adj0.adjust_weight = 0.5f;
+    dp_seq_results q0 = DP_SEQ_RESULTS_INIT;
+    q0.pose_ret = q0.pos_ret = q0.loss = q0.hist_scratch = PTR;
+    dp_seq_extra e0 = DP_SEQ_EXTRA_INIT;
+    e0.loss_terms = e0.joint_pos = PTR; e0.row_step[1] = c.row_step1;
+    dp_skeleton_in s0 = DP_SKELETON_IN_INIT;
+    s0.offsets = PTR; s0.stride = DP_SKELETON_STRIDE;
+    Array<dp_term> terms(c.terms);
+    dp_terms t0 = DP_TERMS_INIT;
+    t0.n_terms = (int)c.terms.size(); t0.terms = terms.p;
+    Array<dp_hold> holds(c.holds);
+    dp_holds h0 = DP_HOLDS_INIT;
+    h0.struct_size = c.holds_size; h0.n_holds = (int)c.holds.size(); h0.holds = holds.p;
+    h0.state = c.holds.empty() ? nullptr : PTR; h0.trace = nullptr;
+    dp_latent_ar r0 = DP_LATENT_AR_INIT;
+    r0.struct_size = c.ar_size; r0.reserved0 = c.ar_reserved0; r0.order = c.order;
+    r0.coeffs = c.null_coeffs ? nullptr : PTR; r0.bias = c.null_bias ? nullptr : PTR; r0.trace = c.with_trace ? PTR : nullptr;
+    dp_gaps g0 = DP_GAPS_INIT;
+    g0.struct_size = c.gaps_size; g0.reserved0 = c.gaps_reserved0; g0.max_hold = c.max_hold; g0.decay = c.decay;
+    g0.state = c.null_gap_state ? nullptr : PTR; g0.present = c.with_present ? (const unsigned char*)PTR : nullptr;
+    g0.trace = c.with_gap_trace ? (unsigned char*)PTR : nullptr;
+    Exact<dp_seq_frames> fr(fr0);
+    Exact<dp_params> p(p0);
+    Exact<dp_seq_state> st(st0);
+    Exact<dp_seq_step> adj(adj0);
+    Exact<dp_seq_results> q(q0);
+    Exact<dp_seq_extra> e(e0);
+    Exact<dp_skeleton_in> s(s0);
+    Exact<dp_terms> t(t0);
+    Exact<dp_holds> h(h0, c.holds_size < sizeof(dp_holds) ? c.holds_size : sizeof(dp_holds));
+    Exact<dp_latent_ar> r(r0, c.ar_size < sizeof(dp_latent_ar) ? c.ar_size : sizeof(dp_latent_ar));
+    Exact<dp_gaps> g(g0, c.gaps_size < sizeof(dp_gaps) ? c.gaps_size : sizeof(dp_gaps));
+    return dp_optimize_sequence_gaps(ctx, 4, PTR, fr.get(), p.get(), t.get(), c.null_holds_struct ? nullptr : h.get(), c.null_ar ? nullptr : r.get(),
+                                   c.null_gaps ? nullptr : g.get(), c.with_skeleton ? s.get() : nullptr, st.get(), adj.get(), q.get(), c.with_extra ? e.get() : nullptr, nullptr);
+}
+
+bool said(dp_ctx* ctx, const char* word) { return std::string(dp_last_error(ctx)).find(word) != std::string::npos; }
+
+} // namespace
+
+int main()
+{
+    dp_ctx* ctx = nullptr;
+    CHECK(dp_debug_host_ctx(&ctx) == DP_OK && ctx);
+    int n = 0;
+    const auto refused = [&](const Case& c, const char* word) {
+        CHECK(run(ctx, c) == DP_ERR_INVALID);
+        if (!said(ctx, word)) { std::fprintf(stderr, "expected '%s' in: %s\n", word, dp_last_error(ctx)); std::exit(1); }
+        CHECK(said(ctx, "dp_optimize_sequence_gaps"));
+        ++n;
+    };
+    const float inf = __builtin_inff(), nan = __builtin_nanf("");
+    // well-formed: this link has no kernel unit, which the library says after every argument check
+    for (int variant = 0; variant < 9; ++variant) {
+        Case c;
+        if (variant == 1) c.null_holds_struct = true;                       // no dp_holds at all
+        if (variant == 2) { c.null_ar = true; c.z_tgt = true; }             // no predictor: the targets are frames->z_tgt
+        if (variant == 3) { c.terms.clear(); c.null_holds_struct = true; }  // n_terms = 0: the plain tracker loss
+        if (variant == 4) { c.with_trace = false; c.with_extra = false; c.with_skeleton = false; c.with_present = false; c.with_gap_trace = false; }
+        if (variant == 5) { c.max_hold = 0; c.decay = 1.f; }
+        if (variant == 6) { c.max_hold = DP_GAP_MAX_HOLD; c.decay = 1e-30f; }
+        if (variant == 7) { c.null_ar = true; c.z_tgt = true; c.holds.clear(); c.with_present = false; }
+        if (variant == 8) { c.order = DP_MAX_AR_ORDER; c.history = DP_MAX_AR_ORDER; }
+        CHECK(run(ctx, c) == DP_ERR_UNSUPPORTED);
+        CHECK(said(ctx, "dp_cons_gap.hip"));
+        ++n;
+    }
+    // dp_gaps' own refusals, in the header's order: each is reported before every later one's fault
+    { Case c; c.null_gaps = true; refused(c, "NULL"); }
+    { Case c; c.gaps_size = 16; c.max_hold = -1; refused(c, "dp_gaps.struct_size"); }   // a block of 16 bytes: only the size, reserved0, max_hold and decay exist
+    { Case c; c.gaps_size = 8; refused(c, "dp_gaps.struct_size"); }
+    { Case c; c.gaps_size = 5000; refused(c, "dp_gaps.struct_size"); }                  // (the block is sizeof(dp_gaps): nothing past the size word is read)
+    { Case c; c.gaps_reserved0 = 3u; c.max_hold = -1; refused(c, "reserved0"); }
+    { Case c; c.max_hold = -1; c.decay = 0.f; refused(c, "dp_gaps.max_hold"); }
+    { Case c; c.max_hold = DP_GAP_MAX_HOLD + 1; c.null_gap_state = true; refused(c, "dp_gaps.max_hold"); }
+    { Case c; c.decay = 0.f; c.null_gap_state = true; refused(c, "dp_gaps.decay"); }
+    { Case c; c.decay = -0.5f; refused(c, "dp_gaps.decay"); }
+    { Case c; c.decay = 1.5f; refused(c, "dp_gaps.decay"); }
+    { Case c; c.decay = inf; refused(c, "dp_gaps.decay"); }
+    { Case c; c.decay = nan; c.null_gap_state = true; refused(c, "dp_gaps.decay"); }
+    { Case c; c.null_gap_state = true; refused(c, "dp_gaps.state is NULL"); }
+    // the order around dp_gaps: everything dp_optimize_sequence_ar checks comes first, dp_latent_ar's own only when `ar` is given
+    { Case c; c.terms[0].joint_a = 22; c.max_hold = -1; refused(c, "term 0"); }
+    { Case c; c.holds_size = 12; c.max_hold = -1; refused(c, "dp_holds.struct_size"); }
+    { Case c; c.row_step1 = -4; c.max_hold = -1; refused(c, "row_step[1]"); }
+    { Case c; c.n_steps = 0; c.max_hold = -1; refused(c, "n_steps must be positive"); }
+    { Case c; c.lr = -1.f; c.max_hold = -1; refused(c, "Adam"); }
+    { Case c; c.ar_size = 12; c.max_hold = -1; refused(c, "dp_latent_ar.struct_size"); }
+    { Case c; c.order = 0; c.max_hold = -1; refused(c, "dp_latent_ar.order"); }
+    { Case c; c.z_tgt = true; c.max_hold = -1; refused(c, "z_tgt must be NULL"); }
+    { Case c; c.null_ar = true; c.max_hold = -1; refused(c, "NULL input array"); }       // without a predictor frames->z_tgt is required
+    { Case c; c.null_ar = true; c.z_tgt = true; c.max_hold = -1; refused(c, "dp_gaps.max_hold"); }
+    CHECK(dp_optimize_sequence_gaps(nullptr, 4, PTR, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DP_ERR_INVALID);
+    dp_destroy(ctx);
+    std::printf("gaps: %d calls, all checks held\n", n);
+    return 0;
+}
