@@ -257,6 +257,10 @@ class DpGaps(_Sized):
                 ("present", C.c_void_p), ("trace", C.c_void_p)]
 
 
+# every symbol include/dragposer_live.h declares (tests/test_live_abi.py)
+LIVE_SYMBOLS = ("dp_live_step",)
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -352,6 +356,7 @@ def load(path=None):
                                             C.POINTER(DpHolds), C.POINTER(DpLatentAR)] + _seq_tail
     lib.dp_optimize_sequence_gaps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
                                               C.POINTER(DpHolds), C.POINTER(DpLatentAR), C.POINTER(DpGaps)] + _seq_tail
+    lib.dp_live_step.argtypes = lib.dp_optimize_sequence_gaps.argtypes
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

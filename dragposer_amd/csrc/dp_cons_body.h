@@ -20,6 +20,10 @@
 // (dp_terms_gap_seq_kernel, dp_terms_gap_ar_seq_kernel, include/dragposer_gaps.h): `trk` is then a per-step value, the lane's code of the
 // step, decided from the joint's row of dp_gaps.state in global memory (dp_cons_gap.h).  The #if DP_CONS_GAP blocks are the only difference;
 // without DP_CONS_GAP the nine kernels above keep their instructions.
+// dp_cons_live.hip includes it twice more with DP_CONS_LIVE 1 on top of DP_CONS_GAP's five, without and with DP_CONS_AR (dp_live_kernel,
+// dp_live_ar_kernel, include/dragposer_live.h): the launch is one step, and the wave appends the step's row to the sequence's three history
+// buffers itself (dp_cons_live.h).  The #if DP_CONS_LIVE blocks are the only difference; without DP_CONS_LIVE the twelve kernels above keep
+// their instructions.
 {
     constexpr bool TBL = DP_CONS_TABLE;
 #if DP_CONS_SKEL
@@ -127,6 +131,9 @@
         for (int k = 0; k < MAX_AR_ORDER; ++k)
             if (k < a.r.order) hb[k * LAT + lane] = a.r.latent_buf[(f * a.r.history + (a.r.history - 1 - k)) * LAT + lane];
     wave_sync();
+#endif
+#if DP_CONS_LIVE // lane c < 27 + NH: column c of the row the step writes to hist_scratch -- NaN from a step refused as bad state
+    float hnew = nan;
 #endif
     for (int stp = 0; stp < a.q.n_steps; ++stp) { // ---- the step loop: frame stp of this sequence, row ft of every per-step array
     const long long ft = (long long)stp * NS + f;
@@ -793,6 +800,20 @@
                 }
                 for (int h = 0; h < NH; ++h) o[LAT + 3 + h] = PB[4 * a.q.height_joints[h] + 1] + gpn[1]; // y of (pos + the new global position)
             }
+#if DP_CONS_LIVE // the same row, a column per lane: lanes < 24 hold z; the displacement and the heights are lane 0's, handed over by v_readfirstlane
+            hnew = z;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float v = uni(dsp[k]);
+                hnew = lane == LAT + k ? v : hnew;
+            }
+#pragma unroll
+            for (int h = 0; h < DP_MAX_HEIGHT_JOINTS; ++h)
+                if (h < NH) {
+                    const float v = uni(PB[4 * a.q.height_joints[h] + 1] + gpn[1]);
+                    hnew = lane == LAT + 3 + h ? v : hnew;
+                }
+#endif
             if (jl) {
                 if (a.pose)
 #pragma unroll
@@ -975,6 +996,28 @@
     if (lane < LAT) a.z[f * LAT + lane] = zc;
     if (lane < 3) a.q.global_pos[f * 3 + lane] = lane == 0 ? gpc[0] : lane == 1 ? gpc[1] : gpc[2];
     if (lane < 4) a.q.global_rot[f * 4 + lane] = lane == 0 ? crc[0] : lane == 1 ? crc[1] : lane == 2 ? crc[2] : crc[3];
+#if DP_CONS_LIVE
+    // dp_sequence_history_kernel's work for this sequence after one step: lane c moves column c of the three buffers up by one row and puts
+    // the step's value in the last.  LIVE_CHUNK rows at a time, a chunk's loads before its stores; the next chunk reads only rows above every
+    // row written so far.  The column is this lane's alone and the sequence this wave's: no barrier, no fence, no atomic.
+    if (lane < LAT + 3 + NH) {
+        const int H = a.l.history;
+        float* col = a.l.latent_buf + f * H * LAT + lane;
+        int stride = LAT;
+        if (lane >= LAT + 3) { col = a.l.heights_buf + f * H * NH + (lane - LAT - 3); stride = NH; }
+        else if (lane >= LAT) { col = a.l.disp_buf + f * H * 3 + (lane - LAT); stride = 3; }
+        for (int t0 = 0; t0 + 1 < H; t0 += LIVE_CHUNK) {
+            float v[LIVE_CHUNK];
+#pragma unroll
+            for (int i = 0; i < LIVE_CHUNK; ++i) v[i] = t0 + i + 1 < H ? col[(long long)(t0 + i + 1) * stride] : 0.f;
+            asm volatile("" ::: "memory"); // (the chunk's loads are issued before its first store)
+#pragma unroll
+            for (int i = 0; i < LIVE_CHUNK; ++i)
+                if (t0 + i + 1 < H) col[(long long)(t0 + i) * stride] = v[i];
+        }
+        col[(long long)(H - 1) * stride] = hnew;
+    }
+#endif
 #else
     if (lane < LAT && a.z) a.z[f * LAT + lane] = pz ? nan : z;
     const bool nonfin = pz || __ballot(lane < LAT && !(fabsf(z) <= 3.0e38f)) != 0ull;

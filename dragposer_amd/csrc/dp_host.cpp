@@ -23,7 +23,8 @@
 #include "../../include/dragposer_holds.h"
 #include "../../include/dragposer_latent_ar.h"
 #include "../../include/dragposer_gaps.h"
-#include "dp_cons_gap.h"
+#include "../../include/dragposer_live.h"
+#include "dp_cons_live.h"
 #include "dp_host_rt.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -1343,6 +1344,8 @@ hipError_t dp_launch_terms_hold_seq(const dpcons::HoldSeqArgs* args, hipStream_t
 hipError_t dp_launch_terms_ar_seq(const dpcons::ArSeqArgs* args, hipStream_t stream) __attribute__((weak));     // (dp_cons_ar.hip, likewise)
 hipError_t dp_launch_terms_gap_seq(const dpcons::GapSeqArgs* args, hipStream_t stream) __attribute__((weak));    // (dp_cons_gap.hip, likewise)
 hipError_t dp_launch_terms_gap_ar_seq(const dpcons::GapArSeqArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_live(const dpcons::LiveSeqArgs* args, hipStream_t stream) __attribute__((weak));           // (dp_cons_live.hip, likewise)
+hipError_t dp_launch_live_ar(const dpcons::LiveArSeqArgs* args, hipStream_t stream) __attribute__((weak));
 #endif
 
 // include/dragposer_latent_ar.h: dp_latent_ar checked, after everything dp_optimize_sequence_holds checks, against the launch's frames and
@@ -1382,7 +1385,9 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
                                      const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream, const char* who, Own own,
                                      const dp_latent_ar* ar = nullptr, const dp_gaps* gaps = nullptr)
 {
-    constexpr bool GAP = std::is_same<A, dpcons::GapSeqArgs>::value, GAP_AR = std::is_same<A, dpcons::GapArSeqArgs>::value;
+    // (include/dragposer_live.h: the gap units' argument blocks and checks, the history append in the kernel instead of a second launch)
+    constexpr bool LIVE = std::is_same<A, dpcons::LiveSeqArgs>::value, LIVE_AR = std::is_same<A, dpcons::LiveArSeqArgs>::value;
+    constexpr bool GAP = std::is_same<A, dpcons::GapSeqArgs>::value || LIVE, GAP_AR = std::is_same<A, dpcons::GapArSeqArgs>::value || LIVE_AR;
     constexpr bool HOLDS = std::is_same<A, dpcons::HoldSeqArgs>::value, AR = std::is_same<A, dpcons::ArSeqArgs>::value || GAP_AR;
     dp_params p;
     if (int rc = take_params(ctx, p_in, p, who)) return rc;
@@ -1403,7 +1408,10 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
     (void)n_seq; (void)latent; (void)stream;
     return refuse_ref8(ctx, who);
 #else
-    if (GAP || GAP_AR) {
+    if (LIVE || LIVE_AR) {
+        if (!dp_launch_live || !dp_launch_live_ar)
+            return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_live.hip");
+    } else if (GAP || GAP_AR) {
         if (!dp_launch_terms_gap_seq || !dp_launch_terms_gap_ar_seq)
             return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_gap.hip");
     } else if (AR ? !dp_launch_terms_ar_seq : HOLDS ? !dp_launch_terms_hold_seq : (!dp_launch_cons_seq || !dp_launch_terms_seq))
@@ -1418,10 +1426,15 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
     fill_loop(a, p, true);
     a.beta1d = p.beta1; a.beta2d = p.beta2; a.lrd = p.lr;
     fill_sequence(a.q, ctx, fr, st, adj, out);
+    if constexpr (LIVE || LIVE_AR) {
+        a.l.latent_buf = st->latent_buf; a.l.disp_buf = st->disp_buf; a.l.heights_buf = st->heights_buf; a.l.history = st->history;
+    }
     {
         DEVICE_GUARD(ctx);
         hipError_t e;
         if constexpr (std::is_same<A, dpcons::SeqConsArgs>::value) e = dp_launch_cons_seq(&a, (hipStream_t)stream);
+        else if constexpr (LIVE) e = dp_launch_live(&a, (hipStream_t)stream);
+        else if constexpr (LIVE_AR) e = dp_launch_live_ar(&a, (hipStream_t)stream);
         else if constexpr (GAP) e = dp_launch_terms_gap_seq(&a, (hipStream_t)stream);
         else if constexpr (GAP_AR) e = dp_launch_terms_gap_ar_seq(&a, (hipStream_t)stream);
         else if constexpr (HOLDS) e = dp_launch_terms_hold_seq(&a, (hipStream_t)stream);
@@ -1429,6 +1442,7 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
         else e = dp_launch_terms_seq(&a, (hipStream_t)stream);
         if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
     }
+    if (LIVE || LIVE_AR) return DP_OK; // (the kernel has appended the step's row itself)
     return append_history(ctx, n_seq, fr, st, out, stream);
 #endif
 }
@@ -1576,6 +1590,31 @@ extern "C" int dp_optimize_sequence_gaps(dp_ctx* ctx, int n_seq, float* latent, 
             return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_gaps: n_sequences must be positive; NULL latent, frames, params, terms, gaps, state or results");
         if (r_in) return sequence_constrained_impl<dpcons::GapArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in, g_in);
         return sequence_constrained_impl<dpcons::GapSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, nullptr, g_in);
+    });
+}
+
+// include/dragposer_live.h: dp_optimize_sequence_gaps for one step, in one launch (A = dpcons::LiveArSeqArgs; `ar` NULL: dpcons::LiveSeqArgs)
+extern "C" int dp_live_step(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                            const dp_holds* h_in, const dp_latent_ar* r_in, const dp_gaps* g_in, const dp_skeleton_in* skel, const dp_seq_state* st,
+                            const dp_seq_step* adj, const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_live_step";
+    const auto own = [&](auto& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
+        if (h_in)
+            if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
+        dp_seq_extra e;
+        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
+        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
+        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
+        return DP_OK;
+    };
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !g_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_live_step: n_sequences must be positive; NULL latent, frames, params, terms, gaps, state or results");
+        if (fr->n_steps != 1) return fail(ctx, DP_ERR_INVALID, "dp_live_step: frames->n_steps is " + std::to_string(fr->n_steps) + ", a live step is one frame");
+        if (r_in) return sequence_constrained_impl<dpcons::LiveArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in, g_in);
+        return sequence_constrained_impl<dpcons::LiveSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, nullptr, g_in);
     });
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/dragposer.h"
+#include "../../include/dragposer_live.h"
 #include "../../include/dragposer_unity.h"
 #include "dp_host_rt.h"
 
@@ -69,6 +70,20 @@ struct DragPoser {
     // buffers, advanced by dp_sequence_advance; the temporal target buffer [window + 1][24]
     void* d_state = nullptr;
     void* d_target = nullptr;
+    // the additions of include/dragposer_unity.h (terms, holds, gaps, the latent AR predictor): while none is configured drag_pose() is the plain
+    // launch above; once any is, a frame is dp_live_step.  Their device state -- hold state, gap state, coefficients, bias -- is one block
+    bool live = false;
+    std::vector<dp_term> terms;
+    int up_axis = 1;
+    std::vector<dp_hold> holds;
+    int gap_max_hold = 0;    // max_hold 0, decay 1 until drag_poser_set_gaps: an absent sample leaves the loss at once
+    float gap_decay = 1.f;
+    int ar_order = 0;
+    void* d_live = nullptr;
+    bool two_launch = false; // drag_poser_debug_two_launch (tools/time_live.py): the same frame as dp_optimize_sequence_gaps, the history in a second launch
+    int last_status = 0;
+    unsigned char codes[NJ] = {0};
+    float hold_rows[DP_MAX_HOLDS * 4] = {0};
 
     int fail(const std::string& m) { err = m; std::fprintf(stderr, "[DragPoserDLL] %s\n", m.c_str()); return -1; }
 };
@@ -77,12 +92,16 @@ namespace {
 
 // floats per frame in the staging blocks
 constexpr int IN_Z0 = 0, IN_ZT = 24, IN_ROT = 48, IN_TP = 52, IN_TR = IN_TP + NJ * 3, IN_W = IN_TR + NJ * 9, IN_TRK = IN_W + NJ * 2,
-              IN_FLOATS = IN_TRK + 8; // tracked: 22 bytes in 8 floats
+              IN_FLOATS = IN_TRK + 8, // tracked: 22 bytes in 8 floats
+              IN_PRS = IN_FLOATS, IN_LIVE_FLOATS = IN_PRS + 8; // a live frame's `present`: 22 bytes in 8 floats
 constexpr int HIST = 60, NHGT = 6; // drag_pose.py:37-41, run_drag.py:153
 constexpr int ST_POS = 0, ST_ROT = 4, ST_LAT = 8, ST_DISP = ST_LAT + HIST * LAT, ST_HGT = ST_DISP + HIST * 3, ST_POSE = ST_HGT + HIST * NHGT,
               ST_GPOS = ST_POSE + 88, ST_FLOATS = ST_GPOS + 4;
 constexpr int OUT_Z = 0, OUT_ZPRE = 24, OUT_POSE = 48, OUT_DISP = 136, OUT_WD = 140, OUT_WR = 144, OUT_POS = 148, OUT_LOSS = OUT_POS + NJ * 3,
-              OUT_ITERS = OUT_LOSS + 4, OUT_FLOATS = OUT_ITERS + 4;
+              OUT_ITERS = OUT_LOSS + 4, OUT_STATUS = OUT_ITERS + 1, OUT_FLOATS = OUT_ITERS + 4,
+              OUT_CODES = OUT_FLOATS, OUT_HOLD = OUT_CODES + 6, OUT_LIVE_FLOATS = OUT_HOLD + DP_MAX_HOLDS * 4; // a live frame's 22 codes (in 6 floats) and hold rows
+constexpr int LV_HOLD = 0, LV_GAP = LV_HOLD + DP_MAX_HOLDS * 4, LV_COEF = LV_GAP + NJ * DP_GAP_STATE_FLOATS, LV_BIAS = LV_COEF + DP_MAX_AR_ORDER * LAT * LAT,
+              LV_FLOATS = LV_BIAS + LAT; // the d_live block
 
 bool parse_bvh_skeleton(const std::string& path, std::vector<int>& parents, std::vector<float>& offsets, std::string& err)
 {
@@ -125,20 +144,32 @@ bool load_bin(const std::string& path, std::map<std::string, Tensor>& out, std::
 {
     std::ifstream f(path, std::ios::binary);
     if (!f) { err = "cannot open " + path + " (export it with tools/export_model_bin.py)"; return false; }
-    char magic[4];
+    f.seekg(0, std::ios::end);
+    const unsigned long long size = (unsigned long long)f.tellg();
+    f.seekg(0, std::ios::beg);
+    // nothing is sized by a length the file states before that length is held against the bytes the file still has
+    const auto left = [&]() -> unsigned long long { const long long at = (long long)f.tellg(); return at < 0 ? 0ull : size - (unsigned long long)at; };
+    char magic[4] = {0, 0, 0, 0};
     unsigned n = 0;
     f.read(magic, 4); f.read((char*)&n, 4);
-    if (std::memcmp(magic, "DPM1", 4) != 0) { err = path + ": not a DPM1 model file"; return false; }
+    if (!f || std::memcmp(magic, "DPM1", 4) != 0) { err = path + ": not a DPM1 model file"; return false; }
     for (unsigned i = 0; i < n && f; ++i) {
         unsigned len = 0, nd = 0;
         f.read((char*)&len, 4);
+        if (!f || len > left()) { err = path + ": truncated"; return false; }
         std::string name(len, '\0');
         f.read(&name[0], len);
         f.read((char*)&nd, 4);
+        if (!f || 4ull * nd > left()) { err = path + ": truncated"; return false; }
         Tensor t;
         t.dims.resize(nd);
-        size_t cnt = 1;
-        for (unsigned d = 0; d < nd; ++d) { f.read((char*)&t.dims[d], 4); cnt *= t.dims[d]; }
+        unsigned long long cnt = 1;
+        for (unsigned d = 0; d < nd; ++d) {
+            f.read((char*)&t.dims[d], 4);
+            if (t.dims[d] != 0 && cnt > size / t.dims[d]) { err = path + ": truncated"; return false; } // (more elements than the file has bytes)
+            cnt *= t.dims[d];
+        }
+        if (!f || cnt * sizeof(float) > left()) { err = path + ": truncated"; return false; }
         t.data.resize(cnt);
         f.read((char*)t.data.data(), cnt * sizeof(float));
         out[name] = std::move(t);
@@ -192,6 +223,25 @@ dp_seq_state seq_state(DragPoser* d)
     return s;
 }
 
+// the hold state [1][n][4] and / or the gap state [1][22][16], zeroed (nothing latched, nothing held), with their host mirrors
+bool zero_live_state(DragPoser* d, bool hold, bool gap)
+{
+    if (!d->ctx || !d->d_live) return true;
+    const std::vector<float> zeros(LV_COEF, 0.f);
+    float* lv = (float*)d->d_live;
+    bool ok = true;
+    if (hold) {
+        std::memset(d->hold_rows, 0, sizeof(d->hold_rows));
+        ok = ok && dp_io_upload(d->ctx, lv + LV_HOLD, zeros.data(), DP_MAX_HOLDS * 4 * sizeof(float), nullptr) == DP_OK &&
+             dp_io_upload(d->ctx, (float*)d->d_out + OUT_HOLD, zeros.data(), DP_MAX_HOLDS * 4 * sizeof(float), nullptr) == DP_OK;
+    }
+    if (gap) {
+        std::memset(d->codes, 0, sizeof(d->codes));
+        ok = ok && dp_io_upload(d->ctx, lv + LV_GAP, zeros.data(), NJ * DP_GAP_STATE_FLOATS * sizeof(float), nullptr) == DP_OK;
+    }
+    return ok && dp_stream_sync(d->ctx, nullptr) == DP_OK;
+}
+
 // device state as DragPose.set_initial_pose leaves it (drag_pose.py:47-64): history filled with the initial latent,
 // zero displacements, the initial heights (the Unity path passes zeros, run_drag.py:93)
 bool reset_device_state(DragPoser* d)
@@ -201,6 +251,7 @@ bool reset_device_state(DragPoser* d)
     st[ST_ROT] = d->cur_rot.w; st[ST_ROT + 1] = d->cur_rot.x; st[ST_ROT + 2] = d->cur_rot.y; st[ST_ROT + 3] = d->cur_rot.z;
     for (int t = 0; t < HIST; ++t) std::memcpy(&st[ST_LAT + t * LAT], d->latent, sizeof(d->latent));
     d->current_index = 0;
+    if (!zero_live_state(d, true, true)) return false;
     return dp_io_upload(d->ctx, d->d_state, st.data(), st.size() * sizeof(float), nullptr) == DP_OK &&
            dp_io_upload(d->ctx, (float*)d->d_out + OUT_Z, d->latent, sizeof(d->latent), nullptr) == DP_OK && // the latent is device-resident (in/out of every frame)
            dp_stream_sync(d->ctx, nullptr) == DP_OK;
@@ -306,7 +357,7 @@ void load_models(DragPoser* d, char* modelPath)
     m.parents = d->parents.data(); m.offsets = d->offsets.data();
     m.weight_dtype = DP_WEIGHTS_FP32;
     if (d->ctx) { // loaded before: release the previous context and its device buffers
-        for (void** p : {&d->d_in, &d->d_out, &d->d_state, &d->d_target}) { if (*p) dp_io_free(d->ctx, *p); *p = nullptr; }
+        for (void** p : {&d->d_in, &d->d_out, &d->d_state, &d->d_target, &d->d_live}) { if (*p) dp_io_free(d->ctx, *p); *p = nullptr; }
         for (float** p : {&d->h_in, &d->h_out}) { if (*p) dp_io_free_host(d->ctx, *p); *p = nullptr; }
         if (d->temporal) dp_temporal_destroy(d->temporal);
         d->temporal = nullptr;
@@ -317,13 +368,22 @@ void load_models(DragPoser* d, char* modelPath)
         // has to call init_drag_model again before the next drag_pose, and the temporal window restarts
         d->initialised = false;
         d->current_index = 0;
+        // ... and so are the additions' device state and coefficients: terms, holds, gaps and the predictor are configured anew
+        d->live = false; d->terms.clear(); d->holds.clear(); d->up_axis = 1; d->gap_max_hold = 0; d->gap_decay = 1.f; d->ar_order = 0;
     }
     if (dp_create(&d->ctx, &m, 0) != DP_OK) { d->fail(std::string("dp_create: ") + dp_last_error(nullptr)); return; }
-    if (dp_io_alloc_host(d->ctx, IN_FLOATS * sizeof(float), (void**)&d->h_in) != DP_OK || dp_io_alloc_host(d->ctx, OUT_FLOATS * sizeof(float), (void**)&d->h_out) != DP_OK ||
-        dp_io_alloc(d->ctx, IN_FLOATS * sizeof(float), &d->d_in) != DP_OK || dp_io_alloc(d->ctx, OUT_FLOATS * sizeof(float), &d->d_out) != DP_OK ||
-        dp_io_alloc(d->ctx, ST_FLOATS * sizeof(float), &d->d_state) != DP_OK) {
+    if (dp_io_alloc_host(d->ctx, IN_LIVE_FLOATS * sizeof(float), (void**)&d->h_in) != DP_OK || dp_io_alloc_host(d->ctx, OUT_LIVE_FLOATS * sizeof(float), (void**)&d->h_out) != DP_OK ||
+        dp_io_alloc(d->ctx, IN_LIVE_FLOATS * sizeof(float), &d->d_in) != DP_OK || dp_io_alloc(d->ctx, OUT_LIVE_FLOATS * sizeof(float), &d->d_out) != DP_OK ||
+        dp_io_alloc(d->ctx, ST_FLOATS * sizeof(float), &d->d_state) != DP_OK || dp_io_alloc(d->ctx, LV_FLOATS * sizeof(float), &d->d_live) != DP_OK) {
         d->fail(std::string("device buffers: ") + dp_last_error(d->ctx));
         return;
+    }
+    {
+        const std::vector<float> zeros(LV_FLOATS, 0.f);
+        if (dp_io_upload(d->ctx, d->d_live, zeros.data(), zeros.size() * sizeof(float), nullptr) != DP_OK || !zero_live_state(d, true, true)) {
+            d->fail(std::string("device buffers: ") + dp_last_error(d->ctx));
+            return;
+        }
     }
     // the temporal predictor is optional: without temporal.bin the plugin runs with the pull term off (and says so)
     const std::string tpath = std::string(modelPath) + "/temporal.bin";
@@ -367,7 +427,7 @@ void set_lambdas(DragPoser* d, float lambdaRot, float lambdaTemporal, int tempor
     if (!d) return;
     d->lambda_rot = lambdaRot; d->lambda_tmp = lambdaTemporal; d->window = temporalFutureWindow;
     d->err.clear();
-    if (lambdaTemporal != 0.f && !d->temporal) {
+    if (lambdaTemporal != 0.f && !d->temporal && d->ar_order == 0) {
         // The reference runs its temporal Transformer here (drag_pose.py:234-294).  Without <modelPath>/temporal.bin this
         // plugin has none: the call is accepted, the pull term stays off, and the difference is REPORTED through
         // drag_poser_last_error (the reference ABI has no return codes) -- and once on stderr.
@@ -389,7 +449,7 @@ void set_global_pos(DragPoser* d, dp_float3 p)
         d->fail(std::string("set_global_pos: ") + dp_last_error(d->ctx));
 }
 
-void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quaternion* resultPose, dp_float3* resultGlobalPos)
+void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, const unsigned char* present, dp_quaternion* resultPose, dp_float3* resultGlobalPos)
 { // run_drag.py:126-176 around DragPose.run with joint_adjustment_indices=None
     if (!d || !tp || !tq || !resultPose || !resultGlobalPos) return;
     d->err.clear();
@@ -400,7 +460,9 @@ void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quate
         return;
     }
     float* in = d->h_in;
-    std::memset(in, 0, IN_FLOATS * sizeof(float));
+    const bool live = d->live;
+    if (present && !live) { d->fail("drag_pose_present: `present` belongs to the gaps: configure terms, holds, gaps or the latent AR predictor first"); return; }
+    std::memset(in, 0, IN_LIVE_FLOATS * sizeof(float));
     std::memcpy(in + IN_Z0, d->latent, sizeof(d->latent)); // (the staged z_tgt stays 0: used when the pull term is off)
     in[IN_ROT] = d->cur_rot.w; in[IN_ROT + 1] = d->cur_rot.x; in[IN_ROT + 2] = d->cur_rot.y; in[IN_ROT + 3] = d->cur_rot.z;
     unsigned char* trk = (unsigned char*)(in + IN_TRK);
@@ -410,6 +472,11 @@ void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quate
         qmat({tq[e].w, tq[e].x, tq[e].y, tq[e].z}, in + IN_TR + 9 * j);
         in[IN_W + 2 * j] = d->weights[2 * e]; in[IN_W + 2 * j + 1] = d->weights[2 * e + 1];
         trk[j] = 1;
+    }
+    if (present) { // scattered through the mask to [1][1][22]; a joint outside the mask is never read
+        unsigned char* prs = (unsigned char*)(in + IN_PRS);
+        std::memset(prs, 1, NJ);
+        for (int e = 0; e < nEE; ++e) prs[d->mask_idx[e]] = present[e] != 0 ? 1 : 0;
     }
     float* di = (float*)d->d_in;
     float* dout = (float*)d->d_out;
@@ -425,7 +492,7 @@ void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quate
     // and restarted the window at switch-on: a different z_tgt for up to window - 1 frames; tests/golden/sequ_switch.npz pins the
     // reference's behaviour).  Where it still departs: a window CHANGED mid-window restarts the window (below).
     const bool have_predictor = d->temporal != nullptr;
-    const bool pull = have_predictor && d->lambda_tmp != 0.f;
+    const bool pull = (have_predictor || (live && d->ar_order > 0)) && d->lambda_tmp != 0.f;
     dp_seq_state st = seq_state(d);
     // (the sequence's global position / rotation live on the device: reset_device_state, set_global_pos; the staged
     //  cur_rot below is what dp_optimize took and is kept for reference)
@@ -469,15 +536,33 @@ void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quate
     // the returned pose, the global position and rotation after the step, the iteration count
     dp_seq_results r = DP_SEQ_RESULTS_INIT;
     r.pose_ret = dout + OUT_POSE; r.pos_ret = dout + OUT_WD; r.world_rot = dout + OUT_WR; r.iters = (int*)(dout + OUT_ITERS); r.loss = dout + OUT_LOSS;
+    r.status = (int*)(dout + OUT_STATUS);
     r.hist_scratch = dout + OUT_POS; // (LAT + 3 + NHGT floats of scratch: the block's joint-position area is unused on this path)
     static_assert(NJ * 3 >= LAT + 3 + NHGT, "the history scratch row fits");
     dp_seq_step step;
     std::memset(&step, 0, sizeof(step));
     step.adjust_joint = -1; step.adjust_target_joint = -1;
     float* out = d->h_out;
-    if (dp_io_upload(d->ctx, di, in, IN_FLOATS * sizeof(float), nullptr) != DP_OK ||
-        dp_optimize_sequence(d->ctx, 1, dout + OUT_Z, &fr, &p, &st, &step, &r, nullptr) != DP_OK ||
-        dp_io_download(d->ctx, out, dout, OUT_FLOATS * sizeof(float), nullptr) != DP_OK || dp_stream_sync(d->ctx, nullptr) != DP_OK) {
+    // the additions (include/dragposer_unity.h): the same frame as one dp_live_step -- the table (or an empty one), the holds, the predictor
+    // (the targets' one source when configured: frames->z_tgt NULL) and the gaps; status, codes and hold rows land in the output block
+    float* lv = (float*)d->d_live;
+    dp_terms ts = DP_TERMS_INIT;
+    ts.n_terms = (int)d->terms.size(); ts.up_axis = d->up_axis; ts.terms = d->terms.data();
+    dp_holds hs = DP_HOLDS_INIT;
+    hs.n_holds = (int)d->holds.size(); hs.holds = d->holds.data(); hs.state = lv + LV_HOLD; hs.trace = dout + OUT_HOLD;
+    dp_latent_ar ar = DP_LATENT_AR_INIT;
+    ar.order = d->ar_order; ar.coeffs = lv + LV_COEF; ar.bias = lv + LV_BIAS;
+    dp_gaps gs = DP_GAPS_INIT;
+    gs.max_hold = d->gap_max_hold; gs.decay = d->gap_decay; gs.state = lv + LV_GAP;
+    gs.present = present ? (const unsigned char*)(di + IN_PRS) : nullptr; gs.trace = (unsigned char*)(dout + OUT_CODES);
+    if (live && d->ar_order > 0) fr.z_tgt = nullptr;
+    const auto launch = [&]() -> int {
+        if (!live) return dp_optimize_sequence(d->ctx, 1, dout + OUT_Z, &fr, &p, &st, &step, &r, nullptr);
+        return (d->two_launch ? dp_optimize_sequence_gaps : dp_live_step)(d->ctx, 1, dout + OUT_Z, &fr, &p, &ts, hs.n_holds > 0 ? &hs : nullptr,
+                                                                          d->ar_order > 0 ? &ar : nullptr, &gs, nullptr, &st, &step, &r, nullptr, nullptr);
+    };
+    if (dp_io_upload(d->ctx, di, in, (live ? IN_LIVE_FLOATS : IN_FLOATS) * sizeof(float), nullptr) != DP_OK || launch() != DP_OK ||
+        dp_io_download(d->ctx, out, dout, (live ? OUT_LIVE_FLOATS : OUT_FLOATS) * sizeof(float), nullptr) != DP_OK || dp_stream_sync(d->ctx, nullptr) != DP_OK) {
         const std::string why = dp_last_error(d->ctx);
         dp_stream_sync(d->ctx, nullptr); // h_in / h_out are page-locked: an upload or download queued before the failure is an asynchronous DMA, and
                                          // the next drag_pose() rewrites h_in -- nothing may still be in flight when this one returns
@@ -489,6 +574,11 @@ void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quate
     for (int a = 0; a < 3; ++a) d->cur_pos[a] = out[OUT_WD + a];
     d->cur_rot = {out[OUT_WR], out[OUT_WR + 1], out[OUT_WR + 2], out[OUT_WR + 3]};
     std::memcpy(&d->last_iters, out + OUT_ITERS, sizeof(int));
+    std::memcpy(&d->last_status, out + OUT_STATUS, sizeof(int));
+    if (live) {
+        std::memcpy(d->codes, out + OUT_CODES, sizeof(d->codes));
+        std::memcpy(d->hold_rows, out + OUT_HOLD, sizeof(d->hold_rows));
+    }
     const float* ret = out + OUT_POSE;
     d->current_index = d->window <= 0 ? 0 : (d->current_index + 1) % d->window; // drag_pose.py:399-402
     // result (run_drag.py:161-176): de-normalised root-space quaternions with the world root -> parent-local rotations
@@ -507,11 +597,102 @@ void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quate
     resultGlobalPos[0] = {d->cur_pos[0], d->cur_pos[1], d->cur_pos[2]};
 }
 
+// ---- the additions of include/dragposer_unity.h.  Each checks its arguments first, then asks for load_models (the state is on the device).
+void set_terms(DragPoser* d, int nTerms, const dp_term* terms, int upAxis)
+{
+    if (!d) return;
+    d->err.clear();
+    if (nTerms < 0 || nTerms > DP_MAX_TERMS) { d->fail("drag_poser_set_terms: nTerms " + std::to_string(nTerms) + " outside 0.." + std::to_string(DP_MAX_TERMS)); return; }
+    if (upAxis < 0 || upAxis > 2) { d->fail("drag_poser_set_terms: upAxis " + std::to_string(upAxis) + " outside 0..2"); return; }
+    if (nTerms > 0 && !terms) { d->fail("drag_poser_set_terms: NULL terms with nTerms > 0"); return; }
+    for (int k = 0; k < nTerms; ++k)
+        if (terms[k].per_frame) { d->fail("drag_poser_set_terms: term " + std::to_string(k) + ": per_frame must be NULL (a device pointer has no meaning across this ABI)"); return; }
+    if (!d->ctx) { d->fail("drag_poser_set_terms: call load_models first"); return; }
+    for (const dp_hold& h : d->holds)
+        if (h.term >= nTerms) { d->fail("drag_poser_set_terms: a hold refers to term " + std::to_string(h.term) + ": call drag_poser_set_holds(0) first"); return; }
+    d->terms.assign(terms, terms + nTerms);
+    d->up_axis = upAxis;
+    d->live = true; // (0 terms clears the table; the frame stays a live step, with an empty one)
+}
+
+void set_holds(DragPoser* d, int nHolds, const dp_hold* holds)
+{
+    if (!d) return;
+    d->err.clear();
+    if (nHolds < 0 || nHolds > DP_MAX_HOLDS) { d->fail("drag_poser_set_holds: nHolds " + std::to_string(nHolds) + " outside 0.." + std::to_string(DP_MAX_HOLDS)); return; }
+    if (nHolds > 0 && !holds) { d->fail("drag_poser_set_holds: NULL holds with nHolds > 0"); return; }
+    if (!d->ctx) { d->fail("drag_poser_set_holds: call load_models first"); return; }
+    for (int h = 0; h < nHolds; ++h)
+        if (holds[h].term < 0 || holds[h].term >= (int)d->terms.size()) {
+            d->fail("drag_poser_set_holds: hold " + std::to_string(h) + ": term " + std::to_string(holds[h].term) + " outside the table of " + std::to_string(d->terms.size()) +
+                    " (drag_poser_set_terms first)");
+            return;
+        }
+    if (!zero_live_state(d, true, false)) { d->fail(std::string("drag_poser_set_holds: ") + dp_last_error(d->ctx)); return; }
+    d->holds.assign(holds, holds + nHolds);
+    d->live = true;
+}
+
+void set_gaps(DragPoser* d, int maxHold, float decay)
+{
+    if (!d) return;
+    d->err.clear();
+    if (maxHold < 0 || maxHold > DP_GAP_MAX_HOLD) { d->fail("drag_poser_set_gaps: maxHold " + std::to_string(maxHold) + " outside 0.." + std::to_string(DP_GAP_MAX_HOLD)); return; }
+    if (!(decay > 0.f && decay <= 1.f)) { d->fail("drag_poser_set_gaps: decay must be a finite number in (0, 1]"); return; }
+    if (!d->ctx) { d->fail("drag_poser_set_gaps: call load_models first"); return; }
+    if (!zero_live_state(d, false, true)) { d->fail(std::string("drag_poser_set_gaps: ") + dp_last_error(d->ctx)); return; }
+    d->gap_max_hold = maxHold; d->gap_decay = decay;
+    d->live = true;
+}
+
+void set_latent_ar(DragPoser* d, int order, const float* coeffs, const float* bias, const char* who = "drag_poser_set_latent_ar")
+{
+    if (!d) return;
+    d->err.clear();
+    const std::string nm = who;
+    if (order < 0 || order > DP_MAX_AR_ORDER) { d->fail(nm + ": order " + std::to_string(order) + " outside 0.." + std::to_string(DP_MAX_AR_ORDER)); return; }
+    if (order > 0 && (!coeffs || !bias)) { d->fail(nm + ": NULL coeffs or bias"); return; }
+    if (!d->ctx) { d->fail(nm + ": call load_models first"); return; }
+    if (order > 0 && d->temporal) { d->fail(nm + ": a temporal predictor (temporal.bin) is loaded: the targets have one source"); return; }
+    if (order > 0) {
+        float* lv = (float*)d->d_live;
+        if (dp_io_upload(d->ctx, lv + LV_COEF, coeffs, (size_t)order * LAT * LAT * sizeof(float), nullptr) != DP_OK ||
+            dp_io_upload(d->ctx, lv + LV_BIAS, bias, LAT * sizeof(float), nullptr) != DP_OK || dp_stream_sync(d->ctx, nullptr) != DP_OK) {
+            const std::string why = dp_last_error(d->ctx);
+            dp_stream_sync(d->ctx, nullptr); // (the caller's arrays may go away when this returns)
+            d->ar_order = 0;                 // (the device's coefficients are no longer one model's)
+            d->fail(nm + ": " + why);
+            return;
+        }
+    }
+    d->ar_order = order;
+    d->live = true;
+}
+
+void load_latent_ar(DragPoser* d, const char* path)
+{ // latent_ar.bin (DPM1, tools/export_latent_ar_bin.py): "coeffs" [order][24][24] and "bias" [24]
+    if (!d || !path) return;
+    d->err.clear();
+    const std::string nm = "drag_poser_load_latent_ar";
+    std::map<std::string, Tensor> T;
+    std::string e;
+    if (!load_bin(path, T, e)) { d->fail(nm + ": " + e); return; }
+    // count, rank and dims before any pointer is formed
+    auto c = T.find("coeffs"), b = T.find("bias");
+    if (T.size() != 2 || c == T.end() || b == T.end()) { d->fail(nm + ": " + path + ": expected the two tensors coeffs and bias"); return; }
+    const Tensor &tc = c->second, &tb = b->second;
+    if (tc.dims.size() != 3 || tb.dims.size() != 1) { d->fail(nm + ": " + path + ": coeffs must have rank 3 and bias rank 1"); return; }
+    if (tc.dims[1] != (unsigned)LAT || tc.dims[2] != (unsigned)LAT || tb.dims[0] != (unsigned)LAT) { d->fail(nm + ": " + path + ": coeffs must be [order][24][24] and bias [24]"); return; }
+    if (tc.dims[0] < 1 || tc.dims[0] > (unsigned)DP_MAX_AR_ORDER) { d->fail(nm + ": " + path + ": order " + std::to_string(tc.dims[0]) + " outside 1.." + std::to_string(DP_MAX_AR_ORDER)); return; }
+    if (tc.data.size() != (size_t)tc.dims[0] * LAT * LAT || tb.data.size() != (size_t)LAT) { d->fail(nm + ": " + path + ": truncated"); return; }
+    set_latent_ar(d, (int)tc.dims[0], tc.data.data(), tb.data.data(), "drag_poser_load_latent_ar");
+}
+
 void destroy_drag_poser(DragPoser* d)
 {
     if (!d) return;
     if (d->ctx) {
-        for (void* p : {d->d_in, d->d_out, d->d_state, d->d_target}) if (p) dp_io_free(d->ctx, p);
+        for (void* p : {d->d_in, d->d_out, d->d_state, d->d_target, d->d_live}) if (p) dp_io_free(d->ctx, p);
         for (float* p : {d->h_in, d->h_out}) if (p) dp_io_free_host(d->ctx, p);
         if (d->temporal) dp_temporal_destroy(d->temporal);
         dp_destroy(d->ctx);
@@ -549,7 +730,18 @@ void init_drag_model(DragPoser* d, dp_float3 pos, dp_quaternion rot) { guarded(d
 void set_optim_params(DragPoser* d, float stopEpsPos, float stopEpsRot, int maxIter, float lr) { guarded(d, "set_optim_params", [&] { impl::set_optim_params(d, stopEpsPos, stopEpsRot, maxIter, lr); }); }
 void set_lambdas(DragPoser* d, float lambdaRot, float lambdaTemporal, int temporalFutureWindow) { guarded(d, "set_lambdas", [&] { impl::set_lambdas(d, lambdaRot, lambdaTemporal, temporalFutureWindow); }); }
 void set_global_pos(DragPoser* d, dp_float3 p) { guarded(d, "set_global_pos", [&] { impl::set_global_pos(d, p); }); }
-void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quaternion* resultPose, dp_float3* resultGlobalPos) { guarded(d, "drag_pose", [&] { impl::drag_pose(d, nEE, tp, tq, resultPose, resultGlobalPos); }); }
+void drag_pose(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, dp_quaternion* resultPose, dp_float3* resultGlobalPos) { guarded(d, "drag_pose", [&] { impl::drag_pose(d, nEE, tp, tq, nullptr, resultPose, resultGlobalPos); }); }
+void drag_pose_present(DragPoser* d, int nEE, dp_float3* tp, dp_quaternion* tq, const unsigned char* present, dp_quaternion* resultPose, dp_float3* resultGlobalPos) { guarded(d, "drag_pose_present", [&] { impl::drag_pose(d, nEE, tp, tq, present, resultPose, resultGlobalPos); }); }
+void drag_poser_set_terms(DragPoser* d, int nTerms, const dp_term* terms, int upAxis) { guarded(d, "drag_poser_set_terms", [&] { impl::set_terms(d, nTerms, terms, upAxis); }); }
+void drag_poser_set_holds(DragPoser* d, int nHolds, const dp_hold* holds) { guarded(d, "drag_poser_set_holds", [&] { impl::set_holds(d, nHolds, holds); }); }
+void drag_poser_set_gaps(DragPoser* d, int maxHold, float decay) { guarded(d, "drag_poser_set_gaps", [&] { impl::set_gaps(d, maxHold, decay); }); }
+void drag_poser_set_latent_ar(DragPoser* d, int order, const float* coeffs, const float* bias) { guarded(d, "drag_poser_set_latent_ar", [&] { impl::set_latent_ar(d, order, coeffs, bias); }); }
+void drag_poser_load_latent_ar(DragPoser* d, char* path) { guarded(d, "drag_poser_load_latent_ar", [&] { impl::load_latent_ar(d, path); }); }
+// private measuring hook (not in include/dragposer_unity.h; tools/time_live.py): the live frame through the two-launch call, the same bits
+void drag_poser_debug_two_launch(DragPoser* d, int on) { if (d) d->two_launch = on != 0; }
+int drag_poser_last_status(const DragPoser* d) { return d ? d->last_status : 0; }
+void drag_poser_get_gap_codes(const DragPoser* d, unsigned char* codes22) { if (d && codes22) std::memcpy(codes22, d->codes, sizeof(d->codes)); }
+void drag_poser_get_hold_state(const DragPoser* d, float* state) { if (d && state) std::memcpy(state, d->hold_rows, d->holds.size() * 4 * sizeof(float)); }
 void destroy_drag_poser(DragPoser* d) { guarded(d, "destroy_drag_poser", [&] { impl::destroy_drag_poser(d); }); }
 
 } // extern "C"

@@ -423,7 +423,7 @@ class DragPose:
             stop_eps_rot=1e-2, max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1,
             temporal_future_window=60, height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None,
             joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None, holds=None, ar=None,
-            gaps=None, present=None):
+            gaps=None, present=None, live=False):
         """One frame for every sequence: one launch for the optimise loop and the epilogue, one for the history buffers, plus two
         row scatters of the targets.  `out_pose` [S,88] / `out_pos` [S,3]: optional caller storage for the returned tensors.
         `constraints` (a dragposer_amd.Constraints): the reference's extra loss terms (drag_pose.py:129-183) join the loss -- the frame
@@ -436,6 +436,9 @@ class DragPose:
         launch of run_frames(ar=), with everything that call takes (`offsets` together with `terms` included); frame by frame its bits.
         `gaps` (a dragposer_amd.Gaps) with `present` [S,E] or None: likewise a one-step run_frames(gaps=), with or without `ar`; `last`
         then holds the frame's `gap_trace` [S,22].
+        `live` (with any of `constraints` / `terms` / `holds` / `ar` / `gaps`): that frame as ONE launch, dp_live_step
+        (include/dragposer_live.h) -- the gap unit appends the frame's row to the history buffers itself; without `gaps` it runs with
+        Gaps(0, 1.0), under which an absent sample leaves the loss at once.  The bits of the same call without `live`.
         `offsets`: the performer's bone offsets, as the reference takes them on every call (drag_pose.py:202) -- [22,3] for every sequence
         or [S,22,3] one per sequence.  The context's own skeleton (or None) runs the launches above unchanged; any other runs the same frame
         with those bones (dp_optimize_sequence_skeleton, include/dragposer_skeleton.h), not together with `constraints` / `terms`: this
@@ -443,6 +446,13 @@ class DragPose:
         the same object frame after frame costs one host synchronisation in all (DragPose._skeleton)."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
+        if live:
+            if constraints is None and terms is None and holds is None and ar is None and gaps is None:
+                raise ValueError("DragPose.run: live= goes with constraints=, terms=, holds=, ar= or gaps=")
+            if gaps is None:
+                from .gaps import Gaps
+
+                gaps = Gaps(0, 1.0)
         if gaps is None and present is not None:
             raise ValueError("DragPose.run: present belongs to gaps=")
         if ar is not None or gaps is not None:
@@ -451,12 +461,16 @@ class DragPose:
             if gaps is not None:
                 gaps.check()
                 present = torch.as_tensor(present, device=self.device).reshape(1, self.S, -1) if present is not None else None
-            return self._run_ar(target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose,
-                                dict(offsets=offsets, stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, max_iter=max_iter,
-                                     min_loss_incr=min_loss_incr, learning_rate=learning_rate, lambda_rot=lambda_rot, lambda_temporal=lambda_temporal,
-                                     temporal_future_window=temporal_future_window, height_indices=height_indices,
-                                     joint_adjustment_indices=joint_adjustment_indices, joint_adjustment_weight=joint_adjustment_weight,
-                                     constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, present=present))
+            kw_frame = dict(offsets=offsets, stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, max_iter=max_iter,
+                            min_loss_incr=min_loss_incr, learning_rate=learning_rate, lambda_rot=lambda_rot, lambda_temporal=lambda_temporal,
+                            temporal_future_window=temporal_future_window, height_indices=height_indices,
+                            joint_adjustment_indices=joint_adjustment_indices, joint_adjustment_weight=joint_adjustment_weight,
+                            constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, present=present)
+            self.opt.live_step = bool(live)  # (run_frames of this one frame: optimize_sequence launches dp_live_step)
+            try:
+                return self._run_ar(target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose, kw_frame)
+            finally:
+                self.opt.live_step = False
         self._holds(holds, terms, constraints, "run")
         skel = self._skeleton(offsets)
         if skel is not None and (constraints is not None or terms is not None):

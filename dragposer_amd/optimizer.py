@@ -77,6 +77,7 @@ class LatentOptimizer:
 
     def __init__(self, model_path=DEFAULT_MODEL, device="cuda:0", weight_dtype="fp32", arrays=None, _lib_path=None):
         self.lib = _lib.load(_lib_path)  # (_lib_path: tests only -- the second implementation kept for cross-checks)
+        self.live_step = False  # DragPose.run(live=True) sets it for its one call: optimize_sequence(gaps=) of one frame is then dp_live_step
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("LatentOptimizer needs a ROCm device (cuda:N); there is no CPU fallback")
@@ -385,7 +386,7 @@ class LatentOptimizer:
                           stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
                           loss=None, scratch=None, status=None, offsets=None, constraints=None, terms=None, loss_extra=None, loss_terms=None,
                           joint_pos=None, holds=None, hold_state=None, hold_trace=None, ar=None, z_tgt_trace=None, gaps=None, gap_state=None,
-                          present=None, gap_trace=None):
+                          present=None, gap_trace=None, live=False):
         """T consecutive frames of S sequences in one launch (include/dragposer.h: dp_optimize_sequence): the optimise loop with the
         reference's while-condition and run()'s epilogue per frame, state carried on the device.  tgt_pos [T,S,22,3] / tgt_rot
         [T,S,22,9] dense per joint; tgt_root [T,S,3] or None (position targets are then tgt_pos + (tgt_root[t] - running global
@@ -411,7 +412,14 @@ class LatentOptimizer:
         without `ar` (without: `z_tgt` as usual); `terms` / `holds` are optional, `constraints` is not taken.  `gap_state` [S,22,16] is
         updated IN PLACE (required); `present` [T,S,22] uint8 or None (NaN samples alone mark gaps); `gap_trace` [T,S,22] uint8 or True
         (allocated here) receives every joint's code of every step and is returned as `gap_trace`.  `status` then also carries
-        DP_STATUS_TRACKER_HELD / _LOST / DP_STATUS_NO_TRACKER."""
+        DP_STATUS_TRACKER_HELD / _LOST / DP_STATUS_NO_TRACKER.
+        `live` (with `gaps`, T = 1): the same frame as ONE launch, dp_live_step (include/dragposer_live.h) -- the kernel appends the step's row
+        to the three history buffers itself; the bits of the call without it."""
+        live = bool(live) or bool(getattr(self, "live_step", False))
+        if live and gaps is None:
+            raise ValueError("optimize_sequence: live= is the one-launch form of gaps= (pass Gaps(0, 1.0) for none to hold)")
+        if live and int(tgt_pos.shape[0]) != 1:
+            raise ValueError("optimize_sequence: live= is one frame, tgt_pos holds " + str(int(tgt_pos.shape[0])))
         if gaps is None and (gap_state is not None or present is not None or gap_trace is not None):
             raise ValueError("optimize_sequence: gap_state / present / gap_trace belong to gaps=")
         if gaps is not None:
@@ -524,7 +532,7 @@ class LatentOptimizer:
                     gap_trace = torch.zeros(T, S, NJ, dtype=torch.uint8, device=dev)
                 gs = gaps.to_struct(S, dev, gap_state, present, gap_trace, steps=T)
                 hold_ref, ar_ref = (mid[0] if mid else None), (mid[1] if len(mid) > 1 else None)
-                fn, mid = self.lib.dp_optimize_sequence_gaps, (hold_ref, ar_ref, C.byref(gs))
+                fn, mid = self.lib.dp_live_step if live else self.lib.dp_optimize_sequence_gaps, (hold_ref, ar_ref, C.byref(gs))
                 if gap_trace is not None:
                     outs["gap_trace"] = gap_trace
             self._call(fn, S, lp, C.byref(fr), C.byref(p), C.byref(own), *mid, C.byref(skel) if skel is not None else None, *tail, C.byref(ex))

@@ -21,6 +21,9 @@
  */
 #ifndef DRAGPOSER_UNITY_H
 #define DRAGPOSER_UNITY_H
+
+#include "dragposer_gaps.h" /* dp_term, dp_hold, the DP_STATUS_* bits (the additions below) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -49,6 +52,37 @@ void drag_poser_get_latent(const DragPoser* dragPoser, float* latent24); /* the 
 void drag_poser_set_latent(DragPoser* dragPoser, const float* latent24); /* also refills the latent history with it (drag_pose.py:50-55) */
 int drag_poser_has_temporal(const DragPoser* dragPoser); /* 1: <modelPath>/temporal.bin was loaded -- lambdaTemporal takes effect
                                                             (the Transformer of temporal_transformer.py on the GPU, dp_temporal_*) */
+
+/* additions: constraint terms, holds, trackers that drop out, and a predictor that needs no training, in the live step.
+ *
+ * While none of the four setters below has been called, drag_pose() is exactly the call above.  Once any has, a frame is ONE launch of
+ * dp_live_step (include/dragposer_live.h): the term table (or an empty one), the holds and the latent AR predictor as configured, and the gaps
+ * as configured -- or max_hold 0, decay 1 when drag_poser_set_gaps was never called: an absent sample then leaves the loss at once, the setting
+ * to start from.  A sample that is NaN, or marked absent through drag_pose_present, no longer ends the session: the
+ * joint is held or leaves the loss (include/dragposer_gaps.h), and drag_poser_last_status() says which.  lambdaTemporal takes effect whenever a
+ * predictor of either kind is present.  All four setters need load_models first (their state lives on the device); load_models called again
+ * forgets all four.  init_drag_model and drag_poser_set_latent zero the hold and gap states.  A frame that fails leaves the handle as it was.
+ * Failures are reported through drag_poser_last_error(). */
+/* the table of include/dragposer_terms.h; 0 terms clears it.  Refused at the call: nTerms outside 0..DP_MAX_TERMS, upAxis outside 0..2, a
+ * non-NULL per_frame (a device pointer has no meaning across this ABI).  Anything else dp_terms refuses surfaces from the next frame, which
+ * is then not committed. */
+void drag_poser_set_terms(DragPoser* dragPoser, int nTerms, const dp_term* terms, int upAxis);
+/* include/dragposer_holds.h; each hold names a term of the table set before.  The hold state is zeroed. */
+void drag_poser_set_holds(DragPoser* dragPoser, int nHolds, const dp_hold* holds);
+/* include/dragposer_gaps.h's rule: maxHold 0..DP_GAP_MAX_HOLD frames, decay in (0, 1].  The gap state is zeroed. */
+void drag_poser_set_gaps(DragPoser* dragPoser, int maxHold, float decay);
+/* include/dragposer_latent_ar.h: coeffs [order][24][24], bias [24], copied; order 0 switches the predictor off.  Refused with a non-zero order
+ * while temporal.bin is loaded: the targets have one source. */
+void drag_poser_set_latent_ar(DragPoser* dragPoser, int order, const float* coeffs, const float* bias);
+/* the same from a latent_ar.bin, written by tools/export_latent_ar_bin.py from a LatentAR .npz */
+void drag_poser_load_latent_ar(DragPoser* dragPoser, char* path);
+/* drag_pose with present [nEndEffectors] (0: that tracker's sample is absent this frame) or NULL; drag_pose is this call with NULL.
+ * A non-NULL present needs one of the four configured. */
+void drag_pose_present(DragPoser* dragPoser, int nEndEffectors, dp_float3* targetEEPos, dp_quaternion* targetEERot, const unsigned char* present,
+                       dp_quaternion* resultPose, dp_float3* resultGlobalPos);
+int drag_poser_last_status(const DragPoser* dragPoser); /* DP_STATUS_* bits of the last frame, DP_STATUS_TRACKER_HELD / _LOST / DP_STATUS_NO_TRACKER included */
+void drag_poser_get_gap_codes(const DragPoser* dragPoser, unsigned char* codes22); /* every joint's code of the last live frame: 1 present, 2 held, 3 lost, 0 no tracker */
+void drag_poser_get_hold_state(const DragPoser* dragPoser, float* state /* [nHolds][4] */); /* (x, y, z, held) after the last live frame */
 
 #ifdef __cplusplus
 }
