@@ -3,6 +3,7 @@ from .constraints import Constraints  # noqa: F401  (the reference's extra loss 
 from .terms import Term, Terms  # noqa: F401  (user-defined constraint terms: include/dragposer_terms.h)
 from .holds import Hold, Holds  # noqa: F401  (joints held where they touched down: include/dragposer_holds.h)
 from .gaps import Gaps  # noqa: F401  (trackers that drop out and come back: include/dragposer_gaps.h)
+from .tethers import Tether, Tethers  # noqa: F401  (joints tied to their own recent path: include/dragposer_tethers.h)
 from .encoder import NativePoseEncoder  # noqa: F401  (the pose encoder in one HIP launch: include/dragposer_encoder.h)
 
 

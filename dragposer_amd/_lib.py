@@ -261,6 +261,23 @@ class DpGaps(_Sized):
 LIVE_SYMBOLS = ("dp_live_step",)
 
 
+# every symbol include/dragposer_tethers.h declares (tests/test_tethers_abi.py)
+TETHER_SYMBOLS = ("dp_optimize_sequence_tethers",)
+DP_MAX_TETHERS = 4
+DP_TETHER_STATE_FLOATS = 8
+
+
+class DpTether(C.Structure):
+    """include/dragposer_tethers.h: dp_tether"""
+    _fields_ = [("term", C.c_int), ("alpha", C.c_float)]
+
+
+class DpTethers(_Sized):
+    """include/dragposer_tethers.h: dp_tethers (tethers: a HOST array of DpTether; state / trace: device pointers)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("n_tethers", C.c_int), ("tethers", C.c_void_p), ("state", C.c_void_p),
+                ("trace", C.c_void_p)]
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -357,6 +374,8 @@ def load(path=None):
     lib.dp_optimize_sequence_gaps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
                                               C.POINTER(DpHolds), C.POINTER(DpLatentAR), C.POINTER(DpGaps)] + _seq_tail
     lib.dp_live_step.argtypes = lib.dp_optimize_sequence_gaps.argtypes
+    lib.dp_optimize_sequence_tethers.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
+                                                 C.POINTER(DpHolds), C.POINTER(DpLatentAR), C.POINTER(DpGaps), C.POINTER(DpTethers)] + _seq_tail
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

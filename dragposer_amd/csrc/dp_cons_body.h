@@ -24,6 +24,10 @@
 // dp_live_ar_kernel, include/dragposer_live.h): the launch is one step, and the wave appends the step's row to the sequence's three history
 // buffers itself (dp_cons_live.h).  The #if DP_CONS_LIVE blocks are the only difference; without DP_CONS_LIVE the twelve kernels above keep
 // their instructions.
+// dp_cons_tether.hip includes it twice more with DP_CONS_TETHER 1 on top of DP_CONS_GAP's five, without and with DP_CONS_AR
+// (dp_terms_tether_seq_kernel, dp_terms_tether_ar_seq_kernel, include/dragposer_tethers.h): a tethered term's row of the wave's block is its
+// tether's, rewritten at each step's `stop` from the joint's new world position (dp_cons_tether.h).  The #if DP_CONS_TETHER blocks are the
+// only difference; without DP_CONS_TETHER the fourteen kernels above keep their instructions.
 {
     constexpr bool TBL = DP_CONS_TABLE;
 #if DP_CONS_SKEL
@@ -35,6 +39,9 @@
     __shared__ __attribute__((aligned(16))) float lds[N_LDS];
 #if DP_CONS_AR
     __shared__ float arh[WPB * AR_W_FLOATS];
+#endif
+#if DP_CONS_TETHER && !DP_TETHER_WPREV_GLOBAL
+    __shared__ float twp[WPB * TETHER_W_FLOATS];
 #endif
     const float* __restrict__ W = a.img;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -122,6 +129,20 @@
         if (hd >= 0 && lds[L_TBL + lane * TW + T_W] != 0.f)
 #pragma unroll
             for (int c = 0; c < 4; ++c) wb[W_ROW + 4 * lane + c] = a.h.state[(f * a.h.n_holds + hd) * 4 + c];
+    }
+#endif
+#if DP_CONS_TETHER // lane t, term t tethered and active: likewise its tether's row; the joint's last world position into the wave's area of twp
+    if (lane < a.n_terms) {
+        const int tk = hold_of(a.t.n_tethers, a.t.terms, lane);
+        if (tk >= 0 && lds[L_TBL + lane * TW + T_W] != 0.f) {
+            const float* const srow = a.t.state + (f * a.t.n_tethers + tk) * TETHER_ROW;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) wb[W_ROW + 4 * lane + c] = srow[c];
+#if !DP_TETHER_WPREV_GLOBAL
+#pragma unroll
+            for (int c = 0; c < 4; ++c) twp[wv * TETHER_W_FLOATS + 4 * tk + c] = srow[4 + c];
+#endif
+        }
     }
 #endif
 #if DP_CONS_AR // lane i: column i of the sequence's last `order` history rows, the newest (h_1) first
@@ -268,6 +289,13 @@
             bt = bt || refused(r[0]) || refused(r[1]) || refused(r[2]) || refused(r[3]) || r[3] < 0.f;
         }
 #endif
+#if DP_CONS_TETHER // (a tethered term likewise: its row is the tether's as the step before left it, screened as a per_frame row)
+        if (tb[T_W] != 0.f && hold_of(a.t.n_tethers, a.t.terms, lane) >= 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) r[c] = wb[W_ROW + 4 * lane + c];
+            bt = bt || refused(r[0]) || refused(r[1]) || refused(r[2]) || refused(r[3]) || r[3] < 0.f;
+        }
+#endif
 #pragma unroll
         for (int c = 0; c < 4; ++c) wb[W_ROW + 4 * lane + c] = r[c];
     }
@@ -305,6 +333,21 @@
             if (hd >= 0 && lds[L_TBL + lane * TW + T_W] != 0.f)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) a.h.trace[(ft * a.h.n_holds + hd) * 4 + c] = wb[W_ROW + 4 * lane + c];
+        }
+#endif
+#if DP_CONS_TETHER // (the tether's state stays as it is: the trace repeats it)
+        if (lane < a.n_terms && a.t.trace) {
+            const int tk = hold_of(a.t.n_tethers, a.t.terms, lane);
+            if (tk >= 0 && lds[L_TBL + lane * TW + T_W] != 0.f) {
+                float* const trow = a.t.trace + (ft * a.t.n_tethers + tk) * TETHER_ROW;
+#if DP_TETHER_WPREV_GLOBAL
+                const float* const wpv = a.t.state + (f * a.t.n_tethers + tk) * TETHER_ROW + 4;
+#else
+                const float* const wpv = twp + wv * TETHER_W_FLOATS + 4 * tk;
+#endif
+#pragma unroll
+                for (int c = 0; c < 4; ++c) { trow[c] = wb[W_ROW + 4 * lane + c]; trow[4 + c] = wpv[c]; }
+            }
         }
 #endif
 #if DP_CONS_AR // (the history stays as it is; the step used no target)
@@ -781,6 +824,40 @@
                 }
             }
 #endif
+#if DP_CONS_TETHER // include/dragposer_tethers.h, "The update": lane t on its own row and its own four words of twp, which no lane reads again
+                   // before the step's closing wave_sync()
+            if (lane < a.n_terms) {
+                const int tk = hold_of(a.t.n_tethers, a.t.terms, lane);
+                const float* tb = lds + L_TBL + lane * TW;
+                if (tk >= 0 && tb[T_W] != 0.f) {
+                    const int ja = __float_as_int(tb[T_JA]);
+                    float* const row = wb + W_ROW + 4 * lane;
+#if DP_TETHER_WPREV_GLOBAL
+                    float* const wpv = a.t.state + (f * a.t.n_tethers + tk) * TETHER_ROW + 4;
+#else
+                    float* const wpv = twp + wv * TETHER_W_FLOATS + 4 * tk;
+#endif
+                    float wp[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) wp[k] = __fadd_rn(gpn[k], __fsub_rn(PB[4 * ja + k], PB[k])); // where a renderer puts joint a
+                    if (fabsf(wp[0]) <= DP_INPUT_LIMIT && fabsf(wp[1]) <= DP_INPUT_LIMIT && fabsf(wp[2]) <= DP_INPUT_LIMIT) {
+                        const bool have = wpv[3] != 0.f;
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            row[k] = have ? __fadd_rn(wp[k], __fmul_rn(tb[T_TALPHA], __fsub_rn(wp[k], wpv[k]))) : wp[k];
+                            wpv[k] = wp[k];
+                        }
+                        row[3] = 1.f;
+                        wpv[3] = 1.f;
+                    }
+                    if (a.t.trace) {
+                        float* const trow = a.t.trace + (fo * a.t.n_tethers + tk) * TETHER_ROW;
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) { trow[c] = row[c]; trow[4 + c] = wpv[c]; }
+                    }
+                }
+            }
+#endif
             float* const o = a.q.hist + fo * (LAT + 3 + NH);
             if (lane < LAT) o[lane] = z;
 #if DP_CONS_AR // the step's history row becomes h_1, the older rows shift: lane i on column i, read again behind the step's closing wave_sync()
@@ -991,6 +1068,20 @@
         if (hd >= 0 && lds[L_TBL + lane * TW + T_W] != 0.f)
 #pragma unroll
             for (int c = 0; c < 4; ++c) a.h.state[(f * a.h.n_holds + hd) * 4 + c] = wb[W_ROW + 4 * lane + c];
+    }
+#endif
+#if DP_CONS_TETHER
+    if (lane < a.n_terms) {
+        const int tk = hold_of(a.t.n_tethers, a.t.terms, lane);
+        if (tk >= 0 && lds[L_TBL + lane * TW + T_W] != 0.f) {
+            float* const srow = a.t.state + (f * a.t.n_tethers + tk) * TETHER_ROW;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) srow[c] = wb[W_ROW + 4 * lane + c];
+#if !DP_TETHER_WPREV_GLOBAL
+#pragma unroll
+            for (int c = 0; c < 4; ++c) srow[4 + c] = twp[wv * TETHER_W_FLOATS + 4 * tk + c];
+#endif
+        }
     }
 #endif
     if (lane < LAT) a.z[f * LAT + lane] = zc;

@@ -24,7 +24,9 @@
 #include "../../include/dragposer_latent_ar.h"
 #include "../../include/dragposer_gaps.h"
 #include "../../include/dragposer_live.h"
+#include "../../include/dragposer_tethers.h"
 #include "dp_cons_live.h"
+#include "dp_cons_tether.h"
 #include "dp_host_rt.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -678,6 +680,7 @@ constexpr Sized TERMS_V510 = {"dp_terms", "dp_terms t = DP_TERMS_INIT;", offseto
 constexpr Sized HOLDS_V530 = {"dp_holds", "dp_holds h = DP_HOLDS_INIT;", offsetof(dp_holds, trace) + sizeof(void*), false};
 constexpr Sized LATENT_AR_V540 = {"dp_latent_ar", "dp_latent_ar r = DP_LATENT_AR_INIT;", offsetof(dp_latent_ar, trace) + sizeof(void*), false};
 constexpr Sized GAPS_V550 = {"dp_gaps", "dp_gaps g = DP_GAPS_INIT;", offsetof(dp_gaps, trace) + sizeof(void*), false};
+constexpr Sized TETHERS_V570 = {"dp_tethers", "dp_tethers t = DP_TETHERS_INIT;", offsetof(dp_tethers, trace) + sizeof(void*), false};
 constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
@@ -1346,6 +1349,8 @@ hipError_t dp_launch_terms_gap_seq(const dpcons::GapSeqArgs* args, hipStream_t s
 hipError_t dp_launch_terms_gap_ar_seq(const dpcons::GapArSeqArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_live(const dpcons::LiveSeqArgs* args, hipStream_t stream) __attribute__((weak));           // (dp_cons_live.hip, likewise)
 hipError_t dp_launch_live_ar(const dpcons::LiveArSeqArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_terms_tether_seq(const dpcons::TetherSeqArgs* args, hipStream_t stream) __attribute__((weak)); // (dp_cons_tether.hip, likewise)
+hipError_t dp_launch_terms_tether_ar_seq(const dpcons::TetherArSeqArgs* args, hipStream_t stream) __attribute__((weak));
 #endif
 
 // include/dragposer_latent_ar.h: dp_latent_ar checked, after everything dp_optimize_sequence_holds checks, against the launch's frames and
@@ -1380,14 +1385,25 @@ static int take_gaps(dp_ctx* ctx, const dp_gaps* g_in, dpcons::GapFields& g, con
     return DP_OK;
 }
 
+// what take_tethers checks dp_tethers against: the table and the holds the call was given (sequence_constrained_impl hands them through)
+struct TetherIn {
+    const dp_tethers* tethers;
+    const dp_terms* terms;
+    const dp_holds* holds;
+};
+static int take_tethers(dp_ctx* ctx, const TetherIn& in, unsigned* tbl, dpcons::TetherFields& t, const char* who);
+
 template <class A, class Own>
 static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
                                      const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream, const char* who, Own own,
-                                     const dp_latent_ar* ar = nullptr, const dp_gaps* gaps = nullptr)
+                                     const dp_latent_ar* ar = nullptr, const dp_gaps* gaps = nullptr, const TetherIn* tethers = nullptr)
 {
     // (include/dragposer_live.h: the gap units' argument blocks and checks, the history append in the kernel instead of a second launch)
     constexpr bool LIVE = std::is_same<A, dpcons::LiveSeqArgs>::value, LIVE_AR = std::is_same<A, dpcons::LiveArSeqArgs>::value;
-    constexpr bool GAP = std::is_same<A, dpcons::GapSeqArgs>::value || LIVE, GAP_AR = std::is_same<A, dpcons::GapArSeqArgs>::value || LIVE_AR;
+    // (include/dragposer_tethers.h: the gap units' argument blocks and checks, dp_tethers checked after dp_gaps)
+    constexpr bool TETHER = std::is_same<A, dpcons::TetherSeqArgs>::value, TETHER_AR = std::is_same<A, dpcons::TetherArSeqArgs>::value;
+    constexpr bool GAP = std::is_same<A, dpcons::GapSeqArgs>::value || LIVE || TETHER;
+    constexpr bool GAP_AR = std::is_same<A, dpcons::GapArSeqArgs>::value || LIVE_AR || TETHER_AR;
     constexpr bool HOLDS = std::is_same<A, dpcons::HoldSeqArgs>::value, AR = std::is_same<A, dpcons::ArSeqArgs>::value || GAP_AR;
     dp_params p;
     if (int rc = take_params(ctx, p_in, p, who)) return rc;
@@ -1404,6 +1420,8 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
         if (int rc = take_latent_ar(ctx, ar, fr, st, a.r, who)) return rc;
     if constexpr (GAP || GAP_AR)
         if (int rc = take_gaps(ctx, gaps, a.g, who)) return rc;
+    if constexpr (TETHER || TETHER_AR)
+        if (int rc = take_tethers(ctx, *tethers, a.tbl, a.t, who)) return rc;
 #ifdef DP_REF8_BUILD
     (void)n_seq; (void)latent; (void)stream;
     return refuse_ref8(ctx, who);
@@ -1411,6 +1429,9 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
     if (LIVE || LIVE_AR) {
         if (!dp_launch_live || !dp_launch_live_ar)
             return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_live.hip");
+    } else if (TETHER || TETHER_AR) {
+        if (!dp_launch_terms_tether_seq || !dp_launch_terms_tether_ar_seq)
+            return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_tether.hip");
     } else if (GAP || GAP_AR) {
         if (!dp_launch_terms_gap_seq || !dp_launch_terms_gap_ar_seq)
             return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_gap.hip");
@@ -1435,6 +1456,8 @@ static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, cons
         if constexpr (std::is_same<A, dpcons::SeqConsArgs>::value) e = dp_launch_cons_seq(&a, (hipStream_t)stream);
         else if constexpr (LIVE) e = dp_launch_live(&a, (hipStream_t)stream);
         else if constexpr (LIVE_AR) e = dp_launch_live_ar(&a, (hipStream_t)stream);
+        else if constexpr (TETHER) e = dp_launch_terms_tether_seq(&a, (hipStream_t)stream);
+        else if constexpr (TETHER_AR) e = dp_launch_terms_tether_ar_seq(&a, (hipStream_t)stream);
         else if constexpr (GAP) e = dp_launch_terms_gap_seq(&a, (hipStream_t)stream);
         else if constexpr (GAP_AR) e = dp_launch_terms_gap_ar_seq(&a, (hipStream_t)stream);
         else if constexpr (HOLDS) e = dp_launch_terms_hold_seq(&a, (hipStream_t)stream);
@@ -1590,6 +1613,74 @@ extern "C" int dp_optimize_sequence_gaps(dp_ctx* ctx, int n_seq, float* latent, 
             return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_gaps: n_sequences must be positive; NULL latent, frames, params, terms, gaps, state or results");
         if (r_in) return sequence_constrained_impl<dpcons::GapArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in, g_in);
         return sequence_constrained_impl<dpcons::GapSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, nullptr, g_in);
+    });
+}
+
+// include/dragposer_tethers.h: dp_tethers checked, after everything dp_optimize_sequence_gaps checks, against the table and the holds the
+// call was given (both accepted by then); each tether's alpha goes into its term's first staged axis_a word (a point-DISTANCE term never
+// reads it, and no hold has put its level there: a tethered term is not held) and the tether-to-term map is filled (dp_cons_tether.h)
+static int take_tethers(dp_ctx* ctx, const TetherIn& in, unsigned* tbl, dpcons::TetherFields& tf, const char* who)
+{
+    const std::string nm = who;
+    dp_tethers ts;
+    if (int rc = take_sized(ctx, in.tethers, ts, TETHERS_V570, who)) return rc;
+    dp_terms tt;
+    copy_sized(in.terms, tt);
+    dp_holds hs;
+    std::memset(&hs, 0, sizeof(hs));
+    if (in.holds) copy_sized(in.holds, hs);
+    if (ts.n_tethers < 0 || ts.n_tethers > DP_MAX_TETHERS)
+        return fail(ctx, DP_ERR_INVALID, nm + ": dp_tethers.n_tethers " + std::to_string(ts.n_tethers) + " outside 0.." + std::to_string(DP_MAX_TETHERS));
+    if (ts.n_tethers > 0 && !ts.tethers) return fail(ctx, DP_ERR_INVALID, nm + ": dp_tethers.tethers is NULL with n_tethers > 0");
+    if (ts.n_tethers > 0 && !ts.state) return fail(ctx, DP_ERR_INVALID, nm + ": dp_tethers.state is NULL with n_tethers > 0");
+    tf.state = ts.state; tf.trace = ts.trace; tf.n_tethers = ts.n_tethers; tf.terms = 0u;
+    for (int k = 0; k < ts.n_tethers; ++k) {
+        const dp_tether& te = ts.tethers[k];
+        const std::string tn = nm + ": tether " + std::to_string(k) + ": ";
+        if (te.term < 0 || te.term >= tt.n_terms)
+            return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " outside the table of " + std::to_string(tt.n_terms));
+        const dp_term& t = tt.terms[te.term];
+        if (t.type != DP_TERM_DISTANCE) return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " is not a DP_TERM_DISTANCE term");
+        if (t.joint_b != -1) return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " has a joint_b (a tether needs a point-DISTANCE term)");
+        if (t.per_frame) return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " has a per_frame array (the tether's state is its row)");
+        for (int g = 0; g < k; ++g)
+            if (ts.tethers[g].term == te.term)
+                return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " is already tethered by tether " + std::to_string(g));
+        for (int h = 0; h < hs.n_holds; ++h)
+            if (hs.holds[h].term == te.term)
+                return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " is held by hold " + std::to_string(h));
+        if (!(te.alpha >= 0.f && te.alpha <= 1.f)) return fail(ctx, DP_ERR_INVALID, tn + "alpha must be a finite number in [0, 1]");
+        ((float*)(tbl + te.term * dpcons::TW))[dpcons::T_TALPHA] = te.alpha;
+        tf.terms |= (unsigned)te.term << (8 * k);
+    }
+    return DP_OK;
+}
+
+// include/dragposer_tethers.h: dp_optimize_sequence_gaps with tethers (A = dpcons::TetherArSeqArgs; `ar` NULL: dpcons::TetherSeqArgs);
+// dp_tethers is checked last (take_tethers, from sequence_constrained_impl)
+extern "C" int dp_optimize_sequence_tethers(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                            const dp_holds* h_in, const dp_latent_ar* r_in, const dp_gaps* g_in, const dp_tethers* te_in,
+                                            const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out,
+                                            const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_tethers";
+    const auto own = [&](auto& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
+        if (h_in)
+            if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
+        dp_seq_extra e;
+        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
+        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
+        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
+        return DP_OK;
+    };
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !g_in || !te_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID,
+                        "dp_optimize_sequence_tethers: n_sequences must be positive; NULL latent, frames, params, terms, gaps, tethers, state or results");
+        const TetherIn tin = {te_in, t_in, h_in};
+        if (r_in) return sequence_constrained_impl<dpcons::TetherArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in, g_in, &tin);
+        return sequence_constrained_impl<dpcons::TetherSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, nullptr, g_in, &tin);
     });
 }
 

@@ -107,6 +107,7 @@ class DragPose:
         self._flip = 0
         self.hold_state = None  # [S,len(holds),4] (x, y, z, held) of run(holds=) / run_frames(holds=); zeroed when a sequence begins
         self.gap_state = None  # [S,22,16] of run(gaps=) / run_frames(gaps=) (include/dragposer_gaps.h); zeroed when a sequence begins
+        self.tether_state = None  # [S,len(tethers),8] of run(tethers=) / run_frames(tethers=) (include/dragposer_tethers.h); zeroed when a sequence begins
         self._skel_obj, self._skel_dev = None, None  # the last `offsets` object run() / run_frames() was given, and what it decided (_skeleton)
 
     def _holds(self, holds, terms, constraints, who):
@@ -118,6 +119,16 @@ class DragPose:
         holds.check(terms)
         if self.hold_state is None or tuple(self.hold_state.shape) != (self.S, len(holds), 4):
             self.hold_state = holds.new_state(self.S, self.device)
+
+    def _tethers(self, tethers, terms, constraints, holds, who):
+        """run()'s / run_frames()'s `tethers`: checked against the table and the holds, `tether_state` allocated (zeros: no path yet) on first use"""
+        if tethers is None:
+            return
+        if terms is None or constraints is not None:
+            raise ValueError(f"DragPose.{who}: tethers= refer to a table, pass terms= (Terms.from_constraints turns constraints into one)")
+        tethers.check(terms, holds)
+        if self.tether_state is None or tuple(self.tether_state.shape) != (self.S, len(tethers), 8):
+            self.tether_state = tethers.new_state(self.S, self.device)
 
     def _index(self, values):
         """device index tensor for a Python list, created once (no host->device copy inside a captured step)"""
@@ -182,6 +193,7 @@ class DragPose:
         self.current_index = 0
         self.target_latent_buffer = None
         self.hold_state = None
+        self.tether_state = None
         self.gap_state = torch.zeros(self.S, NJ, 16, device=self.device)
 
     def set_initial_state(self, latent, init_global_pos, initial_global_rot, initial_heights):
@@ -197,6 +209,7 @@ class DragPose:
         self.current_index = 0
         self.target_latent_buffer = None
         self.hold_state = None
+        self.tether_state = None
         self.gap_state = torch.zeros(self.S, NJ, 16, device=self.device)
 
     # ------------------------------------------------------------------ temporal target (drag_pose.py:234-294)
@@ -272,7 +285,7 @@ class DragPose:
     def run_frames(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, target_root=None, stop_eps_pos=1e-2, stop_eps_rot=1e-2,
                    max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1, temporal_future_window=60,
                    height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01, offsets=None,
-                   constraints=None, terms=None, holds=None, ar=None, gaps=None, present=None):
+                   constraints=None, terms=None, holds=None, ar=None, gaps=None, present=None, tethers=None):
         """T consecutive frames of every sequence -- T calls of run() -- with the frame loop on the device: one kernel launch per
         stretch of frames between two temporal predictions (all T of them when there is no predictor or lambda_temporal is 0).
         target_ee_pos [T,S,E,3], target_ee_rot [T,S,E,3,3]; `target_root` [T,S,3] or None: given, the position targets of frame t
@@ -296,9 +309,19 @@ class DragPose:
         usual stretches; the state lives in `gap_state` [S,22,16], zeroed when a sequence begins, and `last_gap_trace` [T,S,22] holds every
         joint's code of every frame (1 present, 2 held, 3 lost, 0 not a tracker).  Without `terms` it runs with an empty table, and
         `constraints` go through Terms.from_constraints, as with `ar`.
+        `tethers` (a dragposer_amd.Tethers, with `terms`): joints tied to their own recent path (dp_optimize_sequence_tethers,
+        include/dragposer_tethers.h), one launch per stretch, with or without `holds`, `ar` and `gaps` (without `gaps` it runs with
+        Gaps(0, 1.0), under which an absent sample leaves the loss at once); the state lives in `tether_state` [S,len(tethers),8], zeroed
+        when a sequence begins and passed through every stretch, and `last_tether_trace` [T,S,len(tethers),8] holds it after every frame.
         Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run_frames: pass constraints or terms, not both")
+        if tethers is not None:
+            self._tethers(tethers, terms, constraints, holds, "run_frames")
+            if gaps is None:
+                from .gaps import Gaps
+
+                gaps = Gaps(0, 1.0)
         if ar is not None:
             _check_ar(self.temporal, ar, "run_frames")
         if gaps is None and present is not None:
@@ -344,6 +367,8 @@ class DragPose:
             self.last_joint_pos = torch.empty(T, S, NJ, 3, device=dev)
         if holds is not None:
             self.last_hold_trace = torch.zeros(T, S, len(holds), 4, device=dev)
+        if tethers is not None:
+            self.last_tether_trace = torch.zeros(T, S, len(tethers), 8, device=dev)
         if ar is not None:
             self.last_z_tgt = torch.zeros(T, S, LATENT, device=dev)
         dense_here = None
@@ -373,6 +398,8 @@ class DragPose:
                   key: self.last_terms[t0:t0 + n], "joint_pos": self.last_joint_pos[t0:t0 + n]}
             if holds is not None:
                 kw.update(holds=holds, hold_state=self.hold_state, hold_trace=self.last_hold_trace[t0:t0 + n])
+            if tethers is not None:
+                kw.update(tethers=tethers, tether_state=self.tether_state, tether_trace=self.last_tether_trace[t0:t0 + n])
             kw.update(gap_kw(t0, n))
             return kw
 
@@ -423,7 +450,7 @@ class DragPose:
             stop_eps_rot=1e-2, max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1,
             temporal_future_window=60, height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None,
             joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None, holds=None, ar=None,
-            gaps=None, present=None, live=False):
+            gaps=None, present=None, live=False, tethers=None):
         """One frame for every sequence: one launch for the optimise loop and the epilogue, one for the history buffers, plus two
         row scatters of the targets.  `out_pose` [S,88] / `out_pos` [S,3]: optional caller storage for the returned tensors.
         `constraints` (a dragposer_amd.Constraints): the reference's extra loss terms (drag_pose.py:129-183) join the loss -- the frame
@@ -439,6 +466,10 @@ class DragPose:
         `live` (with any of `constraints` / `terms` / `holds` / `ar` / `gaps`): that frame as ONE launch, dp_live_step
         (include/dragposer_live.h) -- the gap unit appends the frame's row to the history buffers itself; without `gaps` it runs with
         Gaps(0, 1.0), under which an absent sample leaves the loss at once.  The bits of the same call without `live`.
+        `tethers` (a dragposer_amd.Tethers, with `terms`): the per-frame composition of include/dragposer_tethers.h -- each tethered term
+        reads its row from `tether_state`, the frame is a one-step run_frames(gaps=) (Gaps(0, 1.0) without `gaps`), and the state is updated
+        after it with the header's arithmetic in torch on the device, no synchronisation: frame by frame the bits of
+        run_frames(terms=, tethers=).  Not together with `live`: dp_live_step has no tethers, run_frames(tethers=) is the one-launch form.
         `offsets`: the performer's bone offsets, as the reference takes them on every call (drag_pose.py:202) -- [22,3] for every sequence
         or [S,22,3] one per sequence.  The context's own skeleton (or None) runs the launches above unchanged; any other runs the same frame
         with those bones (dp_optimize_sequence_skeleton, include/dragposer_skeleton.h), not together with `constraints` / `terms`: this
@@ -446,6 +477,14 @@ class DragPose:
         the same object frame after frame costs one host synchronisation in all (DragPose._skeleton)."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
+        if tethers is not None:
+            if live:
+                raise ValueError("DragPose.run: live= has no tethers (dp_live_step); run_frames(tethers=) is their one-launch form")
+            self._tethers(tethers, terms, constraints, holds, "run")
+            if gaps is None:
+                from .gaps import Gaps
+
+                gaps = Gaps(0, 1.0)
         if live:
             if constraints is None and terms is None and holds is None and ar is None and gaps is None:
                 raise ValueError("DragPose.run: live= goes with constraints=, terms=, holds=, ar= or gaps=")
@@ -466,11 +505,16 @@ class DragPose:
                             temporal_future_window=temporal_future_window, height_indices=height_indices,
                             joint_adjustment_indices=joint_adjustment_indices, joint_adjustment_weight=joint_adjustment_weight,
                             constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, present=present)
+            if tethers is not None:  # (tethered terms read this frame's state rows; the update follows the frame)
+                kw_frame["terms"] = tethers.frame_terms(terms, self.tether_state)
             self.opt.live_step = bool(live)  # (run_frames of this one frame: optimize_sequence launches dp_live_step)
             try:
-                return self._run_ar(target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose, kw_frame)
+                ret = self._run_ar(target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose, kw_frame)
             finally:
                 self.opt.live_step = False
+            if tethers is not None:
+                tethers.update(terms, self.tether_state, self.last_joint_pos[0], self.current_global_pos)
+            return ret
         self._holds(holds, terms, constraints, "run")
         skel = self._skeleton(offsets)
         if skel is not None and (constraints is not None or terms is not None):

@@ -76,6 +76,54 @@ def foot_skate(gt_bvh, eval_bvh, contact_lo, floor_level=0.0, up=1, joints=FOOT_
     return (float(d.mean()) if d.size else float("nan")), int(d.size)
 
 
+def motion_jitter(world_pos):
+    """the jitter of a motion: the mean over frames 1..F-2 and all joints of |W(t+1) - 2 W(t) + W(t-1)|, the second difference of the joints'
+    world positions [F, J, 3], in the positions' units (per frame squared).  nan for fewer than three frames."""
+    w = np.asarray(world_pos, np.float64)
+    if w.shape[0] < 3:
+        return float("nan")
+    return float(np.linalg.norm(w[2:] - 2.0 * w[1:-1] + w[:-2], axis=-1).mean())
+
+
+def jitter(gt_bvh, eval_bvh):
+    """--tether's extra line: motion_jitter of the result and of the ground truth over the same frames.  World positions by
+    eval_pos_error's FK, each file's own root trajectory.  -> (the reconstruction's, the ground truth's)"""
+    gq, gpos, parents, offsets = local_quats_from_bvh(gt_bvh)
+    eq, epos, _, _ = local_quats_from_bvh(eval_bvh)
+    n = min(len(gq), len(eq))
+    root = lambda p: np.asarray(p)[:n].reshape(n, -1, 3)[:, 0]
+    gp, _ = Q.fk(gq[:n], root(gpos), offsets, parents)
+    ep, _ = Q.fk(eq[:n], root(epos), offsets, parents)
+    return motion_jitter(ep), motion_jitter(gp)
+
+
+def parse_tethers(items):
+    """--tether J:HI:WEIGHT[:ALPHA], up to four times -> [(joint, hi, weight, alpha)]"""
+    out = []
+    for item in items:
+        parts = item.split(":")
+        try:
+            if len(parts) not in (3, 4):
+                raise ValueError("three or four fields")
+            j, hi, w, alpha = int(parts[0]), float(parts[1]), float(parts[2]), (float(parts[3]) if len(parts) == 4 else 0.0)
+            if not (0 <= j < NJ and np.isfinite(hi) and hi >= 0.0 and np.isfinite(w) and w >= 0.0 and 0.0 <= alpha <= 1.0):
+                raise ValueError("J is a joint, HI and WEIGHT are finite and not negative, ALPHA lies in [0, 1]")
+        except ValueError as e:
+            raise SystemExit(f"--tether: expected J:HI:WEIGHT[:ALPHA], got {item!r} ({e})")
+        out.append((j, hi, w, alpha))
+    if len(out) > 4:
+        raise SystemExit(f"--tether: at most 4 tethers, got {len(out)}")
+    return out
+
+
+def tether_terms(specs, base):
+    """--tether: a point-DISTANCE term (lo = 0, hi = HI) per tethered joint and a tether on it, appended to the table `base` -> (Terms, Tethers)"""
+    from .tethers import Tether, Tethers
+
+    ts = [Term.distance(j, point=(0.0, 0.0, 0.0), lo=0.0, hi=hi, weight=w) for j, hi, w, _ in specs]
+    return Terms(base.terms + ts, base.up_axis), Tethers([Tether(len(base) + i, alpha) for i, (_, _, _, alpha) in enumerate(specs)])
+
+
 def foot_lock_terms(args, cons):
     """--foot-lock: two horizontal soft pins on FOOT_LOCK_JOINTS and their holds, appended to the reference's terms as a table when
     --constraints reference is given -> (Terms, Holds)"""
@@ -194,6 +242,12 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
     if getattr(args, "foot_lock", False):
         terms, holds = foot_lock_terms(args, cons)
         extra = dict(terms=terms, holds=holds)
+    if getattr(args, "tether_specs", None):
+        base = extra.get("terms")
+        if base is None:
+            base = Terms.from_constraints(cons) if cons is not None else Terms(up_axis=args.up_axis)
+        extra.pop("constraints", None)
+        extra["terms"], extra["tethers"] = tether_terms(args.tether_specs, base)
     if ar is not None:
         extra["ar"] = ar
     if getattr(args, "gaps_model", None) is not None:
@@ -254,12 +308,19 @@ def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
     out = dict(mpjpe=mpjpe, mpeepe=mpeepe, time=elapsed, frames=n, out=out_path, mean_iters=float(res["iters"].mean()))
     if blank is not None:
         out.update(mpjpe_blanked=blank[0], mpeepe_blanked=blank[1])
-    if getattr(args, "foot_lock", False):
+    if getattr(args, "tether_specs", None):
+        print("Tethers: " + ", ".join(f"joint {j} hi {hi} weight {w} alpha {a}" for j, hi, w, a in args.tether_specs) +
+              " (DragPose.run_frames(tethers=), include/dragposer_tethers.h)")
+    if getattr(args, "foot_lock", False) or getattr(args, "tether_specs", None):
         up = Constraints.reference().up_axis if getattr(args, "constraints", None) == "reference" else args.up_axis
         skate, pairs = foot_skate(BVH().load(q["path"]), BVH().load(out_path), args.contact_height[0], args.floor_level, up)
         print(f"Foot skate: {skate} (mean horizontal displacement per frame of joints {FOOT_LOCK_JOINTS[0]} and {FOOT_LOCK_JOINTS[1]} over "
               f"{pairs} ground-truth contact frames)")
         out.update(foot_skate=skate, contact_frames=pairs)
+    if getattr(args, "tether_specs", None):
+        jit, jit_gt = jitter(BVH().load(q["path"]), BVH().load(out_path))
+        print(f"Jitter: {jit} (mean |W(t+1) - 2 W(t) + W(t-1)| over the inner frames and all {NJ} joints; the ground truth's own: {jit_gt})")
+        out.update(jitter=jit, jitter_gt=jit_gt)
     if getattr(args, "keep_frames", False):
         out.update(poses=res["poses"], pos=res["pos"], iters=res["iters"])
     return out
@@ -339,6 +400,13 @@ def main(argv=None):
     ap.add_argument("--up-axis", type=int, choices=(0, 1, 2), default=2,
                     help="the axis heights are measured along and the pins drop (default z, the shipped example clips' up; --constraints "
                          "reference keeps its own, y)")
+    ap.add_argument("--tether", action="append", default=None, metavar="J:HI:WEIGHT[:ALPHA]",
+                    help="tie joint J to its own recent path: a point-DISTANCE term on it (lo = 0, hi = HI metres per frame free, weight WEIGHT) whose "
+                         "point follows the joint's own reconstructed position, extrapolated by ALPHA times the last frame's motion (default 0) "
+                         "(DragPose.run_frames(terms=, tethers=), include/dragposer_tethers.h; with --per-frame DragPose.run(terms=, tethers=), same "
+                         "results).  Up to four times; the terms are appended to --foot-lock's and --constraints reference's table.  Prints the foot "
+                         "skate line and one more, the jitter of the result beside the ground truth's own.  No default: nobody has tuned one "
+                         "(DESIGN.md section 13h)")
     ap.add_argument("--latent-ar", default=None, metavar="hold | cv[:DAMPING] | FILE.npz",
                     help="without a temporal checkpoint: pull the latent towards a linear autoregressive prediction from the sequence's own "
                          "recent latents, with the configuration's lambda_temporal instead of 0 (DragPose.run_frames(ar=), "
@@ -385,6 +453,7 @@ def main(argv=None):
         from .ar import parse
 
         args.latent_ar_model, args.latent_ar_text = parse(args.latent_ar)
+    args.tether_specs = parse_tethers(args.tether) if args.tether else None
     args.gaps_model = None
     if args.gaps is not None:
         from .gaps import Gaps

@@ -386,7 +386,7 @@ class LatentOptimizer:
                           stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
                           loss=None, scratch=None, status=None, offsets=None, constraints=None, terms=None, loss_extra=None, loss_terms=None,
                           joint_pos=None, holds=None, hold_state=None, hold_trace=None, ar=None, z_tgt_trace=None, gaps=None, gap_state=None,
-                          present=None, gap_trace=None, live=False):
+                          present=None, gap_trace=None, live=False, tethers=None, tether_state=None, tether_trace=None):
         """T consecutive frames of S sequences in one launch (include/dragposer.h: dp_optimize_sequence): the optimise loop with the
         reference's while-condition and run()'s epilogue per frame, state carried on the device.  tgt_pos [T,S,22,3] / tgt_rot
         [T,S,22,9] dense per joint; tgt_root [T,S,3] or None (position targets are then tgt_pos + (tgt_root[t] - running global
@@ -414,8 +414,24 @@ class LatentOptimizer:
         (allocated here) receives every joint's code of every step and is returned as `gap_trace`.  `status` then also carries
         DP_STATUS_TRACKER_HELD / _LOST / DP_STATUS_NO_TRACKER.
         `live` (with `gaps`, T = 1): the same frame as ONE launch, dp_live_step (include/dragposer_live.h) -- the kernel appends the step's row
-        to the three history buffers itself; the bits of the call without it."""
+        to the three history buffers itself; the bits of the call without it.
+        `tethers` (a dragposer_amd.Tethers, with `terms` and `gaps`): joints tied to their own recent path, dp_optimize_sequence_tethers
+        (include/dragposer_tethers.h), with or without `holds` and `ar`; pass Gaps(0, 1.0) for none to hold.  `tether_state`
+        [S,len(tethers),8] is updated IN PLACE (required); `tether_trace` [T,S,len(tethers),8] or True (allocated here) receives the state
+        after every step and is returned as `tether_trace`.  Not together with `live`."""
         live = bool(live) or bool(getattr(self, "live_step", False))
+        if tethers is None and (tether_state is not None or tether_trace is not None):
+            raise ValueError("optimize_sequence: tether_state / tether_trace belong to tethers=")
+        if tethers is not None:
+            if live:
+                raise ValueError("optimize_sequence: tethers= are not part of dp_live_step (include/dragposer_tethers.h, Not covered)")
+            if terms is None or constraints is not None:
+                raise ValueError("optimize_sequence: tethers= refer to a table, pass terms= (Terms.from_constraints turns constraints into one)")
+            if gaps is None:
+                raise ValueError("optimize_sequence: tethers= is dp_optimize_sequence_gaps with tethers, pass gaps= (Gaps(0, 1.0) for none to hold)")
+            if tether_state is None:
+                raise ValueError("optimize_sequence: tethers= needs tether_state [S,len(tethers),8]")
+            tethers.check(terms, holds)
         if live and gaps is None:
             raise ValueError("optimize_sequence: live= is the one-launch form of gaps= (pass Gaps(0, 1.0) for none to hold)")
         if live and int(tgt_pos.shape[0]) != 1:
@@ -535,6 +551,13 @@ class LatentOptimizer:
                 fn, mid = self.lib.dp_live_step if live else self.lib.dp_optimize_sequence_gaps, (hold_ref, ar_ref, C.byref(gs))
                 if gap_trace is not None:
                     outs["gap_trace"] = gap_trace
+            if tethers is not None:
+                if tether_trace is True:
+                    tether_trace = torch.zeros(T, S, len(tethers), 8, dtype=torch.float32, device=dev)
+                ts, keep_t = tethers.to_struct(terms, S, dev, tether_state, tether_trace, steps=T, holds=holds)
+                fn, mid = self.lib.dp_optimize_sequence_tethers, mid + (C.byref(ts),)
+                if tether_trace is not None:
+                    outs["tether_trace"] = tether_trace
             self._call(fn, S, lp, C.byref(fr), C.byref(p), C.byref(own), *mid, C.byref(skel) if skel is not None else None, *tail, C.byref(ex))
             del keep
             return outs

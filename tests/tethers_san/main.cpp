@@ -1,0 +1,195 @@
+// tests/tethers_san/main.cpp -- dp_optimize_sequence_tethers (include/dragposer_tethers.h) under AddressSanitizer and
+// UndefinedBehaviorSanitizer: a stand-alone program that links dp_host.cpp against tests/host_san/fake_hip.cpp (no HIP runtime, no kernel
+// unit) and walks take_tethers through well-formed and malformed structs, in the header's order, on a context without a device.  Every
+// sized struct is handed over in a heap block of exactly struct_size bytes, the term table in one of exactly n_terms entries, the holds and
+// the tethers arrays in ones of exactly n_holds and n_tethers entries, so a read past what the caller owns is an error here.  Device
+// pointers are a constant that is never dereferenced.  Built and run by tests/test_tethers_san.py; every condition is exact.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dragposer_tethers.h"
+
+extern "C" int dp_debug_host_ctx(dp_ctx**); // the library's private hook: a context with no device behind it
+
+#define CHECK(cond)                                                                      \
+    do {                                                                                 \
+        if (!(cond)) {                                                                   \
+            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
+            std::exit(1);                                                                \
+        }                                                                                \
+    } while (0)
+
+namespace {
+
+float* const PTR = (float*)0x10000; // stands for a device pointer
+
+// a T in a heap block of exactly `size` bytes (default: sizeof(T))
+template <class T>
+struct Exact {
+    void* block;
+    explicit Exact(const T& init, size_t size = sizeof(T)) : block(std::malloc(size)) { std::memcpy(block, &init, size < sizeof(T) ? size : sizeof(T)); }
+    ~Exact() { std::free(block); }
+    Exact(const Exact&) = delete;
+    const T* get() const { return (const T*)block; }
+};
+template <class T>
+struct Array { // exactly n entries (n = 0: a NULL pointer)
+    T* p;
+    explicit Array(const std::vector<T>& v) : p(v.empty() ? nullptr : (T*)std::malloc(v.size() * sizeof(T)))
+    {
+        if (p) std::memcpy(p, v.data(), v.size() * sizeof(T));
+    }
+    ~Array() { std::free(p); }
+    Array(const Array&) = delete;
+};
+
+std::vector<dp_term> good_terms()
+{ // 0: a plane; 1: the held pin; 2, 3: the tethered band and pin; 4: a joint-DISTANCE term
+    dp_term plane = DP_TERM_INIT;
+    plane.type = DP_TERM_PLANE; plane.joint_a = 4; plane.weight = 1.f;
+    dp_term pin = DP_TERM_INIT;
+    pin.type = DP_TERM_DISTANCE; pin.joint_a = 8; pin.weight = 0.8f; pin.flags = DP_TERM_DROP_UP;
+    dp_term band = DP_TERM_INIT;
+    band.type = DP_TERM_DISTANCE; band.joint_a = 6; band.weight = 0.6f; band.p1 = 0.02f;
+    dp_term damp = DP_TERM_INIT;
+    damp.type = DP_TERM_DISTANCE; damp.joint_a = 19; damp.weight = 0.f; // (an inert tether is accepted like any other)
+    dp_term pair = DP_TERM_INIT;
+    pair.type = DP_TERM_DISTANCE; pair.joint_a = 3; pair.joint_b = 7; pair.weight = 2.f; pair.p0 = 0.1f; pair.p1 = 0.3f;
+    return {plane, pin, band, damp, pair};
+}
+
+struct Case { // what one call is made of; the defaults are well-formed
+    std::vector<dp_term> terms = good_terms();
+    std::vector<dp_hold> holds = {{1, 0.f, 0.02f, 0.05f}};
+    std::vector<dp_tether> tethers = {{2, 0.f}, {3, 1.f}};
+    bool null_holds_struct = false, null_ar = false, z_tgt = false, with_extra = true, with_skeleton = true;
+    bool null_tethers = false, null_tether_array = false, null_tether_state = false, with_tether_trace = true;
+    unsigned tethers_size = sizeof(dp_tethers), tethers_reserved0 = 0u;
+    int n_tethers = -100; // (-100: the array's length)
+    int order = 2, max_hold = 3;
+    float decay = 0.7f, lr = 1e-2f;
+};
+
+int run(dp_ctx* ctx, const Case& c)
+{
+    dp_seq_frames fr0{};
+    fr0.n_steps = 3; fr0.tgt_pos = fr0.tgt_rot = fr0.w = PTR; fr0.tracked = (const unsigned char*)PTR;
+    fr0.z_tgt = c.z_tgt ? PTR : nullptr;
+    dp_params p0 = DP_PARAMS_INIT;
+    p0.n_iter = 10; p0.lr = c.lr; p0.beta1 = 0.9f; p0.beta2 = 0.999f; p0.eps = 1e-8f; p0.lambda_rot = 1.f; p0.lambda_tmp = 0.02f;
+    dp_seq_state st0{};
+    st0.global_pos = st0.global_rot = st0.latent_buf = st0.disp_buf = st0.heights_buf = PTR; st0.history = 60; st0.n_heights = 2;
+    st0.height_joints[0] = 4; st0.height_joints[1] = 8;
+    dp_seq_step adj0{};
+    adj0.adjust_joint = 0; adj0.adjust_target_joint = 13; adj0.adjust_weight = 0.5f;
+    dp_seq_results q0 = DP_SEQ_RESULTS_INIT;
+    q0.pose_ret = q0.pos_ret = q0.loss = q0.hist_scratch = PTR;
+    dp_seq_extra e0 = DP_SEQ_EXTRA_INIT;
+    e0.loss_terms = e0.joint_pos = PTR;
+    dp_skeleton_in s0 = DP_SKELETON_IN_INIT;
+    s0.offsets = PTR; s0.stride = DP_SKELETON_STRIDE;
+    Array<dp_term> terms(c.terms);
+    dp_terms t0 = DP_TERMS_INIT;
+    t0.n_terms = (int)c.terms.size(); t0.terms = terms.p;
+    Array<dp_hold> holds(c.holds);
+    dp_holds h0 = DP_HOLDS_INIT;
+    h0.n_holds = (int)c.holds.size(); h0.holds = holds.p; h0.state = c.holds.empty() ? nullptr : PTR;
+    dp_latent_ar r0 = DP_LATENT_AR_INIT;
+    r0.order = c.order; r0.coeffs = r0.bias = PTR;
+    dp_gaps g0 = DP_GAPS_INIT;
+    g0.max_hold = c.max_hold; g0.decay = c.decay; g0.state = PTR;
+    Array<dp_tether> tethers(c.tethers);
+    dp_tethers te0 = DP_TETHERS_INIT;
+    te0.struct_size = c.tethers_size; te0.reserved0 = c.tethers_reserved0;
+    te0.n_tethers = c.n_tethers == -100 ? (int)c.tethers.size() : c.n_tethers;
+    te0.tethers = c.null_tether_array ? nullptr : tethers.p;
+    te0.state = c.null_tether_state || c.tethers.empty() ? nullptr : PTR; te0.trace = c.with_tether_trace ? PTR : nullptr;
+    Exact<dp_seq_frames> fr(fr0);
+    Exact<dp_params> p(p0);
+    Exact<dp_seq_state> st(st0);
+    Exact<dp_seq_step> adj(adj0);
+    Exact<dp_seq_results> q(q0);
+    Exact<dp_seq_extra> e(e0);
+    Exact<dp_skeleton_in> s(s0);
+    Exact<dp_terms> t(t0);
+    Exact<dp_holds> h(h0);
+    Exact<dp_latent_ar> r(r0);
+    Exact<dp_gaps> g(g0);
+    Exact<dp_tethers> te(te0, c.tethers_size < sizeof(dp_tethers) ? c.tethers_size : sizeof(dp_tethers));
+    return dp_optimize_sequence_tethers(ctx, 4, PTR, fr.get(), p.get(), t.get(), c.null_holds_struct ? nullptr : h.get(), c.null_ar ? nullptr : r.get(),
+                                        g.get(), c.null_tethers ? nullptr : te.get(), c.with_skeleton ? s.get() : nullptr, st.get(), adj.get(), q.get(),
+                                        c.with_extra ? e.get() : nullptr, nullptr);
+}
+
+bool said(dp_ctx* ctx, const char* word) { return std::string(dp_last_error(ctx)).find(word) != std::string::npos; }
+
+} // namespace
+
+int main()
+{
+    dp_ctx* ctx = nullptr;
+    CHECK(dp_debug_host_ctx(&ctx) == DP_OK && ctx);
+    int n = 0;
+    const auto refused = [&](const Case& c, const char* word) {
+        CHECK(run(ctx, c) == DP_ERR_INVALID);
+        if (!said(ctx, word)) { std::fprintf(stderr, "expected '%s' in: %s\n", word, dp_last_error(ctx)); std::exit(1); }
+        CHECK(said(ctx, "dp_optimize_sequence_tethers"));
+        ++n;
+    };
+    const float inf = __builtin_inff(), nan = __builtin_nanf("");
+    // well-formed: this link has no kernel unit, which the library says after every argument check
+    for (int variant = 0; variant < 9; ++variant) {
+        Case c;
+        if (variant == 1) c.null_holds_struct = true;                        // no dp_holds at all
+        if (variant == 2) { c.null_ar = true; c.z_tgt = true; }              // no predictor: the targets are frames->z_tgt
+        if (variant == 3) c.tethers.clear();                                 // n_tethers = 0: NULL tethers and state are accepted
+        if (variant == 4) { c.with_tether_trace = false; c.with_extra = false; c.with_skeleton = false; }
+        if (variant == 5) c.tethers = {{2, 0.5f}};                           // one tether, of an array of exactly one
+        if (variant == 6) { c.null_holds_struct = true; c.tethers = {{1, 1.f}, {2, 0.f}, {3, 0.25f}}; } // the pin is free to be tethered without its hold
+        if (variant == 7) { c.holds.clear(); c.tethers = {{3, 0.f}, {1, 1.f}, {2, 1.f}}; c.null_ar = true; c.z_tgt = true; }
+        if (variant == 8) { c.tethers = {{3, 0.f}}; c.terms.resize(4); }     // the table's last term, of a table of exactly four
+        CHECK(run(ctx, c) == DP_ERR_UNSUPPORTED);
+        CHECK(said(ctx, "dp_cons_tether.hip"));
+        ++n;
+    }
+    // dp_tethers' own refusals, in the header's order: each is reported before every later one's fault
+    { Case c; c.null_tethers = true; refused(c, "NULL"); }
+    { Case c; c.tethers_size = 16; c.n_tethers = -1; refused(c, "dp_tethers.struct_size"); }  // a block of 16 bytes: only the size, reserved0 and n_tethers exist
+    { Case c; c.tethers_size = 8; refused(c, "dp_tethers.struct_size"); }
+    { Case c; c.tethers_size = 5000; refused(c, "dp_tethers.struct_size"); }                  // (the block is sizeof(dp_tethers): nothing past the size word is read)
+    { Case c; c.tethers_reserved0 = 3u; c.n_tethers = -1; refused(c, "reserved0"); }
+    { Case c; c.n_tethers = -1; c.null_tether_array = true; refused(c, "dp_tethers.n_tethers -1"); }
+    { Case c; c.n_tethers = DP_MAX_TETHERS + 1; c.null_tether_state = true; refused(c, "dp_tethers.n_tethers 5"); } // (the array of two is not read)
+    { Case c; c.null_tether_array = true; c.null_tether_state = true; refused(c, "dp_tethers.tethers is NULL"); }
+    { Case c; c.null_tether_state = true; c.tethers[0].alpha = 2.f; refused(c, "dp_tethers.state is NULL"); }
+    { Case c; c.tethers[0].term = -1; c.tethers[0].alpha = 2.f; refused(c, "tether 0: term -1 outside the table of 5"); }
+    { Case c; c.tethers[1].term = 5; c.tethers[1].alpha = nan; refused(c, "tether 1: term 5 outside the table of 5"); }
+    { Case c; c.tethers[0].term = 0; c.tethers[0].alpha = 2.f; refused(c, "tether 0: term 0 is not a DP_TERM_DISTANCE term"); }
+    { Case c; c.tethers[1].term = 4; c.tethers[1].alpha = 2.f; refused(c, "tether 1: term 4 has a joint_b"); }
+    { Case c; c.terms[2].per_frame = PTR; c.tethers[0].alpha = 2.f; refused(c, "tether 0: term 2 has a per_frame array"); }
+    { Case c; c.tethers[1].term = 2; c.tethers[1].alpha = 2.f; refused(c, "tether 1: term 2 is already tethered by tether 0"); }
+    { Case c; c.tethers[1].term = 1; c.tethers[1].alpha = 2.f; refused(c, "tether 1: term 1 is held by hold 0"); }
+    { Case c; c.tethers[0].alpha = -0.25f; refused(c, "tether 0: alpha"); }
+    { Case c; c.tethers[1].alpha = 1.0000001f; refused(c, "tether 1: alpha"); }
+    { Case c; c.tethers[0].alpha = nan; refused(c, "tether 0: alpha"); }
+    { Case c; c.tethers[1].alpha = inf; refused(c, "tether 1: alpha"); }
+    { Case c; c.tethers[1].alpha = -inf; refused(c, "tether 1: alpha"); }
+    // the order around dp_tethers: everything dp_optimize_sequence_gaps checks comes first
+    { Case c; c.terms[0].joint_a = 22; c.n_tethers = -1; refused(c, "term 0"); }
+    { Case c; c.holds[0].term = 9; c.n_tethers = -1; refused(c, "hold 0"); }
+    { Case c; c.lr = -1.f; c.n_tethers = -1; refused(c, "Adam"); }
+    { Case c; c.order = 0; c.n_tethers = -1; refused(c, "dp_latent_ar.order"); }
+    { Case c; c.z_tgt = true; c.n_tethers = -1; refused(c, "z_tgt must be NULL"); }
+    { Case c; c.null_ar = true; c.n_tethers = -1; refused(c, "NULL input array"); }  // without a predictor frames->z_tgt is required
+    { Case c; c.max_hold = -1; c.n_tethers = -1; refused(c, "dp_gaps.max_hold"); }
+    { Case c; c.decay = 0.f; c.tethers[0].alpha = 2.f; refused(c, "dp_gaps.decay"); }
+    { Case c; c.null_ar = true; c.z_tgt = true; c.n_tethers = -1; refused(c, "dp_tethers.n_tethers"); }
+    CHECK(dp_optimize_sequence_tethers(nullptr, 4, PTR, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr) == DP_ERR_INVALID);
+    dp_destroy(ctx);
+    std::printf("tethers: %d calls, all checks held\n", n);
+    return 0;
+}

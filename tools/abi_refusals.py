@@ -27,7 +27,8 @@ PTR = 0x10000  # stands for a device pointer: never dereferenced on a context wi
 PLAIN = ("dp_optimize", "dp_forward", "dp_optimize_sequence")
 BATCH_PTRS = ("z0", "z_tgt", "cur_rot", "tgt_pos", "tgt_rot", "w", "tracked")
 _last = {T: T._fields_[-1][0] for T in (_lib.DpParams, _lib.DpResult, _lib.DpSeqResults, _lib.DpSkeletonIn, _lib.DpGradIn,
-                                        _lib.DpConstraints, _lib.DpTerms)}
+                                        _lib.DpConstraints, _lib.DpTerms, _lib.DpHolds, _lib.DpLatentAR, _lib.DpGaps, _lib.DpTethers,
+                                        _lib.DpSeqExtra)}
 
 
 def min_size(T):
@@ -114,6 +115,47 @@ def _sequence(skel=False):
     return a
 
 
+def _tethers():
+    """dp_optimize_sequence_tethers (include/dragposer_tethers.h): a table of a plane and two point-DISTANCE terms, a hold on the first of
+    them and a tether on the second, the predictor and the gap rule beside them"""
+    fr, st, res = seq_args()
+    fr.z_tgt = None  # (the predictor is the targets' one source)
+    rows = (_lib.DpTerm * 3)(_lib.DpTerm(type=_lib.DP_TERM_PLANE, joint_a=3, weight=1.0),
+                             _lib.DpTerm(type=_lib.DP_TERM_DISTANCE, joint_a=8, joint_b=-1, weight=0.8),
+                             _lib.DpTerm(type=_lib.DP_TERM_DISTANCE, joint_a=6, joint_b=-1, weight=0.6, p1=0.02))
+    t = sized(_lib.DpTerms, n_terms=3, terms=C.addressof(rows))
+    hold = _lib.DpHold(term=1, level=0.0, contact_lo=0.02, contact_hi=0.05)
+    tether = _lib.DpTether(term=2, alpha=0.5)
+    a = {"n_seq": 2, "latent": C.c_void_p(PTR), "fr": fr, "p": params(), "t": t,
+         "holds": sized(_lib.DpHolds, n_holds=1, holds=C.addressof(hold), state=PTR),
+         "ar": sized(_lib.DpLatentAR, order=2, coeffs=PTR, bias=PTR), "gaps": sized(_lib.DpGaps, max_hold=3, decay=0.7, state=PTR),
+         "tethers": sized(_lib.DpTethers, n_tethers=1, tethers=C.addressof(tether), state=PTR, trace=PTR), "skel": skeleton(), "st": st,
+         "adj": _lib.DpSeqStep(adjust_joint=-1), "out": res, "extra": sized(_lib.DpSeqExtra)}
+    a["t"]._rows, a["holds"]._hold, a["tethers"]._tether = rows, hold, tether
+    return a
+
+
+def tether_cases():
+    """dp_tethers' own refusals in the header's order, each with a later stage's fault beside it, and the stages before dp_tethers"""
+    def entry(name, value):
+        return (f"tethers[0].{name} = {value}", lambda a: setattr(a["tethers"]._tether, name, value), False)
+
+    def term(i, name, value):
+        return (f"terms[{i}].{name} = {value}", lambda a: setattr(a["t"]._rows[i], name, value), False)
+
+    late = entry("alpha", 2.0)
+    out = [[field("tethers", "n_tethers", v), late] for v in (-1, _lib.DP_MAX_TETHERS + 1)]
+    out += [[field("tethers", "tethers", None), field("tethers", "state", None)], [field("tethers", "state", None), late],
+            [field("tethers", "n_tethers", 0, benign=True), field("tethers", "tethers", None, benign=True), field("tethers", "state", None, benign=True)],
+            [field("tethers", "trace", None, benign=True)]]
+    out += [[entry("term", v), late] for v in (-1, 3)]
+    out += [[entry("term", 0), late], [term(2, "joint_b", 4), late], [term(2, "per_frame", PTR), late], [entry("term", 1), late]]
+    out += [[entry("alpha", v)] for v in (-0.25, 1.5, float("nan"), float("inf"))]
+    out += [[field("gaps", "decay", 0.0), late], [field("ar", "order", 0), late], [field("holds", "n_holds", 9), late],
+            [field("holds", "reserved0", 3), late], [null_arg("holds", benign=True)], [null_arg("ar"), late]]
+    return out
+
+
 def _advance():
     _, st, _ = seq_args()
     return {"n_seq": 2, "res": result(), "st": st, "step": _lib.DpSeqStep(adjust_joint=-1)}
@@ -131,10 +173,12 @@ ENTRY_POINTS = {
     "dp_optimize_sequence": _sequence,
     "dp_optimize_sequence_skeleton": lambda: _sequence(skel=True),
     "dp_sequence_advance": _advance,
+    "dp_optimize_sequence_tethers": _tethers,
 }
 OPTIONAL = {("dp_optimize", "out"), ("dp_optimize_skeleton", "out"), ("dp_forward_vjp", "dcur_rot"), ("dp_forward_vjp", "status"),
             ("dp_forward_vjp_skeleton", "dcur_rot"), ("dp_forward_vjp_skeleton", "doffsets"), ("dp_forward_vjp_skeleton", "status"),
             ("dp_optimize_sequence", "adj"), ("dp_optimize_sequence_skeleton", "adj")}
+OPTIONAL |= {("dp_optimize_sequence_tethers", k) for k in ("holds", "skel", "adj", "extra")}
 
 
 # a defect: (label, function that spoils the argument dict, benign)
@@ -193,6 +237,8 @@ def cases(ep, args):
         out.append([field("in", "z0", None) if "in" in args else field("fr", "tgt_pos", None), field("p", "lr", 0.0)])
     if "p" in args and "skel" in args:
         out.append([field("skel", "stride", 5), field("p", "kernel", 7)])
+    if ep == "dp_optimize_sequence_tethers":
+        out += tether_cases()
     out.append([])
     return [(" + ".join(d[0] for d in c) or "well-formed", c) for c in out]
 
