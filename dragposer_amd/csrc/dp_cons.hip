@@ -47,16 +47,5 @@ __global__ __launch_bounds__(WPB * 64) void dp_terms_kernel(TermArgs a)
 #include "dp_cons_body.h"
 #undef DP_CONS_TABLE
 
-hipError_t dp_launch_cons(const Args* args, hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((args->n_frames + WPB - 1) / WPB);
-    hipLaunchKernelGGL(dp_cons_kernel, dim3(grid), dim3(WPB * 64), 0, stream, *args);
-    return hipGetLastError();
-}
-
-hipError_t dp_launch_terms(const TermArgs* args, hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((args->n_frames + WPB - 1) / WPB);
-    hipLaunchKernelGGL(dp_terms_kernel, dim3(grid), dim3(WPB * 64), 0, stream, *args);
-    return hipGetLastError();
-}
+hipError_t dp_launch_cons(const Args* args, hipStream_t stream) { return launch_waves(dp_cons_kernel, args, stream); }
+hipError_t dp_launch_terms(const TermArgs* args, hipStream_t stream) { return launch_waves(dp_terms_kernel, args, stream); }

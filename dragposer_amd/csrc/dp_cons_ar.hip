@@ -16,19 +16,6 @@ using namespace dpcons;
 
 #include "dp_cons_dev.h"
 
-namespace {
-
-// the hold on term t, or -1 (dp_cons_hold.hip's helper)
-DEV int hold_of(int n, unsigned map, int t)
-{
-    int h = -1;
-#pragma unroll
-    for (int k = 0; k < MAX_HOLDS; ++k) h = k < n && (int)((map >> (8 * k)) & 0xffu) == t ? k : h;
-    return h;
-}
-
-} // namespace
-
 #define DP_CONS_SKEL 1
 #define DP_CONS_SEQ 1
 #define DP_CONS_HOLD 1
@@ -39,9 +26,4 @@ __global__ __launch_bounds__(WPB * 64) void dp_terms_ar_seq_kernel(ArSeqArgs a)
 #include "dp_cons_body.h"
 #undef DP_CONS_TABLE
 
-hipError_t dp_launch_terms_ar_seq(const ArSeqArgs* args, hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((args->n_frames + WPB - 1) / WPB);
-    hipLaunchKernelGGL(dp_terms_ar_seq_kernel, dim3(grid), dim3(WPB * 64), 0, stream, *args);
-    return hipGetLastError();
-}
+hipError_t dp_launch_terms_ar_seq(const ArSeqArgs* args, hipStream_t stream) { return launch_waves(dp_terms_ar_seq_kernel, args, stream); }

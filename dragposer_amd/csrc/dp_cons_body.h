@@ -1,33 +1,30 @@
-// dp_cons_body.h -- the body of dp_cons.hip's two kernels, included once for each (no include guard): dp_cons_kernel (the four reference
-// terms, DP_CONS_TABLE 0) and dp_terms_kernel (the term table, DP_CONS_TABLE 1).  A textual body rather than a function both kernels
-// call: passed through a function, even an inlined one, the argument block is loaded whole at entry and the four-term kernel's code
-// changes (78 -> 122 SGPRs parked in VGPR lanes); included, dp_cons_kernel compiles to the same instructions as before the table existed.
-// Everything but the terms is shared; the #if DP_CONS_TABLE blocks are the only difference.  Helpers: dp_cons_dev.h.
-// dp_cons_skel.hip includes it twice more under DP_CONS_SKEL 1 (dp_cons_skel_kernel, dp_terms_skel_kernel): the bones are then each frame's
-// own (include/dragposer_skeleton.h), read and screened in the prologue and kept in the wave's block (dp_cons_skel.h) instead of L_OFF.  The
-// #if DP_CONS_SKEL blocks are the only difference; with DP_CONS_SKEL 0 the text compiles to the instructions it gave before they existed.
-// dp_cons_seq.hip includes it twice more under DP_CONS_SKEL 1 and DP_CONS_SEQ 1 (dp_cons_seq_kernel, dp_terms_seq_kernel): a wave is then a
-// SEQUENCE and runs a.q.n_steps frames of it -- the screening, the iteration loop and the results below once per step, run()'s epilogue
-// (dp_sequence_advance_kernel's arithmetic) at each step's `stop`, the latent, global position and global rotation carried in registers
-// (dp_cons_seq.h).  The #if DP_CONS_SEQ blocks are the only difference; with DP_CONS_SEQ 0 the four kernels above keep their instructions.
-// dp_cons_hold.hip includes it once more under DP_CONS_TABLE 1, DP_CONS_SKEL 1, DP_CONS_SEQ 1 and DP_CONS_HOLD 1 (dp_terms_hold_seq_kernel,
-// include/dragposer_holds.h): a held term's row of the wave's block is its hold's state, updated by run()'s epilogue (dp_cons_hold.h).  The
-// #if DP_CONS_HOLD blocks are the only difference; without DP_CONS_HOLD the six kernels above keep their instructions.
-// dp_cons_ar.hip includes it once more with DP_CONS_AR 1 on top of those four (dp_terms_ar_seq_kernel, include/dragposer_latent_ar.h): a
-// step's z_tgt row is formed from the sequence's last history rows, kept in a second LDS array (dp_cons_ar.h).  The #if DP_CONS_AR blocks are
-// the only difference; without DP_CONS_AR the seven kernels above keep their instructions.
-// dp_cons_gap.hip includes it twice more with DP_CONS_GAP 1 on top of DP_CONS_HOLD's four, without and with DP_CONS_AR
-// (dp_terms_gap_seq_kernel, dp_terms_gap_ar_seq_kernel, include/dragposer_gaps.h): `trk` is then a per-step value, the lane's code of the
-// step, decided from the joint's row of dp_gaps.state in global memory (dp_cons_gap.h).  The #if DP_CONS_GAP blocks are the only difference;
-// without DP_CONS_GAP the nine kernels above keep their instructions.
-// dp_cons_live.hip includes it twice more with DP_CONS_LIVE 1 on top of DP_CONS_GAP's five, without and with DP_CONS_AR (dp_live_kernel,
-// dp_live_ar_kernel, include/dragposer_live.h): the launch is one step, and the wave appends the step's row to the sequence's three history
-// buffers itself (dp_cons_live.h).  The #if DP_CONS_LIVE blocks are the only difference; without DP_CONS_LIVE the twelve kernels above keep
-// their instructions.
-// dp_cons_tether.hip includes it twice more with DP_CONS_TETHER 1 on top of DP_CONS_GAP's five, without and with DP_CONS_AR
-// (dp_terms_tether_seq_kernel, dp_terms_tether_ar_seq_kernel, include/dragposer_tethers.h): a tethered term's row of the wave's block is its
-// tether's, rewritten at each step's `stop` from the joint's new world position (dp_cons_tether.h).  The #if DP_CONS_TETHER blocks are the
-// only difference; without DP_CONS_TETHER the fourteen kernels above keep their instructions.
+// dp_cons_body.h -- the body of every kernel of the eight dp_cons*.hip units: one frame (or one sequence) per wave, optimised with Adam and
+// the while-condition in one launch (dp_cons.hip's header has the phases).  Not a header in the usual sense: no include guard, it opens with
+// the kernel's `{`, and a unit includes it once behind each `__global__ ... void name(Block a)` with the DP_CONS_* macros below set for that
+// kernel.  It is text rather than a function the kernels call because, passed through a function, even an inlined one, the argument block is
+// loaded whole at entry and the code changes (dp_cons_kernel: 78 -> 122 SGPRs, the surplus parked in VGPR lanes); included, each kernel
+// reads the fields it uses where it uses them.  Every difference between two kernels is an #if on one of these macros, and a macro that is
+// 0 or undefined leaves no instruction behind: a unit added with a new macro does not change the kernels of the others.  Helpers:
+// dp_cons_dev.h (and hold_of, dp_cons_hold.h).
+//
+//   macro            1 switches                                                                      defined to 1 by (kernels)
+//   DP_CONS_TABLE    the terms: a staged table of up to 16 PLANE / DISTANCE / ALIGN terms            every unit, per kernel: 0 for dp_cons_kernel,
+//                    (include/dragposer_terms.h) instead of the reference's four                     dp_cons_skel_kernel, dp_cons_seq_kernel; 1 for the rest
+//   DP_CONS_SKEL     the bones: each frame's own skeleton, read and screened in the prologue and     every unit but dp_cons.hip
+//                    kept in the wave's block (dp_cons_skel.h) instead of L_OFF
+//   DP_CONS_SEQ      a wave is a sequence: a.q.n_steps frames, each with the screening, the loop     dp_cons_seq.hip and the five units below
+//                    and the results, run()'s epilogue at its `stop`; latent, global position
+//                    and rotation carried in registers (dp_cons_seq.h)
+//   DP_CONS_HOLD     a held term's row of the wave's block is its hold's state, updated by the       dp_cons_hold.hip (dp_terms_hold_seq_kernel) and the four
+//                    epilogue (dp_cons_hold.h, include/dragposer_holds.h)                            units below
+//   DP_CONS_AR       a step's z_tgt row is formed from the sequence's last history rows, kept in     dp_cons_ar.hip (dp_terms_ar_seq_kernel); the second kernel
+//                    a second LDS array (dp_cons_ar.h, include/dragposer_latent_ar.h)                of dp_cons_gap.hip, dp_cons_live.hip, dp_cons_tether.hip
+//   DP_CONS_GAP      `trk` is the lane's code of the step, decided from the joint's row of           dp_cons_gap.hip (dp_terms_gap_seq_kernel, dp_terms_gap_ar_seq_kernel),
+//                    dp_gaps.state in global memory (dp_cons_gap.h, include/dragposer_gaps.h)        dp_cons_live.hip, dp_cons_tether.hip
+//   DP_CONS_LIVE     the launch is one step and the wave appends its row to the three history        dp_cons_live.hip (dp_live_kernel, dp_live_ar_kernel)
+//                    buffers itself (dp_cons_live.h, include/dragposer_live.h)
+//   DP_CONS_TETHER   a tethered term's row is its tether's, rewritten at each `stop` from the        dp_cons_tether.hip (dp_terms_tether_seq_kernel,
+//                    joint's new world position (dp_cons_tether.h, include/dragposer_tethers.h)      dp_terms_tether_ar_seq_kernel)
 {
     constexpr bool TBL = DP_CONS_TABLE;
 #if DP_CONS_SKEL

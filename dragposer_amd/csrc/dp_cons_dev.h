@@ -1,5 +1,5 @@
-// dp_cons_dev.h -- device helpers of dp_cons_body.h, shared by its units: dp_cons.hip (the context's skeleton), dp_cons_skel.hip
-// (per-frame skeletons) and dp_cons_seq.hip (the frame loop of a sequence in the launch).  Included after dp_cons.h, dp_math.h and dp_vjp.h, inside a unit that says `using namespace dpcons;`.
+// dp_cons_dev.h -- device helpers of dp_cons_body.h and the launcher of its kernels, shared by its eight units (dp_cons.hip ..
+// dp_cons_tether.hip).  Included after the unit's dp_cons*.h, dp_math.h and dp_vjp.h, inside a unit that says `using namespace dpcons;`.
 #pragma once
 
 #define DEV __device__ __forceinline__
@@ -48,5 +48,14 @@ DEV bool reads_gp(const Args& a) { return a.w_floor != 0.f; }
 DEV bool reads_gp(const TermArgs& a) { return a.need_gp != 0; }
 
 DEV int uni_i(int x) { return __builtin_amdgcn_readfirstlane(x); } // (an int the wave holds in every lane)
+
+// host: what every dp_launch_* of these units does -- a wave per frame (or sequence), WPB waves per workgroup, the argument block by value
+template <class A>
+hipError_t launch_waves(void (*kernel)(A), const A* args, hipStream_t stream)
+{
+    const unsigned grid = (unsigned)((args->n_frames + WPB - 1) / WPB);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(WPB * 64), 0, stream, *args);
+    return hipGetLastError();
+}
 
 } // namespace

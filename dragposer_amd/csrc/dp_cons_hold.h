@@ -32,6 +32,18 @@ struct HoldSeqArgs : SeqTermArgs {
     HoldFields h;
 };
 
+#ifdef __HIPCC__
+// the hold on term t, or -1 (n and map: HoldFields::n_holds and ::terms, wave-uniform; re-derived where it is needed, never kept).  The
+// one copy for dp_cons_hold.hip and the four units on top of it; dp_cons_tether.h's map has the same width, so it walks that one too.
+__device__ __forceinline__ int hold_of(int n, unsigned map, int t)
+{
+    int h = -1;
+#pragma unroll
+    for (int k = 0; k < MAX_HOLDS; ++k) h = k < n && (int)((map >> (8 * k)) & 0xffu) == t ? k : h;
+    return h;
+}
+#endif
+
 } // namespace dpcons
 
 hipError_t dp_launch_terms_hold_seq(const dpcons::HoldSeqArgs* args, hipStream_t stream);

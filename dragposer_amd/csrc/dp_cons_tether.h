@@ -7,6 +7,7 @@
 namespace dpcons {
 
 constexpr int MAX_TETHERS = 4; // DP_MAX_TETHERS
+static_assert(MAX_TETHERS == MAX_HOLDS, "hold_of (dp_cons_hold.h) walks both maps");
 constexpr int TETHER_ROW = 8;  // DP_TETHER_STATE_FLOATS: (x, y, z, live) the term's row, (wx, wy, wz, have) the joint's last world position
 
 // LDS: dp_cons_gap.h's two layouts, unchanged, and one more array with one area per wave.  A tether's row (x, y, z, live) of the wave's

@@ -1338,20 +1338,54 @@ static int take_seq_extra(dp_ctx* ctx, const dp_seq_extra* e_in, dp_seq_extra& e
     return DP_OK;
 }
 
-// dp_cons_seq.hip is a unit a link of the host code may leave out (a host-only program without the kernel units): its two launchers are weak
-// references here, and a library without them refuses the calls with DP_ERR_UNSUPPORTED, as the header states.
-#ifndef DP_REF8_BUILD
+// The sequence units are units a link of the host code may leave out (a host-only program without the kernel units, the plug-in without
+// dp_cons_tether.hip): their launchers are weak references here, and a library without one refuses the call with DP_ERR_UNSUPPORTED, as
+// the headers state.
 hipError_t dp_launch_cons_seq(const dpcons::SeqConsArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_terms_seq(const dpcons::SeqTermArgs* args, hipStream_t stream) __attribute__((weak));
-hipError_t dp_launch_terms_hold_seq(const dpcons::HoldSeqArgs* args, hipStream_t stream) __attribute__((weak)); // (dp_cons_hold.hip, likewise)
-hipError_t dp_launch_terms_ar_seq(const dpcons::ArSeqArgs* args, hipStream_t stream) __attribute__((weak));     // (dp_cons_ar.hip, likewise)
-hipError_t dp_launch_terms_gap_seq(const dpcons::GapSeqArgs* args, hipStream_t stream) __attribute__((weak));    // (dp_cons_gap.hip, likewise)
+hipError_t dp_launch_terms_hold_seq(const dpcons::HoldSeqArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_terms_ar_seq(const dpcons::ArSeqArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_terms_gap_seq(const dpcons::GapSeqArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_terms_gap_ar_seq(const dpcons::GapArSeqArgs* args, hipStream_t stream) __attribute__((weak));
-hipError_t dp_launch_live(const dpcons::LiveSeqArgs* args, hipStream_t stream) __attribute__((weak));           // (dp_cons_live.hip, likewise)
+hipError_t dp_launch_live(const dpcons::LiveSeqArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_live_ar(const dpcons::LiveArSeqArgs* args, hipStream_t stream) __attribute__((weak));
-hipError_t dp_launch_terms_tether_seq(const dpcons::TetherSeqArgs* args, hipStream_t stream) __attribute__((weak)); // (dp_cons_tether.hip, likewise)
+hipError_t dp_launch_terms_tether_seq(const dpcons::TetherSeqArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_terms_tether_ar_seq(const dpcons::TetherArSeqArgs* args, hipStream_t stream) __attribute__((weak));
-#endif
+
+// One description per argument block of sequence_constrained_impl -- a new variant is a row here and its entry point.  Which optional parts a
+// block has (a.h, a.r, a.g, a.t, a.l) is read off the block itself (has_h .. has_l below).
+template <class A>
+struct SeqVariant {
+    hipError_t (*launch)(const A*, hipStream_t); // NULL: the link left the unit out
+    const char* unit;                            // ... and the refusal names it
+    bool appends_history;                        // the kernel appends the step's row itself: no second launch
+};
+template <class A> static SeqVariant<A> seq_variant();
+template <> SeqVariant<dpcons::SeqConsArgs> seq_variant() { return {dp_launch_cons_seq, "dp_cons_seq.hip", false}; }
+template <> SeqVariant<dpcons::SeqTermArgs> seq_variant() { return {dp_launch_terms_seq, "dp_cons_seq.hip", false}; }
+template <> SeqVariant<dpcons::HoldSeqArgs> seq_variant() { return {dp_launch_terms_hold_seq, "dp_cons_hold.hip", false}; }
+template <> SeqVariant<dpcons::ArSeqArgs> seq_variant() { return {dp_launch_terms_ar_seq, "dp_cons_ar.hip", false}; }
+template <> SeqVariant<dpcons::GapSeqArgs> seq_variant() { return {dp_launch_terms_gap_seq, "dp_cons_gap.hip", false}; }
+template <> SeqVariant<dpcons::GapArSeqArgs> seq_variant() { return {dp_launch_terms_gap_ar_seq, "dp_cons_gap.hip", false}; }
+template <> SeqVariant<dpcons::LiveSeqArgs> seq_variant() { return {dp_launch_live, "dp_cons_live.hip", true}; }
+template <> SeqVariant<dpcons::LiveArSeqArgs> seq_variant() { return {dp_launch_live_ar, "dp_cons_live.hip", true}; }
+template <> SeqVariant<dpcons::TetherSeqArgs> seq_variant() { return {dp_launch_terms_tether_seq, "dp_cons_tether.hip", false}; }
+template <> SeqVariant<dpcons::TetherArSeqArgs> seq_variant() { return {dp_launch_terms_tether_ar_seq, "dp_cons_tether.hip", false}; }
+
+#define DP_HAS_MEMBER(m)                                                   \
+    template <class A, class = void> struct has_##m : std::false_type {}; \
+    template <class A> struct has_##m<A, std::void_t<decltype(&A::m)>> : std::true_type {}
+DP_HAS_MEMBER(h); DP_HAS_MEMBER(r); DP_HAS_MEMBER(g); DP_HAS_MEMBER(t); DP_HAS_MEMBER(l); // HoldFields, ArFields, GapFields, TetherFields, LiveFields
+#undef DP_HAS_MEMBER
+
+// What a call with a term table brought beyond its frames and state, NULL where it has none (dp_optimize_sequence_constrained: all of it)
+struct SeqParts {
+    const dp_terms* terms = nullptr;
+    const dp_holds* holds = nullptr;
+    const dp_latent_ar* ar = nullptr;
+    const dp_gaps* gaps = nullptr;
+    const dp_tethers* tethers = nullptr;
+};
 
 // include/dragposer_latent_ar.h: dp_latent_ar checked, after everything dp_optimize_sequence_holds checks, against the launch's frames and
 // state, and written into the argument block
@@ -1385,133 +1419,25 @@ static int take_gaps(dp_ctx* ctx, const dp_gaps* g_in, dpcons::GapFields& g, con
     return DP_OK;
 }
 
-// what take_tethers checks dp_tethers against: the table and the holds the call was given (sequence_constrained_impl hands them through)
-struct TetherIn {
-    const dp_tethers* tethers;
-    const dp_terms* terms;
-    const dp_holds* holds;
-};
-static int take_tethers(dp_ctx* ctx, const TetherIn& in, unsigned* tbl, dpcons::TetherFields& t, const char* who);
-
-template <class A, class Own>
-static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
-                                     const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream, const char* who, Own own,
-                                     const dp_latent_ar* ar = nullptr, const dp_gaps* gaps = nullptr, const TetherIn* tethers = nullptr)
+// What entry k of a call's holds or tethers (E: dp_hold, dp_tether) may refer to: a point-DISTANCE term of the accepted table without a
+// per_frame array, which no earlier entry refers to.  "" or what is wrong with it (noun, verb: "hold", "held" / "tether", "tethered")
+template <class E>
+static std::string check_term_ref(const dp_terms& ts, const E* entries, int k, const std::string& noun, const char* verb)
 {
-    // (include/dragposer_live.h: the gap units' argument blocks and checks, the history append in the kernel instead of a second launch)
-    constexpr bool LIVE = std::is_same<A, dpcons::LiveSeqArgs>::value, LIVE_AR = std::is_same<A, dpcons::LiveArSeqArgs>::value;
-    // (include/dragposer_tethers.h: the gap units' argument blocks and checks, dp_tethers checked after dp_gaps)
-    constexpr bool TETHER = std::is_same<A, dpcons::TetherSeqArgs>::value, TETHER_AR = std::is_same<A, dpcons::TetherArSeqArgs>::value;
-    constexpr bool GAP = std::is_same<A, dpcons::GapSeqArgs>::value || LIVE || TETHER;
-    constexpr bool GAP_AR = std::is_same<A, dpcons::GapArSeqArgs>::value || LIVE_AR || TETHER_AR;
-    constexpr bool HOLDS = std::is_same<A, dpcons::HoldSeqArgs>::value, AR = std::is_same<A, dpcons::ArSeqArgs>::value || GAP_AR;
-    dp_params p;
-    if (int rc = take_params(ctx, p_in, p, who)) return rc;
-    dp_seq_results out;
-    if (int rc = take_sized(ctx, out_in, out, SEQ_RESULTS_V500, who)) return rc;
-    A a;
-    std::memset(&a, 0, sizeof(a));
-    if (int rc = own(a)) return rc;
-    if (sk)
-        if (int rc = take_skeleton(ctx, sk, a.skel, a.skel_stride, who)) return rc;
-    if (int rc = check_sequence(ctx, fr, st, adj, out, who, AR)) return rc;
-    if (int rc = check_adam(ctx, p, who)) return rc;
-    if constexpr (AR)
-        if (int rc = take_latent_ar(ctx, ar, fr, st, a.r, who)) return rc;
-    if constexpr (GAP || GAP_AR)
-        if (int rc = take_gaps(ctx, gaps, a.g, who)) return rc;
-    if constexpr (TETHER || TETHER_AR)
-        if (int rc = take_tethers(ctx, *tethers, a.tbl, a.t, who)) return rc;
-#ifdef DP_REF8_BUILD
-    (void)n_seq; (void)latent; (void)stream;
-    return refuse_ref8(ctx, who);
-#else
-    if (LIVE || LIVE_AR) {
-        if (!dp_launch_live || !dp_launch_live_ar)
-            return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_live.hip");
-    } else if (TETHER || TETHER_AR) {
-        if (!dp_launch_terms_tether_seq || !dp_launch_terms_tether_ar_seq)
-            return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_tether.hip");
-    } else if (GAP || GAP_AR) {
-        if (!dp_launch_terms_gap_seq || !dp_launch_terms_gap_ar_seq)
-            return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_gap.hip");
-    } else if (AR ? !dp_launch_terms_ar_seq : HOLDS ? !dp_launch_terms_hold_seq : (!dp_launch_cons_seq || !dp_launch_terms_seq))
-        return fail(ctx, DP_ERR_UNSUPPORTED,
-                    std::string(who) + ": this library was linked without " + (AR ? "dp_cons_ar.hip" : HOLDS ? "dp_cons_hold.hip" : "dp_cons_seq.hip"));
-    if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
-    a.img = ctx->d_vjpimg.get();
-    if (!sk) { a.skel = ctx->d_vjpimg.get() + dpvjp::OFF_BONE; a.skel_stride = 0; } // (the image's bone rows: what the per-frame kernels stage)
-    a.z0 = latent; a.z = latent; a.z_tgt = fr->z_tgt; a.cur_rot = st->global_rot; a.tgt_pos = fr->tgt_pos; a.tgt_rot = fr->tgt_rot; a.w = fr->w;
-    a.tracked = fr->tracked; a.n_frames = n_seq;
-    a.pose = out.pose_ret; a.world_rot = out.world_rot; a.iters = out.iters; a.loss = out.loss; a.status = out.status;
-    fill_loop(a, p, true);
-    a.beta1d = p.beta1; a.beta2d = p.beta2; a.lrd = p.lr;
-    fill_sequence(a.q, ctx, fr, st, adj, out);
-    if constexpr (LIVE || LIVE_AR) {
-        a.l.latent_buf = st->latent_buf; a.l.disp_buf = st->disp_buf; a.l.heights_buf = st->heights_buf; a.l.history = st->history;
-    }
-    {
-        DEVICE_GUARD(ctx);
-        hipError_t e;
-        if constexpr (std::is_same<A, dpcons::SeqConsArgs>::value) e = dp_launch_cons_seq(&a, (hipStream_t)stream);
-        else if constexpr (LIVE) e = dp_launch_live(&a, (hipStream_t)stream);
-        else if constexpr (LIVE_AR) e = dp_launch_live_ar(&a, (hipStream_t)stream);
-        else if constexpr (TETHER) e = dp_launch_terms_tether_seq(&a, (hipStream_t)stream);
-        else if constexpr (TETHER_AR) e = dp_launch_terms_tether_ar_seq(&a, (hipStream_t)stream);
-        else if constexpr (GAP) e = dp_launch_terms_gap_seq(&a, (hipStream_t)stream);
-        else if constexpr (GAP_AR) e = dp_launch_terms_gap_ar_seq(&a, (hipStream_t)stream);
-        else if constexpr (HOLDS) e = dp_launch_terms_hold_seq(&a, (hipStream_t)stream);
-        else if constexpr (AR) e = dp_launch_terms_ar_seq(&a, (hipStream_t)stream);
-        else e = dp_launch_terms_seq(&a, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
-    }
-    if (LIVE || LIVE_AR) return DP_OK; // (the kernel has appended the step's row itself)
-    return append_history(ctx, n_seq, fr, st, out, stream);
-#endif
+    const int term = entries[k].term;
+    const std::string tn = "term " + std::to_string(term);
+    if (term < 0 || term >= ts.n_terms) return tn + " outside the table of " + std::to_string(ts.n_terms);
+    const dp_term& t = ts.terms[term];
+    if (t.type != DP_TERM_DISTANCE) return tn + " is not a DP_TERM_DISTANCE term";
+    if (t.joint_b != -1) return tn + " has a joint_b (a " + noun + " needs a point-DISTANCE term)";
+    if (t.per_frame) return tn + " has a per_frame array (the " + noun + "'s state is its row)";
+    for (int g = 0; g < k; ++g)
+        if (entries[g].term == term) return tn + " is already " + verb + " by " + noun + " " + std::to_string(g);
+    return "";
 }
 
-extern "C" int dp_optimize_sequence_constrained(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in,
-                                                const dp_constraints* c_in, const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj,
-                                                const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
-{
-    const char* who = "dp_optimize_sequence_constrained";
-    const auto own = [&](dpcons::SeqConsArgs& a) -> int {
-        if (int rc = take_constraints(ctx, c_in, a, who, st)) return rc;
-        dp_seq_extra e;
-        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
-        a.loss_extra = e.loss_extra; a.pos = e.joint_pos;
-        return DP_OK;
-    };
-    return entry(ctx, who, [&] {
-        if (n_seq <= 0 || !latent || !fr || !p_in || !c_in || !st || !out)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_constrained: n_sequences must be positive; NULL latent, frames, params, constraints, state or results");
-        return sequence_constrained_impl<dpcons::SeqConsArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own);
-    });
-}
-
-extern "C" int dp_optimize_sequence_terms(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
-                                          const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out,
-                                          const dp_seq_extra* extra, void* stream)
-{
-    const char* who = "dp_optimize_sequence_terms";
-    const auto own = [&](dpcons::SeqTermArgs& a) -> int {
-        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
-        dp_seq_extra e;
-        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
-        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
-        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
-        return DP_OK;
-    };
-    return entry(ctx, who, [&] {
-        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !st || !out)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_terms: n_sequences must be positive; NULL latent, frames, params, terms, state or results");
-        return sequence_constrained_impl<dpcons::SeqTermArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own);
-    });
-}
-
-// include/dragposer_holds.h: dp_optimize_sequence_terms with holds (A = dpcons::HoldSeqArgs).  take_holds runs after take_terms has accepted
-// the table t_in: it checks dp_holds against it, puts each hold's level and thresholds into its term's staged axis_a words (a point-DISTANCE
-// term never reads them) and fills the hold-to-term map (dp_cons_hold.h).
+// include/dragposer_holds.h: dp_holds checked after take_terms has accepted the table t_in, against it; each hold's level and thresholds go
+// into its term's staged axis_a words (a point-DISTANCE term never reads them) and the hold-to-term map is filled (dp_cons_hold.h).
 static int take_holds(dp_ctx* ctx, const dp_holds* h_in, const dp_terms* t_in, dpcons::HoldSeqArgs& a, const char* who)
 {
     const std::string nm = who;
@@ -1527,15 +1453,8 @@ static int take_holds(dp_ctx* ctx, const dp_holds* h_in, const dp_terms* t_in, d
     for (int h = 0; h < hs.n_holds; ++h) {
         const dp_hold& hd = hs.holds[h];
         const std::string hn = nm + ": hold " + std::to_string(h) + ": ";
-        if (hd.term < 0 || hd.term >= ts.n_terms)
-            return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " outside the table of " + std::to_string(ts.n_terms));
-        const dp_term& t = ts.terms[hd.term];
-        if (t.type != DP_TERM_DISTANCE) return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " is not a DP_TERM_DISTANCE term");
-        if (t.joint_b != -1) return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " has a joint_b (a hold needs a point-DISTANCE term)");
-        if (t.per_frame) return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " has a per_frame array (the hold's state is its row)");
-        for (int g = 0; g < h; ++g)
-            if (hs.holds[g].term == hd.term)
-                return fail(ctx, DP_ERR_INVALID, hn + "term " + std::to_string(hd.term) + " is already held by hold " + std::to_string(g));
+        const std::string why = check_term_ref(ts, hs.holds, h, "hold", "held");
+        if (!why.empty()) return fail(ctx, DP_ERR_INVALID, hn + why);
         if (!std::isfinite(hd.level) || !std::isfinite(hd.contact_lo) || !std::isfinite(hd.contact_hi))
             return fail(ctx, DP_ERR_INVALID, hn + "non-finite level, contact_lo or contact_hi");
         if (hd.contact_lo > hd.contact_hi) return fail(ctx, DP_ERR_INVALID, hn + "contact_lo is above contact_hi");
@@ -1546,80 +1465,10 @@ static int take_holds(dp_ctx* ctx, const dp_holds* h_in, const dp_terms* t_in, d
     return DP_OK;
 }
 
-extern "C" int dp_optimize_sequence_holds(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
-                                          const dp_holds* h_in, const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj,
-                                          const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
-{
-    const char* who = "dp_optimize_sequence_holds";
-    const auto own = [&](dpcons::HoldSeqArgs& a) -> int {
-        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
-        if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
-        dp_seq_extra e;
-        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
-        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
-        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
-        return DP_OK;
-    };
-    return entry(ctx, who, [&] {
-        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !h_in || !st || !out)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_holds: n_sequences must be positive; NULL latent, frames, params, terms, holds, state or results");
-        return sequence_constrained_impl<dpcons::HoldSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own);
-    });
-}
-
-// include/dragposer_latent_ar.h: dp_optimize_sequence_holds with the step's z_tgt formed in the launch (A = dpcons::ArSeqArgs); `holds` may be
-// NULL, and dp_latent_ar is checked last (take_latent_ar, from sequence_constrained_impl)
-extern "C" int dp_optimize_sequence_ar(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
-                                       const dp_holds* h_in, const dp_latent_ar* r_in, const dp_skeleton_in* skel, const dp_seq_state* st,
-                                       const dp_seq_step* adj, const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
-{
-    const char* who = "dp_optimize_sequence_ar";
-    const auto own = [&](dpcons::ArSeqArgs& a) -> int {
-        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
-        if (h_in)
-            if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
-        dp_seq_extra e;
-        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
-        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
-        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
-        return DP_OK;
-    };
-    return entry(ctx, who, [&] {
-        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !r_in || !st || !out)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_ar: n_sequences must be positive; NULL latent, frames, params, terms, ar, state or results");
-        return sequence_constrained_impl<dpcons::ArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in);
-    });
-}
-
-// include/dragposer_gaps.h: dp_optimize_sequence_ar with a tracker set decided per step (A = dpcons::GapArSeqArgs; `ar` NULL:
-// dpcons::GapSeqArgs, dp_optimize_sequence_holds' frames->z_tgt); dp_gaps is checked last (take_gaps, from sequence_constrained_impl)
-extern "C" int dp_optimize_sequence_gaps(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
-                                         const dp_holds* h_in, const dp_latent_ar* r_in, const dp_gaps* g_in, const dp_skeleton_in* skel,
-                                         const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
-{
-    const char* who = "dp_optimize_sequence_gaps";
-    const auto own = [&](auto& a) -> int {
-        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
-        if (h_in)
-            if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
-        dp_seq_extra e;
-        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
-        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
-        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
-        return DP_OK;
-    };
-    return entry(ctx, who, [&] {
-        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !g_in || !st || !out)
-            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_gaps: n_sequences must be positive; NULL latent, frames, params, terms, gaps, state or results");
-        if (r_in) return sequence_constrained_impl<dpcons::GapArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in, g_in);
-        return sequence_constrained_impl<dpcons::GapSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, nullptr, g_in);
-    });
-}
-
 // include/dragposer_tethers.h: dp_tethers checked, after everything dp_optimize_sequence_gaps checks, against the table and the holds the
 // call was given (both accepted by then); each tether's alpha goes into its term's first staged axis_a word (a point-DISTANCE term never
 // reads it, and no hold has put its level there: a tethered term is not held) and the tether-to-term map is filled (dp_cons_tether.h)
-static int take_tethers(dp_ctx* ctx, const TetherIn& in, unsigned* tbl, dpcons::TetherFields& tf, const char* who)
+static int take_tethers(dp_ctx* ctx, const SeqParts& in, unsigned* tbl, dpcons::TetherFields& tf, const char* who)
 {
     const std::string nm = who;
     dp_tethers ts;
@@ -1637,15 +1486,8 @@ static int take_tethers(dp_ctx* ctx, const TetherIn& in, unsigned* tbl, dpcons::
     for (int k = 0; k < ts.n_tethers; ++k) {
         const dp_tether& te = ts.tethers[k];
         const std::string tn = nm + ": tether " + std::to_string(k) + ": ";
-        if (te.term < 0 || te.term >= tt.n_terms)
-            return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " outside the table of " + std::to_string(tt.n_terms));
-        const dp_term& t = tt.terms[te.term];
-        if (t.type != DP_TERM_DISTANCE) return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " is not a DP_TERM_DISTANCE term");
-        if (t.joint_b != -1) return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " has a joint_b (a tether needs a point-DISTANCE term)");
-        if (t.per_frame) return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " has a per_frame array (the tether's state is its row)");
-        for (int g = 0; g < k; ++g)
-            if (ts.tethers[g].term == te.term)
-                return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " is already tethered by tether " + std::to_string(g));
+        const std::string why = check_term_ref(tt, ts.tethers, k, "tether", "tethered");
+        if (!why.empty()) return fail(ctx, DP_ERR_INVALID, tn + why);
         for (int h = 0; h < hs.n_holds; ++h)
             if (hs.holds[h].term == te.term)
                 return fail(ctx, DP_ERR_INVALID, tn + "term " + std::to_string(te.term) + " is held by hold " + std::to_string(h));
@@ -1656,6 +1498,157 @@ static int take_tethers(dp_ctx* ctx, const TetherIn& in, unsigned* tbl, dpcons::
     return DP_OK;
 }
 
+// Every whole-sequence launch of dp_cons_body.h's kernels (A: a block with a seq_variant row), whose caller has refused a NULL argument.
+// own(a) validates the entry point's own structs and writes them into the zeroed block; the parts a block has beyond them are checked
+// after Adam in the order the layers were stacked: dp_latent_ar, dp_gaps, dp_tethers.
+template <class A, class Own>
+static int sequence_constrained_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
+                                     const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, void* stream, const char* who, Own own,
+                                     const SeqParts& parts)
+{
+    const SeqVariant<A> v = seq_variant<A>();
+    dp_params p;
+    if (int rc = take_params(ctx, p_in, p, who)) return rc;
+    dp_seq_results out;
+    if (int rc = take_sized(ctx, out_in, out, SEQ_RESULTS_V500, who)) return rc;
+    A a;
+    std::memset(&a, 0, sizeof(a));
+    if (int rc = own(a)) return rc;
+    if (sk)
+        if (int rc = take_skeleton(ctx, sk, a.skel, a.skel_stride, who)) return rc;
+    if (int rc = check_sequence(ctx, fr, st, adj, out, who, has_r<A>::value)) return rc;
+    if (int rc = check_adam(ctx, p, who)) return rc;
+    if constexpr (has_r<A>::value)
+        if (int rc = take_latent_ar(ctx, parts.ar, fr, st, a.r, who)) return rc;
+    if constexpr (has_g<A>::value)
+        if (int rc = take_gaps(ctx, parts.gaps, a.g, who)) return rc;
+    if constexpr (has_t<A>::value)
+        if (int rc = take_tethers(ctx, parts, a.tbl, a.t, who)) return rc;
+    if (REF8_BUILD) return refuse_ref8(ctx, who);
+    if (!v.launch) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without " + v.unit);
+    if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+    a.img = ctx->d_vjpimg.get();
+    if (!sk) { a.skel = ctx->d_vjpimg.get() + dpvjp::OFF_BONE; a.skel_stride = 0; } // (the image's bone rows: what the per-frame kernels stage)
+    a.z0 = latent; a.z = latent; a.z_tgt = fr->z_tgt; a.cur_rot = st->global_rot; a.tgt_pos = fr->tgt_pos; a.tgt_rot = fr->tgt_rot; a.w = fr->w;
+    a.tracked = fr->tracked; a.n_frames = n_seq;
+    a.pose = out.pose_ret; a.world_rot = out.world_rot; a.iters = out.iters; a.loss = out.loss; a.status = out.status;
+    fill_loop(a, p, true);
+    a.beta1d = p.beta1; a.beta2d = p.beta2; a.lrd = p.lr;
+    fill_sequence(a.q, ctx, fr, st, adj, out);
+    if constexpr (has_l<A>::value) {
+        a.l.latent_buf = st->latent_buf; a.l.disp_buf = st->disp_buf; a.l.heights_buf = st->heights_buf; a.l.history = st->history;
+    }
+    {
+        DEVICE_GUARD(ctx);
+        const hipError_t e = v.launch(&a, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
+    }
+    if (v.appends_history) return DP_OK;
+    return append_history(ctx, n_seq, fr, st, out, stream);
+}
+
+// ... with a term table (every entry point but dp_optimize_sequence_constrained): own(a) is the table, the holds if the call has any,
+// dp_seq_extra, then each term's step between rows (dp_cons_seq.h)
+template <class A>
+static int sequence_terms_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_skeleton_in* sk,
+                               const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out, const dp_seq_extra* extra, void* stream,
+                               const char* who, const SeqParts& parts)
+{
+    const auto own = [&](A& a) -> int {
+        if (int rc = take_terms(ctx, parts.terms, a, who, st)) return rc;
+        if constexpr (has_h<A>::value)
+            if (parts.holds)
+                if (int rc = take_holds(ctx, parts.holds, parts.terms, a, who)) return rc;
+        dp_seq_extra e;
+        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
+        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
+        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k];
+        return DP_OK;
+    };
+    return sequence_constrained_impl<A>(ctx, n_seq, latent, fr, p_in, sk, st, adj, out, stream, who, own, parts);
+}
+
+extern "C" int dp_optimize_sequence_constrained(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in,
+                                                const dp_constraints* c_in, const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj,
+                                                const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_constrained";
+    const auto own = [&](dpcons::SeqConsArgs& a) -> int {
+        if (int rc = take_constraints(ctx, c_in, a, who, st)) return rc;
+        dp_seq_extra e;
+        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
+        a.loss_extra = e.loss_extra; a.pos = e.joint_pos;
+        return DP_OK;
+    };
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !c_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_constrained: n_sequences must be positive; NULL latent, frames, params, constraints, state or results");
+        return sequence_constrained_impl<dpcons::SeqConsArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, SeqParts{});
+    });
+}
+
+extern "C" int dp_optimize_sequence_terms(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                          const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out,
+                                          const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_terms";
+    SeqParts parts;
+    parts.terms = t_in;
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_terms: n_sequences must be positive; NULL latent, frames, params, terms, state or results");
+        return sequence_terms_impl<dpcons::SeqTermArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
+    });
+}
+
+// include/dragposer_holds.h: dp_optimize_sequence_terms with holds (A = dpcons::HoldSeqArgs)
+extern "C" int dp_optimize_sequence_holds(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                          const dp_holds* h_in, const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj,
+                                          const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_holds";
+    SeqParts parts;
+    parts.terms = t_in; parts.holds = h_in;
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !h_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_holds: n_sequences must be positive; NULL latent, frames, params, terms, holds, state or results");
+        return sequence_terms_impl<dpcons::HoldSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
+    });
+}
+
+// include/dragposer_latent_ar.h: dp_optimize_sequence_holds with the step's z_tgt formed in the launch (A = dpcons::ArSeqArgs); `holds` may be
+// NULL, and dp_latent_ar is checked last (take_latent_ar, from sequence_constrained_impl)
+extern "C" int dp_optimize_sequence_ar(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                       const dp_holds* h_in, const dp_latent_ar* r_in, const dp_skeleton_in* skel, const dp_seq_state* st,
+                                       const dp_seq_step* adj, const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_ar";
+    SeqParts parts;
+    parts.terms = t_in; parts.holds = h_in; parts.ar = r_in;
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !r_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_ar: n_sequences must be positive; NULL latent, frames, params, terms, ar, state or results");
+        return sequence_terms_impl<dpcons::ArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
+    });
+}
+
+// include/dragposer_gaps.h: dp_optimize_sequence_ar with a tracker set decided per step (A = dpcons::GapArSeqArgs; `ar` NULL:
+// dpcons::GapSeqArgs, dp_optimize_sequence_holds' frames->z_tgt); dp_gaps is checked last (take_gaps, from sequence_constrained_impl)
+extern "C" int dp_optimize_sequence_gaps(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                         const dp_holds* h_in, const dp_latent_ar* r_in, const dp_gaps* g_in, const dp_skeleton_in* skel,
+                                         const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_gaps";
+    SeqParts parts;
+    parts.terms = t_in; parts.holds = h_in; parts.ar = r_in; parts.gaps = g_in;
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !g_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_gaps: n_sequences must be positive; NULL latent, frames, params, terms, gaps, state or results");
+        if (r_in) return sequence_terms_impl<dpcons::GapArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
+        return sequence_terms_impl<dpcons::GapSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
+    });
+}
+
 // include/dragposer_tethers.h: dp_optimize_sequence_gaps with tethers (A = dpcons::TetherArSeqArgs; `ar` NULL: dpcons::TetherSeqArgs);
 // dp_tethers is checked last (take_tethers, from sequence_constrained_impl)
 extern "C" int dp_optimize_sequence_tethers(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
@@ -1664,23 +1657,14 @@ extern "C" int dp_optimize_sequence_tethers(dp_ctx* ctx, int n_seq, float* laten
                                             const dp_seq_extra* extra, void* stream)
 {
     const char* who = "dp_optimize_sequence_tethers";
-    const auto own = [&](auto& a) -> int {
-        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
-        if (h_in)
-            if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
-        dp_seq_extra e;
-        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
-        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
-        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
-        return DP_OK;
-    };
+    SeqParts parts;
+    parts.terms = t_in; parts.holds = h_in; parts.ar = r_in; parts.gaps = g_in; parts.tethers = te_in;
     return entry(ctx, who, [&] {
         if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !g_in || !te_in || !st || !out)
             return fail(ctx, DP_ERR_INVALID,
                         "dp_optimize_sequence_tethers: n_sequences must be positive; NULL latent, frames, params, terms, gaps, tethers, state or results");
-        const TetherIn tin = {te_in, t_in, h_in};
-        if (r_in) return sequence_constrained_impl<dpcons::TetherArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in, g_in, &tin);
-        return sequence_constrained_impl<dpcons::TetherSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, nullptr, g_in, &tin);
+        if (r_in) return sequence_terms_impl<dpcons::TetherArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
+        return sequence_terms_impl<dpcons::TetherSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
     });
 }
 
@@ -1690,22 +1674,14 @@ extern "C" int dp_live_step(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_
                             const dp_seq_step* adj, const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
 {
     const char* who = "dp_live_step";
-    const auto own = [&](auto& a) -> int {
-        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
-        if (h_in)
-            if (int rc = take_holds(ctx, h_in, t_in, a, who)) return rc;
-        dp_seq_extra e;
-        if (int rc = take_seq_extra(ctx, extra, e, who)) return rc;
-        a.loss_terms = e.loss_terms; a.pos = e.joint_pos;
-        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)e.row_step[k]; // (dp_cons_seq.h)
-        return DP_OK;
-    };
+    SeqParts parts;
+    parts.terms = t_in; parts.holds = h_in; parts.ar = r_in; parts.gaps = g_in;
     return entry(ctx, who, [&] {
         if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !g_in || !st || !out)
             return fail(ctx, DP_ERR_INVALID, "dp_live_step: n_sequences must be positive; NULL latent, frames, params, terms, gaps, state or results");
         if (fr->n_steps != 1) return fail(ctx, DP_ERR_INVALID, "dp_live_step: frames->n_steps is " + std::to_string(fr->n_steps) + ", a live step is one frame");
-        if (r_in) return sequence_constrained_impl<dpcons::LiveArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, r_in, g_in);
-        return sequence_constrained_impl<dpcons::LiveSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, stream, who, own, nullptr, g_in);
+        if (r_in) return sequence_terms_impl<dpcons::LiveArSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
+        return sequence_terms_impl<dpcons::LiveSeqArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
     });
 }
 
