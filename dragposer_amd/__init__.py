@@ -1,6 +1,7 @@
 from .autograd import decode_fk  # noqa: F401  (differentiable decode + FK: include/dragposer_grad.h)
 from .constraints import Constraints  # noqa: F401  (the reference's extra loss terms: include/dragposer_constraints.h)
 from .terms import Term, Terms  # noqa: F401  (user-defined constraint terms: include/dragposer_terms.h)
+from .points import Point, Points  # noqa: F401  (terms on weighted joint combinations: include/dragposer_points.h)
 from .holds import Hold, Holds  # noqa: F401  (joints held where they touched down: include/dragposer_holds.h)
 from .gaps import Gaps  # noqa: F401  (trackers that drop out and come back: include/dragposer_gaps.h)
 from .tethers import Tether, Tethers  # noqa: F401  (joints tied to their own recent path: include/dragposer_tethers.h)

@@ -278,6 +278,16 @@ class DpTethers(_Sized):
                 ("trace", C.c_void_p)]
 
 
+# every symbol include/dragposer_points.h declares (tests/test_points_abi.py)
+POINT_SYMBOLS = ("dp_optimize_terms_points", "dp_optimize_terms_points_skeleton", "dp_optimize_sequence_terms_points")
+DP_MAX_POINTS = 4
+
+
+class DpPoints(_Sized):
+    """include/dragposer_points.h: dp_points (coeff: a HOST array [n_points][22] of floats)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("n_points", C.c_int), ("reserved1", C.c_int), ("coeff", C.c_void_p)]
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -376,6 +386,12 @@ def load(path=None):
     lib.dp_live_step.argtypes = lib.dp_optimize_sequence_gaps.argtypes
     lib.dp_optimize_sequence_tethers.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
                                                  C.POINTER(DpHolds), C.POINTER(DpLatentAR), C.POINTER(DpGaps), C.POINTER(DpTethers)] + _seq_tail
+    lib.dp_optimize_terms_points.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpTerms), C.POINTER(DpPoints),
+                                             C.POINTER(DpResult), C.c_void_p]
+    lib.dp_optimize_terms_points_skeleton.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpParams), C.POINTER(DpTerms), C.POINTER(DpPoints),
+                                                      C.POINTER(DpSkeletonIn), C.POINTER(DpResult), C.c_void_p]
+    lib.dp_optimize_sequence_terms_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
+                                                      C.POINTER(DpPoints)] + _seq_tail
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

@@ -1,4 +1,4 @@
-// dp_cons_body.h -- the body of every kernel of the eight dp_cons*.hip units: one frame (or one sequence) per wave, optimised with Adam and
+// dp_cons_body.h -- the body of every kernel of the nine dp_cons*.hip units: one frame (or one sequence) per wave, optimised with Adam and
 // the while-condition in one launch (dp_cons.hip's header has the phases).  Not a header in the usual sense: no include guard, it opens with
 // the kernel's `{`, and a unit includes it once behind each `__global__ ... void name(Block a)` with the DP_CONS_* macros below set for that
 // kernel.  It is text rather than a function the kernels call because, passed through a function, even an inlined one, the argument block is
@@ -25,9 +25,18 @@
 //                    buffers itself (dp_cons_live.h, include/dragposer_live.h)
 //   DP_CONS_TETHER   a tethered term's row is its tether's, rewritten at each `stop` from the        dp_cons_tether.hip (dp_terms_tether_seq_kernel,
 //                    joint's new world position (dp_cons_tether.h, include/dragposer_tethers.h)      dp_terms_tether_ar_seq_kernel)
+//   DP_CONS_POINTS   a PLANE or DISTANCE term's index 22 + k is point k, sum_j m_k[j] P_j: formed      dp_cons_points.hip (dp_terms_points_kernel,
+//                    per iteration into the wave's block, the selectors `j == ja` replaced by the    dp_terms_points_skel_kernel, dp_terms_points_seq_kernel)
+//                    lane's coefficient (dp_cons_points.h, include/dragposer_points.h)
 {
     constexpr bool TBL = DP_CONS_TABLE;
+#if DP_CONS_POINTS // (the table layouts with the points' area behind each wave's block and the coefficients behind the last: dp_cons_points.h)
+    constexpr int N_LDS = DP_CONS_SKEL ? PT_SK_LDS_FLOATS : PT_LDS_FLOATS, W_STRIDE = DP_CONS_SKEL ? PT_SK_W_STRIDE : PT_W_STRIDE;
+    constexpr int W_PT = DP_CONS_SKEL ? PT_SK_W_PT : PT_W_PT, L_COEF = DP_CONS_SKEL ? PT_SK_L_COEF : PT_L_COEF;
 #if DP_CONS_SKEL
+    constexpr int W_SK = W_SKEL_T;
+#endif
+#elif DP_CONS_SKEL
     constexpr int N_LDS = TBL ? SK_LDS_FLOATS_T : SK_LDS_FLOATS, W_STRIDE = TBL ? SK_W_FLOATS_T : SK_W_FLOATS;
     constexpr int W_SK = TBL ? W_SKEL_T : W_SKEL;
 #else
@@ -60,6 +69,9 @@
 #endif
 #if DP_CONS_TABLE
     for (int i = tid; i < a.n_terms * TW; i += WPB * 64) ((unsigned*)lds)[L_TBL + i] = a.tbl[i];
+#endif
+#if DP_CONS_POINTS // (every row: a row beyond n_points is zero and no term names it)
+    if (tid < PT_COEF_FLOATS) lds[L_COEF + tid] = a.pt.coeff[tid];
 #endif
     __syncthreads();
     if (tid < NJ) { // ancestors of tid (itself included), parked in sub[] for the moment
@@ -520,6 +532,20 @@
             for (int k = 0; k < 9; ++k) GB[9 * j + k] = G[k];
         }
         wave_sync();
+#if DP_CONS_POINTS
+        // the points' positions: lane 4k + c forms component c of P_(22+k) = sum_j m_k[j] P_j, one fmaf per joint in joint order from 0, so
+        // that a unit point's sum is its joint's position exactly (0 + 0 P_i = 0, 0 + 1 P_j = P_j, P_j + 0 P_i = P_j)
+        if (a.pt.n_points > 0) {
+            if (lane < 4 * a.pt.n_points && (lane & 3) != 3) {
+                const float* mk = lds + L_COEF + (lane >> 2) * PT_NJ;
+                float s = 0.f;
+#pragma unroll UNR
+                for (int i = 0; i < NJ; ++i) s = fmaf(mk[i], PB[4 * i + (lane & 3)], s);
+                wb[W_PT + lane] = s;
+            }
+            wave_sync();
+        }
+#endif
 
         // ---- losses and upstream gradients (drag_pose.py:115-127 and the Additional Losses block, 129-183)
         float dpj = 0.f, drj = 0.f, gPj[3] = {0.f, 0.f, 0.f}, gGj[9];
@@ -657,31 +683,64 @@
                 const int type = uni_i(ti[T_TYPE]), ja = uni_i(ti[T_JA]), jb = uni_i(ti[T_JB]), fl = uni_i(ti[T_FLAGS]);
                 const bool drop = (fl & DP_TERM_DROP_UP) != 0;
                 float val = 0.f;
+#if DP_CONS_POINTS
+                // An index below 22 is a joint, 22 + k is point k: its position row (the format of W_P's) and this lane's coefficient of it --
+                // 1 or 0 for a joint, the other kernels' `j == ja`; m_k[j] for a point, lane j reading word j of row k.  Wave-uniform bases.
+                // (ALIGN never names a point: the host refuses it.)
+                const float* const PA = ja < NJ ? PB + 4 * ja : wb + W_PT + 4 * (ja - NJ);
+                const float* const PBb = jb < NJ ? PB + 4 * (jb < 0 ? 0 : jb) : wb + W_PT + 4 * (jb - NJ);
+                const float ca = ja < NJ ? (j == ja ? 1.f : 0.f) : (jl ? lds[L_COEF + (ja - NJ) * PT_NJ + j] : 0.f);
+                const float cb = jb < NJ ? (j == jb ? 1.f : 0.f) : (jl ? lds[L_COEF + (jb - NJ) * PT_NJ + j] : 0.f);
+#endif
                 if (type == DP_TERM_PLANE) { // d = dir . (g + P_a - point)
                     float dd = 0.f;
 #pragma unroll
+#if DP_CONS_POINTS
+                    for (int c = 0; c < 3; ++c) dd = fmaf(tb[T_DIR + c], (gp[c] + PA[c]) - RW[4 * t + c], dd);
+#else
                     for (int c = 0; c < 3; ++c) dd = fmaf(tb[T_DIR + c], (gp[c] + PB[4 * ja + c]) - RW[4 * t + c], dd);
+#endif
                     float g = dd;
                     if (fl & DP_TERM_ONE_SIDED) g = dd < 0.f ? dd : 0.f; // -relu(-d)
                     val = ws * (g * g);
+#if DP_CONS_POINTS // (the factor times the coefficient: at 1 the factor itself, and the fmaf is the joint's)
+                    if (ca != 0.f) {
+                        const float gf = 2.f * ws * g;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) gPj[c] = fmaf(__fmul_rn(ca, gf), tb[T_DIR + c], gPj[c]);
+                    }
+#else
                     if (j == ja)
 #pragma unroll
                         for (int c = 0; c < 3; ++c) gPj[c] = fmaf(2.f * ws * g, tb[T_DIR + c], gPj[c]);
+#endif
                 } else if (type == DP_TERM_DISTANCE) { // q = |h(P_a - P_b)|^2 or |h(g + P_a - point)|^2
                     float u[3];
                     if (jb >= 0) {
 #pragma unroll
+#if DP_CONS_POINTS
+                        for (int c = 0; c < 3; ++c) u[c] = PA[c] - PBb[c];
+#else
                         for (int c = 0; c < 3; ++c) u[c] = PB[4 * ja + c] - PB[4 * jb + c];
+#endif
                     } else {
 #pragma unroll
+#if DP_CONS_POINTS
+                        for (int c = 0; c < 3; ++c) u[c] = (gp[c] + PA[c]) - RW[4 * t + c];
+#else
                         for (int c = 0; c < 3; ++c) u[c] = (gp[c] + PB[4 * ja + c]) - RW[4 * t + c];
+#endif
                     }
                     if (drop) flatten(u, up);
                     const float q = u[0] * u[0] + u[1] * u[1] + u[2] * u[2];
                     const float xh = q - tb[T_P1], xl = tb[T_P0] - q; // (p0, p1 staged as lo^2, hi^2)
                     const float dq = (xh > 0.f ? ws : 0.f) - (xl > 0.f ? ws : 0.f);
                     val = ws * ((xh > 0.f ? xh : 0.f) + (xl > 0.f ? xl : 0.f));
+#if DP_CONS_POINTS // (1 - 0, 0 - 1, 0 - 0 and 1 - 1 for two joints, as below; the same point twice: m - m = 0)
+                    const float sgn = ca - cb;
+#else
                     const float sgn = (j == ja ? 1.f : 0.f) - (j == jb ? 1.f : 0.f);
+#endif
 #pragma unroll
                     for (int c = 0; c < 3; ++c) gPj[c] += sgn * 2.f * dq * u[c];
                 } else { // DP_TERM_ALIGN: u = h(G_a axis_a), v = h(G_b axis_b) or h(dir)

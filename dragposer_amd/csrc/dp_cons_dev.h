@@ -1,5 +1,5 @@
-// dp_cons_dev.h -- device helpers of dp_cons_body.h and the launcher of its kernels, shared by its eight units (dp_cons.hip ..
-// dp_cons_tether.hip).  Included after the unit's dp_cons*.h, dp_math.h and dp_vjp.h, inside a unit that says `using namespace dpcons;`.
+// dp_cons_dev.h -- device helpers of dp_cons_body.h and the launcher of its kernels, shared by its nine units (dp_cons.hip ..
+// dp_cons_points.hip).  Included after the unit's dp_cons*.h, dp_math.h and dp_vjp.h, inside a unit that says `using namespace dpcons;`.
 #pragma once
 
 #define DEV __device__ __forceinline__

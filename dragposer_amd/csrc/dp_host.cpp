@@ -25,8 +25,10 @@
 #include "../../include/dragposer_gaps.h"
 #include "../../include/dragposer_live.h"
 #include "../../include/dragposer_tethers.h"
+#include "../../include/dragposer_points.h"
 #include "dp_cons_live.h"
 #include "dp_cons_tether.h"
+#include "dp_cons_points.h"
 #include "dp_host_rt.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -681,6 +683,7 @@ constexpr Sized HOLDS_V530 = {"dp_holds", "dp_holds h = DP_HOLDS_INIT;", offseto
 constexpr Sized LATENT_AR_V540 = {"dp_latent_ar", "dp_latent_ar r = DP_LATENT_AR_INIT;", offsetof(dp_latent_ar, trace) + sizeof(void*), false};
 constexpr Sized GAPS_V550 = {"dp_gaps", "dp_gaps g = DP_GAPS_INIT;", offsetof(dp_gaps, trace) + sizeof(void*), false};
 constexpr Sized TETHERS_V570 = {"dp_tethers", "dp_tethers t = DP_TETHERS_INIT;", offsetof(dp_tethers, trace) + sizeof(void*), false};
+constexpr Sized POINTS_V580 = {"dp_points", "dp_points p = DP_POINTS_INIT;", offsetof(dp_points, coeff) + sizeof(void*), false};
 constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
@@ -1022,6 +1025,7 @@ static int constrained_impl(dp_ctx* ctx, const dp_batch* in, const dp_params* p_
     if (int rc = check_batch(ctx, in, who)) return rc;
     if (int rc = check_adam(ctx, p, who)) return rc;
     if (REF8_BUILD) return refuse_ref8(ctx, who);
+    if (!launch_fn) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_cons_points.hip"); // (the one weak per-frame unit)
     if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
     DEVICE_GUARD(ctx);
     a.img = ctx->d_vjpimg.get();
@@ -1108,8 +1112,9 @@ extern "C" int dp_optimize_constrained_skeleton(dp_ctx* ctx, const dp_batch* in,
     });
 }
 
-// one term of the table: "" when it is well-formed, otherwise what is wrong with it
-static std::string check_term(const dp_term& t)
+// one term of the table: "" when it is well-formed, otherwise what is wrong with it (n_idx: the indices a term may name, 22 joints and,
+// through the entry points of include/dragposer_points.h, up to DP_MAX_POINTS points behind them -- take_points narrows that to the call's)
+static std::string check_term(const dp_term& t, int n_idx)
 {
     const auto fin = [](float x) { return std::fabs(x) <= 3.0e38f; };
     const auto unit = [](const float* v) {
@@ -1119,8 +1124,8 @@ static std::string check_term(const dp_term& t)
     const auto zero = [](const float* v) { return v[0] == 0.f && v[1] == 0.f && v[2] == 0.f; };
     if (t.type != DP_TERM_PLANE && t.type != DP_TERM_DISTANCE && t.type != DP_TERM_ALIGN) return "unknown type " + std::to_string(t.type);
     if (t.flags & ~(DP_TERM_ONE_SIDED | DP_TERM_DROP_UP)) return "unknown flag bits " + std::to_string(t.flags);
-    if (t.joint_a < 0 || t.joint_a >= NJ) return "joint_a " + std::to_string(t.joint_a) + " outside 0..21";
-    if (t.joint_b < -1 || t.joint_b >= NJ) return "joint_b " + std::to_string(t.joint_b) + " outside -1..21";
+    if (t.joint_a < 0 || t.joint_a >= n_idx) return "joint_a " + std::to_string(t.joint_a) + " outside 0.." + std::to_string(n_idx - 1);
+    if (t.joint_b < -1 || t.joint_b >= n_idx) return "joint_b " + std::to_string(t.joint_b) + " outside -1.." + std::to_string(n_idx - 1);
     if (t.type == DP_TERM_PLANE && t.joint_b != -1) return "a PLANE has no second joint (joint_b must be -1)";
     if (!(t.weight >= 0.f && t.weight <= 3.0e38f)) return "the weight is negative or not finite";
     for (int c = 0; c < 3; ++c)
@@ -1138,7 +1143,7 @@ static std::string check_term(const dp_term& t)
 
 // include/dragposer_terms.h: dp_terms validated and written into the argument block (constrained_impl's own(a)), for dp_optimize_terms,
 // dp_optimize_terms_skeleton and, with `seq` (the launch's state), dp_optimize_sequence_terms (who names the caller in the messages)
-static int take_terms(dp_ctx* ctx, const dp_terms* t_in, dpcons::TermArgs& a, const char* who, const dp_seq_state* seq = nullptr)
+static int take_terms(dp_ctx* ctx, const dp_terms* t_in, dpcons::TermArgs& a, const char* who, const dp_seq_state* seq = nullptr, int n_idx = NJ)
 {
     const std::string nm = who;
     dp_terms ts;
@@ -1152,7 +1157,7 @@ static int take_terms(dp_ctx* ctx, const dp_terms* t_in, dpcons::TermArgs& a, co
     bool need_gp = false;
     for (int k = 0; k < ts.n_terms; ++k) {
         const dp_term& t = ts.terms[k];
-        const std::string why = check_term(t);
+        const std::string why = check_term(t, n_idx);
         if (!why.empty()) return fail(ctx, DP_ERR_INVALID, nm + ": term " + std::to_string(k) + ": " + why);
         need_gp = need_gp || (t.weight != 0.f && (t.type == DP_TERM_PLANE || (t.type == DP_TERM_DISTANCE && t.joint_b < 0)));
     }
@@ -1351,6 +1356,9 @@ hipError_t dp_launch_live(const dpcons::LiveSeqArgs* args, hipStream_t stream) _
 hipError_t dp_launch_live_ar(const dpcons::LiveArSeqArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_terms_tether_seq(const dpcons::TetherSeqArgs* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_terms_tether_ar_seq(const dpcons::TetherArSeqArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_terms_points(const dpcons::PointTermArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_terms_points_skel(const dpcons::PointTermSkelArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_terms_points_seq(const dpcons::PointSeqTermArgs* args, hipStream_t stream) __attribute__((weak));
 
 // One description per argument block of sequence_constrained_impl -- a new variant is a row here and its entry point.  Which optional parts a
 // block has (a.h, a.r, a.g, a.t, a.l) is read off the block itself (has_h .. has_l below).
@@ -1371,11 +1379,13 @@ template <> SeqVariant<dpcons::LiveSeqArgs> seq_variant() { return {dp_launch_li
 template <> SeqVariant<dpcons::LiveArSeqArgs> seq_variant() { return {dp_launch_live_ar, "dp_cons_live.hip", true}; }
 template <> SeqVariant<dpcons::TetherSeqArgs> seq_variant() { return {dp_launch_terms_tether_seq, "dp_cons_tether.hip", false}; }
 template <> SeqVariant<dpcons::TetherArSeqArgs> seq_variant() { return {dp_launch_terms_tether_ar_seq, "dp_cons_tether.hip", false}; }
+template <> SeqVariant<dpcons::PointSeqTermArgs> seq_variant() { return {dp_launch_terms_points_seq, "dp_cons_points.hip", false}; }
 
 #define DP_HAS_MEMBER(m)                                                   \
     template <class A, class = void> struct has_##m : std::false_type {}; \
     template <class A> struct has_##m<A, std::void_t<decltype(&A::m)>> : std::true_type {}
 DP_HAS_MEMBER(h); DP_HAS_MEMBER(r); DP_HAS_MEMBER(g); DP_HAS_MEMBER(t); DP_HAS_MEMBER(l); // HoldFields, ArFields, GapFields, TetherFields, LiveFields
+DP_HAS_MEMBER(pt);                                                                        // PointFields
 #undef DP_HAS_MEMBER
 
 // What a call with a term table brought beyond its frames and state, NULL where it has none (dp_optimize_sequence_constrained: all of it)
@@ -1385,6 +1395,7 @@ struct SeqParts {
     const dp_latent_ar* ar = nullptr;
     const dp_gaps* gaps = nullptr;
     const dp_tethers* tethers = nullptr;
+    const dp_points* points = nullptr;
 };
 
 // include/dragposer_latent_ar.h: dp_latent_ar checked, after everything dp_optimize_sequence_holds checks, against the launch's frames and
@@ -1416,6 +1427,47 @@ static int take_gaps(dp_ctx* ctx, const dp_gaps* g_in, dpcons::GapFields& g, con
     if (!(gs.decay > 0.f && gs.decay <= 1.f)) return fail(ctx, DP_ERR_INVALID, nm + ": dp_gaps.decay must be a finite number in (0, 1]");
     if (!gs.state) return fail(ctx, DP_ERR_INVALID, nm + ": dp_gaps.state is NULL");
     g.state = gs.state; g.present = gs.present; g.trace = gs.trace; g.decay = gs.decay; g.max_hold = (float)gs.max_hold;
+    return DP_OK;
+}
+
+// include/dragposer_points.h: dp_points checked after take_terms has accepted the table t_in (with indices up to 21 + DP_MAX_POINTS), against
+// it, and the coefficients written into the argument block (rows beyond n_points stay zero)
+static_assert(DP_MAX_POINTS == dpcons::MAX_POINTS && NJ == dpcons::PT_NJ, "dp_cons_points.h's table holds DP_MAX_POINTS rows of a coefficient per joint");
+static int take_points(dp_ctx* ctx, const dp_points* q_in, const dp_terms* t_in, dpcons::PointFields& pt, const char* who)
+{
+    const std::string nm = who;
+    dp_points ps;
+    if (int rc = take_sized(ctx, q_in, ps, POINTS_V580, who)) return rc;
+    if (ps.reserved1 != 0) return fail(ctx, DP_ERR_INVALID, nm + ": dp_points.reserved1 is " + std::to_string(ps.reserved1) + ", must be 0");
+    if (ps.n_points < 0 || ps.n_points > DP_MAX_POINTS)
+        return fail(ctx, DP_ERR_INVALID, nm + ": dp_points.n_points " + std::to_string(ps.n_points) + " outside 0.." + std::to_string(DP_MAX_POINTS));
+    if (ps.n_points > 0 && !ps.coeff) return fail(ctx, DP_ERR_INVALID, nm + ": dp_points.coeff is NULL with n_points > 0");
+    for (int k = 0; k < ps.n_points; ++k)
+        for (int j = 0; j < NJ; ++j)
+            if (!(std::fabs(ps.coeff[k * NJ + j]) <= 3.0e38f))
+                return fail(ctx, DP_ERR_INVALID, nm + ": point " + std::to_string(k) + ": the coefficient of joint " + std::to_string(j) + " is not finite");
+    for (int k = 0; k < ps.n_points; ++k) {
+        double sum = 0.0;
+        for (int j = 0; j < NJ; ++j) sum += (double)ps.coeff[k * NJ + j];
+        if (!(std::fabs(sum - 1.0) <= 1e-4))
+            return fail(ctx, DP_ERR_INVALID, nm + ": point " + std::to_string(k) + ": the coefficients sum to " + std::to_string(sum) + ", not to 1 within 1e-4");
+    }
+    dp_terms ts;
+    copy_sized(t_in, ts);
+    for (int k = 0; k < ts.n_terms; ++k) {
+        const dp_term& t = ts.terms[k];
+        const int hi = std::max(t.joint_a, t.joint_b);
+        if (hi >= NJ + ps.n_points)
+            return fail(ctx, DP_ERR_INVALID, nm + ": term " + std::to_string(k) + ": index " + std::to_string(hi) + " names a point, and dp_points has " +
+                                                 std::to_string(ps.n_points) + " (indices up to " + std::to_string(NJ + ps.n_points - 1) + ")");
+    }
+    for (int k = 0; k < ts.n_terms; ++k) {
+        const dp_term& t = ts.terms[k];
+        if (t.type == DP_TERM_ALIGN && std::max(t.joint_a, t.joint_b) >= NJ)
+            return fail(ctx, DP_ERR_INVALID, nm + ": term " + std::to_string(k) + ": an ALIGN term names a point, and a point has no rotation");
+    }
+    pt.n_points = ps.n_points;
+    for (int i = 0; i < ps.n_points * NJ; ++i) pt.coeff[i] = ps.coeff[i];
     return DP_OK;
 }
 
@@ -1555,7 +1607,9 @@ static int sequence_terms_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_s
                                const char* who, const SeqParts& parts)
 {
     const auto own = [&](A& a) -> int {
-        if (int rc = take_terms(ctx, parts.terms, a, who, st)) return rc;
+        if (int rc = take_terms(ctx, parts.terms, a, who, st, has_pt<A>::value ? NJ + DP_MAX_POINTS : NJ)) return rc;
+        if constexpr (has_pt<A>::value)
+            if (int rc = take_points(ctx, parts.points, parts.terms, a.pt, who)) return rc;
         if constexpr (has_h<A>::value)
             if (parts.holds)
                 if (int rc = take_holds(ctx, parts.holds, parts.terms, a, who)) return rc;
@@ -1598,6 +1652,54 @@ extern "C" int dp_optimize_sequence_terms(dp_ctx* ctx, int n_seq, float* latent,
         if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !st || !out)
             return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_terms: n_sequences must be positive; NULL latent, frames, params, terms, state or results");
         return sequence_terms_impl<dpcons::SeqTermArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
+    });
+}
+
+// include/dragposer_points.h: dp_optimize_terms, dp_optimize_terms_skeleton and dp_optimize_sequence_terms with points (A = dpcons::PointTermArgs,
+// PointTermSkelArgs, PointSeqTermArgs); dp_points is checked behind the table (take_points)
+extern "C" int dp_optimize_terms_points(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_terms* t_in, const dp_points* q_in,
+                                        const dp_result* out_in, void* stream)
+{
+    const char* who = "dp_optimize_terms_points";
+    const auto own = [&](dpcons::PointTermArgs& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who, nullptr, NJ + DP_MAX_POINTS)) return rc;
+        return take_points(ctx, q_in, t_in, a.pt, who);
+    };
+    return entry(ctx, who, [&] {
+        if (!in || !p_in || !t_in || !q_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms_points: NULL batch, params, terms, points or result");
+        return constrained_impl<dpcons::PointTermArgs>(ctx, in, p_in, out_in, stream, who, own, dp_launch_terms_points);
+    });
+}
+
+extern "C" int dp_optimize_terms_points_skeleton(dp_ctx* ctx, const dp_batch* in, const dp_params* p_in, const dp_terms* t_in, const dp_points* q_in,
+                                                 const dp_skeleton_in* skel, const dp_result* out_in, void* stream)
+{
+    const char* who = "dp_optimize_terms_points_skeleton";
+    const auto own = [&](dpcons::PointTermSkelArgs& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who, nullptr, NJ + DP_MAX_POINTS)) return rc;
+        if (int rc = take_points(ctx, q_in, t_in, a.pt, who)) return rc;
+        return take_skeleton(ctx, skel, a.skel, a.skel_stride, who);
+    };
+    return entry(ctx, who, [&] {
+        if (!in || !p_in || !t_in || !q_in || !out_in)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms_points_skeleton: NULL batch, params, terms, points or result");
+        if (!skel) return refuse_null_skeleton(ctx, who);
+        return constrained_impl<dpcons::PointTermSkelArgs>(ctx, in, p_in, out_in, stream, who, own, dp_launch_terms_points_skel);
+    });
+}
+
+extern "C" int dp_optimize_sequence_terms_points(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_params* p_in, const dp_terms* t_in,
+                                                 const dp_points* q_in, const dp_skeleton_in* skel, const dp_seq_state* st, const dp_seq_step* adj,
+                                                 const dp_seq_results* out, const dp_seq_extra* extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_terms_points";
+    SeqParts parts;
+    parts.terms = t_in; parts.points = q_in;
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !q_in || !st || !out)
+            return fail(ctx, DP_ERR_INVALID,
+                        "dp_optimize_sequence_terms_points: n_sequences must be positive; NULL latent, frames, params, terms, points, state or results");
+        return sequence_terms_impl<dpcons::PointSeqTermArgs>(ctx, n_seq, latent, fr, p_in, skel, st, adj, out, extra, stream, who, parts);
     });
 }
 

@@ -52,6 +52,14 @@ def _check_ar(temporal, ar, who):
         raise ValueError(f"DragPose.{who}: ar.order {ar.order} exceeds the history of {HISTORY} frames")
 
 
+def _points_alone(terms, who, **layers):
+    """a table with points (include/dragposer_points.h) runs through its own entry points, which take none of the sequence layers"""
+    if terms is not None and getattr(terms, "has_points", False):
+        for name, given in layers.items():
+            if given is not None and given is not False:
+                raise ValueError(f"DragPose.{who}: a table with points does not go with {name}= (include/dragposer_points.h, Not in)")
+
+
 class DragPose:
     def __init__(self, generator_model, temporal_model, means_latent, stds_latent, device=None, device_gpu=None, n_sequences=1,
                  offsets=None, native_temporal=False, native_encoder=False):
@@ -309,6 +317,8 @@ class DragPose:
         usual stretches; the state lives in `gap_state` [S,22,16], zeroed when a sequence begins, and `last_gap_trace` [T,S,22] holds every
         joint's code of every frame (1 present, 2 held, 3 lost, 0 not a tracker).  Without `terms` it runs with an empty table, and
         `constraints` go through Terms.from_constraints, as with `ar`.
+        A `terms` table with points (include/dragposer_points.h) runs through dp_optimize_sequence_terms_points, `offsets` allowed, none
+        of `holds` / `ar` / `gaps` / `tethers`.
         `tethers` (a dragposer_amd.Tethers, with `terms`): joints tied to their own recent path (dp_optimize_sequence_tethers,
         include/dragposer_tethers.h), one launch per stretch, with or without `holds`, `ar` and `gaps` (without `gaps` it runs with
         Gaps(0, 1.0), under which an absent sample leaves the loss at once); the state lives in `tether_state` [S,len(tethers),8], zeroed
@@ -316,6 +326,7 @@ class DragPose:
         Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run_frames: pass constraints or terms, not both")
+        _points_alone(terms, "run_frames", holds=holds, gaps=gaps, ar=ar, tethers=tethers)
         if tethers is not None:
             self._tethers(tethers, terms, constraints, holds, "run_frames")
             if gaps is None:
@@ -466,6 +477,8 @@ class DragPose:
         `live` (with any of `constraints` / `terms` / `holds` / `ar` / `gaps`): that frame as ONE launch, dp_live_step
         (include/dragposer_live.h) -- the gap unit appends the frame's row to the history buffers itself; without `gaps` it runs with
         Gaps(0, 1.0), under which an absent sample leaves the loss at once.  The bits of the same call without `live`.
+        A `terms` table with points (Terms(..., points=), include/dragposer_points.h) runs through dp_optimize_terms_points, with
+        `offsets` allowed (dp_optimize_terms_points_skeleton) and none of `holds` / `ar` / `gaps` / `tethers` / `live`.
         `tethers` (a dragposer_amd.Tethers, with `terms`): the per-frame composition of include/dragposer_tethers.h -- each tethered term
         reads its row from `tether_state`, the frame is a one-step run_frames(gaps=) (Gaps(0, 1.0) without `gaps`), and the state is updated
         after it with the header's arithmetic in torch on the device, no synchronisation: frame by frame the bits of
@@ -477,6 +490,7 @@ class DragPose:
         the same object frame after frame costs one host synchronisation in all (DragPose._skeleton)."""
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
+        _points_alone(terms, "run", holds=holds, gaps=gaps, ar=ar, tethers=tethers, live=bool(live))
         if tethers is not None:
             if live:
                 raise ValueError("DragPose.run: live= has no tethers (dp_live_step); run_frames(tethers=) is their one-launch form")
@@ -517,7 +531,8 @@ class DragPose:
             return ret
         self._holds(holds, terms, constraints, "run")
         skel = self._skeleton(offsets)
-        if skel is not None and (constraints is not None or terms is not None):
+        with_points = terms is not None and terms.has_points  # (routed with its bones: dp_optimize_terms_points_skeleton)
+        if skel is not None and (constraints is not None or terms is not None) and not with_points:
             raise ValueError("DragPose.run: offsets other than the context's skeleton cannot be combined with " +
                              ("constraints=" if constraints is not None else "terms=") + " here: call LatentOptimizer.optimize_constrained / "
                              "optimize_terms with offsets= (dp_optimize_constrained_skeleton / dp_optimize_terms_skeleton), or create the "
@@ -555,7 +570,7 @@ class DragPose:
         if constraints is not None or terms is not None:
             return self._run_constrained(constraints if terms is None else terms, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot,
                                          lambda_temporal if pull else 0.0, stop_eps_pos, stop_eps_rot, min_loss_incr, temporal_future_window,
-                                         verbose, squeeze, holds)
+                                         verbose, squeeze, holds, skel if with_points else None)
         self.opt.optimize_sequence(self.latent, trk["tgt_pos"].unsqueeze(0), trk["tgt_rot"].unsqueeze(0), None, trk["w"], trk["tracked"], z_tgt,
                                    (0, (int(temporal_future_window) + 1) * LATENT), self.current_global_pos, self.current_global_rot,
                                    self.latent_buffer, self.displacement_buffer, self.heights_buffer, tuple(int(h) for h in height_indices),
@@ -600,7 +615,7 @@ class DragPose:
         return pose, gpos
 
     def _run_constrained(self, constraints, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot, lambda_tmp,
-                         stop_eps_pos, stop_eps_rot, min_loss_incr, window, verbose, squeeze, holds=None):
+                         stop_eps_pos, stop_eps_rot, min_loss_incr, window, verbose, squeeze, holds=None, skel=None):
         """run()'s frame with extra loss terms: the optimise loop (dp_optimize_constrained for a Constraints, dp_optimize_terms for a
         Terms table) and run()'s epilogue (dp_sequence_advance)"""
         from .terms import Terms
@@ -621,7 +636,8 @@ class DragPose:
             constraints = holds.frame_terms(table_in, self.hold_state)
         run(self.latent, z_tgt, self.current_global_rot, trk["tgt_pos"], trk["tgt_rot"], trk["w"], trk["tracked"], constraints,
             global_pos=self.current_global_pos, n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_tmp),
-            stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, out=fr, outputs=tuple(fr))
+            stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, out=fr, outputs=tuple(fr),
+            **({} if skel is None else {"offsets": skel}))
         self.opt.sequence_advance(fr, self.current_global_pos, self.current_global_rot, self.latent_buffer, self.displacement_buffer,
                                   self.heights_buffer, tuple(int(h) for h in height_indices), pose_ret=pose, pos_ret=gpos, adjust=adjust,
                                   tgt_pos=trk["tgt_pos"] if adjust is not None else None)

@@ -116,6 +116,33 @@ def parse_tethers(items):
     return out
 
 
+def parse_balance(item, masses_path=None):
+    """--balance RADIUS:WEIGHT [--balance-masses FILE] -> (radius, weight, 22 masses or None: uniform)"""
+    try:
+        radius, weight = (float(x) for x in item.split(":"))
+        if not (np.isfinite(radius) and radius >= 0.0 and np.isfinite(weight) and weight >= 0.0):
+            raise ValueError("RADIUS and WEIGHT are finite and not negative")
+    except ValueError as e:
+        raise SystemExit(f"--balance: expected RADIUS:WEIGHT, got {item!r} ({e})")
+    masses = None
+    if masses_path is not None:
+        masses = [float(x) for x in open(masses_path).read().replace(",", " ").split()]
+        if len(masses) != NJ:
+            raise SystemExit(f"--balance-masses: {masses_path} holds {len(masses)} numbers, expected {NJ}")
+    return radius, weight, masses
+
+
+def balance_terms(spec, base):
+    """--balance: one DISTANCE term (DROP_UP, lo = 0, hi = RADIUS) between the centroid of all joints and the midpoint of joints 4 and 8,
+    appended to the table `base` -> a Terms with the two points (include/dragposer_points.h)"""
+    from .points import Point, Points
+
+    radius, weight, masses = spec
+    pts = Points([Point.centroid(masses), Point.midpoint(*FOOT_LOCK_JOINTS)])
+    term = Term.distance(pts.joint(0), pts.joint(1), lo=0.0, hi=radius, weight=weight, drop_up=True)
+    return Terms(base.terms + [term], base.up_axis, pts)
+
+
 def tether_terms(specs, base):
     """--tether: a point-DISTANCE term (lo = 0, hi = HI) per tethered joint and a tether on it, appended to the table `base` -> (Terms, Tethers)"""
     from .tethers import Tether, Tethers
@@ -248,6 +275,9 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
             base = Terms.from_constraints(cons) if cons is not None else Terms(up_axis=args.up_axis)
         extra.pop("constraints", None)
         extra["terms"], extra["tethers"] = tether_terms(args.tether_specs, base)
+    if getattr(args, "balance_spec", None) is not None:
+        base = Terms.from_constraints(cons) if cons is not None else Terms(up_axis=args.up_axis)
+        extra = dict(terms=balance_terms(args.balance_spec, base))
     if ar is not None:
         extra["ar"] = ar
     if getattr(args, "gaps_model", None) is not None:
@@ -311,7 +341,12 @@ def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
     if getattr(args, "tether_specs", None):
         print("Tethers: " + ", ".join(f"joint {j} hi {hi} weight {w} alpha {a}" for j, hi, w, a in args.tether_specs) +
               " (DragPose.run_frames(tethers=), include/dragposer_tethers.h)")
-    if getattr(args, "foot_lock", False) or getattr(args, "tether_specs", None):
+    if getattr(args, "balance_spec", None) is not None:
+        r, w, masses = args.balance_spec
+        print(f"Balance: radius {r} weight {w}, the centroid of all joints ({'uniform masses' if masses is None else 'masses ' + args.balance_masses}) "
+              f"within the radius of the midpoint of joints {FOOT_LOCK_JOINTS[0]} and {FOOT_LOCK_JOINTS[1]}, horizontally "
+              "(DragPose.run_frames(terms=<with points>), include/dragposer_points.h)")
+    if getattr(args, "foot_lock", False) or getattr(args, "tether_specs", None) or getattr(args, "balance_spec", None) is not None:
         up = Constraints.reference().up_axis if getattr(args, "constraints", None) == "reference" else args.up_axis
         skate, pairs = foot_skate(BVH().load(q["path"]), BVH().load(out_path), args.contact_height[0], args.floor_level, up)
         print(f"Foot skate: {skate} (mean horizontal displacement per frame of joints {FOOT_LOCK_JOINTS[0]} and {FOOT_LOCK_JOINTS[1]} over "
@@ -407,6 +442,16 @@ def main(argv=None):
                          "results).  Up to four times; the terms are appended to --foot-lock's and --constraints reference's table.  Prints the foot "
                          "skate line and one more, the jitter of the result beside the ground truth's own.  No default: nobody has tuned one "
                          "(DESIGN.md section 13h)")
+    ap.add_argument("--balance", default=None, metavar="RADIUS:WEIGHT",
+                    help="keep the centre of mass over the feet: one DISTANCE term (the up component dropped, lo = 0, hi = RADIUS metres, weight "
+                         "WEIGHT) between the centroid of all 22 joints and the midpoint of joints 4 and 8 -- two points of "
+                         "include/dragposer_points.h (DragPose.run_frames(terms=Terms(..., points=)); with --per-frame DragPose.run, same results).  "
+                         "Alone or appended to --constraints reference's table; not together with --foot-lock, --tether, --latent-ar or --gaps "
+                         "(a table with points takes none of those layers).  Prints its settings and the foot skate line.  No default: "
+                         "single runs on the shipped clips favour a wide radius at a small weight (0.2:0.1), which nobody has repeated "
+                         "(DESIGN.md section 13i)")
+    ap.add_argument("--balance-masses", default=None, metavar="FILE",
+                    help="--balance: 22 numbers (white space or commas), the joints' masses for the centroid, normalised to sum 1 (default: uniform)")
     ap.add_argument("--latent-ar", default=None, metavar="hold | cv[:DAMPING] | FILE.npz",
                     help="without a temporal checkpoint: pull the latent towards a linear autoregressive prediction from the sequence's own "
                          "recent latents, with the configuration's lambda_temporal instead of 0 (DragPose.run_frames(ar=), "
@@ -454,6 +499,14 @@ def main(argv=None):
 
         args.latent_ar_model, args.latent_ar_text = parse(args.latent_ar)
     args.tether_specs = parse_tethers(args.tether) if args.tether else None
+    args.balance_spec = None
+    if args.balance_masses is not None and args.balance is None:
+        raise SystemExit("--balance-masses belongs to --balance")
+    if args.balance is not None:
+        for flag, given in (("--foot-lock", args.foot_lock), ("--tether", args.tether), ("--latent-ar", args.latent_ar), ("--gaps", args.gaps)):
+            if given:
+                raise SystemExit(f"--balance and {flag}: a table with points takes no holds, tethers, latent predictor or gaps (include/dragposer_points.h)")
+        args.balance_spec = parse_balance(args.balance, args.balance_masses)
     args.gaps_model = None
     if args.gaps is not None:
         from .gaps import Gaps

@@ -252,11 +252,11 @@ class LatentOptimizer:
         self._call(fn, B, C.c_void_p(zp), C.c_void_p(cp), *tail)
         return tensors
 
-    def _optimize_extra(self, fn, inputs, pargs, global_pos, outputs, out, validate_targets, extra, width, gp_error, to_struct, skel=None):
+    def _optimize_extra(self, fn, inputs, pargs, global_pos, outputs, out, validate_targets, extra, width, gp_error, to_struct, skel=None, mid=()):
         """What optimize_constrained and optimize_terms share: `optimize`'s batch, parameters and results, the per-frame output of their own
         (`extra` [B, width]) and the root positions some of their terms need (`gp_error`: what to say when those are missing, or None).
         to_struct(global_pos pointer, `extra`'s pointer) -> (the extension struct, what it keeps alive).  `skel`: the dp_skeleton_in of the
-        per-frame-skeleton form of `fn`, which takes it after the extension struct."""
+        per-frame-skeleton form of `fn`, which takes it after the extension struct; `mid`: what `fn` takes between the two."""
         z0, tgt_rot, tracked = inputs[0], inputs[4], inputs[6]
         B, dev = int(z0.shape[0]), self.device
         if validate_targets:
@@ -273,7 +273,7 @@ class LatentOptimizer:
         elif gp_error:
             raise ValueError(gp_error)
         s, keep = to_struct(gp, _check(t, extra, (B, width), torch.float32, dev) if width else None)
-        self._call(fn, C.byref(batch), C.byref(p), C.byref(s), *(() if skel is None else (C.byref(skel),)), C.byref(res))
+        self._call(fn, C.byref(batch), C.byref(p), C.byref(s), *mid, *(() if skel is None else (C.byref(skel),)), C.byref(res))
         del keep
         return tensors
 
@@ -302,15 +302,21 @@ class LatentOptimizer:
         the frame, required when an active PLANE or point-DISTANCE term exists.  A term's per-frame rows are its `per_frame` [B,4]
         device tensor.  Returns `optimize`'s dict plus `loss_terms` [B, len(terms)] (each weighted term of the last forward pass).
         `kernel` is ignored; `validate_targets` as in `optimize`.  `offsets` [22,3] / [B,22,3]: per-frame skeletons as in
-        `optimize_constrained` (dp_optimize_terms_skeleton); None = the context's skeleton (dp_optimize_terms, unchanged)."""
+        `optimize_constrained` (dp_optimize_terms_skeleton); None = the context's skeleton (dp_optimize_terms, unchanged).
+        A table with points (`Terms(..., points=Points([...]))`: terms on weighted joint combinations, include/dragposer_points.h) runs
+        through dp_optimize_terms_points / dp_optimize_terms_points_skeleton, everything else alike."""
         skel = self._skeleton(offsets, int(z0.shape[0]), "optimize_terms") if offsets is not None else None
         terms.check()
+        fn, mid, keep_p = (self.lib.dp_optimize_terms if skel is None else self.lib.dp_optimize_terms_skeleton), (), None
+        if terms.has_points:
+            ps, keep_p = terms.points.to_struct()
+            fn, mid = (self.lib.dp_optimize_terms_points if skel is None else self.lib.dp_optimize_terms_points_skeleton), (C.byref(ps),)
         return self._optimize_extra(
-            self.lib.dp_optimize_terms if skel is None else self.lib.dp_optimize_terms_skeleton, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked),
+            fn, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked),
             (n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, max_trackers), global_pos, outputs, out,
             validate_targets, "loss_terms", len(terms),
             "optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]" if terms.needs_global_pos else None,
-            lambda gp, lt: terms.to_struct(int(z0.shape[0]), self.device, gp, lt), skel=skel)
+            lambda gp, lt: terms.to_struct(int(z0.shape[0]), self.device, gp, lt), skel=skel, mid=mid)
 
     def forward_vjp(self, z, cur_rot, grads, out=None, offsets=None, doffsets=False):
         """dL/dz [B,24] and dL/dcur_rot [B,4] of decode + FK at (z, cur_rot) for upstream gradients `grads` = {output name: dL/d(that
@@ -418,8 +424,15 @@ class LatentOptimizer:
         `tethers` (a dragposer_amd.Tethers, with `terms` and `gaps`): joints tied to their own recent path, dp_optimize_sequence_tethers
         (include/dragposer_tethers.h), with or without `holds` and `ar`; pass Gaps(0, 1.0) for none to hold.  `tether_state`
         [S,len(tethers),8] is updated IN PLACE (required); `tether_trace` [T,S,len(tethers),8] or True (allocated here) receives the state
-        after every step and is returned as `tether_trace`.  Not together with `live`."""
+        after every step and is returned as `tether_trace`.  Not together with `live`.
+        A `terms` table with points (include/dragposer_points.h) runs through dp_optimize_sequence_terms_points, `offsets` allowed; not
+        together with `holds`, `gaps`, `ar`, `tethers` or `live`."""
         live = bool(live) or bool(getattr(self, "live_step", False))
+        if terms is not None and terms.has_points:
+            for name, given in (("holds", holds is not None), ("gaps", gaps is not None), ("ar", ar is not None), ("tethers", tethers is not None),
+                                ("live", live)):
+                if given:
+                    raise ValueError(f"optimize_sequence: a table with points does not go with {name}= (include/dragposer_points.h, Not in)")
         if tethers is None and (tether_state is not None or tether_trace is not None):
             raise ValueError("optimize_sequence: tether_state / tether_trace belong to tethers=")
         if tethers is not None:
@@ -529,6 +542,9 @@ class LatentOptimizer:
                 ex.row_step[:len(terms)] = terms.row_steps(S)
                 fn = self.lib.dp_optimize_sequence_terms
             mid = ()
+            if terms is not None and terms.has_points:
+                ps, keep_p = terms.points.to_struct()
+                fn, mid = self.lib.dp_optimize_sequence_terms_points, (C.byref(ps),)
             if holds is not None:
                 if hold_trace is True:
                     hold_trace = torch.zeros(T, S, len(holds), 4, dtype=torch.float32, device=dev)

@@ -78,19 +78,22 @@ class Term:
     def needs_global_pos(self):
         return self.active and (self.type == PLANE or (self.type == DISTANCE and self.joint_b < 0))
 
-    def check(self, i=0):
-        """ValueError for what dp_optimize_terms refuses as DP_ERR_INVALID (the header's list)"""
+    def check(self, i=0, n_points=0):
+        """ValueError for what dp_optimize_terms refuses as DP_ERR_INVALID (the header's list).  `n_points`: the table's points
+        (dragposer_amd.Points, include/dragposer_points.h), which a PLANE or DISTANCE term may name as 22 + k"""
         def bad(msg):
             raise ValueError(f"term {i}: {msg}")
+
+        NJ = 22 + (int(n_points) if self.type in (PLANE, DISTANCE) else 0)
 
         if self.type not in (PLANE, DISTANCE, ALIGN):
             bad(f"unknown type {self.type}")
         if int(self.flags) & ~(ONE_SIDED | DROP_UP):
             bad(f"unknown flag bits {self.flags}")
         if not 0 <= self.joint_a < NJ:
-            bad(f"joint_a {self.joint_a} outside 0..21")
+            bad(f"joint_a {self.joint_a} outside 0..{NJ - 1}" + (": an ALIGN term cannot name a point" if self.type == ALIGN and n_points else ""))
         if not -1 <= self.joint_b < NJ:
-            bad(f"joint_b {self.joint_b} outside -1..21")
+            bad(f"joint_b {self.joint_b} outside -1..{NJ - 1}" + (": an ALIGN term cannot name a point" if self.type == ALIGN and n_points else ""))
         if self.type == PLANE and self.joint_b != -1:
             bad("a PLANE has no second joint")
         if not (math.isfinite(self.weight) and self.weight >= 0.0):
@@ -129,9 +132,17 @@ class Term:
 
 @dataclass
 class Terms:
-    """The table (dp_terms): up to 16 terms and the up axis DROP_UP zeroes.  Terms() is the plain tracker loss."""
+    """The table (dp_terms): up to 16 terms and the up axis DROP_UP zeroes.  Terms() is the plain tracker loss.  `points`: a
+    dragposer_amd.Points of up to 4 weighted joint combinations; a PLANE or DISTANCE term names point k as joint 22 + k
+    (points.joint(k)), and the table then runs through the entry points of include/dragposer_points.h."""
     terms: list = field(default_factory=list)
     up_axis: int = 1
+    points: Optional[object] = None
+
+    @property
+    def has_points(self):
+        """the table runs through the entry points of include/dragposer_points.h (an empty Points too: n_points = 0, dp_optimize_terms' bits)"""
+        return self.points is not None
 
     def __len__(self):
         return len(self.terms)
@@ -166,8 +177,10 @@ class Terms:
             raise ValueError(f"Terms: at most {MAX_TERMS} terms, got {len(self.terms)}")
         if self.up_axis not in (0, 1, 2):
             raise ValueError("Terms.up_axis must be 0, 1 or 2")
+        if self.points is not None:
+            self.points.check()
         for i, t in enumerate(self.terms):
-            t.check(i)
+            t.check(i, len(self.points) if self.points is not None else 0)
 
     def row_steps(self, B):
         """dp_seq_extra.row_step of a whole-sequence launch: floats between two frames' rows of each term's per_frame (0: [B,4], held)"""
@@ -178,7 +191,7 @@ class Terms:
         from dataclasses import replace
 
         cut = lambda t: replace(t, per_frame=t.per_frame[t0:t1]) if t.per_frame is not None and t.per_frame.dim() == 3 else t
-        return Terms([cut(t) for t in self.terms], self.up_axis)
+        return Terms([cut(t) for t in self.terms], self.up_axis, self.points)
 
     def to_struct(self, B, device, global_pos_ptr=None, loss_terms_ptr=None, steps=None):
         """-> (_lib.DpTerms, the DpTerm array it points to: keep both alive for the call).  `steps`: as Term.to_struct"""
