@@ -594,10 +594,37 @@ DEV void lds_store3(float* p, float a, float b, float c)
     asm volatile("ds_write2_b32 %0, %1, %2 offset1:1\n\tds_write_b32 %0, %3 offset:8" : : "v"(ad), "v"(a), "v"(b), "v"(c) : "memory");
 }
 
+// ---- The kinematics' LDS reads are issued ahead of their waits (a lone wave has nothing to put under an LDS round trip, ~130 cycles, but
+// its own arithmetic).  LDS operations of a wave execute in order, so a read may follow the store it depends on with no wait between them,
+// whichever lane stored.  W4_EARLY_READS, one bit per change (-DW4_EARLY_READS=0 restores the old order, for A/Bs; outputs are bit-identical
+// with every value):
+//   1  stage G requests its two own-torque entries together with its six table entries (one round trip instead of two)
+//   2  bL2's first streamed chunk is requested BEHIND stage G's reads, not in front of them (reads come back in order)
+//   4  stage T's reads are issued from inside stage J, directly behind the stores they depend on: the root's and the joint's quaternion
+//      and the displacement behind the quaternion stores, the seven bones behind the bone stores
+#ifndef W4_EARLY_READS
+#define W4_EARLY_READS 7
+#endif
+// stage T's operands: one tracker per lane.  The reads run with EVERY lane active: a lane without a tracker holds the root's record
+// (tracker_finish / load_tracker: j = 0 -> QS_IDENT, the root's path), valid slots of its own frame block.
+struct TRd { f4 q0v, qtv, dv, bn[MAX_PATH]; };
+DEV void t_reads_q(const TRec& t, const float* fb, TRd& r)
+{
+    r.q0v = *(const f4*)(fb + FB_QS); r.qtv = *(const f4*)(fb + t.qs); r.dv = *(const f4*)(fb + FB_QS + 4 * QS_DISP);
+}
+DEV void t_reads_bn(const TRec& t, const float* fb, TRd& r)
+{ // all reads in flight together: one LDS latency, not seven
+    const unsigned plo = t.plo, phi = t.phi;
+#pragma unroll
+    for (int k = 0; k < MAX_PATH; ++k) r.bn[k] = *(const f4*)(fb + FB_BN + 4 * ((k < 6) ? ((plo >> (5 * k)) & 31u) : (phi & 31u)));
+}
+
 // ---- stage J: both items of my quad, packed
 struct JOut { f2 q[4], u[3], inv; };
-DEV void j_stage(const PairC& c, float* fb, const f4 y01, const f4 y23, JOut& o)
+template <bool TREADS> DEV void j_stage(const PairC& c, float* fb, const f4 y01, const f4 y23, JOut& o, const TRec& t, TRd& tr)
 { // y01 / y23: the transposed blocks of layer 2 -- channels (0, 1) / (2, 3), each as a side A | side B register pair (dp_w4.h)
+  // TREADS: stage T's reads of lane's tracker `t` are issued here (W4_EARLY_READS & 4).  The stores are asm statements with a memory
+  // clobber: the compiler keeps the loads behind them; the scheduling barriers keep them in front of the arithmetic that covers them.
     const f2 rq[4] = {f2{y01[0], y01[1]}, f2{y01[2], y01[3]}, f2{y23[0], y23[1]}, f2{y23[2], y23[3]}}; // (de-normalised by layer 2 itself)
     const f2 nn = rq[0] * rq[0] + rq[1] * rq[1] + rq[2] * rq[2] + rq[3] * rq[3];
 #if W4_BP // (the displacement is a side-A item of the body-part layout, a side-B item of the dense one)
@@ -612,15 +639,27 @@ DEV void j_stage(const PairC& c, float* fb, const f4 y01, const f4 y23, JOut& o)
     for (int k = 0; k < 4; ++k) o.q[k] = rq[k] * o.inv; // (the displacement item passes its de-normalised channels through)
     // child bone u = R(q) off = off + 2 (w t + v x t), t = v x off
     const f2 w = o.q[0], vx = o.q[1], vy = o.q[2], vz = o.q[3];
+    if constexpr (TREADS) { // the quaternions leave first; the bone arithmetic runs under the round trip of the reads behind them
+        lds_store4(fb + c.qsA, o.q[0].x, o.q[1].x, o.q[2].x, o.q[3].x);
+        lds_store4(fb + c.qsB, o.q[0].y, o.q[1].y, o.q[2].y, o.q[3].y);
+        t_reads_q(t, fb, tr);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     const f2 tx = vy * c.off[2] - vz * c.off[1], ty = vz * c.off[0] - vx * c.off[2], tz = vx * c.off[1] - vy * c.off[0];
     const f2 cx = vy * tz - vz * ty, cy = vz * tx - vx * tz, cz = vx * ty - vy * tx;
     o.u[0] = c.off[0] + 2.f * (w * tx + cx);
     o.u[1] = c.off[1] + 2.f * (w * ty + cy);
     o.u[2] = c.off[2] + 2.f * (w * tz + cz);
-    lds_store4(fb + c.qsA, o.q[0].x, o.q[1].x, o.q[2].x, o.q[3].x);
-    lds_store4(fb + c.qsB, o.q[0].y, o.q[1].y, o.q[2].y, o.q[3].y);
+    if constexpr (!TREADS) {
+        lds_store4(fb + c.qsA, o.q[0].x, o.q[1].x, o.q[2].x, o.q[3].x);
+        lds_store4(fb + c.qsB, o.q[0].y, o.q[1].y, o.q[2].y, o.q[3].y);
+    }
     lds_store3(fb + c.bnA, o.u[0].x, o.u[1].x, o.u[2].x);
     lds_store3(fb + c.bnB, o.u[0].y, o.u[1].y, o.u[2].y);
+    if constexpr (TREADS) {
+        t_reads_bn(t, fb, tr);
+        __builtin_amdgcn_sched_barrier(0);
+    }
 }
 
 // Quaternion products on register pairs (w, x), (y, z): eight packed instructions each, the operand swaps and signs of the
@@ -657,32 +696,42 @@ DEV void quat_mul_conj_b(f2 a0, f2 a1, f2 b0, f2 b1, f2& o0, f2& o1)
 }
 
 // ---- stage T: one tracker per lane
-DEV void t_stage(const TRec& t, float* fb, bool losses)
-{
-    if (!t.act) return;
-    const f4 q0v = *(const f4*)(fb + FB_QS), qtv = *(const f4*)(fb + t.qs), dv = *(const f4*)(fb + FB_QS + 4 * QS_DISP);
+template <bool AHEAD> DEV void t_finish(const TRec& t, float* fb, bool losses, TRd& rd)
+{ // the arithmetic and the stores.  AHEAD: the reads were issued from inside stage J and are still in flight.  Then every lane runs the
+  // arithmetic (a lane without a tracker on the root's record: finite, and never stored) and only the stores stand under the lane mask.
+  // With the whole stage under the mask the compiler adds a branch round it for the wave that tracks nothing, the reads are still
+  // pending where the two paths meet, and the wait it puts there -- in front of stage G's reads -- costs the ordinary path the
+  // completion of this stage's stores.
+    if constexpr (!AHEAD) {
+        if (!t.act) return;
+    }
+    const f4 q0v = rd.q0v, qtv = rd.qtv;
+    const Q4 q0 = {q0v.x, q0v.y, q0v.z, q0v.w};
+    V3 at = rot_conj(q0, t.tp); // target position in the root frame
+    // rotation error  s = conj(q0) (x) qT (x) conj(qt):  scalar part c = <q0 (x) qt, qT>,  |M - T|_F^2 = 8 |vec s|^2
+    f2 r0, r1, s0, s1;
+    quat_mul_conj_a(f2{q0v.x, q0v.y}, f2{q0v.z, q0v.w}, t.qT0, t.qT1, r0, r1);
+    quat_mul_conj_b(r0, r1, f2{qtv.x, qtv.y}, f2{qtv.z, qtv.w}, s0, s1);
+    if constexpr (AHEAD) {
+        // The part above needs the two quaternions only and runs under the bones' round trip: the empty statement stands where the wave
+        // waits for the displacement and the bones, and takes the results above as operands so that they are computed in front of it.
+        // It also keeps the unused fourth words of the reads alive until here -- a register the compiler re-uses while its read is in
+        // flight makes it wait for EVERY read at that point (seen in the ISA: lgkmcnt(0) straight behind the last request).
+        asm volatile("" : "+v"(rd.dv), "+v"(rd.bn[0]), "+v"(rd.bn[1]), "+v"(rd.bn[2]), "+v"(rd.bn[3]), "+v"(rd.bn[4]), "+v"(rd.bn[5]), "+v"(rd.bn[6]),
+                          "+v"(s0), "+v"(s1), "+v"(at.x), "+v"(at.y), "+v"(at.z));
+        static_assert(MAX_PATH == 7, "the statement above names every bone read");
+    }
+    const f4 dv = rd.dv;
     f2 pxy = f2{dv.x, dv.y}; // root-frame position: displacement + the bones on the path (short paths end in the zero slot)
     float pz = dv.z;
-    {
-        const unsigned plo = t.plo, phi = t.phi;
-        f4 bn[MAX_PATH]; // all reads in flight together: one LDS latency, not seven
 #pragma unroll
-        for (int k = 0; k < MAX_PATH; ++k) bn[k] = *(const f4*)(fb + FB_BN + 4 * ((k < 6) ? ((plo >> (5 * k)) & 31u) : (phi & 31u)));
-#pragma unroll
-        for (int k = 0; k < MAX_PATH; ++k) { pxy += f2{bn[k].x, bn[k].y}; pz += bn[k].z; }
-    }
-    const Q4 q0 = {q0v.x, q0v.y, q0v.z, q0v.w};
-    const V3 at = rot_conj(q0, t.tp); // target position in the root frame
+    for (int k = 0; k < MAX_PATH; ++k) { pxy += f2{rd.bn[k].x, rd.bn[k].y}; pz += rd.bn[k].z; }
     // (x, y) components in packed registers, z beside them: the same operations, fewer instructions
     const f2 exy = pxy - f2{at.x, at.y};
     const float ez = pz - at.z;
     const f2 gpxy = t.cgp * exy;
     const float gpz = t.cgp * ez;
     const V3 e = {exy.x, exy.y, ez}, gp = {gpxy.x, gpxy.y, gpz};
-    // rotation error  s = conj(q0) (x) qT (x) conj(qt):  scalar part c = <q0 (x) qt, qT>,  |M - T|_F^2 = 8 |vec s|^2
-    f2 r0, r1, s0, s1;
-    quat_mul_conj_a(f2{q0v.x, q0v.y}, f2{q0v.z, q0v.w}, t.qT0, t.qT1, r0, r1);
-    quat_mul_conj_b(r0, r1, f2{qtv.x, qtv.y}, f2{qtv.z, qtv.w}, s0, s1);
     const Q4 s = {s0.x, s0.y, s1.x, s1.y};
     const float k = t.k8 * s.w;
     const float ownx = k * s.x;
@@ -693,22 +742,43 @@ DEV void t_stage(const TRec& t, float* fb, bool losses)
     const V3 rt = {ag.x + own.x, rtyz.x, rtyz.y};
     // (12-byte stores: the readers take 16 bytes and ignore the fourth word)
     typedef float f3 __attribute__((ext_vector_type(3)));
+    if constexpr (AHEAD) {
+        if (!t.act) return;
+    }
     *(f3*)(fb + FB_GP + 4 * t.rank) = f3{gp.x, gp.y, gp.z};
     *(f3*)(fb + FB_RT + 4 * t.rank) = f3{rt.x, rt.y, rt.z};
     *(f3*)(fb + t.wt) = f3{own.x, own.y, own.z};
     if (losses) // (uniform) read by the epilogue
         *(f2*)(fb + FB_LP + 2 * t.rank) = f2{t.clp * (e.x * e.x + e.y * e.y + e.z * e.z), t.clr8 * (s.x * s.x + s.y * s.y + s.z * s.z)};
 }
+DEV void t_stage(const TRec& t, float* fb, bool losses)
+{ // reads and arithmetic in one place, behind stage J: ranks >= 16 (a second pass, rare), and every pass with W4_EARLY_READS & 4 off
+    if (!t.act) return;
+    TRd rd;
+    t_reads_q(t, fb, rd);
+    t_reads_bn(t, fb, rd);
+    t_finish<false>(t, fb, losses, rd);
+}
 
 // ---- stage G: both items of my quad, packed -> their quads of dL/dy
-DEV void g_stage(const PairC& c, const float* fb, const JOut& j, unsigned tmask, int Emax, f4& gyA, f4& gyB)
+// in two halves: g_reads issues the reads (the caller puts the requests that may wait longer behind them), g_stage waits for them
+struct GRd { f4 g[6], wa, wb; };
+template <bool WAB> DEV void g_reads(const PairC& c, const float* fb, GRd& r)
+{
+    const float* tab = fb + c.tab;
+#pragma unroll
+    for (int u = 0; u < 6; ++u) r.g[u] = *(const f4*)(tab + 4 * u);
+    if constexpr (WAB) { // the own torques depend on nothing stage G computes: one round trip with the table (behind it: the sums want the table first)
+        __builtin_amdgcn_sched_barrier(0);
+        r.wa = *(const f4*)(fb + c.wtA); r.wb = *(const f4*)(fb + c.wtB);
+    }
+}
+template <bool WAB> DEV void g_stage(const PairC& c, const float* fb, const JOut& j, unsigned tmask, int Emax, GRd& r, f4& gyA, f4& gyB)
 {
     f2 S[3] = {splat2(0.f), splat2(0.f), splat2(0.f)};
     {
         const float* tab = fb + c.tab;
-        f4 g[6];
-#pragma unroll
-        for (int u = 0; u < 6; ++u) g[u] = *(const f4*)(tab + 4 * u);
+        f4* const g = r.g;
 #pragma unroll
         for (int u = 0; u < 6; ++u) asm volatile("" : "+v"(g[u])); // (keeps the reads 16 bytes wide: the fourth word is unused, and hipcc would
                                                                     //  narrow them to ds_read_b96 -- 8 LDS cycles in 8-lane groups against ds_read_b128's 4)
@@ -727,7 +797,8 @@ DEV void g_stage(const PairC& c, const float* fb, const JOut& j, unsigned tmask,
             }
         }
     }
-    f4 wa = *(const f4*)(fb + c.wtA), wb = *(const f4*)(fb + c.wtB);
+    if constexpr (!WAB) { r.wa = *(const f4*)(fb + c.wtA); r.wb = *(const f4*)(fb + c.wtB); }
+    f4 wa = r.wa, wb = r.wb;
     asm volatile("" : "+v"(wa), "+v"(wb)); // (16-byte reads, as above)
     // torque: bone x S (+ own rotation torque); on the root the sum over the trackers' root torques itself
     f2 t0 = j.u[1] * S[2] - j.u[2] * S[1] + c.rho * S[0];
@@ -1369,17 +1440,27 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
         STAMP(2);
 
         // ================= kinematics
+        // (every instantiation takes the changes that cost it no spill, counted at compile time.  The body-part units: all three.  The dense
+        //  units have 40 vector registers fewer to spare: stage T's forty operands across stage J spill 2-4 registers in the fixed-count
+        //  kernels, and the late chunk 2 in the long sequence kernel -- they keep the old order there)
+        constexpr int ER = W4_EARLY_READS & (W4_BP ? 7 : (EARLY ? 1 : 3));
+        constexpr bool G_WAB = (ER & 1) != 0, WQ_LATE = (ER & 2) != 0, T_EARLY = (ER & 4) != 0;
+        TRd trd;
 #ifndef W4_ABLATE_J
-        j_stage(pc, fb, y01, y23, jo);
+        j_stage<T_EARLY>(pc, fb, y01, y23, jo, trk, trd);
 #else
         jo.q[0] = f2{y01[0], y01[1]}; jo.q[1] = f2{y01[2], y01[3]}; jo.q[2] = f2{y23[0], y23[1]}; jo.q[3] = f2{y23[2], y23[3]};
         jo.u[0] = jo.q[0]; jo.u[1] = jo.q[1]; jo.u[2] = jo.q[2]; jo.inv = splat2(1.f);
+        if constexpr (T_EARLY) { t_reads_q(trk, fb, trd); t_reads_bn(trk, fb, trd); }
 #endif
+        // (no instruction: a compiler fence between stage J's stores and the reads behind them -- the second pass's, and with T_EARLY off
+        //  every read of stage T; the stores' own memory clobber is what holds the reads issued from inside stage J behind them)
         wave_sync();
         STAMP(3);
         if (!optimise) break; // forward-only launch (uniform)
 #ifndef W4_ABLATE_T // (diagnostic builds, tools/ablate_w4.sh: a stage left out to time the rest -- results are wrong by construction)
-        t_stage(trk, fb, EARLY || last);
+        if constexpr (T_EARLY) t_finish<true>(trk, fb, EARLY || last, trd);
+        else t_stage(trk, fb, EARLY || last);
         for (int base = 16; base < Emax; base += 16) t_stage(load_tracker(a, fb, E, base + b), fb, EARLY || last); // (uniform, rare)
 #endif
         // bL2's weights leave LDS in three chunks (a read costs the wave its issue time wherever it stands -- the four waves of
@@ -1390,11 +1471,23 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
         f4 wq[NQ], wr[8], ws[10];
         // (uniform; mode 2 leaves groups 1..8 out, see bl2 below: its chain goes from group 0 straight to group 9, so groups 9.. take the
         //  first chunk's registers and its place here -- requested at the head of the chain they would come back an LDS round trip late)
-        if (EARLY || b2_mode != 2) load_w<NQ>(wq, w2 + B2_RES * 64);
-        else load_w<NQ>(wq, w2 + 9 * 64);
-        __builtin_amdgcn_sched_barrier(0);
+        // The chunk is not needed before bL2 and reads come back in order: WQ_LATE requests it BEHIND stage G's reads (and, EARLY, the stop
+        // test's), which the wave is about to wait for.
+        const auto load_wq = [&] {
+            if (EARLY || b2_mode != 2) load_w<NQ>(wq, w2 + B2_RES * 64);
+            else load_w<NQ>(wq, w2 + 9 * 64);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        if constexpr (!WQ_LATE) load_wq();
         wave_sync();
         STAMP(4);
+        GRd grd;
+        if constexpr (WQ_LATE) { // one group of requests: stage G's first, (EARLY: the stop test's, below,) the chunk last
+#ifndef W4_ABLATE_G
+            g_reads<G_WAB>(pc, fb, grd);
+#endif
+            if constexpr (!EARLY) load_wq();
+        }
         unsigned actmask = 0xFu, stopmask = 0u; // bit r: frame f0 + r runs this iteration / stops after its step
         if (EARLY) {
             bool was_act = false, stop_now = false;
@@ -1430,10 +1523,12 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
             }
             actmask = (unsigned)__ballot(was_act && b == 0) & 0xFu;
             stopmask = (unsigned)__ballot(stop_now && b == 0) & 0xFu;
+            if constexpr (WQ_LATE) load_wq();
         }
         f4 gyA, gyB;
 #ifndef W4_ABLATE_G
-        g_stage(pc, fb, jo, tmask, Emax, gyA, gyB);
+        if constexpr (!WQ_LATE) g_reads<G_WAB>(pc, fb, grd);
+        g_stage<G_WAB>(pc, fb, jo, tmask, Emax, grd, gyA, gyB);
 #else
         gyA = f4{jo.q[0].x, jo.q[1].x, jo.q[2].x, jo.q[3].x}; gyB = f4{jo.q[0].y, jo.q[1].y, jo.q[2].y, jo.q[3].y};
 #endif
