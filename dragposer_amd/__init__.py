@@ -5,6 +5,7 @@ from .points import Point, Points  # noqa: F401  (terms on weighted joint combin
 from .holds import Hold, Holds  # noqa: F401  (joints held where they touched down: include/dragposer_holds.h)
 from .gaps import Gaps  # noqa: F401  (trackers that drop out and come back: include/dragposer_gaps.h)
 from .tethers import Tether, Tethers  # noqa: F401  (joints tied to their own recent path: include/dragposer_tethers.h)
+from .lm import LM  # noqa: F401  (a Levenberg-Marquardt solver for the per-frame problem: include/dragposer_lm.h)
 from .encoder import NativePoseEncoder  # noqa: F401  (the pose encoder in one HIP launch: include/dragposer_encoder.h)
 
 

@@ -288,6 +288,26 @@ class DpPoints(_Sized):
     _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("n_points", C.c_int), ("reserved1", C.c_int), ("coeff", C.c_void_p)]
 
 
+# every symbol include/dragposer_lm.h declares (tests/test_lm_abi.py)
+LM_SYMBOLS = ("dp_optimize_lm",)
+DP_LM_MAX_STEPS = 64
+
+
+class DpLmParams(_Sized):
+    """include/dragposer_lm.h: dp_lm_params, with DP_LM_PARAMS_INIT's defaults"""
+    _fields_ = [("struct_size", C.c_uint), ("n_steps", C.c_int), ("lambda_rot", C.c_float), ("lambda_tmp", C.c_float), ("mu0", C.c_float),
+                ("mu_up", C.c_float), ("mu_down", C.c_float), ("mu_min", C.c_float), ("mu_max", C.c_float), ("early_stop", C.c_int),
+                ("stop_eps_pos", C.c_float), ("stop_eps_rot", C.c_float)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **dict(dict(n_steps=3, lambda_rot=1.0, lambda_tmp=0.0, mu0=1e-2, mu_up=4.0, mu_down=1.0 / 3.0, mu_min=1e-6, mu_max=1e6), **k))
+
+
+class DpLmExtra(_Sized):
+    """include/dragposer_lm.h: dp_lm_extra (device pointers)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("mu", C.c_void_p), ("n_accepted", C.c_void_p), ("loss0", C.c_void_p)]
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -392,6 +412,7 @@ def load(path=None):
                                                       C.POINTER(DpSkeletonIn), C.POINTER(DpResult), C.c_void_p]
     lib.dp_optimize_sequence_terms_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
                                                       C.POINTER(DpPoints)] + _seq_tail
+    lib.dp_optimize_lm.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpLmParams), C.POINTER(DpResult), C.POINTER(DpLmExtra), C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

@@ -26,10 +26,12 @@
 #include "../../include/dragposer_live.h"
 #include "../../include/dragposer_tethers.h"
 #include "../../include/dragposer_points.h"
+#include "../../include/dragposer_lm.h"
 #include "dp_cons_live.h"
 #include "dp_cons_tether.h"
 #include "dp_cons_points.h"
 #include "dp_host_rt.h"
+#include "dp_lm.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
 #include "dp_vjp.h"
@@ -684,6 +686,8 @@ constexpr Sized LATENT_AR_V540 = {"dp_latent_ar", "dp_latent_ar r = DP_LATENT_AR
 constexpr Sized GAPS_V550 = {"dp_gaps", "dp_gaps g = DP_GAPS_INIT;", offsetof(dp_gaps, trace) + sizeof(void*), false};
 constexpr Sized TETHERS_V570 = {"dp_tethers", "dp_tethers t = DP_TETHERS_INIT;", offsetof(dp_tethers, trace) + sizeof(void*), false};
 constexpr Sized POINTS_V580 = {"dp_points", "dp_points p = DP_POINTS_INIT;", offsetof(dp_points, coeff) + sizeof(void*), false};
+constexpr Sized LM_PARAMS_V590 = {"dp_lm_params", "dp_lm_params p = DP_LM_PARAMS_INIT;", offsetof(dp_lm_params, stop_eps_rot) + sizeof(float), false};
+constexpr Sized LM_EXTRA_V590 = {"dp_lm_extra", "dp_lm_extra e = DP_LM_EXTRA_INIT;", offsetof(dp_lm_extra, loss0) + sizeof(void*), false};
 constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
@@ -1208,6 +1212,66 @@ extern "C" int dp_optimize_terms_skeleton(dp_ctx* ctx, const dp_batch* in, const
         if (!in || !p_in || !t_in || !out_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_terms_skeleton: NULL batch, params, terms or result");
         if (!skel) return refuse_null_skeleton(ctx, who);
         return constrained_impl<dpcons::TermSkelArgs>(ctx, in, p_in, out_in, stream, who, own, dp_launch_terms_skel);
+    });
+}
+
+// include/dragposer_lm.h: dp_lm_params and dp_lm_extra validated and written into the kernel's argument block, in the header's order of
+// refusals (dp_lm_params has no reserved0: its size word alone is checked, like dp_params')
+// (its launcher is a weak reference, like those of the sequence units below: a library linked without dp_lm.hip refuses the call)
+hipError_t dp_launch_lm(const dplm::Args* args, hipStream_t stream) __attribute__((weak));
+static int take_lm(dp_ctx* ctx, const dp_lm_params* p_in, const dp_lm_extra* e_in, dplm::Args& a, const char* who)
+{
+    const std::string w = who;
+    dp_lm_params p;
+    dp_lm_extra e;
+    std::memset(&e, 0, sizeof(e));
+    if (e_in)
+        if (int rc = take_sized(ctx, e_in, e, LM_EXTRA_V590, who)) return rc;
+    copy_sized(p_in, p);
+    if (p.n_steps < 1 || p.n_steps > DP_LM_MAX_STEPS)
+        return fail(ctx, DP_ERR_INVALID, w + ": n_steps " + std::to_string(p.n_steps) + " outside 1.." + std::to_string(DP_LM_MAX_STEPS));
+    const auto fin = [](float x) { return std::fabs(x) <= 3.0e38f; };
+    if (!(p.lambda_rot >= 0.f && fin(p.lambda_rot)) || !(p.lambda_tmp >= 0.f && fin(p.lambda_tmp)))
+        return fail(ctx, DP_ERR_INVALID, w + ": lambda_rot or lambda_tmp is negative or not finite");
+    const float rest[7] = {p.mu0, p.mu_up, p.mu_down, p.mu_min, p.mu_max, p.stop_eps_pos, p.stop_eps_rot};
+    for (float x : rest)
+        if (!fin(x)) return fail(ctx, DP_ERR_INVALID, w + ": mu0, mu_up, mu_down, mu_min, mu_max or a stop threshold is not finite");
+    if (!(p.mu_down > 0.f && p.mu_down < 1.f)) return fail(ctx, DP_ERR_INVALID, w + ": mu_down must lie in (0, 1)");
+    if (!(p.mu_up > 1.f)) return fail(ctx, DP_ERR_INVALID, w + ": mu_up must be greater than 1");
+    if (!(p.mu_min > 0.f) || p.mu_min > p.mu_max) return fail(ctx, DP_ERR_INVALID, w + ": need 0 < mu_min <= mu_max");
+    if (p.mu0 < p.mu_min || p.mu0 > p.mu_max) return fail(ctx, DP_ERR_INVALID, w + ": mu0 outside [mu_min, mu_max]");
+    a.n_steps = p.n_steps; a.early_stop = p.early_stop ? 1 : 0;
+    a.lam_rot = p.lambda_rot; a.lam_tmp = p.lambda_tmp;
+    a.mu0 = p.mu0; a.mu_up = p.mu_up; a.mu_down = p.mu_down; a.mu_min = p.mu_min; a.mu_max = p.mu_max;
+    a.stop_eps_pos = p.stop_eps_pos; a.stop_eps_rot = p.stop_eps_rot;
+    a.mu = e.mu; a.n_accepted = e.n_accepted; a.loss0 = e.loss0;
+    return DP_OK;
+}
+
+extern "C" int dp_optimize_lm(dp_ctx* ctx, const dp_batch* in, const dp_lm_params* p_in, const dp_result* out_in, const dp_lm_extra* e_in, void* stream)
+{
+    const char* who = "dp_optimize_lm";
+    return entry(ctx, who, [&] {
+        if (!in || !p_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_lm: NULL batch or params");
+        if (p_in->struct_size < LM_PARAMS_V590.min_size || p_in->struct_size > 4096u)
+            return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_lm_params.struct_size is " + std::to_string(p_in->struct_size) + ", this library expects at least " +
+                                                 std::to_string(LM_PARAMS_V590.min_size) + "  (" + LM_PARAMS_V590.init + ")");
+        dp_result out;
+        if (int rc = take_result(ctx, out_in, out, who)) return rc;
+        dplm::Args a;
+        std::memset(&a, 0, sizeof(a));
+        if (int rc = take_lm(ctx, p_in, e_in, a, who)) return rc;
+        if (int rc = check_batch(ctx, in, who)) return rc;
+        if (REF8_BUILD) return refuse_ref8(ctx, who);
+        if (!dp_launch_lm) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_lm.hip");
+        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+        DEVICE_GUARD(ctx);
+        a.img = ctx->d_vjpimg.get();
+        fill_batch(a, *in);
+        fill_results(a, out);
+        const hipError_t e = dp_launch_lm(&a, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
+        return (int)DP_OK;
     });
 }
 

@@ -52,6 +52,13 @@ def _check_ar(temporal, ar, who):
         raise ValueError(f"DragPose.{who}: ar.order {ar.order} exceeds the history of {HISTORY} frames")
 
 
+def _solver_alone(who, **layers):
+    """solver=LM(...) has the trackers and the pull in its loss and nothing else (include/dragposer_lm.h, Not covered)"""
+    for name, given in layers.items():
+        if given is not None:
+            raise ValueError(f"DragPose.{who}: solver= does not go with {name}= (include/dragposer_lm.h, Not covered)")
+
+
 def _points_alone(terms, who, **layers):
     """a table with points (include/dragposer_points.h) runs through its own entry points, which take none of the sequence layers"""
     if terms is not None and getattr(terms, "has_points", False):
@@ -114,6 +121,7 @@ class DragPose:
         self._out = [None, None]
         self._flip = 0
         self.hold_state = None  # [S,len(holds),4] (x, y, z, held) of run(holds=) / run_frames(holds=); zeroed when a sequence begins
+        self.lm_mu = None  # [S] the damping of run(solver=LM(...)) (include/dragposer_lm.h), kept from frame to frame; reset when a sequence begins
         self.gap_state = None  # [S,22,16] of run(gaps=) / run_frames(gaps=) (include/dragposer_gaps.h); zeroed when a sequence begins
         self.tether_state = None  # [S,len(tethers),8] of run(tethers=) / run_frames(tethers=) (include/dragposer_tethers.h); zeroed when a sequence begins
         self._skel_obj, self._skel_dev = None, None  # the last `offsets` object run() / run_frames() was given, and what it decided (_skeleton)
@@ -202,6 +210,7 @@ class DragPose:
         self.target_latent_buffer = None
         self.hold_state = None
         self.tether_state = None
+        self.lm_mu = None
         self.gap_state = torch.zeros(self.S, NJ, 16, device=self.device)
 
     def set_initial_state(self, latent, init_global_pos, initial_global_rot, initial_heights):
@@ -218,6 +227,7 @@ class DragPose:
         self.target_latent_buffer = None
         self.hold_state = None
         self.tether_state = None
+        self.lm_mu = None
         self.gap_state = torch.zeros(self.S, NJ, 16, device=self.device)
 
     # ------------------------------------------------------------------ temporal target (drag_pose.py:234-294)
@@ -293,7 +303,7 @@ class DragPose:
     def run_frames(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, target_root=None, stop_eps_pos=1e-2, stop_eps_rot=1e-2,
                    max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1, temporal_future_window=60,
                    height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01, offsets=None,
-                   constraints=None, terms=None, holds=None, ar=None, gaps=None, present=None, tethers=None):
+                   constraints=None, terms=None, holds=None, ar=None, gaps=None, present=None, tethers=None, solver=None):
         """T consecutive frames of every sequence -- T calls of run() -- with the frame loop on the device: one kernel launch per
         stretch of frames between two temporal predictions (all T of them when there is no predictor or lambda_temporal is 0).
         target_ee_pos [T,S,E,3], target_ee_rot [T,S,E,3,3]; `target_root` [T,S,3] or None: given, the position targets of frame t
@@ -323,7 +333,25 @@ class DragPose:
         include/dragposer_tethers.h), one launch per stretch, with or without `holds`, `ar` and `gaps` (without `gaps` it runs with
         Gaps(0, 1.0), under which an absent sample leaves the loss at once); the state lives in `tether_state` [S,len(tethers),8], zeroed
         when a sequence begins and passed through every stretch, and `last_tether_trace` [T,S,len(tethers),8] holds it after every frame.
+        `solver` (a dragposer_amd.LM): every frame solved by Levenberg-Marquardt steps (include/dragposer_lm.h).  This is the HOST loop over
+        run(solver=), frame by frame its bits: the frame loop is not on the device, and none of the other layers goes with it.
         Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
+        if solver is not None:
+            _solver_alone("run_frames", constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, tethers=tethers, target_root=target_root)
+            tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=self.device)
+            tR = torch.as_tensor(target_ee_rot, dtype=torch.float32, device=self.device)
+            T = int(tp.shape[0])
+            poses, gposs = torch.empty(T, self.S, 88, device=self.device), torch.empty(T, self.S, 3, device=self.device)
+            iters, status = (torch.empty(T, self.S, dtype=torch.int32, device=self.device) for _ in range(2))
+            for t in range(T):
+                self.run(tp[t].reshape(self.S, -1, 3), tR[t].reshape(self.S, -1, 3, 3), mask_joints, weights_joints, offsets=offsets, stop_eps_pos=stop_eps_pos,
+                         stop_eps_rot=stop_eps_rot, lambda_rot=lambda_rot, lambda_temporal=lambda_temporal, temporal_future_window=temporal_future_window,
+                         height_indices=height_indices, joint_adjustment_indices=joint_adjustment_indices,
+                         joint_adjustment_weight=joint_adjustment_weight, out_pose=poses[t], out_pos=gposs[t], solver=solver)
+                iters[t].copy_(self.last["iters"])
+                status[t].copy_(self.last["status"])
+            self.last_status = status
+            return poses, gposs, iters
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run_frames: pass constraints or terms, not both")
         _points_alone(terms, "run_frames", holds=holds, gaps=gaps, ar=ar, tethers=tethers)
@@ -461,7 +489,7 @@ class DragPose:
             stop_eps_rot=1e-2, max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1,
             temporal_future_window=60, height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None,
             joint_adjustment_weight=0.01, verbose=False, out_pose=None, out_pos=None, constraints=None, terms=None, holds=None, ar=None,
-            gaps=None, present=None, live=False, tethers=None):
+            gaps=None, present=None, live=False, tethers=None, solver=None):
         """One frame for every sequence: one launch for the optimise loop and the epilogue, one for the history buffers, plus two
         row scatters of the targets.  `out_pose` [S,88] / `out_pos` [S,3]: optional caller storage for the returned tensors.
         `constraints` (a dragposer_amd.Constraints): the reference's extra loss terms (drag_pose.py:129-183) join the loss -- the frame
@@ -487,7 +515,18 @@ class DragPose:
         or [S,22,3] one per sequence.  The context's own skeleton (or None) runs the launches above unchanged; any other runs the same frame
         with those bones (dp_optimize_sequence_skeleton, include/dragposer_skeleton.h), not together with `constraints` / `terms`: this
         class does not route that combination; LatentOptimizer.optimize_constrained / optimize_terms take `offsets=` themselves.  Passing
-        the same object frame after frame costs one host synchronisation in all (DragPose._skeleton)."""
+        the same object frame after frame costs one host synchronisation in all (DragPose._skeleton).
+        `solver` (a dragposer_amd.LM; None = Adam, the default): the frame's latent is found by Levenberg-Marquardt steps instead --
+        dp_optimize_lm followed by dp_sequence_advance (two launches, include/dragposer_lm.h); max_iter, learning_rate and min_loss_incr are
+        not used, stop_eps_pos / stop_eps_rot are the early stop's thresholds unless the LM carries its own.  The damping is kept per sequence
+        in `lm_mu` [S] and reset when a sequence begins.  Not together with constraints= / terms= / holds= / ar= / gaps= / tethers= / live= or
+        offsets other than the context's skeleton: the LM loss has the trackers and the pull only."""
+        if solver is not None:
+            _solver_alone("run", constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, tethers=tethers, live=live or None,
+                          present=present)
+            solver.check()
+            if self._skeleton(offsets) is not None:
+                raise ValueError("DragPose.run: solver= runs on the context's skeleton only (include/dragposer_lm.h, Not covered)")
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
         _points_alone(terms, "run", holds=holds, gaps=gaps, ar=ar, tethers=tethers, live=bool(live))
@@ -567,6 +606,9 @@ class DragPose:
         o = self._out[self._flip]
         z_tgt = self.target_latent_buffer[:, self.current_index:]
         pull = self.temporal is not None and float(lambda_temporal) != 0.0  # (no predictor: the buffer is zeros, the term is off; run_frames() alike)
+        if solver is not None:
+            return self._run_lm(solver, trk, o, pose, gpos, adjust, height_indices, lambda_rot, lambda_temporal if pull else 0.0, stop_eps_pos,
+                                stop_eps_rot, temporal_future_window, verbose, squeeze)
         if constraints is not None or terms is not None:
             return self._run_constrained(constraints if terms is None else terms, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot,
                                          lambda_temporal if pull else 0.0, stop_eps_pos, stop_eps_rot, min_loss_incr, temporal_future_window,
@@ -610,6 +652,35 @@ class DragPose:
             l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
             print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "
                   f"Loss Temporal: {l[:, 2].mean():.5f} // Iter: {it.float().mean():.1f}")
+        if squeeze and S == 1:
+            return pose[0], gpos[0]
+        return pose, gpos
+
+    def _run_lm(self, solver, trk, o, pose, gpos, adjust, height_indices, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, window, verbose, squeeze):
+        """run(solver=LM(...)): the frame's latent by dp_optimize_lm, then run()'s epilogue (dp_sequence_advance)"""
+        S = self.S
+        if o.get("lm_frame") is None:
+            o["lm_frame"] = self.opt.allocate_outputs(S, ("z", "z_pre", "pose", "disp", "world_disp", "world_rot", "pos", "loss", "iters", "status"))
+            o["lm_frame"].update(n_accepted=torch.empty(S, dtype=torch.int32, device=self.device), loss0=torch.empty(S, 3, device=self.device))
+        fr = o["lm_frame"]
+        if self.lm_mu is None:
+            self.lm_mu = torch.full((S,), float(solver.mu0), device=self.device)
+        z_tgt = self.target_latent_buffer[:, self.current_index].contiguous()
+        self.opt.optimize_lm(self.latent, z_tgt, self.current_global_rot, trk["tgt_pos"], trk["tgt_rot"], trk["w"], trk["tracked"], lm=solver,
+                             lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_tmp), mu=self.lm_mu, stop_eps_pos=stop_eps_pos,
+                             stop_eps_rot=stop_eps_rot, out=fr, outputs=tuple(fr) + ("mu",))
+        self.opt.sequence_advance(fr, self.current_global_pos, self.current_global_rot, self.latent_buffer, self.displacement_buffer,
+                                  self.heights_buffer, tuple(int(h) for h in height_indices), pose_ret=pose, pos_ret=gpos, adjust=adjust,
+                                  tgt_pos=trk["tgt_pos"] if adjust is not None else None)
+        self.latent.copy_(fr["z"])
+        o["z"].copy_(self.latent)
+        self.last = dict(iters=fr["iters"], loss=fr["loss"], z=o["z"], pose=pose, pos=gpos, status=fr["status"], n_accepted=fr["n_accepted"],
+                         loss0=fr["loss0"], joint_pos=fr["pos"])
+        if verbose:
+            l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
+            print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "
+                  f"Loss Temporal: {l[:, 2].mean():.5f} // Iter: {it.float().mean():.1f}")
+        self.current_index = 0 if window == 0 else (self.current_index + 1) % window
         if squeeze and S == 1:
             return pose[0], gpos[0]
         return pose, gpos

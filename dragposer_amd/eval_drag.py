@@ -284,6 +284,8 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
         if extra.get("constraints") is None:
             extra.pop("constraints", None)
         extra["gaps"] = args.gaps_model
+    if getattr(args, "solver_model", None) is not None:
+        extra = dict(solver=args.solver_model)
     poses = torch.zeros(T, S, 88, device=dev)
     out_pos = torch.zeros(T, S, 3, device=dev)
     iters = torch.zeros(T, S, dtype=torch.int32, device=dev)
@@ -466,6 +468,10 @@ def main(argv=None):
                          "frames at a weight that decays by DECAY per frame, and leaves the loss after that until it returns "
                          "(DragPose.run_frames(gaps=), include/dragposer_gaps.h; with --per-frame DragPose.run(gaps=), same results).  No default: "
                          "nobody has tuned one")
+    ap.add_argument("--solver", default=None, metavar="lm[:STEPS]",
+                    help="solve every frame by Levenberg-Marquardt steps (default 3) instead of Adam: DragPose.run(solver=LM(STEPS)), dp_optimize_lm "
+                         "followed by dp_sequence_advance per frame (include/dragposer_lm.h); implies --per-frame (the frame loop is on the host); "
+                         "not with --constraints, --foot-lock, --tether, --balance, --latent-ar or --gaps, and for a BVH with the model's own skeleton")
     ap.add_argument("--lockstep", action="store_true",
                     help="directory input: advance all files together, one kernel launch per frame index for all of them "
                          "(same per-file results; the reference evaluates them one after the other)")
@@ -507,6 +513,23 @@ def main(argv=None):
             if given:
                 raise SystemExit(f"--balance and {flag}: a table with points takes no holds, tethers, latent predictor or gaps (include/dragposer_points.h)")
         args.balance_spec = parse_balance(args.balance, args.balance_masses)
+    args.solver_model = None
+    if args.solver is not None:
+        from .lm import LM
+
+        name, _, steps = args.solver.partition(":")
+        try:
+            if name != "lm":
+                raise ValueError("unknown solver " + repr(name))
+            args.solver_model = LM(steps=int(steps) if steps else 3).check()
+        except ValueError as e:
+            raise SystemExit(f"--solver: expected lm[:STEPS] with 1 <= STEPS <= 64 ({e})")
+        for flag, given in (("--constraints", args.constraints), ("--foot-lock", args.foot_lock), ("--tether", args.tether), ("--balance", args.balance),
+                            ("--latent-ar", args.latent_ar), ("--gaps", args.gaps)):
+            if given:
+                raise SystemExit(f"--solver and {flag}: the LM loss has the trackers and the pull only (include/dragposer_lm.h, Not covered)")
+        args.per_frame = True
+        print(f"Solver: Levenberg-Marquardt, {args.solver_model.steps} steps per frame (DragPose.run(solver=), include/dragposer_lm.h)")
     args.gaps_model = None
     if args.gaps is not None:
         from .gaps import Gaps

@@ -318,6 +318,36 @@ class LatentOptimizer:
             "optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]" if terms.needs_global_pos else None,
             lambda gp, lt: terms.to_struct(int(z0.shape[0]), self.device, gp, lt), skel=skel, mid=mid)
 
+    def optimize_lm(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, lm=None, lambda_rot=1.0, lambda_tmp=0.02, mu=None, stop_eps_pos=0.0,
+                    stop_eps_rot=0.0, outputs=None, out=None):
+        """`optimize`'s problem solved by Levenberg-Marquardt steps instead of Adam (`lm`: a dragposer_amd.LM; None = LM()):
+        include/dragposer_lm.h, dp_optimize_lm (one launch).  Inputs as in `optimize`.  `mu` [B] fp32 on the device: the damping of every
+        frame, read and updated IN PLACE (a caller keeps it from frame to frame); None: every frame starts at lm.mu0.  Returns `optimize`'s
+        dict (every array belongs to the returned z; z_pre = z; iters = the steps executed) plus `n_accepted` [B] int32, `loss0` [B,3] (the
+        loss at z0) and `mu` [B] (the damping after the call).  `stop_eps_pos` / `stop_eps_rot`: the early stop's thresholds unless `lm`
+        carries its own.  Asynchronous on torch's current stream."""
+        from .lm import LM
+
+        lm = (lm if lm is not None else LM()).check()
+        B, dev = int(z0.shape[0]), self.device
+        batch = self._batch(z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked)
+        p = lm.to_struct(lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot)
+        own = {"n_accepted": ((B,), torch.int32), "loss0": ((B, 3), torch.float32), "mu": ((B,), torch.float32)}
+        names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS) + tuple(own)
+        res, tensors = self._outputs(B, [n for n in names if n not in own and n != "clock"], out)
+        ex = _lib.DpLmExtra()
+        for name, (shape, dtype) in own.items():
+            if name == "mu":
+                t = mu if mu is not None else torch.full(shape, float(lm.mu0), dtype=dtype, device=dev)
+            elif name in names:
+                t = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
+            else:
+                continue
+            setattr(ex, name, _check(t, name, shape, dtype, dev))
+            tensors[name] = t
+        self._call(self.lib.dp_optimize_lm, C.byref(batch), C.byref(p), C.byref(res), C.byref(ex))
+        return tensors
+
     def forward_vjp(self, z, cur_rot, grads, out=None, offsets=None, doffsets=False):
         """dL/dz [B,24] and dL/dcur_rot [B,4] of decode + FK at (z, cur_rot) for upstream gradients `grads` = {output name: dL/d(that
         output)} over any subset of pose, disp, world_disp, world_rot, pos, rot (shapes as `forward` returns them; missing = zero):

@@ -1,0 +1,132 @@
+// tests/lm_san/main.cpp -- dp_optimize_lm (include/dragposer_lm.h) under AddressSanitizer and UndefinedBehaviorSanitizer: a stand-alone
+// program that links dp_host.cpp against tests/host_san/fake_hip.cpp (no HIP runtime, no kernel unit) and walks the call's refusals, in the
+// header's order, on a context without a device.  Every sized struct is handed over in a heap block of exactly struct_size bytes, so a
+// read past what the caller owns is an error here.  Device pointers are a constant that is never dereferenced.  Built and run by
+// tests/test_lm_san.py; every condition is exact.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "../../include/dragposer_lm.h"
+
+extern "C" int dp_debug_host_ctx(dp_ctx**); // the library's private hook: a context with no device behind it
+
+#define CHECK(cond)                                                                      \
+    do {                                                                                 \
+        if (!(cond)) {                                                                   \
+            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
+            std::exit(1);                                                                \
+        }                                                                                \
+    } while (0)
+
+namespace {
+
+float* const PTR = (float*)0x10000; // stands for a device pointer
+
+// a T in a heap block of exactly `size` bytes (default: sizeof(T))
+template <class T>
+struct Exact {
+    void* block;
+    explicit Exact(const T& init, size_t size = sizeof(T)) : block(std::malloc(size)) { std::memcpy(block, &init, size < sizeof(T) ? size : sizeof(T)); }
+    ~Exact() { std::free(block); }
+    Exact(const Exact&) = delete;
+    const T* get() const { return (const T*)block; }
+};
+
+struct Case { // what one call is made of; the defaults are well-formed
+    dp_lm_params p = DP_LM_PARAMS_INIT;
+    unsigned result_size = sizeof(dp_result), extra_size = sizeof(dp_lm_extra), extra_reserved0 = 0u;
+    bool null_batch = false, null_params = false, null_result = false, null_extra = false, with_outputs = true, null_z_tgt = false;
+    int n_frames = 4;
+};
+
+int run(dp_ctx* ctx, const Case& c)
+{
+    dp_batch b0{};
+    b0.n_frames = c.n_frames;
+    b0.z0 = b0.cur_rot = b0.tgt_pos = b0.tgt_rot = b0.w = PTR; b0.tracked = (const unsigned char*)PTR;
+    b0.z_tgt = c.null_z_tgt ? nullptr : PTR;
+    dp_result r0 = DP_RESULT_INIT;
+    r0.struct_size = c.result_size;
+    if (c.with_outputs) { r0.z = r0.z_pre = r0.pose = r0.pos = r0.loss = PTR; r0.iters = r0.status = (int*)PTR; }
+    dp_lm_extra e0 = DP_LM_EXTRA_INIT;
+    e0.struct_size = c.extra_size; e0.reserved0 = c.extra_reserved0;
+    if (c.with_outputs) { e0.mu = e0.loss0 = PTR; e0.n_accepted = (int*)PTR; }
+    Exact<dp_batch> b(b0);
+    Exact<dp_lm_params> p(c.p, c.p.struct_size < sizeof(dp_lm_params) ? c.p.struct_size : sizeof(dp_lm_params));
+    Exact<dp_result> r(r0, c.result_size < sizeof(dp_result) ? c.result_size : sizeof(dp_result));
+    Exact<dp_lm_extra> e(e0, c.extra_size < sizeof(dp_lm_extra) ? c.extra_size : sizeof(dp_lm_extra));
+    return dp_optimize_lm(ctx, c.null_batch ? nullptr : b.get(), c.null_params ? nullptr : p.get(), c.null_result ? nullptr : r.get(),
+                          c.null_extra ? nullptr : e.get(), nullptr);
+}
+
+bool said(dp_ctx* ctx, const char* word) { return std::string(dp_last_error(ctx)).find(word) != std::string::npos; }
+
+} // namespace
+
+int main()
+{
+    dp_ctx* ctx = nullptr;
+    CHECK(dp_debug_host_ctx(&ctx) == DP_OK && ctx);
+    int n = 0;
+    const auto refused = [&](const Case& c, const char* word) {
+        CHECK(run(ctx, c) == DP_ERR_INVALID);
+        if (!said(ctx, word)) { std::fprintf(stderr, "expected '%s' in: %s\n", word, dp_last_error(ctx)); std::exit(1); }
+        CHECK(said(ctx, "dp_optimize_lm"));
+        ++n;
+    };
+    const float inf = __builtin_inff(), nan = __builtin_nanf("");
+    // well-formed: this link has no kernel unit, which the library says after every argument check
+    for (int variant = 0; variant < 6; ++variant) {
+        Case c;
+        if (variant == 1) c.null_extra = true;
+        if (variant == 2) c.null_result = true;                                   // no result wanted
+        if (variant == 3) c.with_outputs = false;                                 // every pointer NULL
+        if (variant == 4) { c.p.n_steps = DP_LM_MAX_STEPS; c.p.early_stop = 1; c.p.stop_eps_pos = 1e-4f; c.p.mu0 = c.p.mu_min; }
+        if (variant == 5) { c.p.mu_min = c.p.mu_max = c.p.mu0 = 1.f; c.p.lambda_rot = 0.f; c.p.lambda_tmp = 0.f; }
+        CHECK(run(ctx, c) == DP_ERR_UNSUPPORTED);
+        CHECK(said(ctx, "dp_lm.hip"));
+        ++n;
+    }
+    // the refusals in the header's order: each is reported before every later one's fault
+    { Case c; c.null_batch = true; c.p.n_steps = 0; refused(c, "NULL batch or params"); }
+    { Case c; c.null_params = true; c.n_frames = 0; refused(c, "NULL batch or params"); }
+    { Case c; c.p.struct_size = 4; c.result_size = 8; refused(c, "dp_lm_params.struct_size"); }       // a block of 4 bytes: only the size word exists
+    { Case c; c.p.struct_size = 44; c.p.n_steps = 0; refused(c, "dp_lm_params.struct_size"); }
+    { Case c; c.p.struct_size = 5000; refused(c, "dp_lm_params.struct_size"); }                       // (the block is sizeof(dp_lm_params): nothing past the size word is read)
+    { Case c; c.result_size = 8; c.extra_size = 8; refused(c, "dp_result.struct_size"); }
+    { Case c; c.extra_size = 8; c.p.n_steps = 0; refused(c, "dp_lm_extra.struct_size"); }
+    { Case c; c.extra_size = 24; c.p.n_steps = 0; refused(c, "dp_lm_extra.struct_size"); }
+    { Case c; c.extra_size = 5000; refused(c, "dp_lm_extra.struct_size"); }
+    { Case c; c.extra_reserved0 = 7u; c.p.n_steps = 0; refused(c, "reserved0"); }
+    { Case c; c.p.n_steps = 0; c.p.lambda_rot = nan; refused(c, "n_steps 0 outside"); }
+    { Case c; c.p.n_steps = DP_LM_MAX_STEPS + 1; c.p.mu_up = 0.f; refused(c, "n_steps 65 outside"); }
+    { Case c; c.p.n_steps = -3; refused(c, "n_steps -3 outside"); }
+    { Case c; c.p.lambda_rot = nan; c.p.mu_down = 2.f; refused(c, "lambda_rot or lambda_tmp"); }
+    { Case c; c.p.lambda_rot = -1.f; refused(c, "lambda_rot or lambda_tmp"); }
+    { Case c; c.p.lambda_tmp = inf; c.p.mu0 = nan; refused(c, "lambda_rot or lambda_tmp"); }
+    { Case c; c.p.mu0 = nan; c.p.mu_down = 2.f; refused(c, "is not finite"); }
+    { Case c; c.p.mu_up = inf; c.p.mu_down = 2.f; refused(c, "is not finite"); }
+    { Case c; c.p.mu_down = nan; refused(c, "is not finite"); }
+    { Case c; c.p.mu_min = -inf; refused(c, "is not finite"); }
+    { Case c; c.p.mu_max = inf; refused(c, "is not finite"); }
+    { Case c; c.p.stop_eps_pos = nan; refused(c, "is not finite"); }
+    { Case c; c.p.stop_eps_rot = inf; c.p.mu_up = 0.5f; refused(c, "is not finite"); }
+    { Case c; c.p.mu_down = 1.f; c.p.mu_up = 1.f; refused(c, "mu_down must lie in (0, 1)"); }
+    { Case c; c.p.mu_down = 0.f; refused(c, "mu_down must lie in (0, 1)"); }
+    { Case c; c.p.mu_down = -0.5f; refused(c, "mu_down must lie in (0, 1)"); }
+    { Case c; c.p.mu_up = 1.f; c.p.mu_min = 2.f; refused(c, "mu_up must be greater than 1"); }
+    { Case c; c.p.mu_up = 0.25f; refused(c, "mu_up must be greater than 1"); }
+    { Case c; c.p.mu_min = 2.f; c.p.mu_max = 1.f; c.p.mu0 = 5.f; refused(c, "0 < mu_min <= mu_max"); }
+    { Case c; c.p.mu_min = 0.f; refused(c, "0 < mu_min <= mu_max"); }
+    { Case c; c.p.mu0 = 1e7f; c.n_frames = 0; refused(c, "mu0 outside [mu_min, mu_max]"); }
+    { Case c; c.p.mu0 = 1e-7f; c.null_z_tgt = true; refused(c, "mu0 outside [mu_min, mu_max]"); }
+    { Case c; c.n_frames = 0; c.null_z_tgt = true; refused(c, "n_frames must be positive"); }
+    { Case c; c.n_frames = -2; refused(c, "n_frames must be positive"); }
+    { Case c; c.null_z_tgt = true; refused(c, "NULL input array"); }
+    CHECK(dp_optimize_lm(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DP_ERR_INVALID);
+    dp_destroy(ctx);
+    std::printf("lm: %d calls, all checks held\n", n);
+    return 0;
+}
