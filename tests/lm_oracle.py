@@ -23,6 +23,58 @@ def warm_inputs(model, B, trackers=6, mixed=False, seed=11):
     return b
 
 
+EVERY_JOINT_COUNTS = (7, 9, 11, 15, 21)  # frames 23..27 of every_joint_inputs
+
+
+def every_joint_inputs(model, warm, seed=11):
+    """28 frames that between them form every joint's rows of J: frame f < 22 tracks joint f alone, frame 22 all 22 joints, frames 23..27
+    the first 7, 9, 11, 15 and 21 joints of np.random.default_rng(3).permutation(22).  Weights of a tracked joint: uniform in [1, 10]
+    (position) and [0.01, 10] (rotation), 0 elsewhere; targets = FK(decode(z_src), cur_rot) of `model` (any tree) on the tracked joints;
+    z_src, z0, z_tgt and cur_rot are warm_inputs' (warm) or synth_inputs' (cold) draws."""
+    B = R.NJ + 1 + len(EVERY_JOINT_COUNTS)
+    b = warm_inputs(model, B, seed=seed) if warm else R.synth_inputs(model, B, seed=seed)
+    tracked = np.zeros((B, R.NJ), np.uint8)
+    tracked[np.arange(R.NJ), np.arange(R.NJ)] = 1
+    tracked[R.NJ] = 1
+    perm = np.random.default_rng(3).permutation(R.NJ)
+    for i, n in enumerate(EVERY_JOINT_COUNTS):
+        tracked[R.NJ + 1 + i, perm[:n]] = 1
+    rng = np.random.default_rng(seed)
+    w = np.stack((rng.uniform(1.0, 10.0, (B, R.NJ)), rng.uniform(0.01, 10.0, (B, R.NJ))), axis=-1) * tracked[..., None]
+    return retarget(model, dict(b, tracked=tracked, w=w.astype(np.float32)))
+
+
+def retarget(model, b):
+    """`b` with tgt_pos / tgt_rot = FK(decode(z_src), cur_rot) of `model` on b's tracked joints (fp32, 0 elsewhere), as synth_inputs forms them"""
+    dt = model.dtype
+    with torch.no_grad():
+        motion, disp = R.decoder_forward(model, torch.as_tensor(b["z_src"]).to(dt))
+        _, _, pos, rot, _ = R.pose_fk(model, motion, disp, torch.as_tensor(b["cur_rot"]).to(dt))
+    trk = torch.as_tensor(b["tracked"]).unsqueeze(-1).to(dt)
+    return dict(b, tgt_pos=(pos * trk).float().numpy(), tgt_rot=(rot.reshape(-1, R.NJ, 9) * trk).float().numpy())
+
+
+def tree_models(raw, path):
+    """the model arrays `raw` (another tree: tests/test_hip_topology.py's _model_arrays) saved at `path` -> (fp64, fp32) OracleModel"""
+    np.savez(path, **raw)
+    return R.OracleModel(path, dtype=torch.float64), R.OracleModel(path, dtype=torch.float32)
+
+
+def zero_problem(model, B, seed=11):
+    """(batch, lambda_tmp) of a problem whose every trial is refused by the Cholesky, in any arithmetic: the 6-tracker warm recipe with every
+    weight 0 and lambda_tmp = 0, so A = 0, g = 0 and every pivot is 0"""
+    b = warm_inputs(model, B, trackers=6, seed=seed)
+    return dict(b, w=np.zeros_like(b["w"])), 0.0
+
+
+def at_target_problem(model, B, seed=11):
+    """(batch, lambda_tmp) of a problem whose every trial is rejected by the strict `<`, in any arithmetic: zero_problem with lambda_tmp =
+    0.02 and z_tgt = z0 (warm_inputs sets it), so A = (lambda_tmp / 24) I, g = 0, delta = 0 and L' == L == 0"""
+    b, _ = zero_problem(model, B, seed)
+    assert np.array_equal(b["z_tgt"], b["z0"])
+    return b, 0.02
+
+
 def _conv(model, b):
     dt = model.dtype
     t = {k: torch.as_tensor(b[k]).to(dt) for k in ("z0", "z_tgt", "cur_rot", "tgt_pos", "tgt_rot", "w")}
@@ -55,17 +107,20 @@ def residual_fn(model, lam_rot, lam_tmp):
     return f
 
 
-def normal_equations(model, z, t, lam_rot, lam_tmp):
-    """-> A [B,24,24], g [B,24] at z"""
+def normal_equations(model, z, t, lam_rot, lam_tmp, jac_hook=None):
+    """-> A [B,24,24], g [B,24] at z.  `jac_hook(J) -> J` (J [B, 66 + 198 + 24, 24]: the position rows of joint j at 3j, its rotation rows at
+    66 + 9j, then the latent pull's) lets a test plant an error in J to show that a comparison would notice it."""
     f = residual_fn(model, lam_rot, lam_tmp)
     trk = t["tracked"].to(model.dtype)
     args = (z, t["cur_rot"], t["z_tgt"], t["tgt_pos"], t["tgt_rot"], t["w"], trk)
     J = torch.func.vmap(torch.func.jacfwd(f))(*args)
     r = torch.func.vmap(f)(*args)
+    if jac_hook is not None:
+        J = jac_hook(J)
     return J.transpose(1, 2) @ J, (J.transpose(1, 2) @ r[..., None])[..., 0]
 
 
-def lm(model, batch, n_steps, lam_rot=1.0, lam_tmp=0.02, mu=None, early_stop=False, stop_eps_pos=0.0, stop_eps_rot=0.0, **kw):
+def lm(model, batch, n_steps, lam_rot=1.0, lam_tmp=0.02, mu=None, early_stop=False, stop_eps_pos=0.0, stop_eps_rot=0.0, jac_hook=None, **kw):
     """n_steps LM steps on every frame of `batch` (a synth_inputs dict).  Returns numpy arrays: z, loss [B,3], loss0 [B,3], n_accepted, iters,
     mu (after), accepted [B,n_steps] (bool), ran [B,n_steps] (bool: the step was executed), margin [B,n_steps] (|L'-L|/L; NaN where not run),
     loss_hist [B,n_steps+1] (total loss of the kept latent)."""
@@ -92,7 +147,7 @@ def lm(model, batch, n_steps, lam_rot=1.0, lam_tmp=0.02, mu=None, early_stop=Fal
         if not bool(active.any()):
             hist.append(loss.sum(1).clone())
             continue
-        A, g = normal_equations(model, z, t, lam_rot, lam_tmp)
+        A, g = normal_equations(model, z, t, lam_rot, lam_tmp, jac_hook)
         H = A + mu_t[:, None, None] * (A * eye)
         Lc, info = torch.linalg.cholesky_ex(H)
         ok = (info == 0) & torch.isfinite(Lc).all(dim=(1, 2))
