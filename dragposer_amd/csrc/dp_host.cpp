@@ -27,11 +27,12 @@
 #include "../../include/dragposer_tethers.h"
 #include "../../include/dragposer_points.h"
 #include "../../include/dragposer_lm.h"
+#include "../../include/dragposer_sequence_lm.h"
 #include "dp_cons_live.h"
 #include "dp_cons_tether.h"
 #include "dp_cons_points.h"
 #include "dp_host_rt.h"
-#include "dp_lm.h"
+#include "dp_lm_seq.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
 #include "dp_vjp.h"
@@ -688,6 +689,7 @@ constexpr Sized TETHERS_V570 = {"dp_tethers", "dp_tethers t = DP_TETHERS_INIT;",
 constexpr Sized POINTS_V580 = {"dp_points", "dp_points p = DP_POINTS_INIT;", offsetof(dp_points, coeff) + sizeof(void*), false};
 constexpr Sized LM_PARAMS_V590 = {"dp_lm_params", "dp_lm_params p = DP_LM_PARAMS_INIT;", offsetof(dp_lm_params, stop_eps_rot) + sizeof(float), false};
 constexpr Sized LM_EXTRA_V590 = {"dp_lm_extra", "dp_lm_extra e = DP_LM_EXTRA_INIT;", offsetof(dp_lm_extra, loss0) + sizeof(void*), false};
+constexpr Sized SEQ_LM_EXTRA_V600 = {"dp_seq_lm_extra", "dp_seq_lm_extra e = DP_SEQ_LM_EXTRA_INIT;", offsetof(dp_seq_lm_extra, joint_pos) + sizeof(void*), false};
 constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
@@ -1219,14 +1221,18 @@ extern "C" int dp_optimize_terms_skeleton(dp_ctx* ctx, const dp_batch* in, const
 // refusals (dp_lm_params has no reserved0: its size word alone is checked, like dp_params')
 // (its launcher is a weak reference, like those of the sequence units below: a library linked without dp_lm.hip refuses the call)
 hipError_t dp_launch_lm(const dplm::Args* args, hipStream_t stream) __attribute__((weak));
-static int take_lm(dp_ctx* ctx, const dp_lm_params* p_in, const dp_lm_extra* e_in, dplm::Args& a, const char* who)
+static int check_lm_params_size(dp_ctx* ctx, const dp_lm_params* p_in, const char* who)
+{
+    if (p_in->struct_size < LM_PARAMS_V590.min_size || p_in->struct_size > 4096u)
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_lm_params.struct_size is " + std::to_string(p_in->struct_size) + ", this library expects at least " +
+                                             std::to_string(LM_PARAMS_V590.min_size) + "  (" + LM_PARAMS_V590.init + ")");
+    return DP_OK;
+}
+// ... the values of a dp_lm_params whose size word has passed (dp_optimize_lm, dp_optimize_sequence_lm)
+static int take_lm_params(dp_ctx* ctx, const dp_lm_params* p_in, dplm::Args& a, const char* who)
 {
     const std::string w = who;
     dp_lm_params p;
-    dp_lm_extra e;
-    std::memset(&e, 0, sizeof(e));
-    if (e_in)
-        if (int rc = take_sized(ctx, e_in, e, LM_EXTRA_V590, who)) return rc;
     copy_sized(p_in, p);
     if (p.n_steps < 1 || p.n_steps > DP_LM_MAX_STEPS)
         return fail(ctx, DP_ERR_INVALID, w + ": n_steps " + std::to_string(p.n_steps) + " outside 1.." + std::to_string(DP_LM_MAX_STEPS));
@@ -1244,6 +1250,15 @@ static int take_lm(dp_ctx* ctx, const dp_lm_params* p_in, const dp_lm_extra* e_i
     a.lam_rot = p.lambda_rot; a.lam_tmp = p.lambda_tmp;
     a.mu0 = p.mu0; a.mu_up = p.mu_up; a.mu_down = p.mu_down; a.mu_min = p.mu_min; a.mu_max = p.mu_max;
     a.stop_eps_pos = p.stop_eps_pos; a.stop_eps_rot = p.stop_eps_rot;
+    return DP_OK;
+}
+static int take_lm(dp_ctx* ctx, const dp_lm_params* p_in, const dp_lm_extra* e_in, dplm::Args& a, const char* who)
+{
+    dp_lm_extra e;
+    std::memset(&e, 0, sizeof(e));
+    if (e_in)
+        if (int rc = take_sized(ctx, e_in, e, LM_EXTRA_V590, who)) return rc;
+    if (int rc = take_lm_params(ctx, p_in, a, who)) return rc;
     a.mu = e.mu; a.n_accepted = e.n_accepted; a.loss0 = e.loss0;
     return DP_OK;
 }
@@ -1253,9 +1268,7 @@ extern "C" int dp_optimize_lm(dp_ctx* ctx, const dp_batch* in, const dp_lm_param
     const char* who = "dp_optimize_lm";
     return entry(ctx, who, [&] {
         if (!in || !p_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_lm: NULL batch or params");
-        if (p_in->struct_size < LM_PARAMS_V590.min_size || p_in->struct_size > 4096u)
-            return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_lm_params.struct_size is " + std::to_string(p_in->struct_size) + ", this library expects at least " +
-                                                 std::to_string(LM_PARAMS_V590.min_size) + "  (" + LM_PARAMS_V590.init + ")");
+        if (int rc = check_lm_params_size(ctx, p_in, who)) return rc;
         dp_result out;
         if (int rc = take_result(ctx, out_in, out, who)) return rc;
         dplm::Args a;
@@ -1464,7 +1477,9 @@ struct SeqParts {
 
 // include/dragposer_latent_ar.h: dp_latent_ar checked, after everything dp_optimize_sequence_holds checks, against the launch's frames and
 // state, and written into the argument block
-static int take_latent_ar(dp_ctx* ctx, const dp_latent_ar* r_in, const dp_seq_frames* fr, const dp_seq_state* st, dpcons::ArFields& r, const char* who)
+// (R: dp_cons_ar.h's ArFields or dp_lm_seq.h's -- the same field names)
+template <class R>
+static int take_latent_ar(dp_ctx* ctx, const dp_latent_ar* r_in, const dp_seq_frames* fr, const dp_seq_state* st, R& r, const char* who)
 {
     const std::string nm = who;
     dp_latent_ar ar;
@@ -1853,6 +1868,49 @@ extern "C" int dp_live_step(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_
 
 // ------------------------------------------------------------------------------------------------
 // per-frame epilogue of S sequences (reference drag_pose.py:369-402), see include/dragposer.h
+// include/dragposer_sequence_lm.h: dp_optimize_lm's frame for n_steps frames of S sequences in one launch (+ one for the history buffers), in the
+// header's order of refusals.  (Its launcher is a weak reference, like dp_launch_lm.)
+hipError_t dp_launch_lm_seq(const dplm::SeqArgs* args, hipStream_t stream) __attribute__((weak));
+extern "C" int dp_optimize_sequence_lm(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_lm_params* p_in, const dp_latent_ar* ar,
+                                       const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, const dp_seq_lm_extra* e_in, void* stream)
+{
+    const char* who = "dp_optimize_sequence_lm";
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !st || !out_in)
+            return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_lm: n_sequences must be positive; NULL latent, frames, params, state or results");
+        if (int rc = check_lm_params_size(ctx, p_in, who)) return rc;
+        dplm::SeqArgs a;
+        std::memset(&a, 0, sizeof(a));
+        if (int rc = take_lm_params(ctx, p_in, a, who)) return rc;
+        dp_seq_results out;
+        if (int rc = take_sized(ctx, out_in, out, SEQ_RESULTS_V500, who)) return rc;
+        if (int rc = check_sequence(ctx, fr, st, adj, out, who, true)) return rc;
+        dp_seq_lm_extra e;
+        std::memset(&e, 0, sizeof(e));
+        if (e_in)
+            if (int rc = take_sized(ctx, e_in, e, SEQ_LM_EXTRA_V600, who)) return rc;
+        if (ar) {
+            if (int rc = take_latent_ar(ctx, ar, fr, st, a.r, who)) return rc;
+        } else if (!fr->z_tgt)
+            return fail(ctx, DP_ERR_INVALID, std::string(who) + ": neither a predictor nor frames->z_tgt: the pull term's targets have no source");
+        if (REF8_BUILD) return refuse_ref8(ctx, who);
+        if (!dp_launch_lm_seq) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_lm_seq.hip");
+        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+        a.img = ctx->d_vjpimg.get();
+        a.z0 = latent; a.z = latent; a.z_tgt = fr->z_tgt; a.cur_rot = st->global_rot; a.tgt_pos = fr->tgt_pos; a.tgt_rot = fr->tgt_rot; a.w = fr->w;
+        a.tracked = fr->tracked; a.n_frames = n_seq;
+        a.pose = out.pose_ret; a.world_rot = out.world_rot; a.iters = out.iters; a.loss = out.loss; a.status = out.status;
+        a.mu = e.mu; a.mu_trace = e.mu_trace; a.n_accepted = e.n_accepted; a.loss0 = e.loss0; a.pos = e.joint_pos;
+        fill_sequence(a.q, ctx, fr, st, adj, out);
+        {
+            DEVICE_GUARD(ctx);
+            const hipError_t err = dp_launch_lm_seq(&a, (hipStream_t)stream);
+            if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(err));
+        }
+        return append_history(ctx, n_seq, fr, st, out, stream);
+    });
+}
+
 static int advance_impl(dp_ctx* ctx, int n_seq, const dp_result* res, const dp_seq_state* st, const dp_seq_step* step, void* stream)
 {
     if (n_seq <= 0 || !res || !st || !step) return fail(ctx, DP_ERR_INVALID, "dp_sequence_advance: bad arguments");

@@ -27,721 +27,13 @@
 #include "dp_math.h"
 #include "dp_vjp.h"
 
-using namespace dplm;
+#include "dp_lm_dev.h"
 
-#define DEV __device__ __forceinline__
-
-namespace {
-
-constexpr int NJ = dpvjp::NJ, LAT = dpvjp::LAT, H0 = dpvjp::H0, H1 = dpvjp::H1;
-constexpr int NYU = 4 * NJ + 3; // decoder outputs that are used (the 92nd is not)
-#define UNR 4
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-DEV void wave_sync()
-{ // orders this wave's LDS writes before its later LDS reads (other lanes' data); no instruction
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-DEV float wsum(float x)
-{ // sum over lanes 0..31 (every lane that contributes is below 32), result in every lane of the half
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) x += __shfl_xor(x, m, 32);
-    return x;
-}
-
-DEV float uni(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); } // lane 0's value, wave-uniform
-
-DEV void mv(const float* M, const float* v, float* o)
-{ // M v with M row-major 3x3
-#pragma unroll
-    for (int r = 0; r < 3; ++r) o[r] = M[3 * r] * v[0] + M[3 * r + 1] * v[1] + M[3 * r + 2] * v[2];
-}
-
-// d rotmat(q) along dq (dp_math.h's rotmat is quadratic in q)
-DEV void rotmat_jvp(const float* q, const float* t, float* D)
-{
-    const float w = q[0], x = q[1], y = q[2], z = q[3], dw = t[0], dx = t[1], dy = t[2], dz = t[3];
-    const float xx = x * dx, yy = y * dy, zz = z * dz;
-    const float xy = dx * y + x * dy, xz = dx * z + x * dz, yz = dy * z + y * dz, wx = dw * x + w * dx, wy = dw * y + w * dy, wz = dw * z + w * dz;
-    D[0] = -4.f * (yy + zz); D[1] = 2.f * (xy - wz);   D[2] = 2.f * (xz + wy);
-    D[3] = 2.f * (xy + wz);  D[4] = -4.f * (xx + zz);  D[5] = 2.f * (yz - wx);
-    D[6] = 2.f * (xz - wy);  D[7] = 2.f * (yz + wx);   D[8] = -4.f * (xx + yy);
-}
-
-// the tangent of q / |q| along dq, for qn = q / |q| and rn = 1 / |q|
-DEV void unit_jvp(const float* qn, float rn, const float* dq, float* o)
-{
-    const float dot = qn[0] * dq[0] + qn[1] * dq[1] + qn[2] * dq[2] + qn[3] * dq[3];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = (dq[c] - qn[c] * dot) * rn;
-}
-
-// dp_math.h's rotmat and quat_mul and mv above, in double: the reported loss's pass
-DEV void rotmat_d(const double* q, double* R)
-{
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double x2 = x + x, y2 = y + y, z2 = z + z;
-    const double xx = x * x2, yy = y * y2, zz = z * z2, xy = x * y2, xz = x * z2, yz = y * z2, wx = w * x2, wy = w * y2, wz = w * z2;
-    R[0] = 1.0 - (yy + zz); R[1] = xy - wz;         R[2] = xz + wy;
-    R[3] = xy + wz;         R[4] = 1.0 - (xx + zz); R[5] = yz - wx;
-    R[6] = xz - wy;         R[7] = yz + wx;         R[8] = 1.0 - (xx + yy);
-}
-DEV void quat_mul_d(const double* a, const double* b, double* o)
-{
-    o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-    o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-    o[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-    o[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-}
-DEV void mv_d(const double* M, const double* v, double* o)
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r) o[r] = M[3 * r] * v[0] + M[3 * r + 1] * v[1] + M[3 * r + 2] * v[2];
-}
-DEV double wsum_d(double x)
-{
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) x += __shfl_xor(x, m, 32);
-    return x;
-}
-
-// include/dragposer.h, DP_STATUS_TARGET_NOT_ROTATION (dp_device.h's test)
-DEV bool not_rotation(const float* m)
-{
-    const float n0 = m[0] * m[0] + m[1] * m[1] + m[2] * m[2], n1 = m[3] * m[3] + m[4] * m[4] + m[5] * m[5], n2 = m[6] * m[6] + m[7] * m[7] + m[8] * m[8];
-    const float d01 = m[0] * m[3] + m[1] * m[4] + m[2] * m[5], d02 = m[0] * m[6] + m[1] * m[7] + m[2] * m[8], d12 = m[3] * m[6] + m[4] * m[7] + m[5] * m[8];
-    const float det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-    const float tol = DP_ROTATION_TOL;
-    return !(fabsf(n0 - 1.f) <= tol && fabsf(n1 - 1.f) <= tol && fabsf(n2 - 1.f) <= tol && fabsf(d01) <= tol && fabsf(d02) <= tol && fabsf(d12) <= tol && det > 0.f);
-}
-
-} // namespace
-
+// the frame, shared with dp_lm_seq.hip (DP_LM_SEQ 1: the step loop of a sequence around it)
+#define DP_LM_SEQ 0
 __global__ __launch_bounds__(WPB * 64) void dp_lm_kernel(Args a)
-{
-    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
-    const float* __restrict__ W = a.img;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int* par = (int*)(lds + L_PAR);
-    const int* Ti = (const int*)W;
-
-    // ---- staging (once per workgroup): padded weight rows, sigma, the skeleton
-    for (int i = tid; i < H0 * LAT; i += WPB * 64) lds[L_A0 + (i / LAT) * S0 + i % LAT] = W[dpvjp::OFF_A0 + i];
-    for (int i = tid; i < H1 * H0; i += WPB * 64) lds[L_A1 + (i / H0) * S1 + i % H0] = W[dpvjp::OFF_A1 + i];
-    for (int i = tid; i < dpvjp::NY * H1; i += WPB * 64) lds[L_A2 + (i / H1) * S2 + i % H1] = W[dpvjp::OFF_A2 + i];
-    if (tid < dpvjp::NY) lds[L_SD + tid] = W[dpvjp::OFF_SD + tid];
-    if (tid < NJ) par[tid] = Ti[dpvjp::OFF_PARENT + tid];
-    if (tid < 3 * NJ) lds[L_OFF + tid] = W[dpvjp::OFF_BONE + tid];
-    __syncthreads();
-
-    const long long f = (long long)blockIdx.x * WPB + wv;
-    if (f >= a.n_frames) return;
-    float* wb = lds + L_WAVE0 + wv * W_FLOATS;
-    float *ZB = wb + W_Z, *HB0 = wb + W_H0, *HB1 = wb + W_H1, *DB0 = wb + W_D0, *DB1 = wb + W_D1, *QB = wb + W_Q, *QN = wb + W_QN, *RN = wb + W_RN,
-          *WR = wb + W_WR, *RB = wb + W_R, *BB = wb + W_B, *VB = wb + W_V, *PB = wb + W_P, *GB = wb + W_G, *SW = wb + W_SW, *TB = wb + W_T,
-          *JB = wb + W_J, *AB = wb + W_A;
-    const float nan = __builtin_nanf("");
-    const int j = lane; // joint of this lane (j < NJ)
-    const bool jl = lane < NJ;
-
-    // ---- screening (include/dragposer.h: DP_STATUS_*), the dp_cons family's
-    float cr[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) cr[k] = a.cur_rot[f * 4 + k];
-    const float z0 = lane < LAT ? a.z0[f * LAT + lane] : 0.f;
-    const float zt = lane < LAT ? a.z_tgt[f * LAT + lane] : 0.f;
-    const bool trk = jl && a.tracked[f * NJ + j] != 0;
-    const bool bs = refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]);
-    bool bt = refused(zt), nrot = false;
-    float wp = 0.f, wrr = 0.f;
-    if (trk) {
-        float m[9];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) bt = bt || refused(a.tgt_pos[(f * NJ + j) * 3 + k]);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { m[k] = a.tgt_rot[(f * NJ + j) * 9 + k]; bt = bt || refused(m[k]); }
-        wp = a.w[(f * NJ + j) * 2];
-        wrr = a.w[(f * NJ + j) * 2 + 1];
-        bt = bt || refused(wp) || refused(wrr);
-        nrot = not_rotation(m);
-    }
-    const bool bad_state = __ballot(bs) != 0ull;
-    const bool bad_tgt = !bad_state && __ballot(bt) != 0ull;
-    const int not_rot = !bad_state && !bad_tgt && __ballot(nrot) != 0ull ? DP_STATUS_TARGET_NOT_ROTATION : 0;
-    const unsigned long long tmask = __ballot(trk);
-    const int E = __popcll(tmask);
-    if (bad_state) { // every result NaN
-        if (lane < LAT) {
-            if (a.z) a.z[f * LAT + lane] = nan;
-            if (a.z_pre) a.z_pre[f * LAT + lane] = nan;
-        }
-        if (jl) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) if (a.pose) a.pose[f * 88 + 4 * j + c] = nan;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) if (a.pos) a.pos[(f * NJ + j) * 3 + c] = nan;
-#pragma unroll
-            for (int c = 0; c < 9; ++c) if (a.rot) a.rot[(f * NJ + j) * 9 + c] = nan;
-        }
-        if (lane < 4 && a.world_rot) a.world_rot[f * 4 + lane] = nan;
-        if (lane < 3) {
-            if (a.disp) a.disp[f * 3 + lane] = nan;
-            if (a.world_disp) a.world_disp[f * 3 + lane] = nan;
-            if (a.loss) a.loss[f * 3 + lane] = nan;
-            if (a.loss0) a.loss0[f * 3 + lane] = nan;
-        }
-        if (lane == 0) {
-            if (a.iters) a.iters[f] = 0;
-            if (a.n_accepted) a.n_accepted[f] = 0;
-            if (a.status) a.status[f] = DP_STATUS_NONFINITE_RESULT | DP_STATUS_BAD_STATE;
-        }
-        return;
-    }
-
-    // per-lane constants of the forward pass
-    const float c0 = lane < H0 ? W[dpvjp::OFF_C0 + lane] : 0.f;
-    const float b1 = lane < H1 ? W[dpvjp::OFF_B1 + lane] : 0.f;
-    const int oB = 64 + lane; // second decoder row of lanes 0..26
-    const float b2A = W[dpvjp::OFF_B2 + lane], sdA = W[dpvjp::OFF_SD + lane], muA = W[dpvjp::OFF_MU + lane];
-    const float b2B = lane < NYU - 64 ? W[dpvjp::OFF_B2 + oB] : 0.f, sdB = lane < NYU - 64 ? W[dpvjp::OFF_SD + oB] : 1.f,
-                muB = lane < NYU - 64 ? W[dpvjp::OFF_MU + oB] : 0.f;
-    const int pj = jl ? par[j] : 0;
-    float off[3] = {0.f, 0.f, 0.f};
-    float sdj[4] = {1.f, 1.f, 1.f, 1.f}, muj[4] = {0.f, 0.f, 0.f, 0.f};
-    if (jl) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) off[c] = lds[L_OFF + 3 * j + c];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { sdj[c] = W[dpvjp::OFF_SD + 4 * j + c]; muj[c] = W[dpvjp::OFF_MU + 4 * j + c]; }
-        SW[2 * j] = trk ? sqrtf(wp / (3.f * (float)E)) : 0.f;
-        SW[2 * j + 1] = trk ? sqrtf(a.lam_rot * wrr / (9.f * (float)E)) : 0.f;
-    }
-    const float ct = a.lam_tmp / 24.f;
-
-    float mu = a.mu ? a.mu[f] : a.mu0;
-    if (!(mu >= a.mu_min && mu <= a.mu_max)) mu = a.mu0;
-    mu = uni(mu);
-
-    float z = z0;          // lane k < 24: component k of the kept latent
-    float zz = z0;         // ... of the latent the forward pass runs on
-    float Lp = 0.f, Lr = 0.f, Lt = 0.f, Ltot = 0.f; // the kept latent's loss
-    int mode = 0;          // 0: the pass of z0;  1: a trial;  2: the kept latent once more, for the results
-    int steps = 0, nacc = 0;
-    bool hit_max = false;
-    for (;;) {
-        if (lane < LAT) ZB[lane] = zz;
-        wave_sync();
-        // ---- decoder (autoencoder.py:224-256, folded), LeakyReLU(0.2) after layers 0 and 1
-        if (lane < H0) {
-            float s = c0;
-#pragma unroll UNR
-            for (int k = 0; k < LAT; ++k) s = fmaf(lds[L_A0 + lane * S0 + k], ZB[k], s);
-            const bool p = s > 0.f;
-            HB0[lane] = p ? s : s * 0.2f;
-            DB0[lane] = p ? 1.f : 0.2f;
-        }
-        wave_sync();
-        if (lane < H1) {
-            float s = b1;
-#pragma unroll UNR
-            for (int k = 0; k < H0; ++k) s = fmaf(lds[L_A1 + lane * S1 + k], HB0[k], s);
-            const bool p = s > 0.f;
-            HB1[lane] = p ? s : s * 0.2f;
-            DB1[lane] = p ? 1.f : 0.2f;
-        }
-        wave_sync();
-        {
-            float s = b2A, t = b2B;
-#pragma unroll UNR
-            for (int k = 0; k < H1; ++k) {
-                const float h = HB1[k];
-                s = fmaf(lds[L_A2 + lane * S2 + k], h, s);
-                if (lane < NYU - 64) t = fmaf(lds[L_A2 + oB * S2 + k], h, t);
-            }
-            QB[lane] = fmaf(s, sdA, muA);
-            if (lane < NYU - 64) QB[oB] = fmaf(t, sdB, muB);
-        }
-        wave_sync();
-        // ---- kinematics, a lane per joint
-        float q[4], qn[4], rn = 1.f, R[9], wr[4] = {1.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) q[c] = jl ? QB[4 * j + c] : (c == 0 ? 1.f : 0.f);
-        rn = 1.f / sqrtf(fmaf(q[0], q[0], fmaf(q[1], q[1], fmaf(q[2], q[2], q[3] * q[3]))));
-#pragma unroll
-        for (int c = 0; c < 4; ++c) qn[c] = q[c] * rn;
-        if (j == 0) { quat_mul(cr, qn, wr); rotmat(wr, R); } // world root rotation, cur_rot as given (drag_pose.py:88)
-        else rotmat(qn, R);
-        if (jl) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) RB[9 * j + k] = R[k];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) QN[4 * j + c] = qn[c];
-            RN[j] = rn;
-        }
-        if (j == 0)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) WR[c] = wr[c];
-        wave_sync();
-        float R0[9], d[3], wd[3];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R0[k] = RB[k];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d[c] = QB[4 * NJ + c];
-        mv(R0, d, wd); // world displacement (drag_pose.py:102)
-        if (jl) {
-            float b[3] = {off[0], off[1], off[2]};
-            if (j == 0) b[0] = b[1] = b[2] = 0.f;
-            else if (pj != 0) mv(RB + 9 * pj, off, b);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) BB[4 * j + c] = b[c];
-        }
-        wave_sync();
-        float vj[3] = {0.f, 0.f, 0.f}, P[3], G[9];
-        if (jl) {
-            int c = j;
-            for (int s = 0; s < NJ && c != 0; ++s) { // the path from j to the root (<= 7 bones)
-                vj[0] += BB[4 * c]; vj[1] += BB[4 * c + 1]; vj[2] += BB[4 * c + 2];
-                c = par[c];
-            }
-        }
-        mv(R0, vj, P);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) P[c] += wd[c];
-        if (j == 0) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) G[k] = R0[k];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) G[3 * r + c] = R0[3 * r] * R[c] + R0[3 * r + 1] * R[3 + c] + R0[3 * r + 2] * R[6 + c];
-        }
-        if (jl) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { PB[4 * j + c] = P[c]; VB[4 * j + c] = vj[c]; }
-#pragma unroll
-            for (int k = 0; k < 9; ++k) GB[9 * j + k] = G[k];
-        }
-        // ---- the loss (drag_pose.py:115-127)
-        float dpj = 0.f, drj = 0.f;
-        if (trk) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float e = P[c] - a.tgt_pos[(f * NJ + j) * 3 + c];
-                dpj = fmaf(e, e, dpj);
-            }
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const float e = G[k] - a.tgt_rot[(f * NJ + j) * 9 + k];
-                drj = fmaf(e, e, drj);
-            }
-            dpj *= wp;
-            drj *= wrr;
-        }
-        const float dzz = zz - zt;
-        const float dtj = lane < LAT ? dzz * dzz : 0.f;
-        const float lp = uni(wsum(dpj)) / (3.f * (float)E), lr = a.lam_rot * (uni(wsum(drj)) / (9.f * (float)E)), lt = a.lam_tmp * (uni(wsum(dtj)) / 24.f);
-        const float tot = (lp + lr) + lt;
-
-        // ---- what the pass was for
-        bool fresh = true; // the wave's block belongs to the kept latent
-        if (mode == 0) {
-            Lp = lp; Lr = lr; Lt = lt; Ltot = tot;
-        } else if (mode == 1) {
-            ++steps;
-            if (tot < Ltot) { // (a NaN rejects)
-                z = zz; Lp = lp; Lr = lr; Lt = lt; Ltot = tot;
-                ++nacc;
-                mu = fmaxf(mu * a.mu_down, a.mu_min);
-                hit_max = false;
-            } else {
-                fresh = false;
-                hit_max = mu >= a.mu_max;
-                mu = fminf(mu * a.mu_up, a.mu_max);
-            }
-        }
-        const bool done = mode == 2 || bad_tgt || steps >= a.n_steps ||
-                          (a.early_stop && ((Lp <= a.stop_eps_pos && Lr <= a.stop_eps_rot) || hit_max));
-        if (done && !fresh) { // the last trial was rejected: the kept latent's pass once more
-            zz = z;
-            mode = 2;
-            continue;
-        }
-        // ---- the loss as it is REPORTED (loss0 after the pass of z0, loss with the results): the latent in the wave's block once more through
-        // the decoder and the kinematics in double, on the same fp32 weights.  Near the solution a residual is millimetres and the fp32 pass
-        // places a joint to 1e-7 .. 1e-6 m, which is 1e-5 .. 1e-4 of the loss; the steps are decided on the fp32 numbers above (they compare
-        // two passes of the same arithmetic), the caller gets the value of the loss at the latent it is handed.  Only when asked for.
-        float rep[3] = {Lp, Lr, Lt};
-        const bool rep0 = mode == 0 && a.loss0 != nullptr, rep1 = done && a.loss != nullptr;
-        if ((rep0 || rep1) && !bad_tgt) {
-            double* const DH0 = (double*)TB; // [40] | [60] | [92] | [22][9] | [22][3]: the tangents' place, idle here
-            double *const DH1 = DH0 + 40, *const DQ = DH1 + 60, *const DR = DQ + 92, *const DB = DR + 198;
-            wave_sync();
-            if (lane < H0) {
-                double s = (double)c0;
-#pragma unroll UNR
-                for (int k = 0; k < LAT; ++k) s = fma((double)lds[L_A0 + lane * S0 + k], (double)ZB[k], s);
-                DH0[lane] = s > 0.0 ? s : s * 0.2;
-            }
-            wave_sync();
-            if (lane < H1) {
-                double s = (double)b1;
-#pragma unroll UNR
-                for (int k = 0; k < H0; ++k) s = fma((double)lds[L_A1 + lane * S1 + k], DH0[k], s);
-                DH1[lane] = s > 0.0 ? s : s * 0.2;
-            }
-            wave_sync();
-            {
-                double s = (double)b2A, t = (double)b2B;
-#pragma unroll UNR
-                for (int k = 0; k < H1; ++k) {
-                    const double h = DH1[k];
-                    s = fma((double)lds[L_A2 + lane * S2 + k], h, s);
-                    if (lane < NYU - 64) t = fma((double)lds[L_A2 + oB * S2 + k], h, t);
-                }
-                DQ[lane] = fma(s, (double)sdA, (double)muA);
-                if (lane < NYU - 64) DQ[oB] = fma(t, (double)sdB, (double)muB);
-            }
-            wave_sync();
-            double qd[4], Rd[9];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) qd[c] = jl ? DQ[4 * j + c] : (c == 0 ? 1.0 : 0.0);
-            const double rnd = 1.0 / sqrt(qd[0] * qd[0] + qd[1] * qd[1] + qd[2] * qd[2] + qd[3] * qd[3]);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) qd[c] *= rnd;
-            if (j == 0) {
-                const double crd[4] = {(double)cr[0], (double)cr[1], (double)cr[2], (double)cr[3]};
-                double wrd[4];
-                quat_mul_d(crd, qd, wrd);
-                rotmat_d(wrd, Rd);
-            } else rotmat_d(qd, Rd);
-            if (jl)
-#pragma unroll
-                for (int k = 0; k < 9; ++k) DR[9 * j + k] = Rd[k];
-            wave_sync();
-            double R0d[9], dd[3], wdd[3];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) R0d[k] = DR[k];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) dd[c] = DQ[4 * NJ + c];
-            mv_d(R0d, dd, wdd);
-            if (jl) {
-                const double od[3] = {(double)off[0], (double)off[1], (double)off[2]};
-                double b[3] = {od[0], od[1], od[2]};
-                if (j == 0) b[0] = b[1] = b[2] = 0.0;
-                else if (pj != 0) mv_d(DR + 9 * pj, od, b);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) DB[3 * j + c] = b[c];
-            }
-            wave_sync();
-            double vd[3] = {0.0, 0.0, 0.0}, Pd[3];
-            if (jl) {
-                int c = j;
-                for (int s = 0; s < NJ && c != 0; ++s) {
-                    vd[0] += DB[3 * c]; vd[1] += DB[3 * c + 1]; vd[2] += DB[3 * c + 2];
-                    c = par[c];
-                }
-            }
-            mv_d(R0d, vd, Pd);
-            double dp64 = 0.0, dr64 = 0.0;
-            if (trk) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double e = (Pd[c] + wdd[c]) - (double)a.tgt_pos[(f * NJ + j) * 3 + c];
-                    dp64 = fma(e, e, dp64);
-                }
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const double g = j == 0 ? R0d[3 * r + c] : R0d[3 * r] * Rd[c] + R0d[3 * r + 1] * Rd[3 + c] + R0d[3 * r + 2] * Rd[6 + c];
-                        const double e = g - (double)a.tgt_rot[(f * NJ + j) * 9 + 3 * r + c];
-                        dr64 = fma(e, e, dr64);
-                    }
-                dp64 *= (double)wp;
-                dr64 *= (double)wrr;
-            }
-            const double dz64 = lane < LAT ? (double)ZB[lane] - (double)zt : 0.0;
-            const double sp64 = wsum_d(dp64), sr64 = wsum_d(dr64), st64 = wsum_d(dz64 * dz64);
-            rep[0] = uni((float)(sp64 / (3.0 * (double)E)));
-            rep[1] = uni((float)((double)a.lam_rot * (sr64 / (9.0 * (double)E))));
-            rep[2] = uni((float)((double)a.lam_tmp * (st64 / 24.0)));
-            wave_sync(); // (the pass's last reads before the tangents take their place back)
-        }
-        if (rep0 && lane < 3) a.loss0[f * 3 + lane] = bad_tgt ? nan : lane == 0 ? rep[0] : lane == 1 ? rep[1] : rep[2];
-        if (done) { // results: all of the kept latent, whose pass this was
-            if (lane < LAT) {
-                if (a.z) a.z[f * LAT + lane] = bad_tgt ? nan : z;
-                if (a.z_pre) a.z_pre[f * LAT + lane] = bad_tgt ? nan : z;
-            }
-            if (jl) {
-                if (a.pose)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) a.pose[f * 88 + 4 * j + c] = (qn[c] - muj[c]) / sdj[c];
-                if (a.pos)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) a.pos[(f * NJ + j) * 3 + c] = P[c];
-                if (a.rot)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) a.rot[(f * NJ + j) * 9 + k] = G[k];
-            }
-            if (lane == 0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    if (a.disp) a.disp[f * 3 + c] = d[c];
-                    if (a.world_disp) a.world_disp[f * 3 + c] = wd[c];
-                }
-                if (a.world_rot)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) a.world_rot[f * 4 + c] = wr[c];
-                if (a.loss) {
-                    a.loss[f * 3] = bad_tgt ? nan : rep[0]; a.loss[f * 3 + 1] = bad_tgt ? nan : rep[1]; a.loss[f * 3 + 2] = bad_tgt ? nan : rep[2];
-                }
-            }
-            break;
-        }
-
-        if (fresh) {
-            wave_sync(); // (the pass's last writes into the wave's block)
-            // ---- tangents on the matrix pipe.  Lane l: row l & 15 of an A tile, K-slot l >> 4; column l & 15 of a B tile.
-            const int lr16 = lane & 15, lk = lane >> 4;
-            {
-                f4 acc[4][2];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-                for (int s = 0; s < H0 / 4; ++s) {
-                    const int k = 4 * s + lk;
-                    const float dk = DB0[k];
-                    float b[2], av[4];
-                    b[0] = dk * lds[L_A0 + k * S0 + lr16];
-                    b[1] = lr16 < LAT - 16 ? dk * lds[L_A0 + k * S0 + 16 + lr16] : 0.f;
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) {
-                        const int row = 16 * mt + lr16;
-                        av[mt] = lds[L_A1 + (row < H1 ? row : H1 - 1) * S1 + k]; // (rows 60..63 of the last tile: results not kept)
-                    }
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], b[nt], acc[mt][nt], 0, 0, 0);
-                }
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = 16 * mt + 4 * lk + r;
-                        if (row < H1) {
-                            const float dr = DB1[row];
-                            TB[row * ST + lr16] = dr * acc[mt][0][r];
-                            if (lr16 < LAT - 16) TB[row * ST + 16 + lr16] = dr * acc[mt][1][r];
-                        }
-                    }
-            }
-            wave_sync();
-            {
-                f4 acc[6][2];
-#pragma unroll
-                for (int mt = 0; mt < 6; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-                for (int s = 0; s < H1 / 4; ++s) {
-                    const int k = 4 * s + lk;
-                    float b[2], av[6];
-                    b[0] = TB[k * ST + lr16];
-                    b[1] = lr16 < LAT - 16 ? TB[k * ST + 16 + lr16] : 0.f;
-#pragma unroll
-                    for (int mt = 0; mt < 6; ++mt) {
-                        const int row = 16 * mt + lr16;
-                        av[mt] = lds[L_A2 + (row < dpvjp::NY ? row : dpvjp::NY - 1) * S2 + k];
-                    }
-#pragma unroll
-                    for (int mt = 0; mt < 6; ++mt)
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], b[nt], acc[mt][nt], 0, 0, 0);
-                }
-                wave_sync(); // (S1's last reads before S2 takes its place)
-#pragma unroll
-                for (int mt = 0; mt < 6; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = 16 * mt + 4 * lk + r;
-                        if (row < NYU) {
-                            const float sd = lds[L_SD + row];
-                            TB[row * ST + lr16] = sd * acc[mt][0][r];
-                            if (lr16 < LAT - 16) TB[row * ST + 16 + lr16] = sd * acc[mt][1][r];
-                        }
-                    }
-            }
-            wave_sync();
-            // ---- J, two tracked joints at a time (one per half of the wave), and A = [J r]^T [J r] over them
-            const int cn = lane & 31, hf = lane >> 5; // column of this lane and its half
-            const bool col = cn < LAT;
-            float dR0[9], dwd[3]; // the root's part of column cn: d R_0, d world_disp
-#pragma unroll
-            for (int k = 0; k < 9; ++k) dR0[k] = 0.f;
-            dwd[0] = dwd[1] = dwd[2] = 0.f;
-            if (col) {
-                float dq[4], dqn[4], dw[4], wq[4], dd[3], t0[3], t1[3];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { dq[c] = TB[c * ST + cn]; wq[c] = WR[c]; }
-                unit_jvp(QN, RN[0], dq, dqn);
-                quat_mul(cr, dqn, dw);
-                rotmat_jvp(wq, dw, dR0);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) dd[c] = TB[(4 * NJ + c) * ST + cn];
-                mv(dR0, d, t0);
-                mv(R0, dd, t1);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) dwd[c] = t0[c] + t1[c];
-            }
-            f4 na[2][2];
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) na[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-            unsigned long long tm = tmask;
-            while (tm != 0ull) {
-                const int j0 = __builtin_ctzll(tm);
-                tm &= tm - 1ull;
-                const int j1 = tm != 0ull ? __builtin_ctzll(tm) : -1;
-                if (tm != 0ull) tm &= tm - 1ull;
-                const int jj = hf == 0 ? j0 : j1; // this half's joint (-1: none)
-                float row[12];
-#pragma unroll
-                for (int r = 0; r < 12; ++r) row[r] = 0.f;
-                if (jj >= 0 && cn <= LAT) {
-                    const float sp = SW[2 * jj], sr = SW[2 * jj + 1];
-                    if (col) {
-                        float dv[3] = {0.f, 0.f, 0.f}; // d v_jj: the bones of the path, each through its parent's quaternion
-                        int c = jj;
-                        for (int s = 0; s < NJ && c != 0; ++s) {
-                            const int p = par[c];
-                            if (p != 0) {
-                                float dq[4], dqn[4], dRp[9], t[3];
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) dq[e] = TB[(4 * p + e) * ST + cn];
-                                unit_jvp(QN + 4 * p, RN[p], dq, dqn);
-                                rotmat_jvp(QN + 4 * p, dqn, dRp);
-                                mv(dRp, lds + L_OFF + 3 * c, t);
-                                dv[0] += t[0]; dv[1] += t[1]; dv[2] += t[2];
-                            }
-                            c = p;
-                        }
-                        float t0[3], t1[3];
-                        mv(dR0, VB + 4 * jj, t0);
-                        mv(R0, dv, t1);
-#pragma unroll
-                        for (int e = 0; e < 3; ++e) row[e] = sp * ((dwd[e] + t0[e]) + t1[e]);
-                        if (jj == 0) {
-#pragma unroll
-                            for (int k = 0; k < 9; ++k) row[3 + k] = sr * dR0[k];
-                        } else {
-                            float dq[4], dqn[4], dRj[9];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) dq[e] = TB[(4 * jj + e) * ST + cn];
-                            unit_jvp(QN + 4 * jj, RN[jj], dq, dqn);
-                            rotmat_jvp(QN + 4 * jj, dqn, dRj);
-                            const float* Rj = RB + 9 * jj;
-#pragma unroll
-                            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                                for (int e = 0; e < 3; ++e)
-                                    row[3 + 3 * r + e] = sr * ((dR0[3 * r] * Rj[e] + dR0[3 * r + 1] * Rj[3 + e] + dR0[3 * r + 2] * Rj[6 + e]) +
-                                                               (R0[3 * r] * dRj[e] + R0[3 * r + 1] * dRj[3 + e] + R0[3 * r + 2] * dRj[6 + e]));
-                        }
-                    } else { // cn == 24: the joint's 12 residuals
-#pragma unroll
-                        for (int e = 0; e < 3; ++e) row[e] = sp * (PB[4 * jj + e] - a.tgt_pos[(f * NJ + jj) * 3 + e]);
-#pragma unroll
-                        for (int k = 0; k < 9; ++k) row[3 + k] = sr * (GB[9 * jj + k] - a.tgt_rot[(f * NJ + jj) * 9 + k]);
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 12; ++r) JB[(12 * hf + r) * SJ + cn] = row[r];
-                wave_sync();
-#pragma unroll
-                for (int s = 0; s < 6; ++s) {
-                    const float v0 = JB[(4 * s + lk) * SJ + lr16], v1 = JB[(4 * s + lk) * SJ + 16 + lr16];
-                    na[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v0, v0, na[0][0], 0, 0, 0);
-                    na[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v0, v1, na[0][1], 0, 0, 0);
-                    na[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v1, v0, na[1][0], 0, 0, 0);
-                    na[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v1, v1, na[1][1], 0, 0, 0);
-                }
-                wave_sync(); // (the rows' last reads before the next pair's writes)
-            }
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = 16 * mt + 4 * lk + r;
-                    if (row <= LAT) {
-                        AB[row * SJ + lr16] = na[mt][0][r];
-                        AB[row * SJ + 16 + lr16] = na[mt][1][r];
-                    }
-                }
-            wave_sync();
-            if (lane < LAT) { // the latent pull: sqrt(lambda_tmp / 24) on the diagonal of J, r = that times (z - z_tgt)
-                AB[lane * SJ + lane] += ct;
-                AB[lane * SJ + LAT] += ct * (z - zt);
-            }
-            wave_sync();
-        }
-
-        // ---- the solve: H = A + mu diag(A), -g as the 25th row; Cholesky in place, lane i on row i
-        float* HM = JB;
-        for (int e = lane; e < 25 * 25; e += 64) {
-            const int r = e / 25, c = e - 25 * r;
-            float v = 0.f;
-            if (r < LAT && c < LAT) v = r == c ? AB[r * SJ + c] * (1.f + mu) : AB[r * SJ + c];
-            else if (r == LAT && c < LAT) v = -AB[c * SJ + LAT];
-            HM[e] = v;
-        }
-        bool ok = true;
-        float myinv = 0.f;
-        // column by column, left-looking: lane i >= k forms s = H_ik - sum_(m<k) L_im L_km from its own row and row k (reads only, one store
-        // per column), the pivot is lane k's s; row 24 (-g) comes out as y, L y = -g
-        const int rw = lane <= LAT ? lane : LAT; // (lanes beyond the 25 rows repeat the last one and store nothing)
-        for (int k = 0; k < LAT; ++k) {
-            wave_sync();
-            float s = HM[rw * 25 + k];
-#pragma unroll 4
-            for (int m = 0; m < k; ++m) s = fmaf(-HM[rw * 25 + m], HM[k * 25 + m], s);
-            const float piv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), k));
-            ok = ok && piv > 0.f && piv <= 3.0e38f;
-            const float inv = 1.f / sqrtf(piv);
-            if (lane == k) myinv = inv;
-            if (lane > k && lane <= LAT) HM[lane * 25 + k] = s * inv;
-        }
-        wave_sync();
-        float acc = lane < LAT ? HM[LAT * 25 + lane] : 0.f, dl = 0.f; // L^T delta = y: lane j reads column j of L, ends with delta_j
-        for (int i = LAT - 1; i >= 0; --i) {
-            const float x = acc * myinv;
-            const float xi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), i));
-            if (lane == i) dl = xi;
-            if (lane < i) acc = fmaf(-HM[i * 25 + lane], xi, acc);
-        }
-        ok = uni(ok ? 1.f : 0.f) != 0.f;
-        zz = ok ? z + dl : nan;
-        mode = 1;
-        wave_sync(); // (the solve's last reads before the pass writes the wave's block)
-    }
-
-    const bool nonfin = bad_tgt || __ballot(lane < LAT && !(fabsf(z) <= 3.0e38f)) != 0ull;
-    if (lane == 0) {
-        if (a.iters) a.iters[f] = steps;
-        if (a.n_accepted) a.n_accepted[f] = nacc;
-        if (a.mu && !bad_tgt) a.mu[f] = mu;
-        if (a.status) a.status[f] = (nonfin ? DP_STATUS_NONFINITE_RESULT : 0) | (bad_tgt ? DP_STATUS_BAD_TARGETS : 0) | not_rot;
-    }
-}
+#include "dp_lm_body.h"
+#undef DP_LM_SEQ
 
 hipError_t dp_launch_lm(const Args* args, hipStream_t stream)
 {

@@ -333,25 +333,20 @@ class DragPose:
         include/dragposer_tethers.h), one launch per stretch, with or without `holds`, `ar` and `gaps` (without `gaps` it runs with
         Gaps(0, 1.0), under which an absent sample leaves the loss at once); the state lives in `tether_state` [S,len(tethers),8], zeroed
         when a sequence begins and passed through every stretch, and `last_tether_trace` [T,S,len(tethers),8] holds it after every frame.
-        `solver` (a dragposer_amd.LM): every frame solved by Levenberg-Marquardt steps (include/dragposer_lm.h).  This is the HOST loop over
-        run(solver=), frame by frame its bits: the frame loop is not on the device, and none of the other layers goes with it.
+        `solver` (a dragposer_amd.LM): every frame solved by Levenberg-Marquardt steps with the frame loop on the device
+        (dp_optimize_sequence_lm, include/dragposer_sequence_lm.h), cut into the same stretches -- frame by frame the bits of run(solver=).
+        `target_root` is honoured, `lm_mu` [S] is carried in place, `last_status`, `last_loss` [T,S,3] and `last_joint_pos` [T,S,22,3] are set.
+        With `solver.predictor` (a dragposer_amd.LatentAR, for a DragPose without a temporal model) the pull term's target of every frame is
+        formed inside ONE launch for all T frames, weighed by `lambda_temporal`, and `last_z_tgt` [T,S,24] holds the targets used.  None of the
+        other layers goes with it.
         Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
         if solver is not None:
-            _solver_alone("run_frames", constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, tethers=tethers, target_root=target_root)
-            tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=self.device)
-            tR = torch.as_tensor(target_ee_rot, dtype=torch.float32, device=self.device)
-            T = int(tp.shape[0])
-            poses, gposs = torch.empty(T, self.S, 88, device=self.device), torch.empty(T, self.S, 3, device=self.device)
-            iters, status = (torch.empty(T, self.S, dtype=torch.int32, device=self.device) for _ in range(2))
-            for t in range(T):
-                self.run(tp[t].reshape(self.S, -1, 3), tR[t].reshape(self.S, -1, 3, 3), mask_joints, weights_joints, offsets=offsets, stop_eps_pos=stop_eps_pos,
-                         stop_eps_rot=stop_eps_rot, lambda_rot=lambda_rot, lambda_temporal=lambda_temporal, temporal_future_window=temporal_future_window,
-                         height_indices=height_indices, joint_adjustment_indices=joint_adjustment_indices,
-                         joint_adjustment_weight=joint_adjustment_weight, out_pose=poses[t], out_pos=gposs[t], solver=solver)
-                iters[t].copy_(self.last["iters"])
-                status[t].copy_(self.last["status"])
-            self.last_status = status
-            return poses, gposs, iters
+            _solver_alone("run_frames", constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, tethers=tethers, present=present)
+            solver.check()
+            if solver.predictor is not None:
+                _check_ar(self.temporal, solver.predictor, "run_frames")
+            if self._skeleton(offsets) is not None:
+                raise ValueError("DragPose.run_frames: solver= runs on the context's skeleton only (include/dragposer_lm.h, Not covered)")
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run_frames: pass constraints or terms, not both")
         _points_alone(terms, "run_frames", holds=holds, gaps=gaps, ar=ar, tethers=tethers)
@@ -395,6 +390,9 @@ class DragPose:
         gpos = torch.empty(T, S, 3, device=dev)
         iters = torch.empty(T, S, dtype=torch.int32, device=dev)
         status = torch.empty(T, S, dtype=torch.int32, device=dev)
+        if solver is not None:
+            return self._run_frames_lm(solver, dense_p, dense_r, root, trk, adjust, poses, gpos, iters, status, stop_eps_pos, stop_eps_rot, lambda_rot,
+                                       lambda_temporal, temporal_future_window, height_indices)
         with_terms = constraints is not None or terms is not None
         if with_terms:
             if terms is not None:
@@ -485,6 +483,48 @@ class DragPose:
             self.last_loss = loss
         return poses, gpos, iters
 
+    def _run_frames_lm(self, solver, dense_p, dense_r, root, trk, adjust, poses, gpos, iters, status, stop_eps_pos, stop_eps_rot, lambda_rot,
+                       lambda_temporal, temporal_future_window, height_indices):
+        """run_frames(solver=LM(...)) behind its preparation: the stretches of run_frames through dp_optimize_sequence_lm; with a predictor, one launch"""
+        dev, S, T = self.device, self.S, int(dense_p.shape[0])
+        loss = torch.empty(T, S, 3, device=dev)
+        self.last_joint_pos = torch.empty(T, S, NJ, 3, device=dev)
+        if self.lm_mu is None:
+            self.lm_mu = torch.full((S,), float(solver.mu0), device=dev)
+        heights = tuple(int(h) for h in height_indices)
+        names = ("pose_ret", "pos_ret", "iters", "status", "loss", "joint_pos")
+
+        def launch(t, n, z_tgt, strides, lam, **kw):
+            self.opt.optimize_sequence_lm(self.latent, dense_p[t:t + n], dense_r[t:t + n], root[t:t + n] if root is not None else None, trk["w"],
+                                          trk["tracked"], z_tgt, strides, self.current_global_pos, self.current_global_rot, self.latent_buffer,
+                                          self.displacement_buffer, self.heights_buffer, heights, lm=solver, lambda_rot=float(lambda_rot),
+                                          lambda_tmp=lam, stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, mu=self.lm_mu, adjust=adjust,
+                                          pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n],
+                                          loss=loss[t:t + n], joint_pos=self.last_joint_pos[t:t + n], outputs=names, **kw)
+
+        if solver.predictor is not None:  # one launch, no stretches: the targets come from inside it
+            self.last_z_tgt = torch.zeros(T, S, LATENT, device=dev)
+            launch(0, T, None, (0, 0), float(lambda_temporal), ar=solver.predictor, z_tgt_trace=self.last_z_tgt)
+        else:  # (the stretches of run_frames, cut as for Adam)
+            have = self.temporal is not None
+            pull = have and float(lambda_temporal) != 0.0
+            window = int(temporal_future_window)
+            zero_tgt = torch.zeros(S, LATENT, device=dev)
+            t = 0
+            while t < T:
+                if have:
+                    self._temporal_targets(window)
+                    n = min(T - t, max(window, 1) - self.current_index)
+                    z_tgt, strides = self.target_latent_buffer[:, self.current_index:], (LATENT, (window + 1) * LATENT)
+                else:
+                    n, z_tgt, strides = T - t, zero_tgt, (0, LATENT)
+                launch(t, n, z_tgt, strides, float(lambda_temporal) if pull else 0.0)
+                t += n
+                self.current_index = 0 if window == 0 else (self.current_index + n) % window
+        self.last_status = status
+        self.last_loss = loss
+        return poses, gpos, iters
+
     def run(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, offsets=None, stop_eps_pos=1e-2,
             stop_eps_rot=1e-2, max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1,
             temporal_future_window=60, height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None,
@@ -519,7 +559,8 @@ class DragPose:
         `solver` (a dragposer_amd.LM; None = Adam, the default): the frame's latent is found by Levenberg-Marquardt steps instead --
         dp_optimize_lm followed by dp_sequence_advance (two launches, include/dragposer_lm.h); max_iter, learning_rate and min_loss_incr are
         not used, stop_eps_pos / stop_eps_rot are the early stop's thresholds unless the LM carries its own.  The damping is kept per sequence
-        in `lm_mu` [S] and reset when a sequence begins.  Not together with constraints= / terms= / holds= / ar= / gaps= / tethers= / live= or
+        in `lm_mu` [S] and reset when a sequence begins.  With `solver.predictor` (a dragposer_amd.LatentAR) the frame is a one-step launch of
+        run_frames(solver=) instead (dp_optimize_sequence_lm), the pull's target formed from the sequence's last latents: its bits.  Not together with constraints= / terms= / holds= / ar= / gaps= / tethers= / live= or
         offsets other than the context's skeleton: the LM loss has the trackers and the pull only."""
         if solver is not None:
             _solver_alone("run", constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, tethers=tethers, live=live or None,
@@ -527,6 +568,12 @@ class DragPose:
             solver.check()
             if self._skeleton(offsets) is not None:
                 raise ValueError("DragPose.run: solver= runs on the context's skeleton only (include/dragposer_lm.h, Not covered)")
+            if solver.predictor is not None:  # the one-step launch of run_frames(solver=): frame by frame its bits
+                _check_ar(self.temporal, solver.predictor, "run")
+                kw_frame = dict(stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, lambda_rot=lambda_rot, lambda_temporal=lambda_temporal,
+                                temporal_future_window=temporal_future_window, height_indices=height_indices,
+                                joint_adjustment_indices=joint_adjustment_indices, joint_adjustment_weight=joint_adjustment_weight, solver=solver)
+                return self._run_ar(target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose, kw_frame)
         if constraints is not None and terms is not None:
             raise ValueError("DragPose.run: pass constraints or terms, not both")
         _points_alone(terms, "run", holds=holds, gaps=gaps, ar=ar, tethers=tethers, live=bool(live))
@@ -644,7 +691,7 @@ class DragPose:
         if out_pos is not None:
             gpos = out_pos.copy_(gpos)
         self.last = dict(iters=iters[0], loss=self.last_loss[0], z=self.latent.clone(), pose=pose, pos=gpos, status=self.last_status[0])
-        if kw.get("ar") is not None:
+        if kw.get("ar") is not None or kw.get("solver") is not None:
             self.last["z_tgt"] = self.last_z_tgt[0]
         if kw.get("gaps") is not None:
             self.last["gap_trace"] = self.last_gap_trace[0]

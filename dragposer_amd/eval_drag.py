@@ -334,7 +334,8 @@ def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
         print(f"Gaps: max_hold {g.max_hold}, decay {g.decay} (DragPose.run_frames(gaps=), include/dragposer_gaps.h)")
     print(f"Time: {elapsed}" + (f"  (shared by {shared} sequences in lock-step)" if shared > 1 else ""))
     if getattr(args, "latent_ar_model", None) is not None:
-        print(f"Latent predictor: {args.latent_ar_text} (DragPose.run_frames(ar=), include/dragposer_latent_ar.h)")
+        how = "solver=LM(predictor=)" if getattr(args, "solver_model", None) is not None else "ar="
+        print(f"Latent predictor: {args.latent_ar_text} (DragPose.run_frames({how}), include/dragposer_latent_ar.h)")
     print(f"Frames: {n}  ({n / elapsed:.1f} frames/s, mean iterations/frame {res['iters'].mean():.1f}, "
           f"lambda_temporal {lam_tmp}{'' if has_temporal else ' -- no temporal checkpoint given: pull term off'})")
     out = dict(mpjpe=mpjpe, mpeepe=mpeepe, time=elapsed, frames=n, out=out_path, mean_iters=float(res["iters"].mean()))
@@ -469,9 +470,11 @@ def main(argv=None):
                          "(DragPose.run_frames(gaps=), include/dragposer_gaps.h; with --per-frame DragPose.run(gaps=), same results).  No default: "
                          "nobody has tuned one")
     ap.add_argument("--solver", default=None, metavar="lm[:STEPS]",
-                    help="solve every frame by Levenberg-Marquardt steps (default 3) instead of Adam: DragPose.run(solver=LM(STEPS)), dp_optimize_lm "
-                         "followed by dp_sequence_advance per frame (include/dragposer_lm.h); implies --per-frame (the frame loop is on the host); "
-                         "not with --constraints, --foot-lock, --tether, --balance, --latent-ar or --gaps, and for a BVH with the model's own skeleton")
+                    help="solve every frame by Levenberg-Marquardt steps (default 3) instead of Adam: DragPose.run_frames(solver=LM(STEPS)), the frame "
+                         "loop on the device (dp_optimize_sequence_lm, include/dragposer_sequence_lm.h); with --per-frame DragPose.run(solver=), "
+                         "dp_optimize_lm followed by dp_sequence_advance per frame, same results.  With --latent-ar the predictor becomes the "
+                         "solver's (LM.predictor) and the configuration's lambda_temporal pulls towards its targets.  Not with --constraints, "
+                         "--foot-lock, --tether, --balance or --gaps, and for a BVH with the model's own skeleton")
     ap.add_argument("--lockstep", action="store_true",
                     help="directory input: advance all files together, one kernel launch per frame index for all of them "
                          "(same per-file results; the reference evaluates them one after the other)")
@@ -525,11 +528,13 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit(f"--solver: expected lm[:STEPS] with 1 <= STEPS <= 64 ({e})")
         for flag, given in (("--constraints", args.constraints), ("--foot-lock", args.foot_lock), ("--tether", args.tether), ("--balance", args.balance),
-                            ("--latent-ar", args.latent_ar), ("--gaps", args.gaps)):
+                            ("--gaps", args.gaps)):
             if given:
                 raise SystemExit(f"--solver and {flag}: the LM loss has the trackers and the pull only (include/dragposer_lm.h, Not covered)")
-        args.per_frame = True
-        print(f"Solver: Levenberg-Marquardt, {args.solver_model.steps} steps per frame (DragPose.run(solver=), include/dragposer_lm.h)")
+        if args.latent_ar is not None:
+            args.solver_model.predictor = args.latent_ar_model
+        print(f"Solver: Levenberg-Marquardt, {args.solver_model.steps} steps per frame (DragPose.{'run' if args.per_frame else 'run_frames'}(solver=), "
+              f"include/dragposer_{'lm' if args.per_frame else 'sequence_lm'}.h)")
     args.gaps_model = None
     if args.gaps is not None:
         from .gaps import Gaps

@@ -1,5 +1,5 @@
-"""The Levenberg-Marquardt solver's settings (include/dragposer_lm.h): LatentOptimizer.optimize_lm(lm=LM(...)) and
-DragPose.run(solver=LM(...)).  Adam stays the default solver everywhere; an LM is asked for by name."""
+"""The Levenberg-Marquardt solver's settings (include/dragposer_lm.h, include/dragposer_sequence_lm.h): LatentOptimizer.optimize_lm(lm=LM(...)),
+LatentOptimizer.optimize_sequence_lm(lm=LM(...)) and DragPose.run / run_frames(solver=LM(...)).  Adam stays the default solver everywhere; an LM is asked for by name."""
 import math
 from dataclasses import dataclass
 
@@ -11,7 +11,9 @@ class LM:
     """`steps` trials per frame (1..64), each one Gauss-Newton step damped by mu: accepted when the loss falls (mu <- max(mu mu_down, mu_min)),
     rejected otherwise (mu <- min(mu mu_up, mu_max)).  `early_stop`: a frame ends before a step once loss_pos <= stop_eps_pos and
     lambda_rot loss_rot <= stop_eps_rot, or after a rejection at mu_max.  The two thresholds given here win over the caller's
-    (DragPose.run passes its own stop_eps_pos / stop_eps_rot when these are None)."""
+    (DragPose.run passes its own stop_eps_pos / stop_eps_rot when these are None).  `predictor` (a dragposer_amd.LatentAR, not part of the C
+    struct): DragPose.run / run_frames then form every frame's pull target from the sequence's own last latents inside the launch,
+    dp_optimize_sequence_lm, weighed by lambda_temporal."""
     steps: int = 3
     mu0: float = 1e-2
     mu_up: float = 4.0
@@ -21,6 +23,7 @@ class LM:
     early_stop: bool = True
     stop_eps_pos: float = None
     stop_eps_rot: float = None
+    predictor: object = None  # a dragposer_amd.LatentAR: the pull term's target formed inside the launch (include/dragposer_sequence_lm.h)
 
     def check(self):
         """raises ValueError for what dp_optimize_lm would refuse, in its order"""
@@ -37,6 +40,11 @@ class LM:
             raise ValueError("LM: need 0 < mu_min <= mu_max")
         if not self.mu_min <= self.mu0 <= self.mu_max:
             raise ValueError("LM: mu0 outside [mu_min, mu_max]")
+        if self.predictor is not None:
+            from .ar import LatentAR
+
+            if not isinstance(self.predictor, LatentAR):
+                raise ValueError(f"LM: predictor must be a dragposer_amd.LatentAR, got {type(self.predictor).__name__}")
         return self
 
     def to_struct(self, lambda_rot, lambda_tmp, stop_eps_pos=0.0, stop_eps_rot=0.0):

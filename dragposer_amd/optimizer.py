@@ -417,6 +417,40 @@ class LatentOptimizer:
             step.pos_ret = _check(pos_ret, "pos_ret", (S, 3), torch.float32, dev)
         self._call(self.lib.dp_sequence_advance, S, C.byref(res), C.byref(st), C.byref(step))
 
+    def _sequence_structs(self, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
+                          heights_buf, height_joints, adjust, own_targets=False):
+        """-> (dp_seq_frames, dp_seq_state, dp_seq_step) of a whole-sequence launch, every tensor checked; own_targets: the launch forms its z_tgt rows"""
+        T, S = int(tgt_pos.shape[0]), int(tgt_pos.shape[1])
+        dev = self.device
+        H, NH = int(latent_buf.shape[1]), len(height_joints)
+        fr = _lib.DpSeqFrames()
+        fr.n_steps = T
+        fr.tgt_pos = _check(tgt_pos, "tgt_pos", (T, S, NJ, 3), torch.float32, dev)
+        fr.tgt_rot = _check(tgt_rot, "tgt_rot", (T, S, NJ, 9), torch.float32, dev)
+        fr.tgt_root = _check(tgt_root, "tgt_root", (T, S, 3), torch.float32, dev) if tgt_root is not None else None
+        fr.w = _check(w, "w", (S, NJ, 2), torch.float32, dev)
+        fr.tracked = _check(tracked, "tracked", (S, NJ), torch.uint8, dev)
+        if own_targets:
+            fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = None, 0, 0
+        else:
+            if z_tgt.device != dev or z_tgt.dtype != torch.float32:
+                raise ValueError("z_tgt: expected an fp32 tensor on the optimiser's device")
+            fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = z_tgt.data_ptr(), int(z_tgt_strides[0]), int(z_tgt_strides[1])
+        st = _lib.DpSeqState()
+        st.global_pos = _check(global_pos, "global_pos", (S, 3), torch.float32, dev)
+        st.global_rot = _check(global_rot, "global_rot", (S, 4), torch.float32, dev)
+        st.latent_buf = _check(latent_buf, "latent_buf", (S, H, LATENT), torch.float32, dev)
+        st.disp_buf = _check(disp_buf, "disp_buf", (S, H, 3), torch.float32, dev)
+        st.heights_buf = _check(heights_buf, "heights_buf", (S, H, NH), torch.float32, dev)
+        st.history, st.n_heights = H, NH
+        for i, j in enumerate(height_joints):
+            st.height_joints[i] = int(j)
+        step = _lib.DpSeqStep()
+        step.adjust_joint = -1
+        if adjust is not None:
+            step.adjust_joint, step.adjust_target_joint, step.adjust_weight = int(adjust[0]), int(adjust[1]), float(adjust[2])
+        return fr, st, step
+
     def optimize_sequence(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
                           heights_buf, height_joints, n_iter=100, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.0,
                           stop_eps_pos=1e-4, stop_eps_rot=1e-2, min_loss_incr=1e-5, adjust=None, pose_ret=None, pos_ret=None, iters=None,
@@ -518,32 +552,8 @@ class LatentOptimizer:
         dev = self.device
         skel = self._skeleton(offsets, S, "optimize_sequence") if offsets is not None else None
         H, NH = int(latent_buf.shape[1]), len(height_joints)
-        fr = _lib.DpSeqFrames()
-        fr.n_steps = T
-        fr.tgt_pos = _check(tgt_pos, "tgt_pos", (T, S, NJ, 3), torch.float32, dev)
-        fr.tgt_rot = _check(tgt_rot, "tgt_rot", (T, S, NJ, 9), torch.float32, dev)
-        fr.tgt_root = _check(tgt_root, "tgt_root", (T, S, 3), torch.float32, dev) if tgt_root is not None else None
-        fr.w = _check(w, "w", (S, NJ, 2), torch.float32, dev)
-        fr.tracked = _check(tracked, "tracked", (S, NJ), torch.uint8, dev)
-        if ar is not None:
-            fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = None, 0, 0
-        else:
-            if z_tgt.device != dev or z_tgt.dtype != torch.float32:
-                raise ValueError("z_tgt: expected an fp32 tensor on the optimiser's device")
-            fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = z_tgt.data_ptr(), int(z_tgt_strides[0]), int(z_tgt_strides[1])
-        st = _lib.DpSeqState()
-        st.global_pos = _check(global_pos, "global_pos", (S, 3), torch.float32, dev)
-        st.global_rot = _check(global_rot, "global_rot", (S, 4), torch.float32, dev)
-        st.latent_buf = _check(latent_buf, "latent_buf", (S, H, LATENT), torch.float32, dev)
-        st.disp_buf = _check(disp_buf, "disp_buf", (S, H, 3), torch.float32, dev)
-        st.heights_buf = _check(heights_buf, "heights_buf", (S, H, NH), torch.float32, dev)
-        st.history, st.n_heights = H, NH
-        for i, j in enumerate(height_joints):
-            st.height_joints[i] = int(j)
-        step = _lib.DpSeqStep()
-        step.adjust_joint = -1
-        if adjust is not None:
-            step.adjust_joint, step.adjust_target_joint, step.adjust_weight = int(adjust[0]), int(adjust[1]), float(adjust[2])
+        fr, st, step = self._sequence_structs(tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf,
+                                              disp_buf, heights_buf, height_joints, adjust, own_targets=ar is not None)
         res = _lib.DpSeqResults()
         outs = {}
         res.world_rot = None
@@ -609,6 +619,71 @@ class LatentOptimizer:
             return outs
         fn, args = (self.lib.dp_optimize_sequence, tail) if skel is None else (self.lib.dp_optimize_sequence_skeleton, (C.byref(skel),) + tail)
         self._call(fn, S, lp, C.byref(fr), C.byref(p), *args)
+        return outs
+
+
+    def optimize_sequence_lm(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
+                             heights_buf, height_joints, lm=None, lambda_rot=1.0, lambda_tmp=0.0, stop_eps_pos=0.0, stop_eps_rot=0.0, mu=None, ar=None,
+                             adjust=None, pose_ret=None, pos_ret=None, iters=None, loss=None, scratch=None, status=None, world_rot=None,
+                             mu_trace=None, n_accepted=None, loss0=None, joint_pos=None, z_tgt_trace=None, outputs=None):
+        """T consecutive frames of S sequences solved by Levenberg-Marquardt steps in one launch (include/dragposer_sequence_lm.h:
+        dp_optimize_sequence_lm): bit for bit what optimize_lm, sequence_advance and a copy of the latent give frame by frame.  Inputs and
+        state as in `optimize_sequence`; `lm`: a dragposer_amd.LM (None = LM(); its `predictor` is not read here).  `mu` [S] fp32: the damping
+        of every sequence, read and updated IN PLACE; None: every sequence starts at lm.mu0.  `ar` (a dragposer_amd.LatentAR): every step's
+        z_tgt row is formed in the launch from the sequence's last history rows -- `z_tgt` must then be None, and `z_tgt_trace` [T,S,24] or
+        True (allocated here) receives the rows.  Returns dict(pose_ret, pos_ret, iters [T,S] = the steps executed, loss [T,S,3], status, world_rot
+        [T,S,4], mu_trace [T,S], n_accepted [T,S], loss0 [T,S,3], joint_pos [T,S,22,3]) and `mu` when given; `outputs`: the subset of those
+        names to produce (the others' pointers are NULL; `loss` and `loss0` each cost a pass in double per frame).  Asynchronous on torch's
+        current stream."""
+        from .lm import LM
+
+        lm = (lm if lm is not None else LM()).check()
+        if ar is None and z_tgt_trace is not None:
+            raise ValueError("optimize_sequence_lm: z_tgt_trace belongs to ar=")
+        if ar is not None and z_tgt is not None:
+            raise ValueError("optimize_sequence_lm: ar= forms the targets itself, pass z_tgt=None")
+        if ar is None and z_tgt is None:
+            raise ValueError("optimize_sequence_lm: pass z_tgt or ar=")
+        T, S = int(tgt_pos.shape[0]), int(tgt_pos.shape[1])
+        dev = self.device
+        H, NH = int(latent_buf.shape[1]), len(height_joints)
+        if ar is not None and ar.order > H:
+            raise ValueError(f"optimize_sequence_lm: latent_buf holds {H} rows, fewer than ar.order = {ar.order}")
+        fr, st, step = self._sequence_structs(tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf,
+                                              disp_buf, heights_buf, height_joints, adjust, own_targets=ar is not None)
+        res, ex, outs = _lib.DpSeqResults(), _lib.DpSeqLmExtra(), {}
+        specs = (("pose_ret", pose_ret, (T, S, 88), torch.float32, res), ("pos_ret", pos_ret, (T, S, 3), torch.float32, res),
+                 ("iters", iters, (T, S), torch.int32, res), ("loss", loss, (T, S, 3), torch.float32, res), ("status", status, (T, S), torch.int32, res),
+                 ("world_rot", world_rot, (T, S, 4), torch.float32, res), ("mu_trace", mu_trace, (T, S), torch.float32, ex),
+                 ("n_accepted", n_accepted, (T, S), torch.int32, ex), ("loss0", loss0, (T, S, 3), torch.float32, ex),
+                 ("joint_pos", joint_pos, (T, S, NJ, 3), torch.float32, ex))
+        if outputs is not None:
+            unknown = [n for n in outputs if n not in [sp[0] for sp in specs]]
+            if unknown:
+                raise ValueError(f"optimize_sequence_lm: unknown output {unknown[0]!r}")
+        for name, t, shape, dtype, struct in specs:
+            if outputs is not None and name not in outputs and t is None:
+                continue
+            t = t if t is not None else torch.empty(shape, dtype=dtype, device=dev)
+            setattr(struct, name, _check(t, name, shape, dtype, dev))
+            outs[name] = t
+        if mu is not None:
+            ex.mu = _check(mu, "mu", (S,), torch.float32, dev)
+            outs["mu"] = mu
+        scratch = scratch if scratch is not None else torch.empty(T, S, LATENT + 3 + NH, device=dev)
+        res.hist_scratch = _check(scratch, "scratch", (T, S, LATENT + 3 + NH), torch.float32, dev)
+        rs, keep = None, None
+        if ar is not None:
+            if z_tgt_trace is True:
+                z_tgt_trace = torch.zeros(T, S, LATENT, dtype=torch.float32, device=dev)
+            rs, keep = ar.to_struct(dev, z_tgt_trace, (T, S, LATENT))
+            if z_tgt_trace is not None:
+                outs["z_tgt_trace"] = z_tgt_trace
+        p = lm.to_struct(lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot)
+        lp = C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev))
+        self._call(self.lib.dp_optimize_sequence_lm, S, lp, C.byref(fr), C.byref(p), C.byref(rs) if rs is not None else None, C.byref(st), C.byref(step),
+                   C.byref(res), C.byref(ex))
+        del keep
         return outs
 
 
