@@ -318,6 +318,10 @@ class DpSeqLmExtra(_Sized):
                 ("loss0", C.c_void_p), ("joint_pos", C.c_void_p)]
 
 
+# every symbol include/dragposer_lm_terms.h declares (tests/test_lm_terms_abi.py)
+LM_TERMS_SYMBOLS = ("dp_optimize_lm_terms",)
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -423,6 +427,8 @@ def load(path=None):
     lib.dp_optimize_sequence_terms_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpTerms),
                                                       C.POINTER(DpPoints)] + _seq_tail
     lib.dp_optimize_lm.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpLmParams), C.POINTER(DpResult), C.POINTER(DpLmExtra), C.c_void_p]
+    lib.dp_optimize_lm_terms.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpLmParams), C.POINTER(DpTerms), C.POINTER(DpResult),
+                                         C.POINTER(DpLmExtra), C.c_void_p]
     lib.dp_optimize_sequence_lm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpLmParams), C.POINTER(DpLatentAR),
                                             C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.POINTER(DpSeqLmExtra), C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]

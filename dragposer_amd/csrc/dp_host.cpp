@@ -28,11 +28,13 @@
 #include "../../include/dragposer_points.h"
 #include "../../include/dragposer_lm.h"
 #include "../../include/dragposer_sequence_lm.h"
+#include "../../include/dragposer_lm_terms.h"
 #include "dp_cons_live.h"
 #include "dp_cons_tether.h"
 #include "dp_cons_points.h"
 #include "dp_host_rt.h"
 #include "dp_lm_seq.h"
+#include "dp_lm_terms.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
 #include "dp_vjp.h"
@@ -1148,9 +1150,12 @@ static std::string check_term(const dp_term& t, int n_idx)
 }
 
 // include/dragposer_terms.h: dp_terms validated and written into the argument block (constrained_impl's own(a)), for dp_optimize_terms,
-// dp_optimize_terms_skeleton and, with `seq` (the launch's state), dp_optimize_sequence_terms (who names the caller in the messages)
-static int take_terms(dp_ctx* ctx, const dp_terms* t_in, dpcons::TermArgs& a, const char* who, const dp_seq_state* seq = nullptr, int n_idx = NJ)
+// dp_optimize_terms_skeleton and, with `seq` (the launch's state), dp_optimize_sequence_terms (who names the caller in the messages).
+// A: dpcons::TermArgs or one derived from it, or dplm::TermArgs (dp_optimize_lm_terms), which carries the same fields under the same names
+template <class A>
+static int take_terms(dp_ctx* ctx, const dp_terms* t_in, A& a, const char* who, const dp_seq_state* seq = nullptr, int n_idx = NJ)
 {
+    static_assert(sizeof(a.tbl) == sizeof(unsigned) * DP_MAX_TERMS * dpcons::TW, "the staged table of dp_cons.h's layout");
     const std::string nm = who;
     dp_terms ts;
     if (int rc = take_sized(ctx, t_in, ts, TERMS_V510, who)) return rc;
@@ -1284,6 +1289,41 @@ extern "C" int dp_optimize_lm(dp_ctx* ctx, const dp_batch* in, const dp_lm_param
         fill_results(a, out);
         const hipError_t e = dp_launch_lm(&a, (hipStream_t)stream);
         if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
+        return (int)DP_OK;
+    });
+}
+
+// include/dragposer_lm_terms.h: dp_optimize_lm with a term table in its loss, in the header's order of refusals -- dp_optimize_lm's up to and
+// including dp_lm_extra, what take_terms refuses, the LM parameters' values, the batch.  (Its launcher is a weak reference, like dp_launch_lm.)
+hipError_t dp_launch_lm_terms(const dplm::TermArgs* args, hipStream_t stream) __attribute__((weak));
+extern "C" int dp_optimize_lm_terms(dp_ctx* ctx, const dp_batch* in, const dp_lm_params* p_in, const dp_terms* t_in, const dp_result* out_in,
+                                    const dp_lm_extra* e_in, void* stream)
+{
+    const char* who = "dp_optimize_lm_terms";
+    return entry(ctx, who, [&] {
+        if (!in || !p_in || !t_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_lm_terms: NULL batch, params or terms");
+        if (int rc = check_lm_params_size(ctx, p_in, who)) return rc;
+        dp_result out;
+        if (int rc = take_result(ctx, out_in, out, who)) return rc;
+        dp_lm_extra e;
+        std::memset(&e, 0, sizeof(e));
+        if (e_in)
+            if (int rc = take_sized(ctx, e_in, e, LM_EXTRA_V590, who)) return rc;
+        dplm::TermArgs a;
+        std::memset(&a, 0, sizeof(a));
+        if (int rc = take_terms(ctx, t_in, a, who)) return rc;
+        if (int rc = take_lm_params(ctx, p_in, a, who)) return rc;
+        a.mu = e.mu; a.n_accepted = e.n_accepted; a.loss0 = e.loss0;
+        if (int rc = check_batch(ctx, in, who)) return rc;
+        if (REF8_BUILD) return refuse_ref8(ctx, who);
+        if (!dp_launch_lm_terms) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_lm_terms.hip");
+        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+        DEVICE_GUARD(ctx);
+        a.img = ctx->d_vjpimg.get();
+        fill_batch(a, *in);
+        fill_results(a, out);
+        const hipError_t err = dp_launch_lm_terms(&a, (hipStream_t)stream);
+        if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(err));
         return (int)DP_OK;
     });
 }

@@ -1,7 +1,12 @@
 // dp_lm_body.h -- the body of dp_lm.hip's and dp_lm_seq.hip's kernel, included behind the kernel's signature (its argument block is `a`) with
 //   DP_LM_SEQ 0  dp_lm_kernel(Args): one frame per wave, as dp_lm.hip describes it
 //   DP_LM_SEQ 1  dp_lm_seq_kernel(SeqArgs): one SEQUENCE per wave, the step loop around the same frame (dp_lm_seq.hip)
+//   DP_LM_TERMS 1 (with DP_LM_SEQ 0)  dp_lm_terms_kernel(TermArgs): the frame with a table of constraint terms in its loss (dp_lm_terms.hip);
+//                 everything it adds stands behind this switch, so the other two kernels keep their instructions
 // TGT_POS(jj, c) / TGT_ROT(jj, k) are joint jj's targets of the frame at hand: the batch's row, or the step's row with the step's shift.
+#ifndef DP_LM_TERMS
+#define DP_LM_TERMS 0
+#endif
 #if DP_LM_SEQ
 #define TGT_POS(jj, c) (a.q.tgt_root ? __fadd_rn(a.tgt_pos[(ft * NJ + (jj)) * 3 + (c)], sh[c]) : a.tgt_pos[(ft * NJ + (jj)) * 3 + (c)])
 #define TGT_ROT(jj, k) a.tgt_rot[(ft * NJ + (jj)) * 9 + (k)]
@@ -13,6 +18,9 @@
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
 #if DP_LM_SEQ
     __shared__ float arh[WPB * AR_W_FLOATS];
+#endif
+#if DP_LM_TERMS
+    __shared__ __attribute__((aligned(16))) float tl[TERM_LDS_FLOATS]; // the term table, then a block of rows per wave (dp_lm_terms.h)
 #endif
     const float* __restrict__ W = a.img;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -26,6 +34,9 @@
     if (tid < dpvjp::NY) lds[L_SD + tid] = W[dpvjp::OFF_SD + tid];
     if (tid < NJ) par[tid] = Ti[dpvjp::OFF_PARENT + tid];
     if (tid < 3 * NJ) lds[L_OFF + tid] = W[dpvjp::OFF_BONE + tid];
+#if DP_LM_TERMS
+    for (int i = tid; i < a.n_terms * TW; i += WPB * 64) ((unsigned*)tl)[TL_TBL + i] = a.tbl[i];
+#endif
     __syncthreads();
 
     const long long f = (long long)blockIdx.x * WPB + wv;
@@ -90,7 +101,16 @@
     const float zt = lane < LAT ? a.z_tgt[f * LAT + lane] : 0.f;
     const bool trk = jl && a.tracked[f * NJ + j] != 0;
 #endif
+#if DP_LM_TERMS
+    float gp[3] = {0.f, 0.f, 0.f}; // global_pos: read, and screened, only when an active PLANE or point-DISTANCE term exists
+    if (a.need_gp)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gp[k] = a.global_pos[f * 3 + k];
+    const bool bs = refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]) || refused(gp[0]) || refused(gp[1]) ||
+                    refused(gp[2]);
+#else
     const bool bs = refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]);
+#endif
     bool bt = refused(zt), nrot = false;
 #if !DP_LM_SEQ
     float wp = 0.f, wrr = 0.f;
@@ -108,8 +128,35 @@
         bt = bt || refused(wp) || refused(wrr);
         nrot = not_rotation(m);
     }
+#if DP_LM_TERMS
+    float* const RW = tl + TL_ROW0 + wv * TW_ROW; // [MAX_TERMS][4] the frame's rows (vector, s_f), defaults filled in
+    float wst = 0.f;                              // lane t: c_t = weight_t * s_f
+    if (lane < a.n_terms) { // lane t: term t's row of this frame (the term's own vector and s_f = 1 without one), the dp_cons family's screening
+        const float* tb = tl + TL_TBL + lane * TW;
+        const int type = __float_as_int(tb[T_TYPE]);
+        const float* pf = *(const float* const*)(tb + T_ROW);
+        float r[4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c] = type == DP_TERM_ALIGN ? tb[T_DIR + c] : tb[T_PT + c];
+        r[3] = 1.f;
+        if (pf && tb[T_W] != 0.f) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) r[c] = pf[f * 4 + c];
+            bt = bt || refused(r[0]) || refused(r[1]) || refused(r[2]) || refused(r[3]) || r[3] < 0.f;
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) RW[4 * lane + c] = r[c];
+        wst = tb[T_W] * r[3];
+    }
+#endif
     const bool bad_state = __ballot(bs) != 0ull;
     const bool bad_tgt = !bad_state && __ballot(bt) != 0ull;
+#if DP_LM_TERMS
+    // the frame's active terms, bit t: c_t != 0.  A term that is off has no row, no part in the loss and a loss slot of 0; the active ones
+    // take their places in the term pass and in the loss's sum in the table's order, so a table without the others gives the same bits
+    const unsigned tact = bad_tgt ? 0u : (unsigned)__ballot(wst != 0.f);
+    wave_sync();
+#endif
     const int not_rot = !bad_state && !bad_tgt && __ballot(nrot) != 0ull ? DP_STATUS_TARGET_NOT_ROTATION : 0;
     const unsigned long long tmask = __ballot(trk);
     const int E = __popcll(tmask);
@@ -165,6 +212,9 @@
             if (a.loss) a.loss[f * 3 + lane] = nan;
             if (a.loss0) a.loss0[f * 3 + lane] = nan;
         }
+#if DP_LM_TERMS
+        if (lane < a.n_terms && a.loss_terms) a.loss_terms[f * a.n_terms + lane] = nan;
+#endif
         if (lane == 0) {
             if (a.iters) a.iters[f] = 0;
             if (a.n_accepted) a.n_accepted[f] = 0;
@@ -321,7 +371,20 @@
         const float dzz = zz - zt;
         const float dtj = lane < LAT ? dzz * dzz : 0.f;
         const float lp = uni(wsum(dpj)) / (3.f * (float)E), lr = a.lam_rot * (uni(wsum(drj)) / (9.f * (float)E)), lt = a.lam_tmp * (uni(wsum(dtj)) / 24.f);
+#if DP_LM_TERMS
+        // the loss that decides the steps: the three numbers, then the frame's active terms c_t T_t in the table's order.  Lane t evaluates
+        // term t on this pass's P_j and G_j with its true T (the bands' relu included), whatever rows the step used
+        float tot = (lp + lr) + lt;
+        if (tact != 0u) {
+            wave_sync(); // (this pass's P_j and G_j are in the wave's block for every lane)
+            float tv = 0.f;
+            if (lane < MAX_TERMS && ((tact >> (lane & (MAX_TERMS - 1))) & 1u) != 0u) tv = term_value<float>(tl + TL_TBL + lane * TW, RW + 4 * lane, wst, PB, 4, GB, gp, a.up);
+            for (unsigned m = tact; m != 0u; m &= m - 1u)
+                tot += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tv), __builtin_ctz(m)));
+        }
+#else
         const float tot = (lp + lr) + lt;
+#endif
 
         // ---- what the pass was for
         bool fresh = true; // the wave's block belongs to the kept latent
@@ -352,7 +415,12 @@
         // places a joint to 1e-7 .. 1e-6 m, which is 1e-5 .. 1e-4 of the loss; the steps are decided on the fp32 numbers above (they compare
         // two passes of the same arithmetic), the caller gets the value of the loss at the latent it is handed.  Only when asked for.
         float rep[3] = {Lp, Lr, Lt};
+#if DP_LM_TERMS
+        const bool rep0 = mode == 0 && a.loss0 != nullptr, rep1 = done && (a.loss != nullptr || (a.loss_terms != nullptr && tact != 0u));
+        float tvr = 0.f; // lane t: loss_terms' slot t, the weighted term at the returned latent from the pass in double (0: the term is off)
+#else
         const bool rep0 = mode == 0 && a.loss0 != nullptr, rep1 = done && a.loss != nullptr;
+#endif
         if ((rep0 || rep1) && !bad_tgt) {
             double* const DH0 = (double*)TB; // [40] | [60] | [92] | [22][9] | [22][3]: the tangents' place, idle here
             double *const DH1 = DH0 + 40, *const DQ = DH1 + 60, *const DR = DQ + 92, *const DB = DR + 198;
@@ -423,6 +491,23 @@
                 }
             }
             mv_d(R0d, vd, Pd);
+#if DP_LM_TERMS
+            if (done && tact != 0u) { // the terms at the returned latent: every joint's P and G in double behind the pass's arrays, lane t on term t
+                double *const DP = DB + 66, *const DG = DP + 66; // [22][3] | [22][9]
+                if (jl) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) DP[3 * j + c] = Pd[c] + wdd[c];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c)
+                            DG[9 * j + 3 * r + c] = j == 0 ? R0d[3 * r + c] : R0d[3 * r] * Rd[c] + R0d[3 * r + 1] * Rd[3 + c] + R0d[3 * r + 2] * Rd[6 + c];
+                }
+                wave_sync();
+                if (lane < MAX_TERMS && ((tact >> (lane & (MAX_TERMS - 1))) & 1u) != 0u)
+                    tvr = (float)term_value<double>(tl + TL_TBL + lane * TW, RW + 4 * lane, wst, DP, 3, DG, gp, a.up);
+            }
+#endif
             double dp64 = 0.0, dr64 = 0.0;
             if (trk) {
 #pragma unroll
@@ -524,6 +609,9 @@
                 if (a.z) a.z[f * LAT + lane] = bad_tgt ? nan : z;
                 if (a.z_pre) a.z_pre[f * LAT + lane] = bad_tgt ? nan : z;
             }
+#if DP_LM_TERMS
+            if (lane < a.n_terms && a.loss_terms) a.loss_terms[f * a.n_terms + lane] = bad_tgt ? nan : tvr;
+#endif
             if (jl) {
                 if (a.pose)
 #pragma unroll
@@ -724,6 +812,42 @@
                 }
                 wave_sync(); // (the rows' last reads before the next pair's writes)
             }
+#if DP_LM_TERMS
+            // ---- the terms' rows (include/dragposer_lm_terms.h), into the same place and the same four tiles.  A round takes the next eight
+            // active terms, four per half of the wave, each in three rows of the half's twelve: lane n < 24 forms column n of its half's terms'
+            // rows, lane 24 their residuals; rows a term does not use, and the rows of a sub-slot without a term, are zero
+            for (unsigned rem = tact; rem != 0u;) {
+                unsigned mine = rem;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (hf != 0) mine &= mine - 1u; // (the second half skips the first half's four)
+                    rem &= rem - 1u;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rem &= rem - 1u;
+#pragma unroll 1
+                for (int sl = 0; sl < 4; ++sl) {
+                    float r3[3] = {0.f, 0.f, 0.f};
+                    if (mine != 0u && cn <= LAT) {
+                        const int t = __builtin_ctz(mine);
+                        term_rows(tl + TL_TBL + t * TW, RW + 4 * t, cn, PB, GB, gp, a.up, par, lds + L_OFF, TB, QN, RN, RB, VB, R0, dR0, dwd, r3);
+                    }
+                    mine &= mine - 1u;
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) JB[(12 * hf + 3 * sl + e) * SJ + cn] = r3[e];
+                }
+                wave_sync();
+#pragma unroll
+                for (int s = 0; s < 6; ++s) {
+                    const float v0 = JB[(4 * s + lk) * SJ + lr16], v1 = JB[(4 * s + lk) * SJ + 16 + lr16];
+                    na[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v0, v0, na[0][0], 0, 0, 0);
+                    na[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v0, v1, na[0][1], 0, 0, 0);
+                    na[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v1, v0, na[1][0], 0, 0, 0);
+                    na[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v1, v1, na[1][1], 0, 0, 0);
+                }
+                wave_sync(); // (the rows' last reads before the next round's writes)
+            }
+#endif
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll

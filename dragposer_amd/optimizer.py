@@ -319,13 +319,17 @@ class LatentOptimizer:
             lambda gp, lt: terms.to_struct(int(z0.shape[0]), self.device, gp, lt), skel=skel, mid=mid)
 
     def optimize_lm(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, lm=None, lambda_rot=1.0, lambda_tmp=0.02, mu=None, stop_eps_pos=0.0,
-                    stop_eps_rot=0.0, outputs=None, out=None):
+                    stop_eps_rot=0.0, outputs=None, out=None, terms=None, global_pos=None):
         """`optimize`'s problem solved by Levenberg-Marquardt steps instead of Adam (`lm`: a dragposer_amd.LM; None = LM()):
         include/dragposer_lm.h, dp_optimize_lm (one launch).  Inputs as in `optimize`.  `mu` [B] fp32 on the device: the damping of every
         frame, read and updated IN PLACE (a caller keeps it from frame to frame); None: every frame starts at lm.mu0.  Returns `optimize`'s
         dict (every array belongs to the returned z; z_pre = z; iters = the steps executed) plus `n_accepted` [B] int32, `loss0` [B,3] (the
         loss at z0) and `mu` [B] (the damping after the call).  `stop_eps_pos` / `stop_eps_rot`: the early stop's thresholds unless `lm`
-        carries its own.  Asynchronous on torch's current stream."""
+        carries its own.  Asynchronous on torch's current stream.
+        `terms` (a dragposer_amd.Terms without points): the table's terms in the LM loss, include/dragposer_lm_terms.h,
+        dp_optimize_lm_terms (one launch); `global_pos` [B,3] as in `optimize_terms`, required when an active PLANE or point-DISTANCE term
+        exists.  The dict then also holds `loss_terms` [B, len(terms)], each weighted term at the returned z.  terms=None: dp_optimize_lm,
+        unchanged."""
         from .lm import LM
 
         lm = (lm if lm is not None else LM()).check()
@@ -334,7 +338,7 @@ class LatentOptimizer:
         p = lm.to_struct(lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot)
         own = {"n_accepted": ((B,), torch.int32), "loss0": ((B, 3), torch.float32), "mu": ((B,), torch.float32)}
         names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS) + tuple(own)
-        res, tensors = self._outputs(B, [n for n in names if n not in own and n != "clock"], out)
+        res, tensors = self._outputs(B, [n for n in names if n not in own and n not in ("clock", "loss_terms")], out)
         ex = _lib.DpLmExtra()
         for name, (shape, dtype) in own.items():
             if name == "mu":
@@ -345,7 +349,24 @@ class LatentOptimizer:
                 continue
             setattr(ex, name, _check(t, name, shape, dtype, dev))
             tensors[name] = t
-        self._call(self.lib.dp_optimize_lm, C.byref(batch), C.byref(p), C.byref(res), C.byref(ex))
+        if terms is None:
+            self._call(self.lib.dp_optimize_lm, C.byref(batch), C.byref(p), C.byref(res), C.byref(ex))
+            return tensors
+        if terms.has_points:
+            raise ValueError("optimize_lm: a table with points does not go with the LM solver (include/dragposer_lm_terms.h, \"Not covered\")")
+        terms.check()
+        gp = None
+        if global_pos is not None:
+            gp = _check(global_pos, "global_pos", (B, 3), torch.float32, dev)
+        elif terms.needs_global_pos:
+            raise ValueError("optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]")
+        lt = None
+        if outputs is None or "loss_terms" in names:
+            lt = out["loss_terms"] if out is not None and "loss_terms" in out else torch.empty(B, len(terms), dtype=torch.float32, device=dev)
+            tensors["loss_terms"] = lt
+        s, keep = terms.to_struct(B, dev, gp, _check(lt, "loss_terms", (B, len(terms)), torch.float32, dev) if lt is not None and len(terms) else None)
+        self._call(self.lib.dp_optimize_lm_terms, C.byref(batch), C.byref(p), C.byref(s), C.byref(res), C.byref(ex))
+        del keep
         return tensors
 
     def forward_vjp(self, z, cur_rot, grads, out=None, offsets=None, doffsets=False):
