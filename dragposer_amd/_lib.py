@@ -321,6 +321,9 @@ class DpSeqLmExtra(_Sized):
 # every symbol include/dragposer_lm_terms.h declares (tests/test_lm_terms_abi.py)
 LM_TERMS_SYMBOLS = ("dp_optimize_lm_terms",)
 
+# every symbol include/dragposer_sequence_lm_terms.h declares (tests/test_lm_sequence_terms_abi.py)
+LM_SEQUENCE_TERMS_SYMBOLS = ("dp_optimize_sequence_lm_terms",)
+
 
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
@@ -431,6 +434,9 @@ def load(path=None):
                                          C.POINTER(DpLmExtra), C.c_void_p]
     lib.dp_optimize_sequence_lm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpLmParams), C.POINTER(DpLatentAR),
                                             C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.POINTER(DpSeqLmExtra), C.c_void_p]
+    lib.dp_optimize_sequence_lm_terms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpLmParams), C.POINTER(DpTerms),
+                                                  C.POINTER(DpLatentAR), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.POINTER(DpSeqResults),
+                                                  C.POINTER(DpSeqLmExtra), C.POINTER(DpSeqExtra), C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

@@ -29,11 +29,13 @@
 #include "../../include/dragposer_lm.h"
 #include "../../include/dragposer_sequence_lm.h"
 #include "../../include/dragposer_lm_terms.h"
+#include "../../include/dragposer_sequence_lm_terms.h"
 #include "dp_cons_live.h"
 #include "dp_cons_tether.h"
 #include "dp_cons_points.h"
 #include "dp_host_rt.h"
 #include "dp_lm_seq.h"
+#include "dp_lm_seq_terms.h"
 #include "dp_lm_terms.h"
 #include "dp_kernel.h"
 #include "dp_sequence.h"
@@ -1908,9 +1910,50 @@ extern "C" int dp_live_step(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_
 
 // ------------------------------------------------------------------------------------------------
 // per-frame epilogue of S sequences (reference drag_pose.py:369-402), see include/dragposer.h
-// include/dragposer_sequence_lm.h: dp_optimize_lm's frame for n_steps frames of S sequences in one launch (+ one for the history buffers), in the
-// header's order of refusals.  (Its launcher is a weak reference, like dp_launch_lm.)
+// include/dragposer_sequence_lm.h and include/dragposer_sequence_lm_terms.h: dp_optimize_lm's frame for n_steps frames of S sequences in one launch
+// (+ one for the history buffers), in the headers' order of refusals.  A: dplm::SeqArgs or dplm::SeqTermArgs; own(a) validates what the entry
+// point brought beyond dp_seq_lm_extra (the table and dp_seq_extra) and stands between that struct and the predictor.  (The launchers are weak
+// references, like dp_launch_lm; the caller has refused a NULL argument.)
 hipError_t dp_launch_lm_seq(const dplm::SeqArgs* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_lm_seq_terms(const dplm::SeqTermArgs* args, hipStream_t stream) __attribute__((weak));
+template <class A, class Own>
+static int sequence_lm_impl(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_lm_params* p_in, const dp_latent_ar* ar,
+                            const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, const dp_seq_lm_extra* e_in, void* stream,
+                            const char* who, Own own, hipError_t (*launch)(const A*, hipStream_t), const char* unit)
+{
+    if (int rc = check_lm_params_size(ctx, p_in, who)) return rc;
+    A a;
+    std::memset(&a, 0, sizeof(a));
+    if (int rc = take_lm_params(ctx, p_in, a, who)) return rc;
+    dp_seq_results out;
+    if (int rc = take_sized(ctx, out_in, out, SEQ_RESULTS_V500, who)) return rc;
+    if (int rc = check_sequence(ctx, fr, st, adj, out, who, true)) return rc;
+    dp_seq_lm_extra e;
+    std::memset(&e, 0, sizeof(e));
+    if (e_in)
+        if (int rc = take_sized(ctx, e_in, e, SEQ_LM_EXTRA_V600, who)) return rc;
+    if (int rc = own(a)) return rc;
+    if (ar) {
+        if (int rc = take_latent_ar(ctx, ar, fr, st, a.r, who)) return rc;
+    } else if (!fr->z_tgt)
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": neither a predictor nor frames->z_tgt: the pull term's targets have no source");
+    if (REF8_BUILD) return refuse_ref8(ctx, who);
+    if (!launch) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without " + unit);
+    if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+    a.img = ctx->d_vjpimg.get();
+    a.z0 = latent; a.z = latent; a.z_tgt = fr->z_tgt; a.cur_rot = st->global_rot; a.tgt_pos = fr->tgt_pos; a.tgt_rot = fr->tgt_rot; a.w = fr->w;
+    a.tracked = fr->tracked; a.n_frames = n_seq;
+    a.pose = out.pose_ret; a.world_rot = out.world_rot; a.iters = out.iters; a.loss = out.loss; a.status = out.status;
+    a.mu = e.mu; a.mu_trace = e.mu_trace; a.n_accepted = e.n_accepted; a.loss0 = e.loss0; a.pos = e.joint_pos;
+    fill_sequence(a.q, ctx, fr, st, adj, out);
+    {
+        DEVICE_GUARD(ctx);
+        const hipError_t err = launch(&a, (hipStream_t)stream);
+        if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(err));
+    }
+    return append_history(ctx, n_seq, fr, st, out, stream);
+}
+
 extern "C" int dp_optimize_sequence_lm(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_lm_params* p_in, const dp_latent_ar* ar,
                                        const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in, const dp_seq_lm_extra* e_in, void* stream)
 {
@@ -1918,36 +1961,34 @@ extern "C" int dp_optimize_sequence_lm(dp_ctx* ctx, int n_seq, float* latent, co
     return entry(ctx, who, [&] {
         if (n_seq <= 0 || !latent || !fr || !p_in || !st || !out_in)
             return fail(ctx, DP_ERR_INVALID, "dp_optimize_sequence_lm: n_sequences must be positive; NULL latent, frames, params, state or results");
-        if (int rc = check_lm_params_size(ctx, p_in, who)) return rc;
-        dplm::SeqArgs a;
-        std::memset(&a, 0, sizeof(a));
-        if (int rc = take_lm_params(ctx, p_in, a, who)) return rc;
-        dp_seq_results out;
-        if (int rc = take_sized(ctx, out_in, out, SEQ_RESULTS_V500, who)) return rc;
-        if (int rc = check_sequence(ctx, fr, st, adj, out, who, true)) return rc;
-        dp_seq_lm_extra e;
-        std::memset(&e, 0, sizeof(e));
-        if (e_in)
-            if (int rc = take_sized(ctx, e_in, e, SEQ_LM_EXTRA_V600, who)) return rc;
-        if (ar) {
-            if (int rc = take_latent_ar(ctx, ar, fr, st, a.r, who)) return rc;
-        } else if (!fr->z_tgt)
-            return fail(ctx, DP_ERR_INVALID, std::string(who) + ": neither a predictor nor frames->z_tgt: the pull term's targets have no source");
-        if (REF8_BUILD) return refuse_ref8(ctx, who);
-        if (!dp_launch_lm_seq) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_lm_seq.hip");
-        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
-        a.img = ctx->d_vjpimg.get();
-        a.z0 = latent; a.z = latent; a.z_tgt = fr->z_tgt; a.cur_rot = st->global_rot; a.tgt_pos = fr->tgt_pos; a.tgt_rot = fr->tgt_rot; a.w = fr->w;
-        a.tracked = fr->tracked; a.n_frames = n_seq;
-        a.pose = out.pose_ret; a.world_rot = out.world_rot; a.iters = out.iters; a.loss = out.loss; a.status = out.status;
-        a.mu = e.mu; a.mu_trace = e.mu_trace; a.n_accepted = e.n_accepted; a.loss0 = e.loss0; a.pos = e.joint_pos;
-        fill_sequence(a.q, ctx, fr, st, adj, out);
-        {
-            DEVICE_GUARD(ctx);
-            const hipError_t err = dp_launch_lm_seq(&a, (hipStream_t)stream);
-            if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(err));
-        }
-        return append_history(ctx, n_seq, fr, st, out, stream);
+        return sequence_lm_impl<dplm::SeqArgs>(ctx, n_seq, latent, fr, p_in, ar, st, adj, out_in, e_in, stream, who, [](dplm::SeqArgs&) { return (int)DP_OK; },
+                                               dp_launch_lm_seq, "dp_lm_seq.hip");
+    });
+}
+
+// ... with a term table in the loss: the table as dp_optimize_sequence_terms takes it (take_terms' `seq` form), then dp_seq_extra, whose
+// joint_pos is refused here (dp_seq_lm_extra.joint_pos is this call's array of joint positions), then each term's step between rows
+extern "C" int dp_optimize_sequence_lm_terms(dp_ctx* ctx, int n_seq, float* latent, const dp_seq_frames* fr, const dp_lm_params* p_in, const dp_terms* t_in,
+                                             const dp_latent_ar* ar, const dp_seq_state* st, const dp_seq_step* adj, const dp_seq_results* out_in,
+                                             const dp_seq_lm_extra* e_in, const dp_seq_extra* term_extra, void* stream)
+{
+    const char* who = "dp_optimize_sequence_lm_terms";
+    const auto own = [&](dplm::SeqTermArgs& a) -> int {
+        if (int rc = take_terms(ctx, t_in, a, who, st)) return rc;
+        dp_seq_extra x;
+        if (int rc = take_seq_extra(ctx, term_extra, x, who)) return rc;
+        if (x.joint_pos)
+            return fail(ctx, DP_ERR_INVALID, std::string(who) + ": dp_seq_extra.joint_pos must be NULL here; the joint positions of every step go to dp_seq_lm_extra.joint_pos");
+        a.loss_terms = x.loss_terms;
+        for (int k = 0; k < a.n_terms; ++k) a.tbl[k * dpcons::TW + dpcons::T_STEP] = (unsigned)x.row_step[k];
+        return DP_OK;
+    };
+    return entry(ctx, who, [&] {
+        if (n_seq <= 0 || !latent || !fr || !p_in || !t_in || !st || !out_in)
+            return fail(ctx, DP_ERR_INVALID,
+                        "dp_optimize_sequence_lm_terms: n_sequences must be positive; NULL latent, frames, params, terms, state or results");
+        return sequence_lm_impl<dplm::SeqTermArgs>(ctx, n_seq, latent, fr, p_in, ar, st, adj, out_in, e_in, stream, who, own, dp_launch_lm_seq_terms,
+                                                   "dp_lm_seq_terms.hip");
     });
 }
 

@@ -3,6 +3,8 @@
 //   DP_LM_SEQ 1  dp_lm_seq_kernel(SeqArgs): one SEQUENCE per wave, the step loop around the same frame (dp_lm_seq.hip)
 //   DP_LM_TERMS 1 (with DP_LM_SEQ 0)  dp_lm_terms_kernel(TermArgs): the frame with a table of constraint terms in its loss (dp_lm_terms.hip);
 //                 everything it adds stands behind this switch, so the other two kernels keep their instructions
+//   DP_LM_SEQ 1 and DP_LM_TERMS 1  dp_lm_seq_terms_kernel(SeqTermArgs): the step loop around the frame with the table (dp_lm_seq_terms.hip).
+//                 What only the two together need stands behind both switches, so the three kernels above keep their instructions
 // TGT_POS(jj, c) / TGT_ROT(jj, k) are joint jj's targets of the frame at hand: the batch's row, or the step's row with the step's shift.
 #ifndef DP_LM_TERMS
 #define DP_LM_TERMS 0
@@ -105,7 +107,11 @@
     float gp[3] = {0.f, 0.f, 0.f}; // global_pos: read, and screened, only when an active PLANE or point-DISTANCE term exists
     if (a.need_gp)
 #pragma unroll
+#if DP_LM_SEQ // (the carried position, as it stands before this step: what the composition hands dp_optimize_lm_terms)
+        for (int k = 0; k < 3; ++k) gp[k] = gpc[k];
+#else
         for (int k = 0; k < 3; ++k) gp[k] = a.global_pos[f * 3 + k];
+#endif
     const bool bs = refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]) || refused(gp[0]) || refused(gp[1]) ||
                     refused(gp[2]);
 #else
@@ -141,7 +147,11 @@
         r[3] = 1.f;
         if (pf && tb[T_W] != 0.f) {
 #pragma unroll
+#if DP_LM_SEQ // (the term's rows of this step: T_STEP floats further per step, 0 = one row held, as dp_cons_body.h reads them)
+            for (int c = 0; c < 4; ++c) r[c] = pf[(long long)stp * __float_as_int(tb[T_STEP]) + f * 4 + c];
+#else
             for (int c = 0; c < 4; ++c) r[c] = pf[f * 4 + c];
+#endif
             bt = bt || refused(r[0]) || refused(r[1]) || refused(r[2]) || refused(r[3]) || r[3] < 0.f;
         }
 #pragma unroll
@@ -177,6 +187,9 @@
             if (a.loss) a.loss[ft * 3 + lane] = nan;
             if (a.loss0) a.loss0[ft * 3 + lane] = nan;
         }
+#if DP_LM_TERMS
+        if (lane < a.n_terms && a.loss_terms) a.loss_terms[ft * a.n_terms + lane] = nan;
+#endif
         if (lane == 0) {
             if (a.iters) a.iters[ft] = 0;
             if (a.n_accepted) a.n_accepted[ft] = 0;
@@ -188,7 +201,9 @@
         for (int k = 0; k < 4; ++k) crc[k] = nan;
 #pragma unroll
         for (int k = 0; k < 3; ++k) gpc[k] = nan;
-        continue; // (nothing of the wave's block was touched: no wave_sync() needed before the next step)
+        // (nothing of the wave's block was touched: no wave_sync() needed before the next step.  With the table, lane t has written row t of
+        // the wave's RW rows and nothing has read them; the next step's lane t writes the same words, in program order)
+        continue;
     }
     if (lane < LAT && a.r.trace) a.r.trace[ft * LAT + lane] = zt;
 #else
@@ -595,6 +610,9 @@
                     a.loss[fo * 3] = bad_tgt ? nan : rep[0]; a.loss[fo * 3 + 1] = bad_tgt ? nan : rep[1]; a.loss[fo * 3 + 2] = bad_tgt ? nan : rep[2];
                 }
             }
+#if DP_LM_TERMS
+            if (lane < a.n_terms && a.loss_terms) a.loss_terms[fo * a.n_terms + lane] = bad_tgt ? nan : tvr;
+#endif
             zc = zr;
 #pragma unroll
             for (int k = 0; k < 3; ++k) gpc[k] = gpn[k];

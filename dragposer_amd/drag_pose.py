@@ -53,7 +53,7 @@ def _check_ar(temporal, ar, who):
 
 
 def _solver_alone(who, **layers):
-    """solver=LM(...) has the trackers and the pull in its loss and nothing else (include/dragposer_lm.h, Not covered)"""
+    """solver=LM(...) has the trackers, the pull and its own table (LM.terms) in its loss and nothing else (include/dragposer_lm.h, Not covered)"""
     for name, given in layers.items():
         if given is not None:
             raise ValueError(f"DragPose.{who}: solver= does not go with {name}= (include/dragposer_lm.h, Not covered)")
@@ -337,8 +337,11 @@ class DragPose:
         (dp_optimize_sequence_lm, include/dragposer_sequence_lm.h), cut into the same stretches -- frame by frame the bits of run(solver=).
         `target_root` is honoured, `lm_mu` [S] is carried in place, `last_status`, `last_loss` [T,S,3] and `last_joint_pos` [T,S,22,3] are set.
         With `solver.predictor` (a dragposer_amd.LatentAR, for a DragPose without a temporal model) the pull term's target of every frame is
-        formed inside ONE launch for all T frames, weighed by `lambda_temporal`, and `last_z_tgt` [T,S,24] holds the targets used.  None of the
-        other layers goes with it.
+        formed inside ONE launch for all T frames, weighed by `lambda_temporal`, and `last_z_tgt` [T,S,24] holds the targets used.  With
+        `solver.terms` (LM(3, terms=Terms([...])): a table without points; `per_frame` [S,4] or [T,S,4], offset per stretch as for Adam) the
+        table's terms join the LM loss (dp_optimize_sequence_lm_terms, include/dragposer_sequence_lm_terms.h), `last_terms`
+        [T,S,len(terms)] holds the weighted terms of every frame, and the frames are the bits of run(solver=) with that frame's table.  The
+        table belongs to the solver as the predictor does: none of the other layers, `terms=` among them, goes with `solver=`.
         Returns (poses [T,S,88], global positions [T,S,3], iterations [T,S])."""
         if solver is not None:
             _solver_alone("run_frames", constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, tethers=tethers, present=present)
@@ -392,7 +395,7 @@ class DragPose:
         status = torch.empty(T, S, dtype=torch.int32, device=dev)
         if solver is not None:
             return self._run_frames_lm(solver, dense_p, dense_r, root, trk, adjust, poses, gpos, iters, status, stop_eps_pos, stop_eps_rot, lambda_rot,
-                                       lambda_temporal, temporal_future_window, height_indices)
+                                       lambda_temporal, temporal_future_window, height_indices, solver.terms)
         with_terms = constraints is not None or terms is not None
         if with_terms:
             if terms is not None:
@@ -484,9 +487,15 @@ class DragPose:
         return poses, gpos, iters
 
     def _run_frames_lm(self, solver, dense_p, dense_r, root, trk, adjust, poses, gpos, iters, status, stop_eps_pos, stop_eps_rot, lambda_rot,
-                       lambda_temporal, temporal_future_window, height_indices):
-        """run_frames(solver=LM(...)) behind its preparation: the stretches of run_frames through dp_optimize_sequence_lm; with a predictor, one launch"""
+                       lambda_temporal, temporal_future_window, height_indices, terms=None):
+        """run_frames(solver=LM(...)) behind its preparation: the stretches of run_frames through dp_optimize_sequence_lm (with `terms`,
+        dp_optimize_sequence_lm_terms); with a predictor, one launch"""
         dev, S, T = self.device, self.S, int(dense_p.shape[0])
+        if terms is not None:
+            for i, term in enumerate(terms.terms):
+                if term.per_frame is not None and term.per_frame.dim() == 3 and int(term.per_frame.shape[0]) != T:
+                    raise ValueError(f"Terms: term {i}: per_frame must be [{S},4] or [{T},{S},4], got {tuple(term.per_frame.shape)}")
+            self.last_terms = torch.empty(T, S, len(terms), device=dev)
         loss = torch.empty(T, S, 3, device=dev)
         self.last_joint_pos = torch.empty(T, S, NJ, 3, device=dev)
         if self.lm_mu is None:
@@ -495,6 +504,8 @@ class DragPose:
         names = ("pose_ret", "pos_ret", "iters", "status", "loss", "joint_pos")
 
         def launch(t, n, z_tgt, strides, lam, **kw):
+            if terms is not None:  # (the stretch's share of the table's rows and of its per-step output)
+                kw.update(terms=terms.frames(t, t + n), loss_terms=self.last_terms[t:t + n])
             self.opt.optimize_sequence_lm(self.latent, dense_p[t:t + n], dense_r[t:t + n], root[t:t + n] if root is not None else None, trk["w"],
                                           trk["tracked"], z_tgt, strides, self.current_global_pos, self.current_global_rot, self.latent_buffer,
                                           self.displacement_buffer, self.heights_buffer, heights, lm=solver, lambda_rot=float(lambda_rot),
@@ -560,8 +571,12 @@ class DragPose:
         dp_optimize_lm followed by dp_sequence_advance (two launches, include/dragposer_lm.h); max_iter, learning_rate and min_loss_incr are
         not used, stop_eps_pos / stop_eps_rot are the early stop's thresholds unless the LM carries its own.  The damping is kept per sequence
         in `lm_mu` [S] and reset when a sequence begins.  With `solver.predictor` (a dragposer_amd.LatentAR) the frame is a one-step launch of
-        run_frames(solver=) instead (dp_optimize_sequence_lm), the pull's target formed from the sequence's last latents: its bits.  Not together with constraints= / terms= / holds= / ar= / gaps= / tethers= / live= or
-        offsets other than the context's skeleton: the LM loss has the trackers and the pull only."""
+        run_frames(solver=) instead (dp_optimize_sequence_lm), the pull's target formed from the sequence's last latents: its bits.  With `solver.terms`
+        (LM(3, terms=Terms([...])), a table without points, `per_frame` [S,4]: this frame's rows) the table's terms join the LM loss:
+        dp_optimize_lm_terms with this frame's current_global_pos, then dp_sequence_advance (two launches, include/dragposer_lm_terms.h), or
+        with `solver.predictor` the one-step launch of run_frames(solver=); `last` then holds `loss_terms` [S,len(terms)].  Not together with
+        constraints= / terms= / holds= / ar= / gaps= / tethers= / live= or offsets other than the context's skeleton: the table, like the
+        predictor, belongs to the solver."""
         if solver is not None:
             _solver_alone("run", constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, tethers=tethers, live=live or None,
                           present=present)
@@ -655,7 +670,7 @@ class DragPose:
         pull = self.temporal is not None and float(lambda_temporal) != 0.0  # (no predictor: the buffer is zeros, the term is off; run_frames() alike)
         if solver is not None:
             return self._run_lm(solver, trk, o, pose, gpos, adjust, height_indices, lambda_rot, lambda_temporal if pull else 0.0, stop_eps_pos,
-                                stop_eps_rot, temporal_future_window, verbose, squeeze)
+                                stop_eps_rot, temporal_future_window, verbose, squeeze, solver.terms)
         if constraints is not None or terms is not None:
             return self._run_constrained(constraints if terms is None else terms, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot,
                                          lambda_temporal if pull else 0.0, stop_eps_pos, stop_eps_rot, min_loss_incr, temporal_future_window,
@@ -703,8 +718,10 @@ class DragPose:
             return pose[0], gpos[0]
         return pose, gpos
 
-    def _run_lm(self, solver, trk, o, pose, gpos, adjust, height_indices, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, window, verbose, squeeze):
-        """run(solver=LM(...)): the frame's latent by dp_optimize_lm, then run()'s epilogue (dp_sequence_advance)"""
+    def _run_lm(self, solver, trk, o, pose, gpos, adjust, height_indices, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, window, verbose, squeeze,
+                terms=None):
+        """run(solver=LM(...)): the frame's latent by dp_optimize_lm (with `terms`, dp_optimize_lm_terms reading the position before the frame),
+        then run()'s epilogue (dp_sequence_advance)"""
         S = self.S
         if o.get("lm_frame") is None:
             o["lm_frame"] = self.opt.allocate_outputs(S, ("z", "z_pre", "pose", "disp", "world_disp", "world_rot", "pos", "loss", "iters", "status"))
@@ -713,9 +730,11 @@ class DragPose:
         if self.lm_mu is None:
             self.lm_mu = torch.full((S,), float(solver.mu0), device=self.device)
         z_tgt = self.target_latent_buffer[:, self.current_index].contiguous()
-        self.opt.optimize_lm(self.latent, z_tgt, self.current_global_rot, trk["tgt_pos"], trk["tgt_rot"], trk["w"], trk["tracked"], lm=solver,
-                             lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_tmp), mu=self.lm_mu, stop_eps_pos=stop_eps_pos,
-                             stop_eps_rot=stop_eps_rot, out=fr, outputs=tuple(fr) + ("mu",))
+        names = tuple(fr) + ("mu",) + (("loss_terms",) if terms is not None else ())
+        got = self.opt.optimize_lm(self.latent, z_tgt, self.current_global_rot, trk["tgt_pos"], trk["tgt_rot"], trk["w"], trk["tracked"], lm=solver,
+                                   lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_tmp), mu=self.lm_mu, stop_eps_pos=stop_eps_pos,
+                                   stop_eps_rot=stop_eps_rot, out=fr, outputs=names, terms=terms,
+                                   global_pos=self.current_global_pos if terms is not None else None)
         self.opt.sequence_advance(fr, self.current_global_pos, self.current_global_rot, self.latent_buffer, self.displacement_buffer,
                                   self.heights_buffer, tuple(int(h) for h in height_indices), pose_ret=pose, pos_ret=gpos, adjust=adjust,
                                   tgt_pos=trk["tgt_pos"] if adjust is not None else None)
@@ -723,6 +742,8 @@ class DragPose:
         o["z"].copy_(self.latent)
         self.last = dict(iters=fr["iters"], loss=fr["loss"], z=o["z"], pose=pose, pos=gpos, status=fr["status"], n_accepted=fr["n_accepted"],
                          loss0=fr["loss0"], joint_pos=fr["pos"])
+        if terms is not None:
+            self.last["loss_terms"] = got["loss_terms"]
         if verbose:
             l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
             print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "

@@ -286,6 +286,8 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
         extra["gaps"] = args.gaps_model
     if getattr(args, "solver_model", None) is not None:
         extra = dict(solver=args.solver_model)
+        if cons is not None:  # (the reference's extra terms as the solver's table in the LM loss: include/dragposer_sequence_lm_terms.h)
+            args.solver_model.terms = Terms.from_constraints(cons)
     poses = torch.zeros(T, S, 88, device=dev)
     out_pos = torch.zeros(T, S, 3, device=dev)
     iters = torch.zeros(T, S, dtype=torch.int32, device=dev)
@@ -473,7 +475,9 @@ def main(argv=None):
                     help="solve every frame by Levenberg-Marquardt steps (default 3) instead of Adam: DragPose.run_frames(solver=LM(STEPS)), the frame "
                          "loop on the device (dp_optimize_sequence_lm, include/dragposer_sequence_lm.h); with --per-frame DragPose.run(solver=), "
                          "dp_optimize_lm followed by dp_sequence_advance per frame, same results.  With --latent-ar the predictor becomes the "
-                         "solver's (LM.predictor) and the configuration's lambda_temporal pulls towards its targets.  Not with --constraints, "
+                         "solver's (LM.predictor) and the configuration's lambda_temporal pulls towards its targets.  With --constraints reference "
+                         "the reference's extra terms join the LM loss as the solver's table, LM(terms=Terms.from_constraints(Constraints.reference())) "
+                         "(dp_optimize_sequence_lm_terms, include/dragposer_sequence_lm_terms.h; --per-frame: dp_optimize_lm_terms).  Not with "
                          "--foot-lock, --tether, --balance or --gaps, and for a BVH with the model's own skeleton")
     ap.add_argument("--lockstep", action="store_true",
                     help="directory input: advance all files together, one kernel launch per frame index for all of them "
@@ -527,14 +531,14 @@ def main(argv=None):
             args.solver_model = LM(steps=int(steps) if steps else 3).check()
         except ValueError as e:
             raise SystemExit(f"--solver: expected lm[:STEPS] with 1 <= STEPS <= 64 ({e})")
-        for flag, given in (("--constraints", args.constraints), ("--foot-lock", args.foot_lock), ("--tether", args.tether), ("--balance", args.balance),
-                            ("--gaps", args.gaps)):
+        for flag, given in (("--foot-lock", args.foot_lock), ("--tether", args.tether), ("--balance", args.balance), ("--gaps", args.gaps)):
             if given:
-                raise SystemExit(f"--solver and {flag}: the LM loss has the trackers and the pull only (include/dragposer_lm.h, Not covered)")
+                raise SystemExit(f"--solver and {flag}: the LM loss has the trackers, the pull and --constraints reference's table only "
+                                 "(include/dragposer_lm.h, Not covered)")
         if args.latent_ar is not None:
             args.solver_model.predictor = args.latent_ar_model
         print(f"Solver: Levenberg-Marquardt, {args.solver_model.steps} steps per frame (DragPose.{'run' if args.per_frame else 'run_frames'}(solver=), "
-              f"include/dragposer_{'lm' if args.per_frame else 'sequence_lm'}.h)")
+              f"include/dragposer_{'lm' if args.per_frame else 'sequence_lm'}{'_terms' if args.constraints else ''}.h)")
     args.gaps_model = None
     if args.gaps is not None:
         from .gaps import Gaps

@@ -13,7 +13,10 @@ class LM:
     lambda_rot loss_rot <= stop_eps_rot, or after a rejection at mu_max.  The two thresholds given here win over the caller's
     (DragPose.run passes its own stop_eps_pos / stop_eps_rot when these are None).  `predictor` (a dragposer_amd.LatentAR, not part of the C
     struct): DragPose.run / run_frames then form every frame's pull target from the sequence's own last latents inside the launch,
-    dp_optimize_sequence_lm, weighed by lambda_temporal."""
+    dp_optimize_sequence_lm, weighed by lambda_temporal.  `terms` (a dragposer_amd.Terms without points, not part of the C struct either): the
+    table's terms join the LM loss of DragPose.run / run_frames(solver=) -- include/dragposer_lm_terms.h, include/dragposer_sequence_lm_terms.h;
+    the table belongs to the solver as the predictor does, and terms= beside solver= stays refused.  LatentOptimizer's calls take their table
+    as an argument of their own and do not read this one."""
     steps: int = 3
     mu0: float = 1e-2
     mu_up: float = 4.0
@@ -23,6 +26,7 @@ class LM:
     early_stop: bool = True
     stop_eps_pos: float = None
     stop_eps_rot: float = None
+    terms: object = None      # a dragposer_amd.Terms without points: the table in the LM loss (include/dragposer_sequence_lm_terms.h)
     predictor: object = None  # a dragposer_amd.LatentAR: the pull term's target formed inside the launch (include/dragposer_sequence_lm.h)
 
     def check(self):
@@ -40,6 +44,14 @@ class LM:
             raise ValueError("LM: need 0 < mu_min <= mu_max")
         if not self.mu_min <= self.mu0 <= self.mu_max:
             raise ValueError("LM: mu0 outside [mu_min, mu_max]")
+        if self.terms is not None:
+            from .terms import Terms
+
+            if not isinstance(self.terms, Terms):
+                raise ValueError(f"LM: terms must be a dragposer_amd.Terms, got {type(self.terms).__name__}")
+            if self.terms.has_points:
+                raise ValueError("LM: a table with points does not go with the LM solver (include/dragposer_sequence_lm_terms.h, Not covered)")
+            self.terms.check()
         if self.predictor is not None:
             from .ar import LatentAR
 

@@ -646,7 +646,7 @@ class LatentOptimizer:
     def optimize_sequence_lm(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
                              heights_buf, height_joints, lm=None, lambda_rot=1.0, lambda_tmp=0.0, stop_eps_pos=0.0, stop_eps_rot=0.0, mu=None, ar=None,
                              adjust=None, pose_ret=None, pos_ret=None, iters=None, loss=None, scratch=None, status=None, world_rot=None,
-                             mu_trace=None, n_accepted=None, loss0=None, joint_pos=None, z_tgt_trace=None, outputs=None):
+                             mu_trace=None, n_accepted=None, loss0=None, joint_pos=None, z_tgt_trace=None, outputs=None, terms=None, loss_terms=None):
         """T consecutive frames of S sequences solved by Levenberg-Marquardt steps in one launch (include/dragposer_sequence_lm.h:
         dp_optimize_sequence_lm): bit for bit what optimize_lm, sequence_advance and a copy of the latent give frame by frame.  Inputs and
         state as in `optimize_sequence`; `lm`: a dragposer_amd.LM (None = LM(); its `predictor` is not read here).  `mu` [S] fp32: the damping
@@ -655,10 +655,22 @@ class LatentOptimizer:
         True (allocated here) receives the rows.  Returns dict(pose_ret, pos_ret, iters [T,S] = the steps executed, loss [T,S,3], status, world_rot
         [T,S,4], mu_trace [T,S], n_accepted [T,S], loss0 [T,S,3], joint_pos [T,S,22,3]) and `mu` when given; `outputs`: the subset of those
         names to produce (the others' pointers are NULL; `loss` and `loss0` each cost a pass in double per frame).  Asynchronous on torch's
-        current stream."""
+        current stream.
+        `terms` (a dragposer_amd.Terms without points; a term's `per_frame` [S,4] held for all frames or [T,S,4]): the table's terms in every
+        step's LM loss, the frame loop still in one launch -- dp_optimize_sequence_lm_terms (include/dragposer_sequence_lm_terms.h), bit for
+        bit what optimize_lm(terms=, global_pos=the running position), sequence_advance and a copy of the latent give frame by frame.  The
+        dict then also holds `loss_terms` [T,S,len(terms)] (storage may be passed; with `outputs`, only when named there).  terms=None:
+        dp_optimize_sequence_lm, unchanged."""
         from .lm import LM
 
         lm = (lm if lm is not None else LM()).check()
+        if terms is None and loss_terms is not None:
+            raise ValueError("optimize_sequence_lm: loss_terms is an output of terms=")
+        if terms is not None:
+            if terms.has_points:
+                raise ValueError("optimize_sequence_lm: a table with points does not go with the LM solver (include/dragposer_sequence_lm_terms.h, "
+                                 "\"Not covered\")")
+            terms.check()
         if ar is None and z_tgt_trace is not None:
             raise ValueError("optimize_sequence_lm: z_tgt_trace belongs to ar=")
         if ar is not None and z_tgt is not None:
@@ -679,7 +691,7 @@ class LatentOptimizer:
                  ("n_accepted", n_accepted, (T, S), torch.int32, ex), ("loss0", loss0, (T, S, 3), torch.float32, ex),
                  ("joint_pos", joint_pos, (T, S, NJ, 3), torch.float32, ex))
         if outputs is not None:
-            unknown = [n for n in outputs if n not in [sp[0] for sp in specs]]
+            unknown = [n for n in outputs if n not in [sp[0] for sp in specs] + (["loss_terms"] if terms is not None else [])]
             if unknown:
                 raise ValueError(f"optimize_sequence_lm: unknown output {unknown[0]!r}")
         for name, t, shape, dtype, struct in specs:
@@ -702,9 +714,21 @@ class LatentOptimizer:
                 outs["z_tgt_trace"] = z_tgt_trace
         p = lm.to_struct(lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot)
         lp = C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev))
-        self._call(self.lib.dp_optimize_sequence_lm, S, lp, C.byref(fr), C.byref(p), C.byref(rs) if rs is not None else None, C.byref(st), C.byref(step),
-                   C.byref(res), C.byref(ex))
-        del keep
+        if terms is None:
+            self._call(self.lib.dp_optimize_sequence_lm, S, lp, C.byref(fr), C.byref(p), C.byref(rs) if rs is not None else None, C.byref(st), C.byref(step),
+                       C.byref(res), C.byref(ex))
+            del keep
+            return outs
+        tx = _lib.DpSeqExtra()
+        if loss_terms is not None or outputs is None or "loss_terms" in outputs:
+            lt = loss_terms if loss_terms is not None else torch.empty(T, S, len(terms), dtype=torch.float32, device=dev)
+            tx.loss_terms = _check(lt, "loss_terms", (T, S, len(terms)), torch.float32, dev) if lt.numel() else None
+            outs["loss_terms"] = lt
+        own, keep_t = terms.to_struct(S, dev, steps=T)
+        tx.row_step[:len(terms)] = terms.row_steps(S)
+        self._call(self.lib.dp_optimize_sequence_lm_terms, S, lp, C.byref(fr), C.byref(p), C.byref(own), C.byref(rs) if rs is not None else None,
+                   C.byref(st), C.byref(step), C.byref(res), C.byref(ex), C.byref(tx))
+        del keep, keep_t
         return outs
 
 

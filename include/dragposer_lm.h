@@ -42,9 +42,11 @@
  * refuses (n_frames, a NULL input array).  Then DP_ERR_UNSUPPORTED from the test-only library, DP_ERR_DEVICE from a context without a
  * device image.
  *
- * Not covered: holds, gaps and tethers in the LM loss; per-frame skeletons; dp_live_step and the plug-in.  Constraint terms in the LM loss
- * are dp_optimize_lm_terms (include/dragposer_lm_terms.h: a term table's rows in [J | r], its relu bands by their active sets).  The frame loop on the device is dp_optimize_sequence_lm's (include/dragposer_sequence_lm.h): a clip in one
- * launch, the bits of this call followed by dp_sequence_advance, frame by frame.
+ * Not covered: points (include/dragposer_points.h), holds, gaps and tethers in the LM loss, per-frame skeletons, dp_live_step and the
+ * plug-in.  A term table in the LM loss is dp_optimize_lm_terms (include/dragposer_lm_terms.h: the table's rows in [J | r], its relu bands by
+ * their active sets).  The frame loop on the device is dp_optimize_sequence_lm's (include/dragposer_sequence_lm.h): a clip in one launch,
+ * the bits of this call followed by dp_sequence_advance, frame by frame -- and with a term table dp_optimize_sequence_lm_terms'
+ * (include/dragposer_sequence_lm_terms.h).
  */
 #ifndef DRAGPOSER_LM_H
 #define DRAGPOSER_LM_H

@@ -36,8 +36,9 @@
  * an active term needs); the LM parameters' values in dp_optimize_lm's order; what the batch refuses.  Then DP_ERR_UNSUPPORTED from
  * the test-only library or a library linked without the kernel, DP_ERR_DEVICE from a context without a device image.
  *
- * Not covered: points (include/dragposer_points.h), per-frame skeletons, holds, gaps, tethers, the sequence launch, dp_live_step and the
- * plug-in.
+ * Not covered: points (include/dragposer_points.h), holds, gaps and tethers in the LM loss, per-frame skeletons, dp_live_step and the
+ * plug-in.  The frame loop on the device with the table is dp_optimize_sequence_lm_terms' (include/dragposer_sequence_lm_terms.h): a clip in
+ * one launch, the bits of this call followed by dp_sequence_advance, frame by frame.
  */
 #ifndef DRAGPOSER_LM_TERMS_H
 #define DRAGPOSER_LM_TERMS_H

@@ -45,8 +45,8 @@
  * coeffs or bias, state->history < order, a non-NULL frames->z_tgt -- "both"); without `ar`, a NULL frames->z_tgt -- "neither".  Then
  * DP_ERR_UNSUPPORTED from the test-only library or a library linked without dp_lm_seq.hip, DP_ERR_DEVICE from a context without a device image.
  *
- * Not covered: what include/dragposer_lm.h does not cover -- constraint terms, holds, gaps and tethers in the LM loss, per-frame skeletons,
- * dp_live_step and the plug-in.
+ * Not covered: points (include/dragposer_points.h), holds, gaps and tethers in the LM loss, per-frame skeletons, dp_live_step and the
+ * plug-in.  A term table in the LM loss of a clip is dp_optimize_sequence_lm_terms (include/dragposer_sequence_lm_terms.h).
  */
 #ifndef DRAGPOSER_SEQUENCE_LM_H
 #define DRAGPOSER_SEQUENCE_LM_H
