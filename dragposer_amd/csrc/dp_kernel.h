@@ -89,6 +89,7 @@ extern "C" int dp_kernel_lds_bytes(void);
 // dp_w4.hip: wave-private kernel, 4 frames per wave, no workgroup barrier inside the loop
 extern "C" hipError_t dp_launch_w4(const KArgs* args, hipStream_t stream, LaunchPick* pick /* nullable */);
 extern "C" hipError_t dp_launch_w4_bp(const KArgs* args, hipStream_t stream, LaunchPick* pick); // body-part layout (dp_w4_bp.hip)
+extern "C" hipError_t dp_launch_w4_bp_lv(const KArgs* args, hipStream_t stream, LaunchPick* pick); // ... its fixed-count optimising launches (dp_w4_bp_lv.hip; called by dp_launch_w4_bp)
 // dp_w4_skel.hip / dp_w4_bp_skel.hip: the same two layouts with the bone offsets read per frame from KArgs::skel (dp_w4_impl.h: W4_SKEL)
 extern "C" hipError_t dp_launch_w4sk(const KArgs* args, hipStream_t stream, LaunchPick* pick);
 extern "C" hipError_t dp_launch_w4sk_bp(const KArgs* args, hipStream_t stream, LaunchPick* pick);

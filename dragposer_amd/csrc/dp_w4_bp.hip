@@ -18,6 +18,8 @@ extern "C" hipError_t dp_launch_w4_bp(const KArgs* args, hipStream_t stream, Lau
     } else if (args->early_stop && args->mode == 0) {
         if (lng) w4_launch<NW, true, false, true>(args, stream, pick);
         else w4_launch<NW, true>(args, stream, pick);
+    } else if (args->mode == 0 && !(DBG_DUMP && args->dbg)) {
+        return dp_launch_w4_bp_lv(args, stream, pick); // fixed-count optimising launches: the kernel with the loop versions (dp_w4_bp_lv.hip)
     } else {
         if (lng) w4_launch<NW, false, false, true>(args, stream, pick);
         else w4_launch<NW, false>(args, stream, pick);
