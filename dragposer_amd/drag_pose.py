@@ -67,6 +67,35 @@ def _points_alone(terms, who, **layers):
                 raise ValueError(f"DragPose.{who}: a table with points does not go with {name}= (include/dragposer_points.h, Not in)")
 
 
+def _tracker_rows(trk, tp, tR):
+    """E, the trackers of `trk`, after checking that the sparse targets [..., E, 3] / [..., E, 9] have one row each"""
+    E = trk["mj"].numel()
+    if tp.shape[-2] != E or tR.shape[-2] != E:
+        raise ValueError("target_ee_pos / target_ee_rot / weights_joints must have one row per entry of mask_joints")
+    return E
+
+
+def _adjust(trk, joint_adjustment_indices, joint_adjustment_weight):
+    """run()'s / run_frames()'s joint adjustment as the launches take it: (joint, target joint, weight) or None"""
+    if joint_adjustment_indices is None:
+        return None
+    joint_index, ee_index = joint_adjustment_indices
+    return (int(joint_index), int(trk["mj_host"][ee_index]), float(joint_adjustment_weight))
+
+
+def _dense(trk, rows, fill=torch.zeros):
+    """[T,S,E,...] rows in tracker-list order -> [T,S,22,...] per joint, the joints that are no trackers filled by `fill`"""
+    dense = fill(rows.shape[:2] + (NJ,) + rows.shape[3:], dtype=rows.dtype, device=rows.device)
+    return dense.index_copy_(2, trk["mj"], rows)
+
+
+def _check_rows(terms, T, S):
+    """a clip of T frames takes a term's `per_frame` as [S,4], held for all frames, or [T,S,4]"""
+    for i, term in enumerate(terms.terms):
+        if term.per_frame is not None and term.per_frame.dim() == 3 and int(term.per_frame.shape[0]) != T:
+            raise ValueError(f"Terms: term {i}: per_frame must be [{S},4] or [{T},{S},4], got {tuple(term.per_frame.shape)}")
+
+
 class DragPose:
     def __init__(self, generator_model, temporal_model, means_latent, stds_latent, device=None, device_gpu=None, n_sequences=1,
                  offsets=None, native_temporal=False, native_encoder=False):
@@ -300,10 +329,33 @@ class DragPose:
         with one workgroup per sequence (include/dragposer.h: dp_temporal_status)"""
         return self._native_temporal.status() if self._native_temporal is not None else 0
 
+    def _stretches(self, T, lambda_temporal, temporal_future_window):
+        """A clip of T frames cut into the stretches between two temporal predictions: yields (t, n, z_tgt, strides, lambda_tmp) for one launch
+        of frames t .. t + n each.  The reference predicts at current_index == 0 whatever lambda_temporal is (drag_pose.py:235-291), so the
+        stretches are cut the same way with the pull term on or off; without a predictor there is nothing to pull towards, the clip is one
+        stretch and the term is off, in run() and here alike (the reference cannot run without one).  The order is behaviour: the prediction
+        is made right before its stretch is yielded, from the history buffers the launch before it advanced, and current_index moves when the
+        caller comes back for the next stretch -- after its launch has returned, and not at all when that raised."""
+        have = self.temporal is not None
+        lambda_tmp = float(lambda_temporal) if have and float(lambda_temporal) != 0.0 else 0.0
+        window = int(temporal_future_window)
+        zero_tgt = torch.zeros(self.S, LATENT, device=self.device)
+        t = 0
+        while t < T:
+            if have:  # frames up to the next prediction (a prediction every `window` frames; every frame when window = 0)
+                self._temporal_targets(window)
+                n = min(T - t, max(window, 1) - self.current_index)
+                z_tgt, strides = self.target_latent_buffer[:, self.current_index:], (LATENT, (window + 1) * LATENT)
+            else:
+                n, z_tgt, strides = T - t, zero_tgt, (0, LATENT)
+            yield t, n, z_tgt, strides, lambda_tmp
+            t += n
+            self.current_index = 0 if window == 0 else (self.current_index + n) % window
+
     def run_frames(self, target_ee_pos, target_ee_rot, mask_joints, weights_joints, target_root=None, stop_eps_pos=1e-2, stop_eps_rot=1e-2,
                    max_iter=100, min_loss_incr=0.00001, learning_rate=1e-3, lambda_rot=1, lambda_temporal=1, temporal_future_window=60,
                    height_indices=(0, 4, 8, 13, 17, 21), joint_adjustment_indices=None, joint_adjustment_weight=0.01, offsets=None,
-                   constraints=None, terms=None, holds=None, ar=None, gaps=None, present=None, tethers=None, solver=None):
+                   constraints=None, terms=None, holds=None, ar=None, gaps=None, present=None, tethers=None, solver=None, _live=False):
         """T consecutive frames of every sequence -- T calls of run() -- with the frame loop on the device: one kernel launch per
         stretch of frames between two temporal predictions (all T of them when there is no predictor or lambda_temporal is 0).
         target_ee_pos [T,S,E,3], target_ee_rot [T,S,E,3,3]; `target_root` [T,S,3] or None: given, the position targets of frame t
@@ -377,18 +429,10 @@ class DragPose:
         tp = tp.reshape(T, S, -1, 3)
         tR = torch.as_tensor(target_ee_rot, dtype=torch.float32, device=dev).reshape(T, S, -1, 9)
         trk = self._trackers(mask_joints, weights_joints)
-        E = trk["mj"].numel()
-        if tp.shape[2] != E or tR.shape[2] != E:
-            raise ValueError("target_ee_pos / target_ee_rot / weights_joints must have one row per entry of mask_joints")
-        dense_p = torch.zeros(T, S, NJ, 3, device=dev)
-        dense_r = torch.zeros(T, S, NJ, 9, device=dev)
-        dense_p.index_copy_(2, trk["mj"], tp)
-        dense_r.index_copy_(2, trk["mj"], tR)
+        E = _tracker_rows(trk, tp, tR)
+        dense_p, dense_r = _dense(trk, tp), _dense(trk, tR)
         root = torch.as_tensor(target_root, dtype=torch.float32, device=dev).reshape(T, S, 3).contiguous() if target_root is not None else None
-        adjust = None
-        if joint_adjustment_indices is not None:
-            joint_index, ee_index = joint_adjustment_indices
-            adjust = (int(joint_index), int(trk["mj_host"][ee_index]), float(joint_adjustment_weight))
+        adjust = _adjust(trk, joint_adjustment_indices, joint_adjustment_weight)
         poses = torch.empty(T, S, 88, device=dev)
         gpos = torch.empty(T, S, 3, device=dev)
         iters = torch.empty(T, S, dtype=torch.int32, device=dev)
@@ -399,9 +443,7 @@ class DragPose:
         with_terms = constraints is not None or terms is not None
         if with_terms:
             if terms is not None:
-                for i, term in enumerate(terms.terms):
-                    if term.per_frame is not None and term.per_frame.dim() == 3 and int(term.per_frame.shape[0]) != T:
-                        raise ValueError(f"Terms: term {i}: per_frame must be [{S},4] or [{T},{S},4], got {tuple(term.per_frame.shape)}")
+                _check_rows(terms, T, S)
             key, width = ("loss_extra", 4) if terms is None else ("loss_terms", len(terms))
             self.last_terms = torch.empty(T, S, width, device=dev)
             self.last_joint_pos = torch.empty(T, S, NJ, 3, device=dev)
@@ -420,69 +462,42 @@ class DragPose:
                 here = torch.as_tensor(present, device=dev).reshape(T, S, -1)
                 if here.shape[2] != E:
                     raise ValueError("present must have one entry per entry of mask_joints")
-                dense_here = torch.ones(T, S, NJ, dtype=torch.uint8, device=dev)
-                dense_here.index_copy_(2, trk["mj"], (here != 0).to(torch.uint8))
-
-        def gap_kw(t0, n):
-            """the stretch's share of the gaps' arguments"""
-            if gaps is None:
-                return {}
-            return dict(gaps=gaps, gap_state=self.gap_state, present=dense_here[t0:t0 + n] if dense_here is not None else None,
-                        gap_trace=self.last_gap_trace[t0:t0 + n])
+                dense_here = _dense(trk, (here != 0).to(torch.uint8), fill=torch.ones)
 
         def extra(t0, n):
-            """the stretch's share of the terms' arguments: the table's rows and the per-step outputs of frames t0 .. t0 + n"""
-            if not with_terms:
-                return gap_kw(t0, n)
-            kw = {"constraints": constraints, "terms": terms.frames(t0, t0 + n) if terms is not None else None,
-                  key: self.last_terms[t0:t0 + n], "joint_pos": self.last_joint_pos[t0:t0 + n]}
+            """the stretch's share of the layers' arguments: the table's rows, the per-step outputs and traces of frames t0 .. t0 + n"""
+            kw = {}
+            if with_terms:
+                kw = {"constraints": constraints, "terms": terms.frames(t0, t0 + n) if terms is not None else None,
+                      key: self.last_terms[t0:t0 + n], "joint_pos": self.last_joint_pos[t0:t0 + n]}
             if holds is not None:
                 kw.update(holds=holds, hold_state=self.hold_state, hold_trace=self.last_hold_trace[t0:t0 + n])
             if tethers is not None:
                 kw.update(tethers=tethers, tether_state=self.tether_state, tether_trace=self.last_tether_trace[t0:t0 + n])
-            kw.update(gap_kw(t0, n))
+            if gaps is not None:  # (`_live`: run(live=True)'s one frame, which the gap unit runs as ONE launch)
+                kw.update(gaps=gaps, gap_state=self.gap_state, present=dense_here[t0:t0 + n] if dense_here is not None else None,
+                          gap_trace=self.last_gap_trace[t0:t0 + n], live=_live)
             return kw
 
-        if ar is not None:  # one launch, no stretches: the targets come from inside it
-            kw = extra(0, T)
-            kw.pop("constraints", None)
-            o = self.opt.optimize_sequence(self.latent, dense_p, dense_r, root, trk["w"], trk["tracked"], None, (0, 0), self.current_global_pos,
-                                       self.current_global_rot, self.latent_buffer, self.displacement_buffer, self.heights_buffer,
-                                       tuple(int(h) for h in height_indices), n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot),
-                                       lambda_tmp=float(lambda_temporal), stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot,
-                                       min_loss_incr=min_loss_incr, adjust=adjust, pose_ret=poses, pos_ret=gpos, iters=iters, status=status,
-                                       offsets=skel, ar=ar, z_tgt_trace=self.last_z_tgt, **kw)
-            self.last_loss = o["loss"]  # [T,S,3] (the third: lambda_temporal times the pull towards last_z_tgt)
-            self.last_status = status
-            return poses, gpos, iters
+        # last_loss [T,S,3] of run_frames(gaps=) is filled stretch by stretch; run_frames(ar=)'s is the one its single launch allocates
+        loss = torch.empty(T, S, 3, device=dev) if gaps is not None and ar is None else None
 
-        # The reference predicts at current_index == 0 whatever lambda_temporal is (drag_pose.py:235-291), so the stretches between two
-        # predictions are cut the same way with the pull term on or off; without a predictor there is nothing to pull towards and the
-        # term is off in run() and here alike (the reference cannot run without one).
-        have = self.temporal is not None
-        pull = have and float(lambda_temporal) != 0.0
-        window = int(temporal_future_window)
-        zero_tgt = torch.zeros(S, LATENT, device=dev)
-        loss = torch.empty(T, S, 3, device=dev) if gaps is not None else None  # (last_loss of run_frames(gaps=), as of run_frames(ar=))
-        t = 0
-        while t < T:
-            if have:  # frames up to the next prediction (a prediction every `window` frames; every frame when window = 0)
-                self._temporal_targets(window)
-                n = min(T - t, max(window, 1) - self.current_index)
-                z_tgt, strides = self.target_latent_buffer[:, self.current_index:], (LATENT, (window + 1) * LATENT)
-            else:
-                n, z_tgt, strides = T - t, zero_tgt, (0, LATENT)
-            self.opt.optimize_sequence(self.latent, dense_p[t:t + n], dense_r[t:t + n], root[t:t + n] if root is not None else None,
-                                       trk["w"], trk["tracked"], z_tgt, strides, self.current_global_pos, self.current_global_rot,
-                                       self.latent_buffer, self.displacement_buffer, self.heights_buffer, tuple(int(h) for h in height_indices),
-                                       n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=float(lambda_temporal) if pull else 0.0,
-                                       stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, adjust=adjust,
-                                       pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n], offsets=skel,
-                                       loss=loss[t:t + n] if loss is not None else None, **extra(t, n))
-            t += n
-            self.current_index = 0 if window == 0 else (self.current_index + n) % window
+        def launch(t, n, z_tgt, strides, lambda_tmp, **kw):
+            return self.opt.optimize_sequence(self.latent, dense_p[t:t + n], dense_r[t:t + n], root[t:t + n] if root is not None else None,
+                                              trk["w"], trk["tracked"], z_tgt, strides, self.current_global_pos, self.current_global_rot,
+                                              self.latent_buffer, self.displacement_buffer, self.heights_buffer, tuple(int(h) for h in height_indices),
+                                              n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=lambda_tmp,
+                                              stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, adjust=adjust,
+                                              pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n], offsets=skel,
+                                              loss=loss[t:t + n] if loss is not None else None, **extra(t, n), **kw)
+
+        if ar is not None:  # one launch, no stretches: the targets come from inside it; the loss's third part is lambda_temporal times the pull towards last_z_tgt
+            loss = launch(0, T, None, (0, 0), float(lambda_temporal), ar=ar, z_tgt_trace=self.last_z_tgt)["loss"]
+        else:
+            for stretch in self._stretches(T, lambda_temporal, temporal_future_window):
+                launch(*stretch)
         self.last_status = status  # [T,S] DP_STATUS_* bits (include/dragposer.h): non-zero where a frame's inputs were not finite
-        if gaps is not None:
+        if loss is not None:
             self.last_loss = loss
         return poses, gpos, iters
 
@@ -492,9 +507,7 @@ class DragPose:
         dp_optimize_sequence_lm_terms); with a predictor, one launch"""
         dev, S, T = self.device, self.S, int(dense_p.shape[0])
         if terms is not None:
-            for i, term in enumerate(terms.terms):
-                if term.per_frame is not None and term.per_frame.dim() == 3 and int(term.per_frame.shape[0]) != T:
-                    raise ValueError(f"Terms: term {i}: per_frame must be [{S},4] or [{T},{S},4], got {tuple(term.per_frame.shape)}")
+            _check_rows(terms, T, S)
             self.last_terms = torch.empty(T, S, len(terms), device=dev)
         loss = torch.empty(T, S, 3, device=dev)
         self.last_joint_pos = torch.empty(T, S, NJ, 3, device=dev)
@@ -517,21 +530,8 @@ class DragPose:
             self.last_z_tgt = torch.zeros(T, S, LATENT, device=dev)
             launch(0, T, None, (0, 0), float(lambda_temporal), ar=solver.predictor, z_tgt_trace=self.last_z_tgt)
         else:  # (the stretches of run_frames, cut as for Adam)
-            have = self.temporal is not None
-            pull = have and float(lambda_temporal) != 0.0
-            window = int(temporal_future_window)
-            zero_tgt = torch.zeros(S, LATENT, device=dev)
-            t = 0
-            while t < T:
-                if have:
-                    self._temporal_targets(window)
-                    n = min(T - t, max(window, 1) - self.current_index)
-                    z_tgt, strides = self.target_latent_buffer[:, self.current_index:], (LATENT, (window + 1) * LATENT)
-                else:
-                    n, z_tgt, strides = T - t, zero_tgt, (0, LATENT)
-                launch(t, n, z_tgt, strides, float(lambda_temporal) if pull else 0.0)
-                t += n
-                self.current_index = 0 if window == 0 else (self.current_index + n) % window
+            for stretch in self._stretches(T, lambda_temporal, temporal_future_window):
+                launch(*stretch)
         self.last_status = status
         self.last_loss = loss
         return poses, gpos, iters
@@ -619,14 +619,11 @@ class DragPose:
                             min_loss_incr=min_loss_incr, learning_rate=learning_rate, lambda_rot=lambda_rot, lambda_temporal=lambda_temporal,
                             temporal_future_window=temporal_future_window, height_indices=height_indices,
                             joint_adjustment_indices=joint_adjustment_indices, joint_adjustment_weight=joint_adjustment_weight,
-                            constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, present=present)
+                            constraints=constraints, terms=terms, holds=holds, ar=ar, gaps=gaps, present=present,
+                            _live=bool(live))  # (run_frames of this one frame: optimize_sequence(live=) launches dp_live_step)
             if tethers is not None:  # (tethered terms read this frame's state rows; the update follows the frame)
                 kw_frame["terms"] = tethers.frame_terms(terms, self.tether_state)
-            self.opt.live_step = bool(live)  # (run_frames of this one frame: optimize_sequence launches dp_live_step)
-            try:
-                ret = self._run_ar(target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose, kw_frame)
-            finally:
-                self.opt.live_step = False
+            ret = self._run_ar(target_ee_pos, target_ee_rot, mask_joints, weights_joints, out_pose, out_pos, verbose, kw_frame)
             if tethers is not None:
                 tethers.update(terms, self.tether_state, self.last_joint_pos[0], self.current_global_pos)
             return ret
@@ -643,9 +640,7 @@ class DragPose:
         tp = torch.as_tensor(target_ee_pos, dtype=torch.float32, device=dev).reshape(S, -1, 3)
         tR = torch.as_tensor(target_ee_rot, dtype=torch.float32, device=dev).reshape(S, -1, 9)
         trk = self._trackers(mask_joints, weights_joints)
-        E = trk["mj"].numel()
-        if tp.shape[1] != E or tR.shape[1] != E:
-            raise ValueError("target_ee_pos / target_ee_rot / weights_joints must have one row per entry of mask_joints")
+        _tracker_rows(trk, tp, tR)
 
         self._temporal_targets(temporal_future_window)
         trk["tgt_pos"].index_copy_(1, trk["mj"], tp)
@@ -654,10 +649,7 @@ class DragPose:
         # one frame = a whole-sequence launch of one step (dp_optimize_sequence): the optimise loop AND run()'s epilogue
         # (drag_pose.py:369-402) in one kernel, the same one run_frames() uses for stretches of frames -- so cutting a sequence into
         # calls of run() or handing it to run_frames() whole gives the same bits
-        adjust = None
-        if joint_adjustment_indices is not None:
-            joint_index, ee_index = joint_adjustment_indices
-            adjust = (int(joint_index), int(trk["mj_host"][ee_index]), float(joint_adjustment_weight))
+        adjust = _adjust(trk, joint_adjustment_indices, joint_adjustment_weight)
         pose = out_pose if out_pose is not None else torch.empty(S, 88, device=dev)
         gpos = out_pos if out_pos is not None else torch.empty(S, 3, device=dev)
         self._flip ^= 1  # two result sets, alternated: `last` stays valid while the next frame runs
@@ -684,12 +676,18 @@ class DragPose:
                                    status=o["status"], offsets=skel)
         o["z"].copy_(self.latent)  # (self.latent is advanced in place by the next frame; `last` must not move with it)
         self.last = dict(iters=o["iters"][0], loss=o["loss"][0], z=o["z"], pose=pose, pos=gpos, status=o["status"][0])
+        return self._end_frame(pose, gpos, verbose, squeeze, temporal_future_window)
+
+    def _end_frame(self, pose, gpos, verbose, squeeze, window=None):
+        """a frame's tail, `last` being set: the reference's printed line, current_index one frame on (`window` None: whoever ran the frame has
+        moved it) and what run() returns -- without the sequence dimension for a single sequence that came without one"""
         if verbose:
             l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
             print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "
                   f"Loss Temporal: {l[:, 2].mean():.5f} // Iter: {it.float().mean():.1f}")
-        self.current_index = 0 if temporal_future_window == 0 else (self.current_index + 1) % temporal_future_window
-        if squeeze and S == 1:
+        if window is not None:
+            self.current_index = 0 if window == 0 else (self.current_index + 1) % window
+        if squeeze and self.S == 1:
             return pose[0], gpos[0]
         return pose, gpos
 
@@ -710,13 +708,7 @@ class DragPose:
             self.last["z_tgt"] = self.last_z_tgt[0]
         if kw.get("gaps") is not None:
             self.last["gap_trace"] = self.last_gap_trace[0]
-        if verbose:
-            l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
-            print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "
-                  f"Loss Temporal: {l[:, 2].mean():.5f} // Iter: {it.float().mean():.1f}")
-        if squeeze and S == 1:
-            return pose[0], gpos[0]
-        return pose, gpos
+        return self._end_frame(pose, gpos, verbose, squeeze)  # (run_frames has moved current_index)
 
     def _run_lm(self, solver, trk, o, pose, gpos, adjust, height_indices, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, window, verbose, squeeze,
                 terms=None):
@@ -744,14 +736,7 @@ class DragPose:
                          loss0=fr["loss0"], joint_pos=fr["pos"])
         if terms is not None:
             self.last["loss_terms"] = got["loss_terms"]
-        if verbose:
-            l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
-            print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "
-                  f"Loss Temporal: {l[:, 2].mean():.5f} // Iter: {it.float().mean():.1f}")
-        self.current_index = 0 if window == 0 else (self.current_index + 1) % window
-        if squeeze and S == 1:
-            return pose[0], gpos[0]
-        return pose, gpos
+        return self._end_frame(pose, gpos, verbose, squeeze, window)
 
     def _run_constrained(self, constraints, trk, o, pose, gpos, adjust, height_indices, max_iter, learning_rate, lambda_rot, lambda_tmp,
                          stop_eps_pos, stop_eps_rot, min_loss_incr, window, verbose, squeeze, holds=None, skel=None):
@@ -788,11 +773,4 @@ class DragPose:
         self.last[key] = fr[key]
         if table:
             self.last["joint_pos"] = fr["pos"]  # [S,22,3] P_j of the frame (world: the current_global_pos before the call + P_j)
-        if verbose:
-            l, it = self.last["loss"].cpu(), self.last["iters"].cpu()
-            print(f"Loss sqrt(Pos): {l[:, 0].sqrt().mean():.5f} // Loss Rot: {l[:, 1].mean():.5f} // "
-                  f"Loss Temporal: {l[:, 2].mean():.5f} // Iter: {it.float().mean():.1f}")
-        self.current_index = 0 if window == 0 else (self.current_index + 1) % window
-        if squeeze and S == 1:
-            return pose[0], gpos[0]
-        return pose, gpos
+        return self._end_frame(pose, gpos, verbose, squeeze, window)

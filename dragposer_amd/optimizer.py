@@ -51,6 +51,143 @@ def _check(t, name, shape, dtype, device):
     return t.data_ptr()
 
 
+def _traced(trace, shape, dtype, device):
+    """a layer's `*_trace` argument: True means a zeroed tensor allocated here"""
+    return torch.zeros(shape, dtype=dtype, device=device) if trace is True else trace
+
+
+_TERMS_NEED_GLOBAL_POS = "optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]"
+
+
+def _own_output(name, width, B, dev, out, tensors, global_pos, gp_error, wanted=True):
+    """What the launches with extra loss terms share: their per-frame output `name` [B, width] (from `out` or allocated here, registered in
+    `tensors`; not `wanted`: none) and the root positions some terms need (`gp_error`: what to say when those are missing, or None).
+    -> (global_pos's pointer or None, the output's pointer or None)"""
+    t = None
+    if wanted:
+        t = out[name] if out is not None and name in out else torch.empty(B, width, dtype=torch.float32, device=dev)
+        tensors[name] = t
+    gp = None
+    if global_pos is not None:
+        gp = _check(global_pos, "global_pos", (B, 3), torch.float32, dev)
+    elif gp_error:
+        raise ValueError(gp_error)
+    return gp, _check(t, name, (B, width), torch.float32, dev) if t is not None and width else None
+
+
+def _seq_state(S, global_pos, global_rot, latent_buf, disp_buf, heights_buf, height_joints, adjust, dev):
+    """-> (dp_seq_state, dp_seq_step with its adjust_* words) of S sequences, every tensor checked; `adjust` = (joint, target_joint, weight) or None"""
+    H, NH = int(latent_buf.shape[1]), len(height_joints)
+    st = _lib.DpSeqState()
+    st.global_pos = _check(global_pos, "global_pos", (S, 3), torch.float32, dev)
+    st.global_rot = _check(global_rot, "global_rot", (S, 4), torch.float32, dev)
+    st.latent_buf = _check(latent_buf, "latent_buf", (S, H, LATENT), torch.float32, dev)
+    st.disp_buf = _check(disp_buf, "disp_buf", (S, H, 3), torch.float32, dev)
+    st.heights_buf = _check(heights_buf, "heights_buf", (S, H, NH), torch.float32, dev)
+    st.history, st.n_heights = H, NH
+    for i, j in enumerate(height_joints):
+        st.height_joints[i] = int(j)
+    step = _lib.DpSeqStep()
+    step.adjust_joint = -1
+    if adjust is not None:
+        step.adjust_joint, step.adjust_target_joint, step.adjust_weight = int(adjust[0]), int(adjust[1]), float(adjust[2])
+    return st, step
+
+
+def _step_outputs(specs, res, scratch, scratch_shape, dev, outputs=None):
+    """The per-step results of a whole-sequence launch.  `specs`: (name, given, shape, dtype, struct) per output -- storage the caller gave is
+    used and means the output is produced; any other output is allocated here when `outputs` (None: all) names it, and its pointer stays NULL
+    otherwise.  `scratch` (given or allocated) becomes res.hist_scratch.  -> ({name: tensor} of what is produced, the scratch: the caller keeps it
+    alive until it has launched)"""
+    outs = {}
+    for name, t, shape, dtype, struct in specs:
+        if outputs is not None and name not in outputs and t is None:
+            continue
+        t = t if t is not None else torch.empty(shape, dtype=dtype, device=dev)
+        setattr(struct, name, _check(t, name, shape, dtype, dev))
+        outs[name] = t
+    scratch = scratch if scratch is not None else torch.empty(scratch_shape, device=dev)
+    res.hist_scratch = _check(scratch, "scratch", scratch_shape, torch.float32, dev)
+    return outs, scratch
+
+
+# optimize_sequence's layers above the term table, lowest rung of the ladder first.  Per layer: its argument; its trace's argument, shape after
+# [T,S] and dtype; the entry point that takes the layers up to it; and (its struct, what that keeps alive) from the call's arguments `a` and the trace.
+_SEQ_LAYERS = (
+    ("holds", "hold_trace", lambda a: (len(a["holds"]), 4), torch.float32, "dp_optimize_sequence_holds",
+     lambda a, trace: a["holds"].to_struct(a["terms"], a["S"], a["dev"], a["hold_state"], trace, steps=a["T"])),
+    ("ar", "z_tgt_trace", lambda a: (LATENT,), torch.float32, "dp_optimize_sequence_ar",
+     lambda a, trace: a["ar"].to_struct(a["dev"], trace, (a["T"], a["S"], LATENT))),
+    ("gaps", "gap_trace", lambda a: (NJ,), torch.uint8, "dp_optimize_sequence_gaps",  # (dp_live_step with live=: the same rung in one launch)
+     lambda a, trace: (a["gaps"].to_struct(a["S"], a["dev"], a["gap_state"], a["present"], trace, steps=a["T"]), None)),
+    ("tethers", "tether_trace", lambda a: (len(a["tethers"]), 8), torch.float32, "dp_optimize_sequence_tethers",
+     lambda a, trace: a["tethers"].to_struct(a["terms"], a["S"], a["dev"], a["tether_state"], trace, steps=a["T"], holds=a["holds"])),
+)
+
+
+def _sequence_refusals(tgt_pos, latent_buf, z_tgt, constraints, terms, loss_extra, loss_terms, joint_pos, holds, hold_state, hold_trace, ar, z_tgt_trace,
+                       gaps, gap_state, present, gap_trace, live, tethers, tether_state, tether_trace):
+    """what optimize_sequence refuses of a combination of layers, before it touches the library; -> `terms` (an empty table where `gaps` or `ar`
+    came without one)"""
+    if terms is not None and terms.has_points:
+        for name, given in (("holds", holds is not None), ("gaps", gaps is not None), ("ar", ar is not None), ("tethers", tethers is not None),
+                            ("live", live)):
+            if given:
+                raise ValueError(f"optimize_sequence: a table with points does not go with {name}= (include/dragposer_points.h, Not in)")
+    if tethers is None and (tether_state is not None or tether_trace is not None):
+        raise ValueError("optimize_sequence: tether_state / tether_trace belong to tethers=")
+    if tethers is not None:
+        if live:
+            raise ValueError("optimize_sequence: tethers= are not part of dp_live_step (include/dragposer_tethers.h, Not covered)")
+        if terms is None or constraints is not None:
+            raise ValueError("optimize_sequence: tethers= refer to a table, pass terms= (Terms.from_constraints turns constraints into one)")
+        if gaps is None:
+            raise ValueError("optimize_sequence: tethers= is dp_optimize_sequence_gaps with tethers, pass gaps= (Gaps(0, 1.0) for none to hold)")
+        if tether_state is None:
+            raise ValueError("optimize_sequence: tethers= needs tether_state [S,len(tethers),8]")
+        tethers.check(terms, holds)
+    if live and gaps is None:
+        raise ValueError("optimize_sequence: live= is the one-launch form of gaps= (pass Gaps(0, 1.0) for none to hold)")
+    if live and int(tgt_pos.shape[0]) != 1:
+        raise ValueError("optimize_sequence: live= is one frame, tgt_pos holds " + str(int(tgt_pos.shape[0])))
+    if gaps is None and (gap_state is not None or present is not None or gap_trace is not None):
+        raise ValueError("optimize_sequence: gap_state / present / gap_trace belong to gaps=")
+    if gaps is not None:
+        gaps.check()
+        if gap_state is None:
+            raise ValueError("optimize_sequence: gaps= needs gap_state [S,22,16]")
+        if constraints is not None:
+            raise ValueError("optimize_sequence: gaps= takes a table, pass terms= (Terms.from_constraints turns constraints into one)")
+        if terms is None:
+            from .terms import Terms
+
+            terms = Terms()
+    if ar is None and z_tgt_trace is not None:
+        raise ValueError("optimize_sequence: z_tgt_trace belongs to ar=")
+    if ar is not None:
+        if z_tgt is not None:
+            raise ValueError("optimize_sequence: ar= forms the targets itself, pass z_tgt=None")
+        if constraints is not None:
+            raise ValueError("optimize_sequence: ar= takes a table, pass terms= (Terms.from_constraints turns constraints into one)")
+        if ar.order > int(latent_buf.shape[1]):
+            raise ValueError(f"optimize_sequence: latent_buf holds {int(latent_buf.shape[1])} rows, fewer than ar.order = {ar.order}")
+        if terms is None:
+            from .terms import Terms
+
+            terms = Terms()
+    if holds is not None and (terms is None or constraints is not None):
+        raise ValueError("optimize_sequence: holds= refer to a table, pass terms= (Terms.from_constraints turns constraints into one)")
+    if holds is None and (hold_state is not None or hold_trace is not None):
+        raise ValueError("optimize_sequence: hold_state / hold_trace belong to holds=")
+    if holds is not None and hold_state is None:
+        raise ValueError("optimize_sequence: holds= needs hold_state [S,len(holds),4]")
+    if constraints is not None and terms is not None:
+        raise ValueError("optimize_sequence: pass constraints or terms, not both")
+    if constraints is None and terms is None and (loss_extra is not None or loss_terms is not None or joint_pos is not None):
+        raise ValueError("optimize_sequence: loss_extra / loss_terms / joint_pos are outputs of constraints= / terms=")
+    return terms
+
+
 class LaunchPlan:
     """A dp_optimize call with its arguments already checked and marshalled (LatentOptimizer.plan).  Holds the input and result
     tensors alive; `plan()` launches on torch's current stream of the optimiser's device and returns the result tensors."""
@@ -77,7 +214,6 @@ class LatentOptimizer:
 
     def __init__(self, model_path=DEFAULT_MODEL, device="cuda:0", weight_dtype="fp32", arrays=None, _lib_path=None):
         self.lib = _lib.load(_lib_path)  # (_lib_path: tests only -- the second implementation kept for cross-checks)
-        self.live_step = False  # DragPose.run(live=True) sets it for its one call: optimize_sequence(gaps=) of one frame is then dp_live_step
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("LatentOptimizer needs a ROCm device (cuda:N); there is no CPU fallback")
@@ -265,14 +401,7 @@ class LatentOptimizer:
         p = self._params(*pargs)
         names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS)
         res, tensors = self._outputs(B, [n for n in names if n != extra], out)
-        t = out[extra] if out is not None and extra in out else torch.empty(B, width, dtype=torch.float32, device=dev)
-        tensors[extra] = t
-        gp = None
-        if global_pos is not None:
-            gp = _check(global_pos, "global_pos", (B, 3), torch.float32, dev)
-        elif gp_error:
-            raise ValueError(gp_error)
-        s, keep = to_struct(gp, _check(t, extra, (B, width), torch.float32, dev) if width else None)
+        s, keep = to_struct(*_own_output(extra, width, B, dev, out, tensors, global_pos, gp_error))
         self._call(fn, C.byref(batch), C.byref(p), C.byref(s), *mid, *(() if skel is None else (C.byref(skel),)), C.byref(res))
         del keep
         return tensors
@@ -315,7 +444,7 @@ class LatentOptimizer:
             fn, (z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked),
             (n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, max_trackers), global_pos, outputs, out,
             validate_targets, "loss_terms", len(terms),
-            "optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]" if terms.needs_global_pos else None,
+            _TERMS_NEED_GLOBAL_POS if terms.needs_global_pos else None,
             lambda gp, lt: terms.to_struct(int(z0.shape[0]), self.device, gp, lt), skel=skel, mid=mid)
 
     def optimize_lm(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, lm=None, lambda_rot=1.0, lambda_tmp=0.02, mu=None, stop_eps_pos=0.0,
@@ -355,16 +484,8 @@ class LatentOptimizer:
         if terms.has_points:
             raise ValueError("optimize_lm: a table with points does not go with the LM solver (include/dragposer_lm_terms.h, \"Not covered\")")
         terms.check()
-        gp = None
-        if global_pos is not None:
-            gp = _check(global_pos, "global_pos", (B, 3), torch.float32, dev)
-        elif terms.needs_global_pos:
-            raise ValueError("optimize_terms: an active PLANE or point-DISTANCE term needs global_pos [B,3]")
-        lt = None
-        if outputs is None or "loss_terms" in names:
-            lt = out["loss_terms"] if out is not None and "loss_terms" in out else torch.empty(B, len(terms), dtype=torch.float32, device=dev)
-            tensors["loss_terms"] = lt
-        s, keep = terms.to_struct(B, dev, gp, _check(lt, "loss_terms", (B, len(terms)), torch.float32, dev) if lt is not None and len(terms) else None)
+        s, keep = terms.to_struct(B, dev, *_own_output("loss_terms", len(terms), B, dev, out, tensors, global_pos,
+                                                       _TERMS_NEED_GLOBAL_POS if terms.needs_global_pos else None, wanted=outputs is None or "loss_terms" in names))
         self._call(self.lib.dp_optimize_lm_terms, C.byref(batch), C.byref(p), C.byref(s), C.byref(res), C.byref(ex))
         del keep
         return tensors
@@ -417,20 +538,8 @@ class LatentOptimizer:
         for name in ("z_pre", "pose", "disp", "world_disp", "world_rot", "pos"):
             shape, dtype = _OUT_SPECS[name]
             setattr(res, name, _check(frame[name], name, (S,) + shape, dtype, dev))
-        H, NH = int(latent_buf.shape[1]), len(height_joints)
-        st = _lib.DpSeqState()
-        st.global_pos = _check(global_pos, "global_pos", (S, 3), torch.float32, dev)
-        st.global_rot = _check(global_rot, "global_rot", (S, 4), torch.float32, dev)
-        st.latent_buf = _check(latent_buf, "latent_buf", (S, H, LATENT), torch.float32, dev)
-        st.disp_buf = _check(disp_buf, "disp_buf", (S, H, 3), torch.float32, dev)
-        st.heights_buf = _check(heights_buf, "heights_buf", (S, H, NH), torch.float32, dev)
-        st.history, st.n_heights = H, NH
-        for i, j in enumerate(height_joints):
-            st.height_joints[i] = int(j)
-        step = _lib.DpSeqStep()
-        step.adjust_joint = -1
+        st, step = _seq_state(S, global_pos, global_rot, latent_buf, disp_buf, heights_buf, height_joints, adjust, dev)
         if adjust is not None:
-            step.adjust_joint, step.adjust_target_joint, step.adjust_weight = int(adjust[0]), int(adjust[1]), float(adjust[2])
             step.tgt_pos = _check(tgt_pos, "tgt_pos", (S, NJ, 3), torch.float32, dev)
         if pose_ret is not None:
             step.pose_ret = _check(pose_ret, "pose_ret", (S, 88), torch.float32, dev)
@@ -443,7 +552,6 @@ class LatentOptimizer:
         """-> (dp_seq_frames, dp_seq_state, dp_seq_step) of a whole-sequence launch, every tensor checked; own_targets: the launch forms its z_tgt rows"""
         T, S = int(tgt_pos.shape[0]), int(tgt_pos.shape[1])
         dev = self.device
-        H, NH = int(latent_buf.shape[1]), len(height_joints)
         fr = _lib.DpSeqFrames()
         fr.n_steps = T
         fr.tgt_pos = _check(tgt_pos, "tgt_pos", (T, S, NJ, 3), torch.float32, dev)
@@ -457,20 +565,7 @@ class LatentOptimizer:
             if z_tgt.device != dev or z_tgt.dtype != torch.float32:
                 raise ValueError("z_tgt: expected an fp32 tensor on the optimiser's device")
             fr.z_tgt, fr.z_tgt_step, fr.z_tgt_seq = z_tgt.data_ptr(), int(z_tgt_strides[0]), int(z_tgt_strides[1])
-        st = _lib.DpSeqState()
-        st.global_pos = _check(global_pos, "global_pos", (S, 3), torch.float32, dev)
-        st.global_rot = _check(global_rot, "global_rot", (S, 4), torch.float32, dev)
-        st.latent_buf = _check(latent_buf, "latent_buf", (S, H, LATENT), torch.float32, dev)
-        st.disp_buf = _check(disp_buf, "disp_buf", (S, H, 3), torch.float32, dev)
-        st.heights_buf = _check(heights_buf, "heights_buf", (S, H, NH), torch.float32, dev)
-        st.history, st.n_heights = H, NH
-        for i, j in enumerate(height_joints):
-            st.height_joints[i] = int(j)
-        step = _lib.DpSeqStep()
-        step.adjust_joint = -1
-        if adjust is not None:
-            step.adjust_joint, step.adjust_target_joint, step.adjust_weight = int(adjust[0]), int(adjust[1]), float(adjust[2])
-        return fr, st, step
+        return (fr,) + _seq_state(S, global_pos, global_rot, latent_buf, disp_buf, heights_buf, height_joints, adjust, dev)
 
     def optimize_sequence(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
                           heights_buf, height_joints, n_iter=100, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, lambda_rot=1.0, lambda_tmp=0.0,
@@ -512,80 +607,19 @@ class LatentOptimizer:
         after every step and is returned as `tether_trace`.  Not together with `live`.
         A `terms` table with points (include/dragposer_points.h) runs through dp_optimize_sequence_terms_points, `offsets` allowed; not
         together with `holds`, `gaps`, `ar`, `tethers` or `live`."""
-        live = bool(live) or bool(getattr(self, "live_step", False))
-        if terms is not None and terms.has_points:
-            for name, given in (("holds", holds is not None), ("gaps", gaps is not None), ("ar", ar is not None), ("tethers", tethers is not None),
-                                ("live", live)):
-                if given:
-                    raise ValueError(f"optimize_sequence: a table with points does not go with {name}= (include/dragposer_points.h, Not in)")
-        if tethers is None and (tether_state is not None or tether_trace is not None):
-            raise ValueError("optimize_sequence: tether_state / tether_trace belong to tethers=")
-        if tethers is not None:
-            if live:
-                raise ValueError("optimize_sequence: tethers= are not part of dp_live_step (include/dragposer_tethers.h, Not covered)")
-            if terms is None or constraints is not None:
-                raise ValueError("optimize_sequence: tethers= refer to a table, pass terms= (Terms.from_constraints turns constraints into one)")
-            if gaps is None:
-                raise ValueError("optimize_sequence: tethers= is dp_optimize_sequence_gaps with tethers, pass gaps= (Gaps(0, 1.0) for none to hold)")
-            if tether_state is None:
-                raise ValueError("optimize_sequence: tethers= needs tether_state [S,len(tethers),8]")
-            tethers.check(terms, holds)
-        if live and gaps is None:
-            raise ValueError("optimize_sequence: live= is the one-launch form of gaps= (pass Gaps(0, 1.0) for none to hold)")
-        if live and int(tgt_pos.shape[0]) != 1:
-            raise ValueError("optimize_sequence: live= is one frame, tgt_pos holds " + str(int(tgt_pos.shape[0])))
-        if gaps is None and (gap_state is not None or present is not None or gap_trace is not None):
-            raise ValueError("optimize_sequence: gap_state / present / gap_trace belong to gaps=")
-        if gaps is not None:
-            gaps.check()
-            if gap_state is None:
-                raise ValueError("optimize_sequence: gaps= needs gap_state [S,22,16]")
-            if constraints is not None:
-                raise ValueError("optimize_sequence: gaps= takes a table, pass terms= (Terms.from_constraints turns constraints into one)")
-            if terms is None:
-                from .terms import Terms
-
-                terms = Terms()
-        if ar is None and z_tgt_trace is not None:
-            raise ValueError("optimize_sequence: z_tgt_trace belongs to ar=")
-        if ar is not None:
-            if z_tgt is not None:
-                raise ValueError("optimize_sequence: ar= forms the targets itself, pass z_tgt=None")
-            if constraints is not None:
-                raise ValueError("optimize_sequence: ar= takes a table, pass terms= (Terms.from_constraints turns constraints into one)")
-            if ar.order > int(latent_buf.shape[1]):
-                raise ValueError(f"optimize_sequence: latent_buf holds {int(latent_buf.shape[1])} rows, fewer than ar.order = {ar.order}")
-            if terms is None:
-                from .terms import Terms
-
-                terms = Terms()
-        if holds is not None and (terms is None or constraints is not None):
-            raise ValueError("optimize_sequence: holds= refer to a table, pass terms= (Terms.from_constraints turns constraints into one)")
-        if holds is None and (hold_state is not None or hold_trace is not None):
-            raise ValueError("optimize_sequence: hold_state / hold_trace belong to holds=")
-        if holds is not None and hold_state is None:
-            raise ValueError("optimize_sequence: holds= needs hold_state [S,len(holds),4]")
-        if constraints is not None and terms is not None:
-            raise ValueError("optimize_sequence: pass constraints or terms, not both")
-        if constraints is None and terms is None and (loss_extra is not None or loss_terms is not None or joint_pos is not None):
-            raise ValueError("optimize_sequence: loss_extra / loss_terms / joint_pos are outputs of constraints= / terms=")
+        live = bool(live)
+        terms = _sequence_refusals(tgt_pos, latent_buf, z_tgt, constraints, terms, loss_extra, loss_terms, joint_pos, holds, hold_state, hold_trace, ar,
+                                   z_tgt_trace, gaps, gap_state, present, gap_trace, live, tethers, tether_state, tether_trace)
         T, S = int(tgt_pos.shape[0]), int(tgt_pos.shape[1])
         dev = self.device
         skel = self._skeleton(offsets, S, "optimize_sequence") if offsets is not None else None
-        H, NH = int(latent_buf.shape[1]), len(height_joints)
         fr, st, step = self._sequence_structs(tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf,
                                               disp_buf, heights_buf, height_joints, adjust, own_targets=ar is not None)
         res = _lib.DpSeqResults()
-        outs = {}
         res.world_rot = None
-        for name, t, shape, dtype in (("pose_ret", pose_ret, (T, S, 88), torch.float32), ("pos_ret", pos_ret, (T, S, 3), torch.float32),
-                                      ("iters", iters, (T, S), torch.int32), ("loss", loss, (T, S, 3), torch.float32),
-                                      ("status", status, (T, S), torch.int32)):
-            t = t if t is not None else torch.empty(shape, dtype=dtype, device=dev)
-            setattr(res, name, _check(t, name, shape, dtype, dev))
-            outs[name] = t
-        scratch = scratch if scratch is not None else torch.empty(T, S, LATENT + 3 + NH, device=dev)
-        res.hist_scratch = _check(scratch, "scratch", (T, S, LATENT + 3 + NH), torch.float32, dev)
+        specs = (("pose_ret", pose_ret, (T, S, 88), torch.float32, res), ("pos_ret", pos_ret, (T, S, 3), torch.float32, res),
+                 ("iters", iters, (T, S), torch.int32, res), ("loss", loss, (T, S, 3), torch.float32, res), ("status", status, (T, S), torch.int32, res))
+        outs, scratch = _step_outputs(specs, res, scratch, (T, S, LATENT + 3 + len(height_joints)), dev)
         p = self._params(n_iter, lr, betas, eps, lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot, min_loss_incr, early=True)
         lp = C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev))
         tail = (C.byref(st), C.byref(step), C.byref(res))
@@ -606,42 +640,29 @@ class LatentOptimizer:
             if terms is not None and terms.has_points:
                 ps, keep_p = terms.points.to_struct()
                 fn, mid = self.lib.dp_optimize_sequence_terms_points, (C.byref(ps),)
-            if holds is not None:
-                if hold_trace is True:
-                    hold_trace = torch.zeros(T, S, len(holds), 4, dtype=torch.float32, device=dev)
-                hs, keep_h = holds.to_struct(terms, S, dev, hold_state, hold_trace, steps=T)
-                fn, mid = self.lib.dp_optimize_sequence_holds, (C.byref(hs),)
-                if hold_trace is not None:
-                    outs["hold_trace"] = hold_trace
-            if ar is not None:
-                if z_tgt_trace is True:
-                    z_tgt_trace = torch.zeros(T, S, LATENT, dtype=torch.float32, device=dev)
-                rs, keep_r = ar.to_struct(dev, z_tgt_trace, (T, S, LATENT))
-                fn, mid = self.lib.dp_optimize_sequence_ar, (mid[0] if mid else None, C.byref(rs))
-                if z_tgt_trace is not None:
-                    outs["z_tgt_trace"] = z_tgt_trace
-            if gaps is not None:
-                if gap_trace is True:
-                    gap_trace = torch.zeros(T, S, NJ, dtype=torch.uint8, device=dev)
-                gs = gaps.to_struct(S, dev, gap_state, present, gap_trace, steps=T)
-                hold_ref, ar_ref = (mid[0] if mid else None), (mid[1] if len(mid) > 1 else None)
-                fn, mid = self.lib.dp_live_step if live else self.lib.dp_optimize_sequence_gaps, (hold_ref, ar_ref, C.byref(gs))
-                if gap_trace is not None:
-                    outs["gap_trace"] = gap_trace
-            if tethers is not None:
-                if tether_trace is True:
-                    tether_trace = torch.zeros(T, S, len(tethers), 8, dtype=torch.float32, device=dev)
-                ts, keep_t = tethers.to_struct(terms, S, dev, tether_state, tether_trace, steps=T, holds=holds)
-                fn, mid = self.lib.dp_optimize_sequence_tethers, mid + (C.byref(ts),)
-                if tether_trace is not None:
-                    outs["tether_trace"] = tether_trace
+            # the layers above the table: the highest one present names the entry point, which takes every layer up to it (absent ones as NULL)
+            a = dict(T=T, S=S, dev=dev, terms=terms, holds=holds, hold_state=hold_state, hold_trace=hold_trace, ar=ar, z_tgt_trace=z_tgt_trace, gaps=gaps,
+                     gap_state=gap_state, present=present, gap_trace=gap_trace, tethers=tethers, tether_state=tether_state, tether_trace=tether_trace)
+            slots, keeps = [], []
+            for layer, trace_name, trace_shape, dtype, entry, to_struct in _SEQ_LAYERS:
+                if a[layer] is None:
+                    slots.append(None)
+                    continue
+                trace = _traced(a[trace_name], (T, S) + trace_shape(a), dtype, dev)
+                s, keep_s = to_struct(a, trace)
+                keeps.append(keep_s)
+                slots.append(C.byref(s))
+                fn, mid = getattr(self.lib, entry), tuple(slots)
+                if trace is not None:
+                    outs[trace_name] = trace
+            if live:
+                fn = self.lib.dp_live_step
             self._call(fn, S, lp, C.byref(fr), C.byref(p), C.byref(own), *mid, C.byref(skel) if skel is not None else None, *tail, C.byref(ex))
-            del keep
+            del keep, keeps
             return outs
         fn, args = (self.lib.dp_optimize_sequence, tail) if skel is None else (self.lib.dp_optimize_sequence_skeleton, (C.byref(skel),) + tail)
         self._call(fn, S, lp, C.byref(fr), C.byref(p), *args)
         return outs
-
 
     def optimize_sequence_lm(self, latent, tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf, disp_buf,
                              heights_buf, height_joints, lm=None, lambda_rot=1.0, lambda_tmp=0.0, stop_eps_pos=0.0, stop_eps_rot=0.0, mu=None, ar=None,
@@ -684,7 +705,7 @@ class LatentOptimizer:
             raise ValueError(f"optimize_sequence_lm: latent_buf holds {H} rows, fewer than ar.order = {ar.order}")
         fr, st, step = self._sequence_structs(tgt_pos, tgt_rot, tgt_root, w, tracked, z_tgt, z_tgt_strides, global_pos, global_rot, latent_buf,
                                               disp_buf, heights_buf, height_joints, adjust, own_targets=ar is not None)
-        res, ex, outs = _lib.DpSeqResults(), _lib.DpSeqLmExtra(), {}
+        res, ex = _lib.DpSeqResults(), _lib.DpSeqLmExtra()
         specs = (("pose_ret", pose_ret, (T, S, 88), torch.float32, res), ("pos_ret", pos_ret, (T, S, 3), torch.float32, res),
                  ("iters", iters, (T, S), torch.int32, res), ("loss", loss, (T, S, 3), torch.float32, res), ("status", status, (T, S), torch.int32, res),
                  ("world_rot", world_rot, (T, S, 4), torch.float32, res), ("mu_trace", mu_trace, (T, S), torch.float32, ex),
@@ -694,40 +715,29 @@ class LatentOptimizer:
             unknown = [n for n in outputs if n not in [sp[0] for sp in specs] + (["loss_terms"] if terms is not None else [])]
             if unknown:
                 raise ValueError(f"optimize_sequence_lm: unknown output {unknown[0]!r}")
-        for name, t, shape, dtype, struct in specs:
-            if outputs is not None and name not in outputs and t is None:
-                continue
-            t = t if t is not None else torch.empty(shape, dtype=dtype, device=dev)
-            setattr(struct, name, _check(t, name, shape, dtype, dev))
-            outs[name] = t
-        if mu is not None:
-            ex.mu = _check(mu, "mu", (S,), torch.float32, dev)
-            outs["mu"] = mu
-        scratch = scratch if scratch is not None else torch.empty(T, S, LATENT + 3 + NH, device=dev)
-        res.hist_scratch = _check(scratch, "scratch", (T, S, LATENT + 3 + NH), torch.float32, dev)
+        if mu is not None:  # (storage given means produced: `mu` is returned when given and never allocated here)
+            specs += (("mu", mu, (S,), torch.float32, ex),)
+        outs, scratch = _step_outputs(specs, res, scratch, (T, S, LATENT + 3 + NH), dev, outputs)
         rs, keep = None, None
         if ar is not None:
-            if z_tgt_trace is True:
-                z_tgt_trace = torch.zeros(T, S, LATENT, dtype=torch.float32, device=dev)
+            z_tgt_trace = _traced(z_tgt_trace, (T, S, LATENT), torch.float32, dev)
             rs, keep = ar.to_struct(dev, z_tgt_trace, (T, S, LATENT))
             if z_tgt_trace is not None:
                 outs["z_tgt_trace"] = z_tgt_trace
         p = lm.to_struct(lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot)
         lp = C.c_void_p(_check(latent, "latent", (S, LATENT), torch.float32, dev))
-        if terms is None:
-            self._call(self.lib.dp_optimize_sequence_lm, S, lp, C.byref(fr), C.byref(p), C.byref(rs) if rs is not None else None, C.byref(st), C.byref(step),
-                       C.byref(res), C.byref(ex))
-            del keep
-            return outs
-        tx = _lib.DpSeqExtra()
-        if loss_terms is not None or outputs is None or "loss_terms" in outputs:
-            lt = loss_terms if loss_terms is not None else torch.empty(T, S, len(terms), dtype=torch.float32, device=dev)
-            tx.loss_terms = _check(lt, "loss_terms", (T, S, len(terms)), torch.float32, dev) if lt.numel() else None
-            outs["loss_terms"] = lt
-        own, keep_t = terms.to_struct(S, dev, steps=T)
-        tx.row_step[:len(terms)] = terms.row_steps(S)
-        self._call(self.lib.dp_optimize_sequence_lm_terms, S, lp, C.byref(fr), C.byref(p), C.byref(own), C.byref(rs) if rs is not None else None,
-                   C.byref(st), C.byref(step), C.byref(res), C.byref(ex), C.byref(tx))
+        fn, head, last, keep_t = self.lib.dp_optimize_sequence_lm, (), (), None
+        if terms is not None:  # (the table goes in before the predictor, its per-step output and row steps after everything else)
+            tx = _lib.DpSeqExtra()
+            if loss_terms is not None or outputs is None or "loss_terms" in outputs:
+                lt = loss_terms if loss_terms is not None else torch.empty(T, S, len(terms), dtype=torch.float32, device=dev)
+                tx.loss_terms = _check(lt, "loss_terms", (T, S, len(terms)), torch.float32, dev) if lt.numel() else None
+                outs["loss_terms"] = lt
+            own, keep_t = terms.to_struct(S, dev, steps=T)
+            tx.row_step[:len(terms)] = terms.row_steps(S)
+            fn, head, last = self.lib.dp_optimize_sequence_lm_terms, (C.byref(own),), (C.byref(tx),)
+        self._call(fn, S, lp, C.byref(fr), C.byref(p), *head, C.byref(rs) if rs is not None else None, C.byref(st), C.byref(step), C.byref(res),
+                   C.byref(ex), *last)
         del keep, keep_t
         return outs
 
