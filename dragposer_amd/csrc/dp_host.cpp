@@ -822,8 +822,9 @@ static int launch(dp_ctx* ctx, KArgs& k, void* stream, int kernel = DP_KERNEL_W4
 }
 
 // host-only, exported for the tests: the instantiation the context's last dp_optimize / dp_forward / dp_optimize_sequence launched, as the
-// launcher recorded it -- out[5] = unit (1 dp_w4.hip, 2 dp_w4_bp.hip, 3 dp_w16*.hip, 4 dp_w4_skel.hip, 5 dp_w4_bp_skel.hip; 0: none yet, or the test-only library), waves per
-// workgroup, and the EARLY, SEQ and LONG template flags
+// launcher recorded it -- out[5] = unit (1 dp_w4.hip, 2 dp_w4_bp.hip, 3 dp_w16*.hip, 4 dp_w4_skel.hip, 5 dp_w4_bp_skel.hip, 6 dp_w4_bp_lv.hip -- the body-part
+// layout's fixed-count optimising launches without the debug dump; 0: none yet, or the test-only library), waves per workgroup, and the EARLY, SEQ and
+// LONG template flags
 extern "C" int dp_debug_last_launch(const dp_ctx* ctx, int* out)
 {
     if (!ctx || !out) return DP_ERR_INVALID;

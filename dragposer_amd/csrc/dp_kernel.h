@@ -73,7 +73,8 @@ struct KArgs {
 };
 
 // Which template instantiation a launch ran (dp_debug_last_launch, for the tests): each launcher fills it at the branch that launches.
-enum { DP_UNIT_NONE = 0, DP_UNIT_W4 = 1, DP_UNIT_W4_BP = 2, DP_UNIT_W16 = 3, DP_UNIT_W4_SKEL = 4, DP_UNIT_W4_BP_SKEL = 5 };
+enum { DP_UNIT_NONE = 0, DP_UNIT_W4 = 1, DP_UNIT_W4_BP = 2, DP_UNIT_W16 = 3, DP_UNIT_W4_SKEL = 4, DP_UNIT_W4_BP_SKEL = 5,
+       DP_UNIT_W4_BP_LV = 6 }; // dp_w4_bp_lv.hip: the body-part kernel with the loop versions (fixed-count optimising launches)
 struct LaunchPick {
     int unit;  // DP_UNIT_*
     int waves; // per workgroup

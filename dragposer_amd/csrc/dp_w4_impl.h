@@ -1527,7 +1527,7 @@ __global__ __launch_bounds__(NW * 64, 1) void W4_KERNEL(const KArgs a)
 template <int NW, bool EARLY, bool SEQ = false, bool LONG = false>
 static void w4_launch(const KArgs* args, hipStream_t stream, LaunchPick* pick)
 {
-    set_pick(pick, W4_SKEL ? (W4_BP ? DP_UNIT_W4_BP_SKEL : DP_UNIT_W4_SKEL) : W4_BP ? DP_UNIT_W4_BP : DP_UNIT_W4, NW, EARLY, SEQ, LONG);
+    set_pick(pick, W4_SKEL ? (W4_BP ? DP_UNIT_W4_BP_SKEL : DP_UNIT_W4_SKEL) : W4_LOOP_VERSIONS != 0 ? DP_UNIT_W4_BP_LV : W4_BP ? DP_UNIT_W4_BP : DP_UNIT_W4, NW, EARLY, SEQ, LONG);
     const int grid = (args->n_frames + NW * FPW - 1) / (NW * FPW);
     hipLaunchKernelGGL((W4_KERNEL<NW, EARLY, SEQ, LONG>), dim3(grid), dim3(NW * 64), 0, stream, *args);
 }

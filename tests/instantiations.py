@@ -7,7 +7,9 @@ import collections
 import ctypes as C
 
 UNIT_W4, UNIT_W4_BP, UNIT_W16 = 1, 2, 3  # dp_debug_last_launch's unit codes (dp_kernel.h: DP_UNIT_*)
-UNIT_NAMES = {UNIT_W4: "w4", UNIT_W4_BP: "w4_bp", UNIT_W16: "w16"}
+UNIT_W4_BP_LV = 6                      # (4 and 5 are the per-frame-skeleton units: tests/skeleton_cases.py)
+UNIT_NAMES = {UNIT_W4: "w4", UNIT_W4_BP: "w4_bp", UNIT_W16: "w16", UNIT_W4_BP_LV: "w4_bplv"}
+KERNEL_NAMES = {UNIT_W4: "dp_w4_kernel", UNIT_W4_BP: "dp_w4_bp_kernel", UNIT_W4_BP_LV: "dp_w4_bplv_kernel"}
 
 Inst = collections.namedtuple("Inst", "unit waves early seq long")
 
@@ -19,6 +21,9 @@ INSTANTIATIONS = (
     Inst(UNIT_W4_BP, 4, 0, 0, 0), Inst(UNIT_W4_BP, 4, 0, 0, 1),
     Inst(UNIT_W4_BP, 4, 1, 0, 0), Inst(UNIT_W4_BP, 4, 1, 0, 1),
     Inst(UNIT_W4_BP, 4, 1, 1, 0), Inst(UNIT_W4_BP, 4, 1, 1, 1),
+    # dp_w4_bp_lv.hip: the body-part layout's fixed-count optimising launches (the iteration loop once per loop version).  What every plain
+    # fixed-count call of the body-part layout runs; dp_w4_bp.hip's two fixed-count rows above are left to dp_forward and the debug dump
+    Inst(UNIT_W4_BP_LV, 4, 0, 0, 0), Inst(UNIT_W4_BP_LV, 4, 0, 0, 1),
     # dp_w16*.hip: one wave per SIMD (4 waves) or two (8 waves); fixed count or early stop, each also LONG
     Inst(UNIT_W16, 4, 0, 0, 0), Inst(UNIT_W16, 4, 0, 0, 1),
     Inst(UNIT_W16, 4, 1, 0, 0), Inst(UNIT_W16, 4, 1, 0, 1),
@@ -28,13 +33,13 @@ INSTANTIATIONS = (
 
 
 def symbol(inst):
-    """the mangled name of the row's kernel: template <int NW, bool EARLY, bool SEQ, bool LONG> dp_w4[_bp]_kernel,
+    """the mangled name of the row's kernel: template <int NW, bool EARLY, bool SEQ, bool LONG> dp_w4_kernel / dp_w4_bp_kernel / dp_w4_bplv_kernel,
     template <int NW, int WPS, bool EARLY, bool LONG> dp_w16_kernel (WPS = waves per SIMD = NW / 4)"""
     b = lambda v: f"Lb{int(v)}E"
     if inst.unit == UNIT_W16:
         assert not inst.seq
         return f"_Z13dp_w16_kernelILi{inst.waves}ELi{inst.waves // 4}E{b(inst.early)}{b(inst.long)}Ev5KArgs"
-    name = "dp_w4_kernel" if inst.unit == UNIT_W4 else "dp_w4_bp_kernel"
+    name = KERNEL_NAMES[inst.unit]
     return f"_Z{len(name)}{name}ILi{inst.waves}E{b(inst.early)}{b(inst.seq)}{b(inst.long)}Ev5KArgs"
 
 

@@ -12,6 +12,9 @@ tests/test_instantiation_coverage.py) is launched, is reported by dp_debug_last_
   with a stop quantity of the oracle's trajectory within 2e-5 of its threshold (`_stop_flip`), whose results must then be the oracle's
   trajectory at the kernel's count (at most 3 of 67 frames, 9 of 192);
 * sequences: dp_optimize_sequence over T steps = T one-step DragPose.run calls, bit for bit, and the first step against the oracle;
+* the body-part layout's fixed-count launches: the plain call runs dp_w4_bp_lv.hip's kernel (rows w4_bplv-*), the call with the debug dump --
+  the only product route to them -- dp_w4_bp.hip's fixed-count kernels (rows w4_bp-4w-fixed*): the same batches, the same oracle check, and
+  the two byte-equal on every per-frame result;
 * dp_w4's two row layouts (dense, body-part) on the same model: bit-identical, in fp32 and bf16;
 * a model the body-part layout does not fit loads dense, refuses the body-part layout, and matches an oracle built from it;
 * dp_w16 with 4 and 8 waves per workgroup: the same bits."""
@@ -19,7 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-from instantiations import INSTANTIATIONS, UNIT_W4, UNIT_W4_BP, UNIT_W16, Inst, inst_id, last_launch, set_layout  # tests/instantiations.py
+from instantiations import INSTANTIATIONS, UNIT_W4, UNIT_W4_BP, UNIT_W4_BP_LV, UNIT_W16, Inst, inst_id, last_launch, set_layout  # tests/instantiations.py
 from oracle import ref_torch as R
 from oracle.analytic import DEFAULT_MODEL, AnalyticOracle
 from sensitivity import kink_distance, tiny_gradient  # tests/sensitivity.py
@@ -47,8 +50,7 @@ def _np(out):
 def _check_against_oracle(out, b, n_iter, es, model_path=DEFAULT_MODEL, what=""):
     """BASELINE.md section 3, with the C oracle's f32 / f64 pair in the reference pair's role"""
     a = [b[k] for k in KEYS]
-    o32 = AnalyticOracle(model_path=model_path, precision="f32").optimize(*a, n_iter, lam_tmp=LAM, **es)
-    o64 = AnalyticOracle(model_path=model_path, precision="f64").optimize(*a, n_iter, lam_tmp=LAM, **es)
+    o32, o64 = _oracle_pair(b, n_iter, es, model_path)
     sens = _mm(o32["pos"], o64["pos"]).max(axis=1) > 0.02
     if es:
         sens |= o32["iters"] != o64["iters"]
@@ -79,6 +81,23 @@ def _check_against_oracle(out, b, n_iter, es, model_path=DEFAULT_MODEL, what="")
     else:
         assert (out["iters"] == n_iter).all(), what
     return o32
+
+
+_PAIRS = {}
+
+
+def _oracle_pair(b, n_iter, es, model_path):
+    """the C oracle's f32 and f64 runs of a batch: computed once per (model, batch, n_iter, stop settings) -- the rows of the dense, the body-part,
+    the loop-version and the dp_w16 unit share them -- and left unchanged"""
+    key = (model_path, n_iter, tuple(sorted(es.items())), tuple(hash(b[k].tobytes()) for k in KEYS))
+    if key not in _PAIRS:
+        a = [b[k] for k in KEYS]
+        pair = tuple(AnalyticOracle(model_path=model_path, precision=p).optimize(*a, n_iter, lam_tmp=LAM, **es) for p in ("f32", "f64"))
+        for r in pair:
+            for v in r.values():
+                v.setflags(write=False)
+        _PAIRS[key] = pair
+    return _PAIRS[key]
 
 
 STOP_ROUNDING = 2e-5  # (relative) how near its threshold a stop quantity must be for two correct implementations to decide it differently
@@ -140,30 +159,42 @@ def batch():
 
 
 def _select(opt, inst):
-    if inst.unit in (UNIT_W4, UNIT_W4_BP):
-        assert set_layout(opt, 1 if inst.unit == UNIT_W4_BP else 0) == (1 if inst.unit == UNIT_W4_BP else 0)
+    if inst.unit in (UNIT_W4, UNIT_W4_BP, UNIT_W4_BP_LV):
+        bp = 0 if inst.unit == UNIT_W4 else 1
+        assert set_layout(opt, bp) == bp
 
 
-def _optimize(opt, b, n_iter, es, kernel, outputs=PER_FRAME):
+def _optimize(opt, b, n_iter, es, kernel, outputs=PER_FRAME, dump=False):
+    """`dump`: through dp_optimize_debug, with a buffer for the first iteration's dump (what keeps a fixed-count launch of the body-part layout
+    on dp_w4_bp.hip's own kernel)"""
     from dragposer_amd.optimizer import to_device_batch
 
-    return _np(opt.optimize(**to_device_batch(b, opt.device), n_iter=n_iter, lambda_tmp=LAM, kernel=kernel, outputs=outputs, **es))
+    kw = dict(_debug=torch.zeros(len(b["z0"]), 240, device=opt.device)) if dump else {}
+    return _np(opt.optimize(**to_device_batch(b, opt.device), n_iter=n_iter, lambda_tmp=LAM, kernel=kernel, outputs=outputs, **es, **kw))
 
 
 def _frame_entry(opt, b, inst, model_path=DEFAULT_MODEL):
-    """a fixed-count or early-stop entry of a dp_w4 unit or of dp_w16 with 4 waves: 67 frames against the oracle, 1 and 61 frames row-equal"""
+    """a fixed-count or early-stop entry of a dp_w4 unit or of dp_w16 with 4 waves: 67 frames against the oracle, 1 and 61 frames row-equal.
+    dp_w4_bp.hip's fixed-count kernels are reached through the debug dump alone (dp_launch_w4_bp): their rows run the same batches that way, and
+    every per-frame result must be, byte for byte, what the plain call -- dp_w4_bp_lv.hip's row -- returns."""
     kernel = "w16" if inst.unit == UNIT_W16 else "w4"
+    dump = inst.unit == UNIT_W4_BP and not inst.early
     for n_iter in ((257, 300) if inst.long else (256,)):
         if inst.long and inst.early and n_iter == 257:
             continue  # (early stop beyond the table: 300 iterations, counts on both sides of 256)
         es = (ES_LONG if inst.long else ES_SHORT) if inst.early else {}
-        out = _optimize(opt, b, n_iter, es, kernel)
+        out = _optimize(opt, b, n_iter, es, kernel, dump=dump)
         assert last_launch(opt) == inst, (last_launch(opt), inst)
         o32 = _check_against_oracle(out, b, n_iter, es, model_path, what=f"{inst_id(inst)}")
+        if dump:
+            lv = _optimize(opt, b, n_iter, es, kernel)
+            assert last_launch(opt) == inst._replace(unit=UNIT_W4_BP_LV), last_launch(opt)
+            for k in PER_FRAME:
+                assert np.ascontiguousarray(lv[k]).tobytes() == np.ascontiguousarray(out[k]).tobytes(), f"{inst_id(inst)} n_iter {n_iter}: {k} differs from the loop-version kernel's"
         if inst.early:
             _assert_counts_spread(o32["iters"], n_iter)
         for B in B_RAGGED:
-            sub = _optimize(opt, {k: b[k][:B] for k in KEYS}, n_iter, es, kernel)
+            sub = _optimize(opt, {k: b[k][:B] for k in KEYS}, n_iter, es, kernel, dump=dump)
             assert last_launch(opt) == inst
             for k in PER_FRAME:
                 np.testing.assert_array_equal(sub[k], out[k][:B], err_msg=f"{inst_id(inst)} B={B} {k}")
@@ -325,7 +356,8 @@ def test_dense_and_body_part_layouts_give_the_same_bits(wd, batch):
     finally:
         o.close()
     assert ran_d == W4_ENTRIES + [Inst(UNIT_W4, 4, 0, 0, 0)], ran_d
-    assert ran_bp == [i._replace(unit=UNIT_W4_BP) for i in ran_d], ran_bp
+    # (body-part: the fixed-count optimising launches go to the loop-version kernel; the while-condition, sequences and dp_forward stay)
+    assert ran_bp == [i._replace(unit=UNIT_W4_BP if i.early else UNIT_W4_BP_LV) for i in W4_ENTRIES] + [Inst(UNIT_W4_BP, 4, 0, 0, 0)], ran_bp
     for name in dense:
         for k in dense[name]:
             np.testing.assert_array_equal(bp[name][k], dense[name][k], err_msg=f"{wd} {name} {k}")

@@ -267,7 +267,7 @@ def _mixed(d):
 @pytest.mark.parametrize("unit", ["w4_bp", "w4_dense", "w16_4w", "w16_8w"])
 @pytest.mark.parametrize("early", [False, True])
 def test_a_frame_that_cannot_be_optimised_does_not_also_report_a_non_rotation(fresh_opt, unit, early):
-    from instantiations import UNIT_W4, UNIT_W4_BP, UNIT_W16, last_launch, set_layout  # tests/instantiations.py
+    from instantiations import UNIT_W4, UNIT_W4_BP, UNIT_W4_BP_LV, UNIT_W16, last_launch, set_layout  # tests/instantiations.py
 
     opt = fresh_opt
     if unit == "w4_dense":
@@ -281,7 +281,7 @@ def test_a_frame_that_cannot_be_optimised_does_not_also_report_a_non_rotation(fr
     out = opt.optimize(**_mixed(d), **kw)
     torch.cuda.synchronize()
     ran = last_launch(opt)
-    assert (ran.unit, ran.waves) == {"w4_bp": (UNIT_W4_BP, 4), "w4_dense": (UNIT_W4, 4), "w16_4w": (UNIT_W16, 4), "w16_8w": (UNIT_W16, 8)}[unit], ran
+    assert (ran.unit, ran.waves) == {"w4_bp": (UNIT_W4_BP if early else UNIT_W4_BP_LV, 4), "w4_dense": (UNIT_W4, 4), "w16_4w": (UNIT_W16, 4), "w16_8w": (UNIT_W16, 8)}[unit], ran
     st = out["status"].cpu().numpy()
     assert {f: int(st[f]) for f in MIXED} == MIXED, {f: int(st[f]) for f in MIXED}
     others = [i for i in range(B) if i not in MIXED]

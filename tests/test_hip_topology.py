@@ -41,7 +41,7 @@ def _model_arrays(parents, seed):
 def test_another_tree_through_dp_w4_against_the_c_oracle(name, tmp_path):
     from dragposer_amd import _lib
     from dragposer_amd.optimizer import LatentOptimizer, to_device_batch
-    from instantiations import UNIT_W4, UNIT_W4_BP, last_launch, set_layout  # tests/instantiations.py
+    from instantiations import UNIT_W4, UNIT_W4_BP_LV, last_launch, set_layout  # tests/instantiations.py
     from oracle.analytic import AnalyticOracle
 
     parents = TREES[name]
@@ -82,7 +82,7 @@ def test_another_tree_through_dp_w4_against_the_c_oracle(name, tmp_path):
             assert (np.abs(out["z"].cpu().numpy() - want["z_final"]) > 1e-3).mean() <= 0.002
             np.testing.assert_allclose(out["loss"].cpu().numpy(), want["loss"], rtol=2e-5, atol=1e-7)
         assert np.sort(err)[-2] <= 0.05 and err.max() <= 5.0, err  # (one frame may sit on a LeakyReLU kink: BASELINE.md section 3)
-        assert last_launch(opt).unit == (UNIT_W4_BP if W4_LAYOUT[name] else UNIT_W4)
+        assert last_launch(opt).unit == (UNIT_W4_BP_LV if W4_LAYOUT[name] else UNIT_W4)  # (fixed count: the body-part layout's loop-version kernel)
         if W4_LAYOUT[name]:  # the same tree through the dense unit: the same bits
             assert set_layout(opt, 0) == 0
             dense = opt.optimize(**d, n_iter=n_iter, lambda_tmp=0.02, kernel="w4", outputs=("z", "pos", "loss", "status"))

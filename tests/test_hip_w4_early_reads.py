@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from adam_reference import temporal_only  # tests/adam_reference.py: the latent of a frame that tracks nothing (lam = LAM is its default)
 from oracle import ref_torch as R
 from oracle.analytic import AnalyticOracle
 
@@ -65,18 +66,6 @@ def build_case(name):
     return b
 
 
-def temporal_only(b, f, n_iter, lr=1e-2, b1=0.9, b2=0.999, eps=1e-8):
-    """the latent of a frame that tracks nothing: Adam on lam * mean((z - z_tgt)^2) alone, in fp64"""
-    z, zt = b["z0"][f].astype(np.float64), b["z_tgt"][f].astype(np.float64)
-    m, v = np.zeros_like(z), np.zeros_like(z)
-    for t in range(1, n_iter + 1):
-        g = 2.0 * LAM / 24.0 * (z - zt)
-        m = b1 * m + (1 - b1) * g
-        v = b2 * v + (1 - b2) * g * g
-        z = z - lr / (1 - b1 ** t) * m / (np.sqrt(v) / np.sqrt(1 - b2 ** t) + eps)
-    return z
-
-
 _REF = {}
 
 
@@ -114,7 +103,7 @@ def opt():
 
 def _run(opt, b, bp, n_iter, early, skeleton=False):
     from dragposer_amd.optimizer import to_device_batch
-    from instantiations import UNIT_W4, UNIT_W4_BP, last_launch, set_layout
+    from instantiations import UNIT_W4, UNIT_W4_BP, UNIT_W4_BP_LV, last_launch, set_layout
     from skeleton_cases import UNIT_W4_BP_SKEL, UNIT_W4_SKEL  # tests/skeleton_cases.py
 
     assert set_layout(opt, bp) == bp
@@ -125,7 +114,7 @@ def _run(opt, b, bp, n_iter, early, skeleton=False):
     out = opt.optimize(**to_device_batch(b, opt.device), n_iter=n_iter, lambda_tmp=LAM, kernel="w4", **kw)
     torch.cuda.synchronize()
     ran = last_launch(opt)
-    assert ran.unit == ((UNIT_W4_BP_SKEL if bp else UNIT_W4_SKEL) if skeleton else (UNIT_W4_BP if bp else UNIT_W4)) and ran.early == int(early), ran
+    assert ran.unit == ((UNIT_W4_BP_SKEL if bp else UNIT_W4_SKEL) if skeleton else ((UNIT_W4_BP if early else UNIT_W4_BP_LV) if bp else UNIT_W4)) and ran.early == int(early), ran
     out = {k: v.cpu().numpy() for k, v in out.items()}
     assert (out["status"] == 0).all()
     return out
