@@ -325,6 +325,27 @@ LM_TERMS_SYMBOLS = ("dp_optimize_lm_terms",)
 LM_SEQUENCE_TERMS_SYMBOLS = ("dp_optimize_sequence_lm_terms",)
 
 
+# every symbol include/dragposer_calibration.h declares (tests/test_fit_bones_abi.py)
+CALIBRATION_SYMBOLS = ("dp_fit_bones_workspace_bytes", "dp_fit_bones")
+DP_FIT_MAX_GROUPS = 24
+DP_FIT_NO_FRAMES, DP_FIT_SINGULAR = 1, 2
+
+
+class DpBoneFit(_Sized):
+    """include/dragposer_calibration.h: dp_bone_fit, with DP_BONE_FIT_INIT's defaults (groups / base / prior: HOST arrays; workspace: a device pointer)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("n_groups", C.c_int), ("ridge", C.c_float), ("groups", C.c_void_p),
+                ("base", C.c_void_p), ("prior", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **dict(dict(n_groups=1, ridge=1e-3), **k))
+
+
+class DpBoneFitResult(_Sized):
+    """include/dragposer_calibration.h: dp_bone_fit_result (device pointers)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("scales", C.c_void_p), ("offsets", C.c_void_p), ("normal", C.c_void_p),
+                ("rms", C.c_void_p), ("info", C.c_void_p), ("status", C.c_void_p)]
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -437,6 +458,9 @@ def load(path=None):
     lib.dp_optimize_sequence_lm_terms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpLmParams), C.POINTER(DpTerms),
                                                   C.POINTER(DpLatentAR), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.POINTER(DpSeqResults),
                                                   C.POINTER(DpSeqLmExtra), C.POINTER(DpSeqExtra), C.c_void_p]
+    lib.dp_fit_bones_workspace_bytes.argtypes = [C.c_int]
+    lib.dp_fit_bones_workspace_bytes.restype = C.c_size_t
+    lib.dp_fit_bones.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpBoneFit), C.POINTER(DpBoneFitResult), C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

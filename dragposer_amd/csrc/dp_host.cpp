@@ -30,9 +30,11 @@
 #include "../../include/dragposer_sequence_lm.h"
 #include "../../include/dragposer_lm_terms.h"
 #include "../../include/dragposer_sequence_lm_terms.h"
+#include "../../include/dragposer_calibration.h"
 #include "dp_cons_live.h"
 #include "dp_cons_tether.h"
 #include "dp_cons_points.h"
+#include "dp_fit.h"
 #include "dp_host_rt.h"
 #include "dp_lm_seq.h"
 #include "dp_lm_seq_terms.h"
@@ -694,6 +696,8 @@ constexpr Sized POINTS_V580 = {"dp_points", "dp_points p = DP_POINTS_INIT;", off
 constexpr Sized LM_PARAMS_V590 = {"dp_lm_params", "dp_lm_params p = DP_LM_PARAMS_INIT;", offsetof(dp_lm_params, stop_eps_rot) + sizeof(float), false};
 constexpr Sized LM_EXTRA_V590 = {"dp_lm_extra", "dp_lm_extra e = DP_LM_EXTRA_INIT;", offsetof(dp_lm_extra, loss0) + sizeof(void*), false};
 constexpr Sized SEQ_LM_EXTRA_V600 = {"dp_seq_lm_extra", "dp_seq_lm_extra e = DP_SEQ_LM_EXTRA_INIT;", offsetof(dp_seq_lm_extra, joint_pos) + sizeof(void*), false};
+constexpr Sized BONE_FIT_V510 = {"dp_bone_fit", "dp_bone_fit f = DP_BONE_FIT_INIT;", offsetof(dp_bone_fit, workspace_bytes) + sizeof(size_t), false};
+constexpr Sized BONE_FIT_RESULT_V510 = {"dp_bone_fit_result", "dp_bone_fit_result r = DP_BONE_FIT_RESULT_INIT;", offsetof(dp_bone_fit_result, status) + sizeof(void*), false};
 constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
@@ -1327,6 +1331,74 @@ extern "C" int dp_optimize_lm_terms(dp_ctx* ctx, const dp_batch* in, const dp_lm
         fill_results(a, out);
         const hipError_t err = dp_launch_lm_terms(&a, (hipStream_t)stream);
         if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(err));
+        return (int)DP_OK;
+    });
+}
+
+// include/dragposer_calibration.h: dp_fit_bones, in the header's order of refusals.  Everything the HOST arrays hold goes into the kernels'
+// argument block here, so the call copies nothing to the device.  (Its launcher is a weak reference, like dp_launch_lm.)
+hipError_t dp_launch_fit(const dpfit::Args* args, hipStream_t stream) __attribute__((weak));
+static_assert(DP_FIT_MAX_GROUPS == dpfit::MAXK, "dp_fit.h's matrix holds DP_FIT_MAX_GROUPS scales");
+extern "C" size_t dp_fit_bones_workspace_bytes(int n_frames)
+{
+    return n_frames > 0 ? (size_t)dpfit::parts_of(n_frames) * dpfit::PART_FLOATS * sizeof(float) : 0;
+}
+extern "C" int dp_fit_bones(dp_ctx* ctx, const dp_batch* in, const dp_bone_fit* f_in, const dp_bone_fit_result* r_in, void* stream)
+{
+    const char* who = "dp_fit_bones";
+    return entry(ctx, who, [&] {
+        const std::string w = who;
+        if (!in || !f_in || !r_in) return fail(ctx, DP_ERR_INVALID, w + ": NULL batch, fit or result");
+        dp_bone_fit ft;
+        if (int rc = take_sized(ctx, f_in, ft, BONE_FIT_V510, who)) return rc;
+        dp_bone_fit_result out;
+        if (int rc = take_sized(ctx, r_in, out, BONE_FIT_RESULT_V510, who)) return rc;
+        if (!out.scales) return fail(ctx, DP_ERR_INVALID, w + ": dp_bone_fit_result.scales is NULL");
+        const int K = ft.n_groups;
+        if (K < 1 || K > DP_FIT_MAX_GROUPS) return fail(ctx, DP_ERR_INVALID, w + ": n_groups " + std::to_string(K) + " outside 1.." + std::to_string(DP_FIT_MAX_GROUPS));
+        if (!ft.groups) return fail(ctx, DP_ERR_INVALID, w + ": dp_bone_fit.groups is NULL");
+        dpfit::Args a;
+        std::memset(&a, 0, sizeof(a));
+        bool owns[DP_FIT_MAX_GROUPS] = {};
+        a.grp[0] = -1;
+        for (int j = 1; j < NJ; ++j) {
+            const int g = ft.groups[j];
+            if (g < -1 || g >= K)
+                return fail(ctx, DP_ERR_INVALID, w + ": groups[" + std::to_string(j) + "] is " + std::to_string(g) + ", outside -1.." + std::to_string(K - 1));
+            if (g >= 0) owns[g] = true;
+            a.grp[j] = g;
+        }
+        for (int g = 0; g < K; ++g)
+            if (!owns[g]) return fail(ctx, DP_ERR_INVALID, w + ": group " + std::to_string(g) + " owns no bone");
+        const auto fin = [](float x) { return std::fabs(x) <= 3.0e38f; };
+        if (ft.base)
+            for (int i = 0; i < 3 * NJ; ++i) {
+                if (!fin(ft.base[i])) return fail(ctx, DP_ERR_INVALID, w + ": base holds a value that is not finite");
+                a.base[i] = ft.base[i];
+            }
+        for (int g = 0; g < K; ++g) {
+            a.prior[g] = ft.prior ? ft.prior[g] : 1.f;
+            if (!fin(a.prior[g])) return fail(ctx, DP_ERR_INVALID, w + ": prior holds a value that is not finite");
+        }
+        if (!(ft.ridge >= 0.f && fin(ft.ridge))) return fail(ctx, DP_ERR_INVALID, w + ": ridge is negative or not finite");
+        const size_t need = dp_fit_bones_workspace_bytes(in->n_frames);
+        if (!ft.workspace || ft.workspace_bytes < need)
+            return fail(ctx, DP_ERR_INVALID, w + ": the workspace is NULL or holds " + std::to_string(ft.workspace_bytes) + " bytes, fewer than the " +
+                                                 std::to_string(need) + " of dp_fit_bones_workspace_bytes(" + std::to_string(in->n_frames) + ")");
+        if (in->n_frames <= 0) return fail(ctx, DP_ERR_INVALID, w + ": n_frames must be positive");
+        if (!in->z0 || !in->cur_rot || !in->tgt_pos || !in->w || !in->tracked) return fail(ctx, DP_ERR_INVALID, w + ": NULL input array");
+        if (REF8_BUILD) return refuse_ref8(ctx, who);
+        if (!dp_launch_fit) return fail(ctx, DP_ERR_UNSUPPORTED, w + ": this library was linked without dp_fit.hip");
+        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+        DEVICE_GUARD(ctx);
+        a.img = ctx->d_vjpimg.get();
+        a.z0 = in->z0; a.cur_rot = in->cur_rot; a.tgt_pos = in->tgt_pos; a.w = in->w; a.tracked = in->tracked;
+        a.n_frames = in->n_frames; a.n_parts = dpfit::parts_of(in->n_frames);
+        a.K = K; a.has_base = ft.base ? 1 : 0; a.ridge = ft.ridge;
+        a.workspace = (float*)ft.workspace;
+        a.scales = out.scales; a.offsets = out.offsets; a.normal = out.normal; a.rms = out.rms; a.info = out.info; a.status = out.status;
+        const hipError_t e = dp_launch_fit(&a, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(e));
         return (int)DP_OK;
     });
 }

@@ -240,6 +240,45 @@ def prepare_file(args, input_path, opt, encoder, cfg, raw):
                 gpos=torch.tensor(m["global_pos"][:n_frames], dtype=torch.float32, device=dev))
 
 
+def calibrate_file(args, q, opt, cfg, raw):
+    """--calibrate: the clip's bone lengths from its own tracker targets (dragposer_amd.calibrate, include/dragposer_calibration.h), as for a
+    performer without a BVH file: FRAMES frames drawn evenly from the clip as independent frames -- z0 = 0, lambda_temporal = 0, cur_rot = the
+    root's rotation one frame earlier, the root's displacement since then in the position targets -- start from the model's skeleton
+    (raw["offsets"]; the clip's OFFSET table is read for the targets and for the printed ratios only).  -> the fitted offsets [22,3] on the device"""
+    from .calibration import BoneGroups, calibrate
+
+    name, n_fit, rounds = args.calibrate_spec
+    groups = getattr(BoneGroups, name)()
+    dev, m, n = opt.device, q["m"], q["n_frames"]
+    if n < 2:
+        raise SystemExit("--calibrate: the clip needs at least two frames")
+    idx = np.unique(np.linspace(1, n - 1, min(n_fit, n - 1)).round().astype(np.int64))
+    B = len(idx)
+    mask_idx = np.nonzero(np.asarray(cfg["mask"]))[0]
+    it, mt = torch.as_tensor(idx, device=dev), torch.as_tensor(mask_idx, device=dev)
+    tgt_pos = torch.zeros(B, NJ, 3, device=dev)
+    tgt_pos[:, mt] = q["tp_rel"][it] + (q["gpos"][it] - q["gpos"][it - 1]).unsqueeze(1)
+    tgt_rot = torch.zeros(B, NJ, 9, device=dev)
+    tgt_rot[:, mt] = q["tR"][it]
+    w = torch.zeros(B, NJ, 2, device=dev)
+    w[:, mt] = torch.as_tensor(np.asarray(cfg["weights"], np.float32)[mask_idx], device=dev)
+    tracked = torch.zeros(B, NJ, dtype=torch.uint8, device=dev)
+    tracked[:, mt] = 1
+    batch = dict(z0=torch.zeros(B, 24, device=dev), z_tgt=torch.zeros(B, 24, device=dev),
+                 cur_rot=torch.as_tensor(np.asarray(m["global_rot"], np.float32)[idx - 1], device=dev).contiguous(),
+                 tgt_pos=tgt_pos, tgt_rot=tgt_rot, w=w, tracked=tracked)
+    cal = calibrate(opt, batch, groups, rounds=rounds, n_iter=50, ridge=1e-3, lambda_tmp=0.0)
+    last = cal.trace[-1]
+    base, true = np.asarray(raw["offsets"], np.float64).reshape(NJ, 3), np.asarray(m["offsets"], np.float64).reshape(NJ, 3)
+    print(f"Calibration: {name}, {B} frames, {rounds} rounds of 50 iterations (dragposer_amd.calibrate, include/dragposer_calibration.h); "
+          f"frames used {last['frames']}, flags {last['flags']}, residual {last['rms'][0]:.5f} -> {last['rms'][1]:.5f}")
+    for k in range(len(groups)):
+        bones = groups.members(k)
+        ratio = float(np.mean(np.linalg.norm(true[bones], axis=-1) / np.linalg.norm(base[bones], axis=-1)))
+        print(f"  group {k}: fitted scale {float(last['scales'][k]):.4f}, true ratio {ratio:.4f} (bones {bones})")
+    return cal.offsets
+
+
 def run_sequences(args, seqs, opt, temporal_pack, cfg):
     """The frame loop (eval_drag.py:181-227) for S prepared sequences advancing in lock-step: one `DragPose.run`
     (two kernel launches) per frame index whatever S.  Sequences shorter than the longest keep receiving their last
@@ -256,7 +295,8 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
     tp_rel = torch.stack([pad(q["tp_rel"]) for q in seqs], dim=1).contiguous()  # [T, S, E, 3]
     tR = torch.stack([pad(q["tR"]) for q in seqs], dim=1).contiguous()
     gpos = torch.stack([pad(q["gpos"]) for q in seqs], dim=1).contiguous()      # [T, S, 3]
-    offsets = torch.stack([q["offsets"] for q in seqs]).contiguous()             # [S, 22, 3]: each clip's own skeleton (eval_drag.py:48,135,209)
+    # [S, 22, 3]: each clip's own skeleton (eval_drag.py:48,135,209) -- or what --calibrate fitted, or with --model-skeleton the model's
+    offsets = torch.stack([q.get("run_offsets", q["offsets"]) for q in seqs]).contiguous()
 
     drag = DragPose(opt, temporal, means_latent, stds_latent, n_sequences=S, native_temporal=not getattr(args, "torch_temporal", False))
     drag.set_initial_state(torch.cat([q["z0"] for q in seqs], dim=0), np.stack([q["m"]["global_pos"][0] for q in seqs]),
@@ -369,6 +409,11 @@ def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
 def evaluate_files(args, paths, opt, encoder, temporal_pack, cfg, raw):
     """one or more files as sequences in lock-step"""
     seqs = [prepare_file(args, p, opt, encoder, cfg, raw) for p in paths]
+    for q in seqs:
+        if getattr(args, "calibrate_spec", None) is not None:
+            q["run_offsets"] = calibrate_file(args, q, opt, cfg, raw)
+        elif getattr(args, "model_skeleton", False):
+            q["run_offsets"] = torch.tensor(np.asarray(raw["offsets"], np.float32).reshape(NJ, 3), device=opt.device)
     results, elapsed, lam_tmp, has_temporal = run_sequences(args, seqs, opt, temporal_pack, cfg)
     out = []
     for q, r in zip(seqs, results):
@@ -479,6 +524,15 @@ def main(argv=None):
                          "the reference's extra terms join the LM loss as the solver's table, LM(terms=Terms.from_constraints(Constraints.reference())) "
                          "(dp_optimize_sequence_lm_terms, include/dragposer_sequence_lm_terms.h; --per-frame: dp_optimize_lm_terms).  Not with "
                          "--foot-lock, --tether, --balance or --gaps, and for a BVH with the model's own skeleton")
+    ap.add_argument("--calibrate", default=None, metavar="GROUPS[:FRAMES[:ROUNDS]]",
+                    help="a performer without a BVH file: ignore the clip's OFFSET table for the optimisation and fit the bone lengths from the "
+                         "tracker targets first -- GROUPS uniform | limbs | symmetric | per_bone (dragposer_amd.BoneGroups), FRAMES frames drawn "
+                         "evenly from the clip (default 256) as independent frames, ROUNDS rounds (default 6) of 50 iterations and one dp_fit_bones "
+                         "each (dragposer_amd.calibrate, include/dragposer_calibration.h) -- then run the clip with the fitted offsets.  Prints "
+                         "the fitted scales beside the clip's true bone-length ratios.  Not with --solver")
+    ap.add_argument("--model-skeleton", action="store_true",
+                    help="ignore the clip's OFFSET table for the optimisation and run on the model's own skeleton (what --calibrate starts from); "
+                         "the targets remain those of the clip's skeleton.  Not with --calibrate or --solver")
     ap.add_argument("--lockstep", action="store_true",
                     help="directory input: advance all files together, one kernel launch per frame index for all of them "
                          "(same per-file results; the reference evaluates them one after the other)")
@@ -520,6 +574,22 @@ def main(argv=None):
             if given:
                 raise SystemExit(f"--balance and {flag}: a table with points takes no holds, tethers, latent predictor or gaps (include/dragposer_points.h)")
         args.balance_spec = parse_balance(args.balance, args.balance_masses)
+    args.calibrate_spec = None
+    if args.calibrate is not None or args.model_skeleton:
+        if args.solver is not None:
+            raise SystemExit("--calibrate / --model-skeleton and --solver: the LM solver runs on the context's skeleton only (include/dragposer_lm.h, Not covered)")
+        if args.calibrate is not None and args.model_skeleton:
+            raise SystemExit("--calibrate and --model-skeleton: give one")
+    if args.calibrate is not None:
+        parts = args.calibrate.split(":")
+        try:
+            if not 1 <= len(parts) <= 3 or parts[0] not in ("uniform", "limbs", "symmetric", "per_bone"):
+                raise ValueError("GROUPS is uniform, limbs, symmetric or per_bone")
+            args.calibrate_spec = (parts[0], int(parts[1]) if len(parts) > 1 else 256, int(parts[2]) if len(parts) > 2 else 6)
+            if args.calibrate_spec[1] < 1 or args.calibrate_spec[2] < 1:
+                raise ValueError("FRAMES and ROUNDS are positive")
+        except ValueError as e:
+            raise SystemExit(f"--calibrate: expected GROUPS[:FRAMES[:ROUNDS]], got {args.calibrate!r} ({e})")
     args.solver_model = None
     if args.solver is not None:
         from .lm import LM

@@ -269,15 +269,16 @@ class LatentOptimizer:
         if rc != _lib.DP_OK:
             self._fail(rc)
 
-    def _batch(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked):
+    def _batch(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, positions_only=False):
+        """positions_only: the launch reads neither z_tgt nor tgt_rot (dp_fit_bones), which then stay NULL"""
         B, dev = int(z0.shape[0]), self.device
         batch = _lib.DpBatch()
         batch.n_frames = B
         batch.z0 = _check(z0, "z0", (B, LATENT), torch.float32, dev)
-        batch.z_tgt = _check(z_tgt, "z_tgt", (B, LATENT), torch.float32, dev)
+        batch.z_tgt = None if positions_only else _check(z_tgt, "z_tgt", (B, LATENT), torch.float32, dev)
         batch.cur_rot = _check(cur_rot, "cur_rot", (B, 4), torch.float32, dev)
         batch.tgt_pos = _check(tgt_pos, "tgt_pos", (B, NJ, 3), torch.float32, dev)
-        batch.tgt_rot = _check(tgt_rot, "tgt_rot", (B, NJ, 9), torch.float32, dev)
+        batch.tgt_rot = None if positions_only else _check(tgt_rot, "tgt_rot", (B, NJ, 9), torch.float32, dev)
         batch.w = _check(w, "w", (B, NJ, 2), torch.float32, dev)
         batch.tracked = _check(tracked, "tracked", (B, NJ), torch.uint8, dev)
         return batch
@@ -487,6 +488,40 @@ class LatentOptimizer:
         s, keep = terms.to_struct(B, dev, *_own_output("loss_terms", len(terms), B, dev, out, tensors, global_pos,
                                                        _TERMS_NEED_GLOBAL_POS if terms.needs_global_pos else None, wanted=outputs is None or "loss_terms" in names))
         self._call(self.lib.dp_optimize_lm_terms, C.byref(batch), C.byref(p), C.byref(s), C.byref(res), C.byref(ex))
+        del keep
+        return tensors
+
+    def fit_bones(self, z, cur_rot, tgt_pos, w, tracked, groups, base=None, prior=None, ridge=1e-3, outputs=None, out=None):
+        """Per-group bone scales from B frames of tracker data in one call (include/dragposer_calibration.h, dp_fit_bones): with the joint
+        rotations fixed at decode + FK of `z` [B,24] under `cur_rot` [B,4], the scales s of off_b = s[group(b)] * base_b that minimise the
+        frames' summed loss_pos + ridge |s - prior|^2.  `tgt_pos`, `w`, `tracked` as in `optimize` (no rotation targets, no z_tgt).
+        `groups`: a dragposer_amd.BoneGroups; `base` [22,3] host values (None: the context's bones); `prior` [K] host values (None: ones).
+        Returns dict(scales [K], offsets [22,3] -- pass it as `offsets=` to the next launch --, normal [K+1,K+1] float64, rms [2] (at the
+        prior, at the scales), info [2] int32 (frames used, DP_FIT_* flags), status [B] int32); `outputs`: the subset to produce (scales
+        always), `out`: storage for any of them.  The workspace is a buffer this optimiser keeps.  Asynchronous on torch's current stream,
+        no host synchronisation."""
+        B, dev, K = int(z.shape[0]), self.device, len(groups)
+        batch = self._batch(z, None, cur_rot, tgt_pos, None, w, tracked, positions_only=True)
+        fit, keep = groups.to_struct(base, prior, ridge)
+        need = int(self.lib.dp_fit_bones_workspace_bytes(B))
+        ws = getattr(self, "_fit_workspace", None)
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._fit_workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+        fit.workspace, fit.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        specs = {"scales": ((K,), torch.float32), "offsets": ((NJ, 3), torch.float32), "normal": ((K + 1, K + 1), torch.float64),
+                 "rms": ((2,), torch.float32), "info": ((2,), torch.int32), "status": ((B,), torch.int32)}
+        names = tuple(specs) if outputs is None else tuple(outputs)
+        unknown = [n for n in names if n not in specs]
+        if unknown:
+            raise ValueError(f"fit_bones: unknown output {unknown[0]!r}")
+        res, tensors = _lib.DpBoneFitResult(), {}
+        for name, (shape, dtype) in specs.items():
+            if name != "scales" and name not in names and not (out is not None and name in out):
+                continue
+            t = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
+            setattr(res, name, _check(t, name, shape, dtype, dev))
+            tensors[name] = t
+        self._call(self.lib.dp_fit_bones, C.byref(batch), C.byref(fit), C.byref(res))
         del keep
         return tensors
 
