@@ -2,47 +2,12 @@
 // stand-alone program that links dp_host.cpp against tests/host_san/fake_hip.cpp (no HIP runtime, no kernel unit) and walks the call's
 // refusals, in the header's order, on a context without a device.  Every sized struct is handed over in a heap block of exactly struct_size
 // bytes and `groups` / `base` / `prior` in blocks of exactly 22 ints / 66 floats / K floats, so a read past what the caller owns is an
-// error here.  Device pointers are a constant that is never dereferenced.  Built and run by tests/test_fit_bones_san.py; every condition
+// error here.  Device pointers are a constant that is never dereferenced.  Built and run by tests/test_host_san.py; every condition
 // is exact.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-
 #include "../../include/dragposer_calibration.h"
-
-extern "C" int dp_debug_host_ctx(dp_ctx**); // the library's private hook: a context with no device behind it
-
-#define CHECK(cond)                                                                      \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                                \
-        }                                                                                \
-    } while (0)
+#include "../host_san/san_support.h"
 
 namespace {
-
-float* const PTR = (float*)0x10000; // stands for a device pointer
-
-// a T in a heap block of exactly `size` bytes (default: sizeof(T))
-template <class T>
-struct Exact {
-    void* block;
-    explicit Exact(const T& init, size_t size = sizeof(T)) : block(std::malloc(size)) { std::memcpy(block, &init, size < sizeof(T) ? size : sizeof(T)); }
-    ~Exact() { std::free(block); }
-    Exact(const Exact&) = delete;
-    const T* get() const { return (const T*)block; }
-};
-
-// n values of T in a heap block of exactly n * sizeof(T) bytes
-template <class T>
-struct Block {
-    T* p;
-    explicit Block(int n) : p((T*)std::malloc((size_t)(n > 0 ? n : 1) * sizeof(T))) {}
-    ~Block() { std::free(p); }
-    Block(const Block&) = delete;
-};
 
 struct Case { // what one call is made of; the defaults are well-formed
     int K = 3, n_frames = 9;
@@ -81,26 +46,17 @@ int run(dp_ctx* ctx, const Case& c)
     r0.scales = c.null_scales ? nullptr : PTR;
     if (c.with_outputs) { r0.offsets = r0.rms = PTR; r0.normal = (double*)PTR; r0.info = r0.status = (int*)PTR; }
     Exact<dp_batch> b(b0);
-    Exact<dp_bone_fit> f(f0, c.fit_size < sizeof(dp_bone_fit) ? c.fit_size : sizeof(dp_bone_fit));
-    Exact<dp_bone_fit_result> r(r0, c.result_size < sizeof(dp_bone_fit_result) ? c.result_size : sizeof(dp_bone_fit_result));
+    Exact<dp_bone_fit> f(f0, cut<dp_bone_fit>(c.fit_size));
+    Exact<dp_bone_fit_result> r(r0, cut<dp_bone_fit_result>(c.result_size));
     return dp_fit_bones(ctx, c.null_batch ? nullptr : b.get(), c.null_fit ? nullptr : f.get(), c.null_result ? nullptr : r.get(), nullptr);
 }
-
-bool said(dp_ctx* ctx, const char* word) { return std::string(dp_last_error(ctx)).find(word) != std::string::npos; }
 
 } // namespace
 
 int main()
 {
-    dp_ctx* ctx = nullptr;
-    CHECK(dp_debug_host_ctx(&ctx) == DP_OK && ctx);
-    int n = 0;
-    const auto refused = [&](const Case& c, const char* word) {
-        CHECK(run(ctx, c) == DP_ERR_INVALID);
-        if (!said(ctx, word)) { std::fprintf(stderr, "expected '%s' in: %s\n", word, dp_last_error(ctx)); std::exit(1); }
-        CHECK(said(ctx, "dp_fit_bones"));
-        ++n;
-    };
+    Walker w("fit_bones", "dp_fit_bones");
+    const auto refused = [&](const Case& c, const char* word) { w.refused(run(w.ctx, c), word); };
     const float inf = __builtin_inff(), nan = __builtin_nanf("");
     CHECK(dp_fit_bones_workspace_bytes(0) == 0 && dp_fit_bones_workspace_bytes(-5) == 0);
     CHECK(dp_fit_bones_workspace_bytes(1) == dp_fit_bones_workspace_bytes(4) && dp_fit_bones_workspace_bytes(5) == 2 * dp_fit_bones_workspace_bytes(4));
@@ -113,9 +69,7 @@ int main()
         if (variant == 4) c.null_unread = true;   // z_tgt and tgt_rot are not read
         if (variant == 5) { c.K = 1; for (int j = 1; j < 22; ++j) c.groups[j] = j < 4 ? 0 : -1; c.ridge = 0.f; c.n_frames = 1; }
         if (variant == 6) { c.K = 21; for (int j = 1; j < 22; ++j) c.groups[j] = j - 1; c.groups[0] = 99; c.n_frames = 4096; } // (entry 0 is ignored)
-        CHECK(run(ctx, c) == DP_ERR_UNSUPPORTED);
-        CHECK(said(ctx, "dp_fit.hip"));
-        ++n;
+        w.unsupported(run(w.ctx, c), "dp_fit.hip");
     }
     // the refusals in the header's order: each is reported before every later one's fault
     { Case c; c.null_batch = true; c.K = 0; refused(c, "NULL batch, fit or result"); }
@@ -152,7 +106,6 @@ int main()
     { Case c; c.n_frames = -2; refused(c, "n_frames must be positive"); }
     { Case c; c.null_z0 = true; refused(c, "NULL input array"); }
     CHECK(dp_fit_bones(nullptr, nullptr, nullptr, nullptr, nullptr) == DP_ERR_INVALID);
-    dp_destroy(ctx);
-    std::printf("fit_bones: %d calls, all checks held\n", n);
+    w.done();
     return 0;
 }

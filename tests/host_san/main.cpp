@@ -6,14 +6,9 @@
 // Every buffer the library reads or writes is a heap block of EXACTLY the documented size (std::vector / malloc), so that one element too many
 // is a sanitizer report.  Strict part: any runtime call aborts.  Fake part: create / destroy of the three handles with every allocation failing
 // in turn.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <new>
 #include <random>
 #include <stdexcept>
-#include <string>
-#include <vector>
 
 #include "../../include/dragposer.h"
 #include "../../include/dragposer_constraints.h"
@@ -23,6 +18,7 @@
 #include "../../include/dragposer_terms.h"
 #include "../../dragposer_amd/csrc/dp_host_rt.h"
 #include "../../dragposer_amd/csrc/dp_kernel.h"
+#include "san_support.h"
 
 // fake_hip.cpp's controls
 void fake_hip_mode(bool fake);
@@ -40,18 +36,9 @@ int dp_debug_pack_w4_bp(const dp_folded*, const dp_model*, float*, float*);
 int dp_debug_pairs_w4(const dp_model*, void*);
 int dp_debug_pairs_w4_bp(const dp_model*, void*);
 int dp_debug_items(const dp_model*, void*);
-int dp_debug_host_ctx(dp_ctx**);
 int dp_debug_encoder_image(const dp_encoder_folded*, float*, int*, int);
 int dp_temporal_debug_pack(const dp_temporal_model*, float*, int);
 }
-
-#define CHECK(cond)                                                                      \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                                \
-        }                                                                                \
-    } while (0)
 
 namespace {
 
@@ -231,8 +218,6 @@ struct Sized {
     Sized(const Sized&) = delete;
     const T* get() const { return (const T*)block; }
 };
-
-float* const PTR = (float*)0x10000; // stands for a device pointer: never dereferenced on a context without a device
 
 struct Call { // the well-formed arguments of every entry point, and the sizes of this call's sized structs (0: sizeof)
     unsigned params = 0, result = 0, seq_results = 0, skel = 0, grad = 0, cons = 0, terms = 0;

@@ -2,37 +2,11 @@
 // program that links dp_host.cpp against tests/host_san/fake_hip.cpp (no HIP runtime, no kernel unit) and walks the call's refusals, in the
 // header's order, on a context without a device.  Every sized struct is handed over in a heap block of exactly struct_size bytes, so a
 // read past what the caller owns is an error here.  Device pointers are a constant that is never dereferenced.  Built and run by
-// tests/test_lm_san.py; every condition is exact.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-
+// tests/test_host_san.py; every condition is exact.
 #include "../../include/dragposer_lm.h"
-
-extern "C" int dp_debug_host_ctx(dp_ctx**); // the library's private hook: a context with no device behind it
-
-#define CHECK(cond)                                                                      \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                                \
-        }                                                                                \
-    } while (0)
+#include "../host_san/san_support.h"
 
 namespace {
-
-float* const PTR = (float*)0x10000; // stands for a device pointer
-
-// a T in a heap block of exactly `size` bytes (default: sizeof(T))
-template <class T>
-struct Exact {
-    void* block;
-    explicit Exact(const T& init, size_t size = sizeof(T)) : block(std::malloc(size)) { std::memcpy(block, &init, size < sizeof(T) ? size : sizeof(T)); }
-    ~Exact() { std::free(block); }
-    Exact(const Exact&) = delete;
-    const T* get() const { return (const T*)block; }
-};
 
 struct Case { // what one call is made of; the defaults are well-formed
     dp_lm_params p = DP_LM_PARAMS_INIT;
@@ -54,28 +28,19 @@ int run(dp_ctx* ctx, const Case& c)
     e0.struct_size = c.extra_size; e0.reserved0 = c.extra_reserved0;
     if (c.with_outputs) { e0.mu = e0.loss0 = PTR; e0.n_accepted = (int*)PTR; }
     Exact<dp_batch> b(b0);
-    Exact<dp_lm_params> p(c.p, c.p.struct_size < sizeof(dp_lm_params) ? c.p.struct_size : sizeof(dp_lm_params));
-    Exact<dp_result> r(r0, c.result_size < sizeof(dp_result) ? c.result_size : sizeof(dp_result));
-    Exact<dp_lm_extra> e(e0, c.extra_size < sizeof(dp_lm_extra) ? c.extra_size : sizeof(dp_lm_extra));
+    Exact<dp_lm_params> p(c.p, cut<dp_lm_params>(c.p.struct_size));
+    Exact<dp_result> r(r0, cut<dp_result>(c.result_size));
+    Exact<dp_lm_extra> e(e0, cut<dp_lm_extra>(c.extra_size));
     return dp_optimize_lm(ctx, c.null_batch ? nullptr : b.get(), c.null_params ? nullptr : p.get(), c.null_result ? nullptr : r.get(),
                           c.null_extra ? nullptr : e.get(), nullptr);
 }
-
-bool said(dp_ctx* ctx, const char* word) { return std::string(dp_last_error(ctx)).find(word) != std::string::npos; }
 
 } // namespace
 
 int main()
 {
-    dp_ctx* ctx = nullptr;
-    CHECK(dp_debug_host_ctx(&ctx) == DP_OK && ctx);
-    int n = 0;
-    const auto refused = [&](const Case& c, const char* word) {
-        CHECK(run(ctx, c) == DP_ERR_INVALID);
-        if (!said(ctx, word)) { std::fprintf(stderr, "expected '%s' in: %s\n", word, dp_last_error(ctx)); std::exit(1); }
-        CHECK(said(ctx, "dp_optimize_lm"));
-        ++n;
-    };
+    Walker w("lm", "dp_optimize_lm");
+    const auto refused = [&](const Case& c, const char* word) { w.refused(run(w.ctx, c), word); };
     const float inf = __builtin_inff(), nan = __builtin_nanf("");
     // well-formed: this link has no kernel unit, which the library says after every argument check
     for (int variant = 0; variant < 6; ++variant) {
@@ -85,9 +50,7 @@ int main()
         if (variant == 3) c.with_outputs = false;                                 // every pointer NULL
         if (variant == 4) { c.p.n_steps = DP_LM_MAX_STEPS; c.p.early_stop = 1; c.p.stop_eps_pos = 1e-4f; c.p.mu0 = c.p.mu_min; }
         if (variant == 5) { c.p.mu_min = c.p.mu_max = c.p.mu0 = 1.f; c.p.lambda_rot = 0.f; c.p.lambda_tmp = 0.f; }
-        CHECK(run(ctx, c) == DP_ERR_UNSUPPORTED);
-        CHECK(said(ctx, "dp_lm.hip"));
-        ++n;
+        w.unsupported(run(w.ctx, c), "dp_lm.hip");
     }
     // the refusals in the header's order: each is reported before every later one's fault
     { Case c; c.null_batch = true; c.p.n_steps = 0; refused(c, "NULL batch or params"); }
@@ -126,7 +89,6 @@ int main()
     { Case c; c.n_frames = -2; refused(c, "n_frames must be positive"); }
     { Case c; c.null_z_tgt = true; refused(c, "NULL input array"); }
     CHECK(dp_optimize_lm(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DP_ERR_INVALID);
-    dp_destroy(ctx);
-    std::printf("lm: %d calls, all checks held\n", n);
+    w.done();
     return 0;
 }

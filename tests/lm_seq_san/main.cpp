@@ -2,39 +2,11 @@
 // a stand-alone program that links dp_host.cpp against tests/host_san/fake_hip.cpp (no HIP runtime, no kernel unit) and walks the call's
 // refusals, in the header's order, on a context without a device.  Every sized struct is handed over in a heap block of exactly struct_size
 // bytes, so a read past what the caller owns is an error here.  Device pointers are a constant that is never dereferenced.  Built and run by
-// tests/test_lm_sequence_san.py; every condition is exact.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-
+// tests/test_host_san.py; every condition is exact.
 #include "../../include/dragposer_sequence_lm.h"
-
-extern "C" int dp_debug_host_ctx(dp_ctx**); // the library's private hook: a context with no device behind it
-
-#define CHECK(cond)                                                                      \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                                \
-        }                                                                                \
-    } while (0)
+#include "../host_san/san_support.h"
 
 namespace {
-
-float* const PTR = (float*)0x10000; // stands for a device pointer
-
-// a T in a heap block of exactly `size` bytes (default: sizeof(T))
-template <class T>
-struct Exact {
-    void* block;
-    explicit Exact(const T& init, size_t size = sizeof(T)) : block(std::malloc(size)) { std::memcpy(block, &init, size < sizeof(T) ? size : sizeof(T)); }
-    ~Exact() { std::free(block); }
-    Exact(const Exact&) = delete;
-    const T* get() const { return (const T*)block; }
-};
-template <class T>
-size_t block_of(unsigned size) { return size < sizeof(T) ? size : sizeof(T); }
 
 struct Case { // what one call is made of; the defaults are well-formed (targets from frames->z_tgt, no predictor)
     dp_lm_params p = DP_LM_PARAMS_INIT;
@@ -73,30 +45,21 @@ int run(dp_ctx* ctx, const Case& c)
     Exact<dp_seq_frames> f(f0);
     Exact<dp_seq_state> s(s0);
     Exact<dp_seq_step> a(a0);
-    Exact<dp_lm_params> p(c.p, block_of<dp_lm_params>(c.p.struct_size));
-    Exact<dp_seq_results> r(r0, block_of<dp_seq_results>(c.results_size));
-    Exact<dp_seq_lm_extra> e(e0, block_of<dp_seq_lm_extra>(c.extra_size));
-    Exact<dp_latent_ar> l(l0, block_of<dp_latent_ar>(c.ar_size));
+    Exact<dp_lm_params> p(c.p, cut<dp_lm_params>(c.p.struct_size));
+    Exact<dp_seq_results> r(r0, cut<dp_seq_results>(c.results_size));
+    Exact<dp_seq_lm_extra> e(e0, cut<dp_seq_lm_extra>(c.extra_size));
+    Exact<dp_latent_ar> l(l0, cut<dp_latent_ar>(c.ar_size));
     return dp_optimize_sequence_lm(ctx, c.n_seq, c.null_latent ? nullptr : PTR, c.null_frames ? nullptr : f.get(), c.null_params ? nullptr : p.get(),
                                    c.with_ar ? l.get() : nullptr, c.null_state ? nullptr : s.get(), c.null_adjust ? nullptr : a.get(),
                                    c.null_out ? nullptr : r.get(), c.null_extra ? nullptr : e.get(), nullptr);
 }
 
-bool said(dp_ctx* ctx, const char* word) { return std::string(dp_last_error(ctx)).find(word) != std::string::npos; }
-
 } // namespace
 
 int main()
 {
-    dp_ctx* ctx = nullptr;
-    CHECK(dp_debug_host_ctx(&ctx) == DP_OK && ctx);
-    int n = 0;
-    const auto refused = [&](const Case& c, const char* word) {
-        CHECK(run(ctx, c) == DP_ERR_INVALID);
-        if (!said(ctx, word)) { std::fprintf(stderr, "expected '%s' in: %s\n", word, dp_last_error(ctx)); std::exit(1); }
-        CHECK(said(ctx, "dp_optimize_sequence_lm"));
-        ++n;
-    };
+    Walker w("lm_seq", "dp_optimize_sequence_lm");
+    const auto refused = [&](const Case& c, const char* word) { w.refused(run(w.ctx, c), word); };
     const float nan = __builtin_nanf("");
     // well-formed: this link has no kernel unit, which the library says after every argument check
     for (int variant = 0; variant < 7; ++variant) {
@@ -107,9 +70,7 @@ int main()
         if (variant == 4) { c.with_ar = true; c.with_z_tgt = false; }              // the predictor is the targets' source
         if (variant == 5) { c.with_ar = true; c.with_z_tgt = false; c.order = DP_MAX_AR_ORDER; c.history = DP_MAX_AR_ORDER; c.n_heights = 0; }
         if (variant == 6) { c.adjust_joint = -1; c.adjust_target = -7; c.p.n_steps = DP_LM_MAX_STEPS; c.p.early_stop = 1; c.n_steps = 1; c.n_seq = 1; }
-        CHECK(run(ctx, c) == DP_ERR_UNSUPPORTED);
-        CHECK(said(ctx, "dp_lm_seq.hip"));
-        ++n;
+        w.unsupported(run(w.ctx, c), "dp_lm_seq.hip");
     }
     // the refusals in the header's order: each is reported before every later one's fault
     { Case c; c.n_seq = 0; c.p.struct_size = 4; refused(c, "n_sequences must be positive"); }
@@ -155,7 +116,6 @@ int main()
     { Case c; c.with_z_tgt = false; refused(c, "neither a predictor nor frames->z_tgt"); }                      // neither
     CHECK(dp_optimize_sequence_lm(nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DP_ERR_INVALID);
     CHECK(said(nullptr, "ctx is NULL"));
-    dp_destroy(ctx);
-    std::printf("lm_seq: %d calls, all checks held\n", n);
+    w.done();
     return 0;
 }

@@ -2,42 +2,15 @@
 // UndefinedBehaviorSanitizer: a stand-alone program that links dp_host.cpp against tests/host_san/fake_hip.cpp (no HIP runtime, no kernel
 // unit) and walks the call's refusals, in the header's order, on a context without a device.  Every sized struct is handed over in a heap
 // block of exactly struct_size bytes, and the table's 16 terms in a block of exactly 16 terms, so a read past what the caller owns is an
-// error here.  Device pointers are constants that are never dereferenced.  Built and run by tests/test_lm_sequence_terms_san.py; every
+// error here.  Device pointers are constants that are never dereferenced.  Built and run by tests/test_host_san.py; every
 // condition is exact.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-
 #include "../../include/dragposer_sequence_lm_terms.h"
-
-extern "C" int dp_debug_host_ctx(dp_ctx**); // the library's private hook: a context with no device behind it
-
-#define CHECK(cond)                                                                      \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                                \
-        }                                                                                \
-    } while (0)
+#include "../host_san/san_support.h"
 
 namespace {
 
-float* const PTR = (float*)0x10000;   // stands for a device pointer
 float* const GPOS = (float*)0x20000;  // ... for the state's global_pos
 float* const OTHER = (float*)0x30000; // ... for a global position that is not the state's
-
-// a T in a heap block of exactly `size` bytes (default: sizeof(T))
-template <class T>
-struct Exact {
-    void* block;
-    explicit Exact(const T& init, size_t size = sizeof(T)) : block(std::malloc(size)) { std::memcpy(block, &init, size < sizeof(T) ? size : sizeof(T)); }
-    ~Exact() { std::free(block); }
-    Exact(const Exact&) = delete;
-    const T* get() const { return (const T*)block; }
-};
-template <class T>
-size_t cut(unsigned size) { return size < sizeof(T) ? size : sizeof(T); }
 
 struct Case { // what one call is made of; the defaults are well-formed: 16 terms of every type, some with per-frame rows stepped per frame
     dp_lm_params p = DP_LM_PARAMS_INIT;
@@ -109,21 +82,12 @@ int run(dp_ctx* ctx, const Case& c)
     return rc;
 }
 
-bool said(dp_ctx* ctx, const char* word) { return std::string(dp_last_error(ctx)).find(word) != std::string::npos; }
-
 } // namespace
 
 int main()
 {
-    dp_ctx* ctx = nullptr;
-    CHECK(dp_debug_host_ctx(&ctx) == DP_OK && ctx);
-    int n = 0;
-    const auto refused = [&](const Case& c, const char* word) {
-        CHECK(run(ctx, c) == DP_ERR_INVALID);
-        if (!said(ctx, word)) { std::fprintf(stderr, "expected '%s' in: %s\n", word, dp_last_error(ctx)); std::exit(1); }
-        CHECK(said(ctx, "dp_optimize_sequence_lm_terms"));
-        ++n;
-    };
+    Walker w("lm_seq_terms", "dp_optimize_sequence_lm_terms");
+    const auto refused = [&](const Case& c, const char* word) { w.refused(run(w.ctx, c), word); };
     const float nan = __builtin_nanf("");
     // well-formed: this link has no kernel unit, which the library says after every argument check
     for (int variant = 0; variant < 8; ++variant) {
@@ -135,9 +99,7 @@ int main()
         if (variant == 5) c.terms_gp = GPOS; // the state's own array is accepted
         if (variant == 6) { c.with_ar = true; c.null_z_tgt = true; }
         if (variant == 7) { c.null_adjust = true; c.n_seq = 1; c.n_steps = 1; }
-        CHECK(run(ctx, c) == DP_ERR_UNSUPPORTED);
-        CHECK(said(ctx, "dp_lm_seq_terms.hip"));
-        ++n;
+        w.unsupported(run(w.ctx, c), "dp_lm_seq_terms.hip");
     }
     // the refusals in the header's order: each is reported before every later one's fault
     // 1. dp_optimize_sequence_lm's, up to and including dp_seq_lm_extra
@@ -192,7 +154,6 @@ int main()
     { Case c; c.with_ar = true; refused(c, "frames->z_tgt must be NULL"); }          // both
     { Case c; c.null_z_tgt = true; refused(c, "neither a predictor nor frames->z_tgt"); } // neither
     CHECK(dp_optimize_sequence_lm_terms(nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DP_ERR_INVALID);
-    dp_destroy(ctx);
-    std::printf("lm_seq_terms: %d calls, all checks held\n", n);
+    w.done();
     return 0;
 }

@@ -3,49 +3,12 @@
 // tests/host_san/fake_hip.cpp (no HIP runtime, no kernel unit) and walks take_points through well-formed and malformed structs, in the
 // header's order, on a context without a device.  dp_points is handed over in a heap block of exactly struct_size bytes, its coefficients
 // in one of exactly n_points * 22 floats and the term table in one of exactly n_terms entries, so a read past what the caller owns is an
-// error here.  Device pointers are a constant that is never dereferenced.  Built and run by tests/test_points_abi.py; every condition is
+// error here.  Device pointers are a constant that is never dereferenced.  Built and run by tests/test_host_san.py; every condition is
 // exact.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "../../include/dragposer_points.h"
-
-extern "C" int dp_debug_host_ctx(dp_ctx**); // the library's private hook: a context with no device behind it
-
-#define CHECK(cond)                                                                      \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                                \
-        }                                                                                \
-    } while (0)
+#include "../host_san/san_support.h"
 
 namespace {
-
-float* const PTR = (float*)0x10000; // stands for a device pointer
-
-// a T in a heap block of exactly `size` bytes (default: sizeof(T))
-template <class T>
-struct Exact {
-    void* block;
-    explicit Exact(const T& init, size_t size = sizeof(T)) : block(std::malloc(size)) { std::memcpy(block, &init, size < sizeof(T) ? size : sizeof(T)); }
-    ~Exact() { std::free(block); }
-    Exact(const Exact&) = delete;
-    const T* get() const { return (const T*)block; }
-};
-template <class T>
-struct Array { // exactly n entries (n = 0: a NULL pointer)
-    T* p;
-    explicit Array(const std::vector<T>& v) : p(v.empty() ? nullptr : (T*)std::malloc(v.size() * sizeof(T)))
-    {
-        if (p) std::memcpy(p, v.data(), v.size() * sizeof(T));
-    }
-    ~Array() { std::free(p); }
-    Array(const Array&) = delete;
-};
 
 std::vector<dp_term> good_terms()
 { // 0: a plane on point 1; 1: the balance band, point 0 against point 1; 2: point 2 pinned; 3: a point against a member joint; 4: an ALIGN of joints
@@ -89,10 +52,10 @@ const char* const NAMES[3] = {"dp_optimize_terms_points", "dp_optimize_terms_poi
 
 int run(dp_ctx* ctx, const Case& c)
 {
-    dp_params p0 = DP_PARAMS_INIT;
-    p0.n_iter = 10; p0.lr = c.lr; p0.beta1 = 0.9f; p0.beta2 = 0.999f; p0.eps = 1e-8f; p0.lambda_rot = 1.f; p0.lambda_tmp = 0.02f;
-    dp_skeleton_in s0 = DP_SKELETON_IN_INIT;
-    s0.offsets = PTR; s0.stride = c.skel_stride;
+    SeqArgs a; // (the params and the skeleton serve the per-frame calls as well)
+    a.frames.z_tgt = PTR;
+    a.params.lr = c.lr; a.params.lambda_tmp = 0.02f;
+    a.skeleton.stride = c.skel_stride;
     Array<dp_term> terms(c.terms);
     dp_terms t0 = DP_TERMS_INIT;
     t0.n_terms = (int)c.terms.size(); t0.terms = terms.p;
@@ -102,10 +65,9 @@ int run(dp_ctx* ctx, const Case& c)
     q0.struct_size = c.points_size; q0.reserved0 = c.reserved0; q0.reserved1 = c.reserved1;
     q0.n_points = c.n_points == -100 ? (int)c.coeff.size() / 22 : c.n_points;
     q0.coeff = c.null_coeff ? nullptr : coeff.p;
-    Exact<dp_params> p(p0);
-    Exact<dp_skeleton_in> s(s0);
+    SeqBlocks s(a);
     Exact<dp_terms> t(t0);
-    Exact<dp_points> q(q0, c.points_size < sizeof(dp_points) ? c.points_size : sizeof(dp_points));
+    Exact<dp_points> q(q0, cut<dp_points>(c.points_size));
     const dp_points* qp = c.null_points ? nullptr : q.get();
     if (c.which != SEQ) {
         dp_batch b0{};
@@ -114,48 +76,26 @@ int run(dp_ctx* ctx, const Case& c)
         r0.z = r0.pos = PTR;
         Exact<dp_batch> b(b0);
         Exact<dp_result> r(r0);
-        if (c.which == FRAME) return dp_optimize_terms_points(ctx, b.get(), p.get(), t.get(), qp, r.get(), nullptr);
-        return dp_optimize_terms_points_skeleton(ctx, b.get(), p.get(), t.get(), qp, s.get(), r.get(), nullptr);
+        if (c.which == FRAME) return dp_optimize_terms_points(ctx, b.get(), s.params.get(), t.get(), qp, r.get(), nullptr);
+        return dp_optimize_terms_points_skeleton(ctx, b.get(), s.params.get(), t.get(), qp, s.skeleton.get(), r.get(), nullptr);
     }
-    dp_seq_frames fr0{};
-    fr0.n_steps = 3; fr0.tgt_pos = fr0.tgt_rot = fr0.w = fr0.z_tgt = PTR; fr0.tracked = (const unsigned char*)PTR;
-    dp_seq_state st0{};
-    st0.global_pos = st0.global_rot = st0.latent_buf = st0.disp_buf = st0.heights_buf = PTR; st0.history = 60; st0.n_heights = 2;
-    st0.height_joints[0] = 4; st0.height_joints[1] = 8;
-    dp_seq_step adj0{};
-    adj0.adjust_joint = 0; adj0.adjust_target_joint = 13; adj0.adjust_weight = 0.5f;
-    dp_seq_results o0 = DP_SEQ_RESULTS_INIT;
-    o0.pose_ret = o0.pos_ret = o0.loss = o0.hist_scratch = PTR;
-    dp_seq_extra e0 = DP_SEQ_EXTRA_INIT;
-    e0.loss_terms = e0.joint_pos = PTR;
     t0.global_pos = nullptr; // (a sequence reads the state's own)
     Exact<dp_terms> ts(t0);
-    Exact<dp_seq_frames> fr(fr0);
-    Exact<dp_seq_state> st(st0);
-    Exact<dp_seq_step> adj(adj0);
-    Exact<dp_seq_results> o(o0);
-    Exact<dp_seq_extra> e(e0);
-    return dp_optimize_sequence_terms_points(ctx, 4, PTR, fr.get(), p.get(), ts.get(), qp, c.with_skeleton ? s.get() : nullptr, st.get(), adj.get(), o.get(),
-                                             c.with_extra ? e.get() : nullptr, nullptr);
+    return dp_optimize_sequence_terms_points(ctx, 4, PTR, s.frames.get(), s.params.get(), ts.get(), qp, c.with_skeleton ? s.skeleton.get() : nullptr, s.state.get(),
+                                             s.step.get(), s.results.get(), c.with_extra ? s.extra.get() : nullptr, nullptr);
 }
-
-bool said(dp_ctx* ctx, const char* word) { return std::string(dp_last_error(ctx)).find(word) != std::string::npos; }
 
 } // namespace
 
 int main()
 {
-    dp_ctx* ctx = nullptr;
-    CHECK(dp_debug_host_ctx(&ctx) == DP_OK && ctx);
-    int n = 0;
+    Walker w("points", NAMES[FRAME]);
     const float inf = __builtin_inff(), nan = __builtin_nanf("");
     for (const Which which : {FRAME, SKEL, SEQ}) {
+        w.entry_point = NAMES[which];
         const auto refused = [&](Case c, const char* word) {
             c.which = which;
-            CHECK(run(ctx, c) == DP_ERR_INVALID);
-            if (!said(ctx, word)) { std::fprintf(stderr, "%s: expected '%s' in: %s\n", NAMES[which], word, dp_last_error(ctx)); std::exit(1); }
-            CHECK(said(ctx, NAMES[which]));
-            ++n;
+            w.refused(run(w.ctx, c), word);
         };
         // well-formed: this link has no kernel unit, which the library says after every argument check
         for (int variant = 0; variant < 6; ++variant) {
@@ -171,9 +111,8 @@ int main()
             }
             if (variant == 4) { c.with_extra = false; c.with_skeleton = false; c.skel_stride = 0; }
             if (variant == 5) { c.terms[1].joint_b = 22; c.coeff[0] += 5e-5f; }                // the same point twice; a sum within the tolerance
-            CHECK(run(ctx, c) == DP_ERR_UNSUPPORTED);
-            CHECK(said(ctx, "dp_cons_points.hip") && said(ctx, NAMES[which]));
-            ++n;
+            w.unsupported(run(w.ctx, c), "dp_cons_points.hip");
+            CHECK(said(w.ctx, NAMES[which]));
         }
         // dp_points' own refusals, in the header's order: each is reported with every later one's fault present as well
         { Case c; c.null_points = true; refused(c, "NULL"); }
@@ -210,7 +149,6 @@ int main()
     CHECK(dp_optimize_terms_points(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DP_ERR_INVALID);
     CHECK(dp_optimize_terms_points_skeleton(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DP_ERR_INVALID);
     CHECK(dp_optimize_sequence_terms_points(nullptr, 4, PTR, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DP_ERR_INVALID);
-    dp_destroy(ctx);
-    std::printf("points: %d calls, all checks held\n", n);
+    w.done();
     return 0;
 }

@@ -1,13 +1,12 @@
 """CPU: terms on weighted joint combinations (include/dragposer_points.h) -- dragposer_amd.Point / Points and what Terms.check accepts
 with them, the header against the C compiler and the binding, the unit's build flags, the three kernels' register and LDS budget, the
-refusals of the three entry points on a context without a device, what the Python layer refuses, and the stand-alone sanitizer program
-tests/points_san/main.cpp.  No compute call is made here (the GPU side is tests/test_hip_points.py)."""
+refusals of the three entry points on a context without a device, and what the Python layer refuses.  No compute call is made here (the
+GPU side is tests/test_hip_points.py, the sanitized walk tests/points_san/main.cpp, run by tests/test_host_san.py)."""
 import ctypes as C
 import os
 import re
 import shutil
 import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
@@ -15,7 +14,7 @@ import __graft_entry__ as G
 from dragposer_amd import Point, Points, _lib
 from dragposer_amd.terms import Term, Terms
 from test_build_quality import _kernel_notes  # (the flags __graft_entry__ compiles each unit with)
-from test_host_san import CSRC, CXXFLAGS, ROOT, SAN
+from test_host_san import ROOT
 from test_sequence_constraints_abi import _args, _host_ctx
 from test_latent_ar_abi import _frames
 from test_terms_abi import _table
@@ -327,28 +326,3 @@ def test_the_test_only_library_declines():
         assert rc == _lib.DP_ERR_UNSUPPORTED and "test-only" in lib.dp_last_error(ctx).decode()
     finally:
         lib.dp_destroy(ctx)
-
-
-# ---------------------------------------------------------------------------------------------- the host code under sanitizers
-SAN_UNITS = [os.path.join(ROOT, "tests", "points_san", "main.cpp"), os.path.join(ROOT, "tests", "host_san", "fake_hip.cpp"),
-             os.path.join(CSRC, "dp_host.cpp"), os.path.join(CSRC, "dp_w16_host.cpp")]  # (dp_create packs dp_w16's image)
-
-
-def test_the_points_calls_under_sanitizers(tmp_path):
-    """tests/points_san/main.cpp, built with -fsanitize=address,undefined against the fake runtime and run as a child process: no GPU,
-    nothing loaded into this interpreter"""
-    cxx = os.environ.get("CXX", "g++")
-
-    def compile_unit(src):
-        obj = str(tmp_path / (os.path.basename(src) + ".o"))
-        subprocess.run([cxx] + CXXFLAGS + ["-c", src, "-o", obj], check=True, timeout=600)
-        return obj
-
-    with ThreadPoolExecutor(max_workers=len(SAN_UNITS)) as ex:
-        objs = list(ex.map(compile_unit, SAN_UNITS))
-    exe = str(tmp_path / "points_san")
-    subprocess.run([cxx] + SAN + ["-static-libasan", "-static-libubsan"] + objs + ["-o", exe], check=True, timeout=600)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "all checks held" in r.stdout and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr

@@ -1,6 +1,7 @@
 """CPU: the additions of include/dragposer_unity.h for the live step (terms, holds, gaps, the latent AR predictor, drag_pose_present and the
 read-backs): declared in the header, exported by libDragPoserDLL.so, and each setter's refusals that need no device -- its argument checks
-first, then its own "call load_models first".  The GPU side is tests/test_hip_unity_live.py, the sanitized walk tests/test_unity_live_san.py."""
+first, then its own "call load_models first".  The GPU side is tests/test_hip_unity_live.py, the sanitized walk tests/unity_san/main.cpp
+(run by tests/test_host_san.py)."""
 import ctypes as C
 import os
 import re

@@ -3,48 +3,11 @@
 // unit) and walks take_tethers through well-formed and malformed structs, in the header's order, on a context without a device.  Every
 // sized struct is handed over in a heap block of exactly struct_size bytes, the term table in one of exactly n_terms entries, the holds and
 // the tethers arrays in ones of exactly n_holds and n_tethers entries, so a read past what the caller owns is an error here.  Device
-// pointers are a constant that is never dereferenced.  Built and run by tests/test_tethers_san.py; every condition is exact.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
+// pointers are a constant that is never dereferenced.  Built and run by tests/test_host_san.py; every condition is exact.
 #include "../../include/dragposer_tethers.h"
-
-extern "C" int dp_debug_host_ctx(dp_ctx**); // the library's private hook: a context with no device behind it
-
-#define CHECK(cond)                                                                      \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                                \
-        }                                                                                \
-    } while (0)
+#include "../host_san/san_support.h"
 
 namespace {
-
-float* const PTR = (float*)0x10000; // stands for a device pointer
-
-// a T in a heap block of exactly `size` bytes (default: sizeof(T))
-template <class T>
-struct Exact {
-    void* block;
-    explicit Exact(const T& init, size_t size = sizeof(T)) : block(std::malloc(size)) { std::memcpy(block, &init, size < sizeof(T) ? size : sizeof(T)); }
-    ~Exact() { std::free(block); }
-    Exact(const Exact&) = delete;
-    const T* get() const { return (const T*)block; }
-};
-template <class T>
-struct Array { // exactly n entries (n = 0: a NULL pointer)
-    T* p;
-    explicit Array(const std::vector<T>& v) : p(v.empty() ? nullptr : (T*)std::malloc(v.size() * sizeof(T)))
-    {
-        if (p) std::memcpy(p, v.data(), v.size() * sizeof(T));
-    }
-    ~Array() { std::free(p); }
-    Array(const Array&) = delete;
-};
 
 std::vector<dp_term> good_terms()
 { // 0: a plane; 1: the held pin; 2, 3: the tethered band and pin; 4: a joint-DISTANCE term
@@ -75,22 +38,9 @@ struct Case { // what one call is made of; the defaults are well-formed
 
 int run(dp_ctx* ctx, const Case& c)
 {
-    dp_seq_frames fr0{};
-    fr0.n_steps = 3; fr0.tgt_pos = fr0.tgt_rot = fr0.w = PTR; fr0.tracked = (const unsigned char*)PTR;
-    fr0.z_tgt = c.z_tgt ? PTR : nullptr;
-    dp_params p0 = DP_PARAMS_INIT;
-    p0.n_iter = 10; p0.lr = c.lr; p0.beta1 = 0.9f; p0.beta2 = 0.999f; p0.eps = 1e-8f; p0.lambda_rot = 1.f; p0.lambda_tmp = 0.02f;
-    dp_seq_state st0{};
-    st0.global_pos = st0.global_rot = st0.latent_buf = st0.disp_buf = st0.heights_buf = PTR; st0.history = 60; st0.n_heights = 2;
-    st0.height_joints[0] = 4; st0.height_joints[1] = 8;
-    dp_seq_step adj0{};
-    adj0.adjust_joint = 0; adj0.adjust_target_joint = 13; adj0.adjust_weight = 0.5f;
-    dp_seq_results q0 = DP_SEQ_RESULTS_INIT;
-    q0.pose_ret = q0.pos_ret = q0.loss = q0.hist_scratch = PTR;
-    dp_seq_extra e0 = DP_SEQ_EXTRA_INIT;
-    e0.loss_terms = e0.joint_pos = PTR;
-    dp_skeleton_in s0 = DP_SKELETON_IN_INIT;
-    s0.offsets = PTR; s0.stride = DP_SKELETON_STRIDE;
+    SeqArgs a;
+    a.frames.z_tgt = c.z_tgt ? PTR : nullptr;
+    a.params.lr = c.lr; a.params.lambda_tmp = 0.02f;
     Array<dp_term> terms(c.terms);
     dp_terms t0 = DP_TERMS_INIT;
     t0.n_terms = (int)c.terms.size(); t0.terms = terms.p;
@@ -107,38 +57,23 @@ int run(dp_ctx* ctx, const Case& c)
     te0.n_tethers = c.n_tethers == -100 ? (int)c.tethers.size() : c.n_tethers;
     te0.tethers = c.null_tether_array ? nullptr : tethers.p;
     te0.state = c.null_tether_state || c.tethers.empty() ? nullptr : PTR; te0.trace = c.with_tether_trace ? PTR : nullptr;
-    Exact<dp_seq_frames> fr(fr0);
-    Exact<dp_params> p(p0);
-    Exact<dp_seq_state> st(st0);
-    Exact<dp_seq_step> adj(adj0);
-    Exact<dp_seq_results> q(q0);
-    Exact<dp_seq_extra> e(e0);
-    Exact<dp_skeleton_in> s(s0);
+    SeqBlocks b(a);
     Exact<dp_terms> t(t0);
     Exact<dp_holds> h(h0);
     Exact<dp_latent_ar> r(r0);
     Exact<dp_gaps> g(g0);
-    Exact<dp_tethers> te(te0, c.tethers_size < sizeof(dp_tethers) ? c.tethers_size : sizeof(dp_tethers));
-    return dp_optimize_sequence_tethers(ctx, 4, PTR, fr.get(), p.get(), t.get(), c.null_holds_struct ? nullptr : h.get(), c.null_ar ? nullptr : r.get(),
-                                        g.get(), c.null_tethers ? nullptr : te.get(), c.with_skeleton ? s.get() : nullptr, st.get(), adj.get(), q.get(),
-                                        c.with_extra ? e.get() : nullptr, nullptr);
+    Exact<dp_tethers> te(te0, cut<dp_tethers>(c.tethers_size));
+    return dp_optimize_sequence_tethers(ctx, 4, PTR, b.frames.get(), b.params.get(), t.get(), c.null_holds_struct ? nullptr : h.get(), c.null_ar ? nullptr : r.get(),
+                                        g.get(), c.null_tethers ? nullptr : te.get(), c.with_skeleton ? b.skeleton.get() : nullptr, b.state.get(), b.step.get(),
+                                        b.results.get(), c.with_extra ? b.extra.get() : nullptr, nullptr);
 }
-
-bool said(dp_ctx* ctx, const char* word) { return std::string(dp_last_error(ctx)).find(word) != std::string::npos; }
 
 } // namespace
 
 int main()
 {
-    dp_ctx* ctx = nullptr;
-    CHECK(dp_debug_host_ctx(&ctx) == DP_OK && ctx);
-    int n = 0;
-    const auto refused = [&](const Case& c, const char* word) {
-        CHECK(run(ctx, c) == DP_ERR_INVALID);
-        if (!said(ctx, word)) { std::fprintf(stderr, "expected '%s' in: %s\n", word, dp_last_error(ctx)); std::exit(1); }
-        CHECK(said(ctx, "dp_optimize_sequence_tethers"));
-        ++n;
-    };
+    Walker w("tethers", "dp_optimize_sequence_tethers");
+    const auto refused = [&](const Case& c, const char* word) { w.refused(run(w.ctx, c), word); };
     const float inf = __builtin_inff(), nan = __builtin_nanf("");
     // well-formed: this link has no kernel unit, which the library says after every argument check
     for (int variant = 0; variant < 9; ++variant) {
@@ -151,9 +86,7 @@ int main()
         if (variant == 6) { c.null_holds_struct = true; c.tethers = {{1, 1.f}, {2, 0.f}, {3, 0.25f}}; } // the pin is free to be tethered without its hold
         if (variant == 7) { c.holds.clear(); c.tethers = {{3, 0.f}, {1, 1.f}, {2, 1.f}}; c.null_ar = true; c.z_tgt = true; }
         if (variant == 8) { c.tethers = {{3, 0.f}}; c.terms.resize(4); }     // the table's last term, of a table of exactly four
-        CHECK(run(ctx, c) == DP_ERR_UNSUPPORTED);
-        CHECK(said(ctx, "dp_cons_tether.hip"));
-        ++n;
+        w.unsupported(run(w.ctx, c), "dp_cons_tether.hip");
     }
     // dp_tethers' own refusals, in the header's order: each is reported before every later one's fault
     { Case c; c.null_tethers = true; refused(c, "NULL"); }
@@ -189,7 +122,6 @@ int main()
     { Case c; c.null_ar = true; c.z_tgt = true; c.n_tethers = -1; refused(c, "dp_tethers.n_tethers"); }
     CHECK(dp_optimize_sequence_tethers(nullptr, 4, PTR, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                        nullptr) == DP_ERR_INVALID);
-    dp_destroy(ctx);
-    std::printf("tethers: %d calls, all checks held\n", n);
+    w.done();
     return 0;
 }

@@ -2,42 +2,19 @@
 // stand-alone program that links dp_unity.cpp and the library's host files against tests/host_san/fake_hip.cpp (one malloc-backed device, no
 // HIP runtime, no kernel unit).  Every array a caller hands over lives in a heap block of exactly its size -- the term table, the holds, the
 // coefficients and the bias, the targets, `present` and the results -- and every device block is a malloc of exactly what the plug-in asked
-// for, so a read or write past either is an error here.  Built and run by tests/test_unity_live_san.py, which passes: the BVH clip, a model
+// for, so a read or write past either is an error here.  Built and run by tests/test_host_san.py, which passes: the BVH clip, a model
 // folder without temporal.bin, one with it, and a folder to write the latent_ar.bin variants into.  Every condition is exact.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <fstream>
-#include <string>
-#include <vector>
 
 #include "../../include/dragposer_unity.h"
+#include "../host_san/san_support.h"
 
 void fake_hip_mode(bool fake); // tests/host_san/fake_hip.cpp
 int fake_hip_outstanding();
 
-#define CHECK(cond)                                                                      \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                                \
-        }                                                                                \
-    } while (0)
-
 namespace {
 
 int n_checks = 0;
-
-template <class T>
-struct Block { // exactly n entries on the heap (n = 0: a NULL pointer)
-    T* p;
-    explicit Block(const std::vector<T>& v) : p(v.empty() ? nullptr : (T*)std::malloc(v.size() * sizeof(T)))
-    {
-        if (p) std::memcpy(p, v.data(), v.size() * sizeof(T));
-    }
-    ~Block() { std::free(p); }
-    Block(const Block&) = delete;
-};
 
 void said(DragPoser* h, const char* word)
 {
@@ -88,22 +65,22 @@ std::string write_bin(const std::string& path, const std::vector<Spec>& ts, long
 
 void setters_before_load_models(DragPoser* h)
 {
-    { Block<dp_term> t(table(17)); drag_poser_set_terms(h, 17, t.p, 1); said(h, "nTerms 17 outside 0..16"); }
-    { Block<dp_term> t(table(2)); drag_poser_set_terms(h, 2, t.p, 3); said(h, "upAxis 3 outside 0..2"); }
-    { Block<dp_term> t(table(2)); drag_poser_set_terms(h, -1, t.p, 1); said(h, "nTerms -1"); }
+    { Array<dp_term> t(table(17)); drag_poser_set_terms(h, 17, t.p, 1); said(h, "nTerms 17 outside 0..16"); }
+    { Array<dp_term> t(table(2)); drag_poser_set_terms(h, 2, t.p, 3); said(h, "upAxis 3 outside 0..2"); }
+    { Array<dp_term> t(table(2)); drag_poser_set_terms(h, -1, t.p, 1); said(h, "nTerms -1"); }
     { drag_poser_set_terms(h, 2, nullptr, 1); said(h, "NULL terms"); }
     {
         std::vector<dp_term> v = table(3);
-        v[2].per_frame = (const float*)0x10000;
-        Block<dp_term> t(v);
+        v[2].per_frame = PTR;
+        Array<dp_term> t(v);
         drag_poser_set_terms(h, 3, t.p, 1);
         said(h, "term 2: per_frame must be NULL");
     }
-    { Block<dp_term> t(table(2)); drag_poser_set_terms(h, 2, t.p, 1); said(h, "drag_poser_set_terms: call load_models first"); }
-    { Block<dp_hold> b(std::vector<dp_hold>(1, dp_hold{1, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); said(h, "drag_poser_set_holds: call load_models first"); }
+    { Array<dp_term> t(table(2)); drag_poser_set_terms(h, 2, t.p, 1); said(h, "drag_poser_set_terms: call load_models first"); }
+    { Array<dp_hold> b(std::vector<dp_hold>(1, dp_hold{1, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); said(h, "drag_poser_set_holds: call load_models first"); }
     drag_poser_set_gaps(h, 5, 0.9f); said(h, "drag_poser_set_gaps: call load_models first");
     {
-        Block<float> A(std::vector<float>(24 * 24, 0.f)), c(std::vector<float>(24, 0.f));
+        Array<float> A(std::vector<float>(24 * 24, 0.f)), c(std::vector<float>(24, 0.f));
         drag_poser_set_latent_ar(h, 1, A.p, c.p);
         said(h, "drag_poser_set_latent_ar: call load_models first");
     }
@@ -112,17 +89,17 @@ void setters_before_load_models(DragPoser* h)
 void setters(DragPoser* h)
 {
     // terms: the table is copied out of a block of exactly nTerms entries
-    { Block<dp_term> t(table(16)); drag_poser_set_terms(h, 16, t.p, 2); fine(h); }
-    { Block<dp_term> t(table(17)); drag_poser_set_terms(h, 17, t.p, 1); said(h, "nTerms 17"); }
-    { Block<dp_term> t(table(2)); drag_poser_set_terms(h, 2, t.p, 1); fine(h); }
+    { Array<dp_term> t(table(16)); drag_poser_set_terms(h, 16, t.p, 2); fine(h); }
+    { Array<dp_term> t(table(17)); drag_poser_set_terms(h, 17, t.p, 1); said(h, "nTerms 17"); }
+    { Array<dp_term> t(table(2)); drag_poser_set_terms(h, 2, t.p, 1); fine(h); }
     // holds
-    { Block<dp_hold> b(std::vector<dp_hold>(5, dp_hold{1, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 5, b.p); said(h, "nHolds 5 outside 0..4"); }
+    { Array<dp_hold> b(std::vector<dp_hold>(5, dp_hold{1, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 5, b.p); said(h, "nHolds 5 outside 0..4"); }
     drag_poser_set_holds(h, -1, nullptr); said(h, "nHolds -1");
     drag_poser_set_holds(h, 2, nullptr); said(h, "NULL holds");
-    { Block<dp_hold> b(std::vector<dp_hold>(1, dp_hold{2, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); said(h, "term 2 outside the table of 2"); }
-    { Block<dp_hold> b(std::vector<dp_hold>(1, dp_hold{-1, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); said(h, "term -1 outside"); }
-    { Block<dp_hold> b(std::vector<dp_hold>(1, dp_hold{1, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); fine(h); }
-    { Block<dp_term> t(table(1)); drag_poser_set_terms(h, 1, t.p, 1); said(h, "a hold refers to term 1"); } // (the table may not shrink under a hold)
+    { Array<dp_hold> b(std::vector<dp_hold>(1, dp_hold{2, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); said(h, "term 2 outside the table of 2"); }
+    { Array<dp_hold> b(std::vector<dp_hold>(1, dp_hold{-1, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); said(h, "term -1 outside"); }
+    { Array<dp_hold> b(std::vector<dp_hold>(1, dp_hold{1, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); fine(h); }
+    { Array<dp_term> t(table(1)); drag_poser_set_terms(h, 1, t.p, 1); said(h, "a hold refers to term 1"); } // (the table may not shrink under a hold)
     // gaps
     drag_poser_set_gaps(h, -1, 0.9f); said(h, "maxHold -1 outside 0..65535");
     drag_poser_set_gaps(h, 65536, 0.9f); said(h, "maxHold 65536");
@@ -133,14 +110,14 @@ void setters(DragPoser* h)
     drag_poser_set_gaps(h, 5, 0.9f); fine(h);
     // the predictor: coeffs in a block of exactly order * 576 floats, the bias in one of 24
     {
-        Block<float> A(std::vector<float>(4 * 576, 0.01f)), c(std::vector<float>(24, 0.f));
+        Array<float> A(std::vector<float>(4 * 576, 0.01f)), c(std::vector<float>(24, 0.f));
         drag_poser_set_latent_ar(h, 5, A.p, c.p); said(h, "order 5 outside 0..4");
         drag_poser_set_latent_ar(h, -1, A.p, c.p); said(h, "order -1");
         drag_poser_set_latent_ar(h, 2, nullptr, c.p); said(h, "NULL coeffs or bias");
         drag_poser_set_latent_ar(h, 2, A.p, nullptr); said(h, "NULL coeffs or bias");
         drag_poser_set_latent_ar(h, 4, A.p, c.p); fine(h);
     }
-    { Block<float> A(std::vector<float>(1 * 576, 0.01f)), c(std::vector<float>(24, 0.f)); drag_poser_set_latent_ar(h, 1, A.p, c.p); fine(h); }
+    { Array<float> A(std::vector<float>(1 * 576, 0.01f)), c(std::vector<float>(24, 0.f)); drag_poser_set_latent_ar(h, 1, A.p, c.p); fine(h); }
     drag_poser_set_latent_ar(h, 0, nullptr, nullptr); fine(h); // off
 }
 
@@ -174,13 +151,13 @@ void a_frame(DragPoser* h, int nEE)
     const int iters = drag_poser_last_iterations(h), status = drag_poser_last_status(h);
     std::vector<dp_float3> tp((size_t)nEE, dp_float3{0.1f, 0.9f, 0.2f});
     tp[1].y = __builtin_nanf(""); // (a sample lost through NaN travels as it is)
-    Block<dp_float3> P(tp);
-    Block<dp_quaternion> Q(std::vector<dp_quaternion>((size_t)nEE, dp_quaternion{0.5f, 0.5f, -0.5f, 0.5f}));
+    Array<dp_float3> P(tp);
+    Array<dp_quaternion> Q(std::vector<dp_quaternion>((size_t)nEE, dp_quaternion{0.5f, 0.5f, -0.5f, 0.5f}));
     std::vector<unsigned char> pr((size_t)nEE, 1);
     pr[nEE - 1] = 0;
-    Block<unsigned char> present(pr);
-    Block<dp_quaternion> pose(std::vector<dp_quaternion>(22, dp_quaternion{9.f, 9.f, 9.f, 9.f}));
-    Block<dp_float3> pos(std::vector<dp_float3>(1, dp_float3{9.f, 9.f, 9.f}));
+    Array<unsigned char> present(pr);
+    Array<dp_quaternion> pose(std::vector<dp_quaternion>(22, dp_quaternion{9.f, 9.f, 9.f, 9.f}));
+    Array<dp_float3> pos(std::vector<dp_float3>(1, dp_float3{9.f, 9.f, 9.f}));
     drag_pose_present(h, nEE, P.p, Q.p, present.p, pose.p, pos.p);
     said(h, "dp_cons_live.hip"); // "this library was linked without ..."
     drag_pose_present(h, nEE, P.p, Q.p, nullptr, pose.p, pos.p);
@@ -195,7 +172,7 @@ void a_frame(DragPoser* h, int nEE)
     std::memset(codes, 7, sizeof(codes));
     drag_poser_get_gap_codes(h, codes);
     for (int j = 0; j < 22; ++j) CHECK(codes[j] == 0);
-    Block<float> rows(std::vector<float>(4, 7.f)); // one hold: exactly [1][4]
+    Array<float> rows(std::vector<float>(4, 7.f)); // one hold: exactly [1][4]
     drag_poser_get_hold_state(h, rows.p);
     for (int c = 0; c < 4; ++c) CHECK(rows.p[c] == 0.f);
     n_checks += 3;
@@ -223,11 +200,11 @@ int main(int argc, char** argv)
     set_optim_params(h, 1e-4f, 1e-2f, 10, 1e-2f);
     init_drag_model(h, dp_float3{0.1f, 0.2f, 0.3f}, dp_quaternion{1.f, 0.f, 0.f, 0.f}); fine(h);
     {   // nothing configured yet: `present` has nothing to belong to
-        Block<dp_float3> P(std::vector<dp_float3>(6, dp_float3{0.f, 1.f, 0.f}));
-        Block<dp_quaternion> Q(std::vector<dp_quaternion>(6, dp_quaternion{1.f, 0.f, 0.f, 0.f}));
-        Block<unsigned char> present(std::vector<unsigned char>(6, 1));
-        Block<dp_quaternion> pose(std::vector<dp_quaternion>(22, dp_quaternion{9.f, 9.f, 9.f, 9.f}));
-        Block<dp_float3> pos(std::vector<dp_float3>(1, dp_float3{9.f, 9.f, 9.f}));
+        Array<dp_float3> P(std::vector<dp_float3>(6, dp_float3{0.f, 1.f, 0.f}));
+        Array<dp_quaternion> Q(std::vector<dp_quaternion>(6, dp_quaternion{1.f, 0.f, 0.f, 0.f}));
+        Array<unsigned char> present(std::vector<unsigned char>(6, 1));
+        Array<dp_quaternion> pose(std::vector<dp_quaternion>(22, dp_quaternion{9.f, 9.f, 9.f, 9.f}));
+        Array<dp_float3> pos(std::vector<dp_float3>(1, dp_float3{9.f, 9.f, 9.f}));
         drag_pose_present(h, 6, P.p, Q.p, present.p, pose.p, pos.p);
         said(h, "`present` belongs to the gaps");
     }
@@ -241,7 +218,7 @@ int main(int argc, char** argv)
     drag_poser_set_latent(h, z); // (it reports through the same message but does not clear it: as before)
     init_drag_model(h, dp_float3{0.f, 0.f, 0.f}, dp_quaternion{1.f, 0.f, 0.f, 0.f}); fine(h);
     load_models(h, argv[2]); fine(h); // again: the device blocks are replaced and the additions forgotten
-    { Block<dp_hold> b(std::vector<dp_hold>(1, dp_hold{0, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); said(h, "term 0 outside the table of 0"); }
+    { Array<dp_hold> b(std::vector<dp_hold>(1, dp_hold{0, 0.f, 0.f, 0.1f})); drag_poser_set_holds(h, 1, b.p); said(h, "term 0 outside the table of 0"); }
     destroy_drag_poser(h);
 
     // beside a loaded temporal model the predictor is refused: the targets have one source
@@ -250,7 +227,7 @@ int main(int argc, char** argv)
     load_models(g, argv[3]); fine(g);
     CHECK(drag_poser_has_temporal(g) == 1);
     {
-        Block<float> A(std::vector<float>(2 * 576, 0.01f)), c(std::vector<float>(24, 0.f));
+        Array<float> A(std::vector<float>(2 * 576, 0.01f)), c(std::vector<float>(24, 0.f));
         drag_poser_set_latent_ar(g, 2, A.p, c.p);
         said(g, "the targets have one source");
         drag_poser_set_latent_ar(g, 0, A.p, c.p); fine(g);
