@@ -6,6 +6,7 @@ from .holds import Hold, Holds  # noqa: F401  (joints held where they touched do
 from .gaps import Gaps  # noqa: F401  (trackers that drop out and come back: include/dragposer_gaps.h)
 from .tethers import Tether, Tethers  # noqa: F401  (joints tied to their own recent path: include/dragposer_tethers.h)
 from .lm import LM  # noqa: F401  (a Levenberg-Marquardt solver for the per-frame problem: include/dragposer_lm.h)
+from .clip import ClipLM  # noqa: F401  (a clip solved jointly, latents tied frame to frame: include/dragposer_clip_lm.h)
 from .encoder import NativePoseEncoder  # noqa: F401  (the pose encoder in one HIP launch: include/dragposer_encoder.h)
 from .calibration import BoneGroups, Calibration, calibrate  # noqa: F401  (bone lengths from tracker data: include/dragposer_calibration.h)
 

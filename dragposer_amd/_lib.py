@@ -346,6 +346,27 @@ class DpBoneFitResult(_Sized):
                 ("rms", C.c_void_p), ("info", C.c_void_p), ("status", C.c_void_p)]
 
 
+# every symbol include/dragposer_clip_lm.h declares (tests/test_clip_lm_abi.py)
+CLIP_LM_SYMBOLS = ("dp_clip_lm_workspace_bytes", "dp_optimize_clip_lm")
+DP_CLIP_REFUSED_FRAME = 1
+
+
+class DpClipLmParams(_Sized):
+    """include/dragposer_clip_lm.h: dp_clip_lm_params, with DP_CLIP_LM_PARAMS_INIT's defaults"""
+    _fields_ = [("struct_size", C.c_uint), ("n_steps", C.c_int), ("lambda_rot", C.c_float), ("lambda_tmp", C.c_float), ("lambda_smooth", C.c_float),
+                ("mu0", C.c_float), ("mu_up", C.c_float), ("mu_down", C.c_float), ("mu_min", C.c_float), ("mu_max", C.c_float)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **dict(dict(n_steps=4, lambda_rot=1.0, lambda_tmp=0.0, lambda_smooth=1.0, mu0=1e-2, mu_up=4.0, mu_down=1.0 / 3.0,
+                                         mu_min=1e-6, mu_max=1e6), **k))
+
+
+class DpClipLmExtra(_Sized):
+    """include/dragposer_clip_lm.h: dp_clip_lm_extra (device pointers)"""
+    _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("mu", C.c_void_p), ("n_accepted", C.c_void_p), ("clip_loss", C.c_void_p),
+                ("loss_hist", C.c_void_p), ("info", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 # every symbol include/dragposer_encoder.h declares (tests/test_encoder_abi.py)
 ENCODER_SYMBOLS = ("dp_fold_encoder", "dp_encoder_create", "dp_encoder_destroy", "dp_encoder_last_error", "dp_encoder_geometry", "dp_encode",
                    "dp_sequence_begin", "dp_debug_encoder_image")
@@ -461,6 +482,10 @@ def load(path=None):
     lib.dp_fit_bones_workspace_bytes.argtypes = [C.c_int]
     lib.dp_fit_bones_workspace_bytes.restype = C.c_size_t
     lib.dp_fit_bones.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpBoneFit), C.POINTER(DpBoneFitResult), C.c_void_p]
+    lib.dp_clip_lm_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.dp_clip_lm_workspace_bytes.restype = C.c_size_t
+    lib.dp_optimize_clip_lm.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.c_int, C.POINTER(DpClipLmParams), C.POINTER(DpResult),
+                                        C.POINTER(DpClipLmExtra), C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

@@ -31,6 +31,8 @@
 #include "../../include/dragposer_lm_terms.h"
 #include "../../include/dragposer_sequence_lm_terms.h"
 #include "../../include/dragposer_calibration.h"
+#include "../../include/dragposer_clip_lm.h"
+#include "dp_clip.h"
 #include "dp_cons_live.h"
 #include "dp_cons_tether.h"
 #include "dp_cons_points.h"
@@ -698,6 +700,7 @@ constexpr Sized LM_EXTRA_V590 = {"dp_lm_extra", "dp_lm_extra e = DP_LM_EXTRA_INI
 constexpr Sized SEQ_LM_EXTRA_V600 = {"dp_seq_lm_extra", "dp_seq_lm_extra e = DP_SEQ_LM_EXTRA_INIT;", offsetof(dp_seq_lm_extra, joint_pos) + sizeof(void*), false};
 constexpr Sized BONE_FIT_V510 = {"dp_bone_fit", "dp_bone_fit f = DP_BONE_FIT_INIT;", offsetof(dp_bone_fit, workspace_bytes) + sizeof(size_t), false};
 constexpr Sized BONE_FIT_RESULT_V510 = {"dp_bone_fit_result", "dp_bone_fit_result r = DP_BONE_FIT_RESULT_INIT;", offsetof(dp_bone_fit_result, status) + sizeof(void*), false};
+constexpr Sized CLIP_LM_EXTRA_V510 = {"dp_clip_lm_extra", "dp_clip_lm_extra e = DP_CLIP_LM_EXTRA_INIT;", offsetof(dp_clip_lm_extra, workspace_bytes) + sizeof(size_t), false};
 constexpr Sized SEQ_EXTRA_V520 = {"dp_seq_extra", "dp_seq_extra e = DP_SEQ_EXTRA_INIT;", offsetof(dp_seq_extra, row_step) + sizeof(int) * DP_MAX_TERMS, false};
 
 static int take_params(dp_ctx* ctx, const dp_params* p, dp_params& o, const char* who)
@@ -1399,6 +1402,72 @@ extern "C" int dp_fit_bones(dp_ctx* ctx, const dp_batch* in, const dp_bone_fit* 
         a.scales = out.scales; a.offsets = out.offsets; a.normal = out.normal; a.rms = out.rms; a.info = out.info; a.status = out.status;
         const hipError_t e = dp_launch_fit(&a, (hipStream_t)stream);
         if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(e));
+        return (int)DP_OK;
+    });
+}
+
+// include/dragposer_clip_lm.h: dp_optimize_clip_lm, in the header's order of refusals.  dp_clip_lm_params has dp_lm_params' fields without the
+// early stop and lambda_smooth among them: its values pass through take_lm_params as a dp_lm_params, so the two calls refuse alike.  (Its
+// launcher is a weak reference, like dp_launch_lm.)
+hipError_t dp_launch_clip(const dpclip::Args* args, hipStream_t stream) __attribute__((weak));
+extern "C" size_t dp_clip_lm_workspace_bytes(int n_sequences, int n_frames)
+{
+    if (n_sequences <= 0 || n_frames <= 0 || n_frames % n_sequences != 0) return 0;
+    return dpclip::layout(n_sequences, n_frames).bytes;
+}
+extern "C" int dp_optimize_clip_lm(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_result* out_in,
+                                   const dp_clip_lm_extra* e_in, void* stream)
+{
+    const char* who = "dp_optimize_clip_lm";
+    return entry(ctx, who, [&] {
+        const std::string w = who;
+        if (!in || !p_in || !e_in) return fail(ctx, DP_ERR_INVALID, w + ": NULL batch, params or extra");
+        constexpr unsigned min_size = (unsigned)(offsetof(dp_clip_lm_params, mu_max) + sizeof(float));
+        if (p_in->struct_size < min_size || p_in->struct_size > 4096u)
+            return fail(ctx, DP_ERR_INVALID, w + ": dp_clip_lm_params.struct_size is " + std::to_string(p_in->struct_size) + ", this library expects at least " +
+                                                 std::to_string(min_size) + "  (dp_clip_lm_params p = DP_CLIP_LM_PARAMS_INIT;)");
+        dp_result out;
+        if (int rc = take_result(ctx, out_in, out, who)) return rc;
+        dp_clip_lm_extra e;
+        if (int rc = take_sized(ctx, e_in, e, CLIP_LM_EXTRA_V510, who)) return rc;
+        dp_clip_lm_params p;
+        copy_sized(p_in, p);
+        dp_lm_params lp = DP_LM_PARAMS_INIT;
+        lp.n_steps = p.n_steps; lp.lambda_rot = p.lambda_rot; lp.lambda_tmp = p.lambda_tmp;
+        lp.mu0 = p.mu0; lp.mu_up = p.mu_up; lp.mu_down = p.mu_down; lp.mu_min = p.mu_min; lp.mu_max = p.mu_max;
+        dplm::Args la;
+        std::memset(&la, 0, sizeof(la));
+        if (int rc = take_lm_params(ctx, &lp, la, who)) return rc;
+        if (int rc = check_batch(ctx, in, who)) return rc;
+        if (n_seq <= 0 || in->n_frames % n_seq != 0)
+            return fail(ctx, DP_ERR_INVALID, w + ": n_sequences " + std::to_string(n_seq) + " must be positive and divide n_frames " + std::to_string(in->n_frames));
+        if (!(p.lambda_smooth >= 0.f && std::fabs(p.lambda_smooth) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": lambda_smooth is negative or not finite");
+        const dpclip::Layout l = dpclip::layout(n_seq, in->n_frames);
+        if (!e.workspace || e.workspace_bytes < l.bytes)
+            return fail(ctx, DP_ERR_INVALID, w + ": the workspace is NULL or holds " + std::to_string(e.workspace_bytes) + " bytes, fewer than the " +
+                                                 std::to_string(l.bytes) + " of dp_clip_lm_workspace_bytes(" + std::to_string(n_seq) + ", " +
+                                                 std::to_string(in->n_frames) + ")");
+        if (REF8_BUILD) return refuse_ref8(ctx, who);
+        if (!dp_launch_clip) return fail(ctx, DP_ERR_UNSUPPORTED, w + ": this library was linked without dp_clip.hip");
+        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+        DEVICE_GUARD(ctx);
+        dpclip::Args a;
+        std::memset(&a, 0, sizeof(a));
+        a.img = ctx->d_vjpimg.get();
+        fill_batch(a, *in);
+        fill_results(a, out);
+        a.mu = e.mu; a.n_accepted = e.n_accepted; a.clip_loss = e.clip_loss; a.loss_hist = e.loss_hist; a.info = e.info;
+        char* const ws = (char*)e.workspace;
+        for (int i = 0; i < 2; ++i) {
+            a.wz[i] = (float*)(ws + l.z[i]); a.wloss[i] = (float*)(ws + l.loss[i]); a.wcpl[i] = (double*)(ws + l.cpl[i]);
+        }
+        a.wag = (float*)(ws + l.ag); a.wli = (float*)(ws + l.li); a.wflags = (int*)(ws + l.flags); a.wtot = (double*)(ws + l.tot);
+        a.wword = (int*)(ws + l.word); a.wsolved = (int*)(ws + l.solved); a.wmu = (float*)(ws + l.mu); a.wnacc = (int*)(ws + l.nacc);
+        a.n_seq = n_seq; a.n_t = in->n_frames / n_seq; a.n_steps = la.n_steps;
+        a.lam_rot = la.lam_rot; a.lam_tmp = la.lam_tmp; a.lam_smooth = p.lambda_smooth;
+        a.mu0 = la.mu0; a.mu_up = la.mu_up; a.mu_down = la.mu_down; a.mu_min = la.mu_min; a.mu_max = la.mu_max;
+        const hipError_t err = dp_launch_clip(&a, (hipStream_t)stream);
+        if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(err));
         return (int)DP_OK;
     });
 }

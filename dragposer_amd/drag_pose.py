@@ -150,6 +150,7 @@ class DragPose:
         self._out = [None, None]
         self._flip = 0
         self.hold_state = None  # [S,len(holds),4] (x, y, z, held) of run(holds=) / run_frames(holds=); zeroed when a sequence begins
+        self.keep_latents = False  # True: run_frames also leaves every frame's latent in `last_latents` [T,S,24] (eval_drag --smooth reads it)
         self.lm_mu = None  # [S] the damping of run(solver=LM(...)) (include/dragposer_lm.h), kept from frame to frame; reset when a sequence begins
         self.gap_state = None  # [S,22,16] of run(gaps=) / run_frames(gaps=) (include/dragposer_gaps.h); zeroed when a sequence begins
         self.tether_state = None  # [S,len(tethers),8] of run(tethers=) / run_frames(tethers=) (include/dragposer_tethers.h); zeroed when a sequence begins
@@ -437,9 +438,14 @@ class DragPose:
         gpos = torch.empty(T, S, 3, device=dev)
         iters = torch.empty(T, S, dtype=torch.int32, device=dev)
         status = torch.empty(T, S, dtype=torch.int32, device=dev)
+        # (keep_latents: the launches' per-step scratch, whose first 24 columns are the step's latent, is kept instead of dropped)
+        hist = torch.empty(T, S, LATENT + 3 + len(height_indices), device=dev) if self.keep_latents else None
         if solver is not None:
-            return self._run_frames_lm(solver, dense_p, dense_r, root, trk, adjust, poses, gpos, iters, status, stop_eps_pos, stop_eps_rot, lambda_rot,
-                                       lambda_temporal, temporal_future_window, height_indices, solver.terms)
+            self._run_frames_lm(solver, dense_p, dense_r, root, trk, adjust, poses, gpos, iters, status, stop_eps_pos, stop_eps_rot, lambda_rot,
+                                lambda_temporal, temporal_future_window, height_indices, solver.terms, hist)
+            if hist is not None:
+                self.last_latents = hist[..., :LATENT].contiguous()
+            return poses, gpos, iters
         with_terms = constraints is not None or terms is not None
         if with_terms:
             if terms is not None:
@@ -489,7 +495,8 @@ class DragPose:
                                               n_iter=max_iter, lr=learning_rate, lambda_rot=float(lambda_rot), lambda_tmp=lambda_tmp,
                                               stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, min_loss_incr=min_loss_incr, adjust=adjust,
                                               pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n], offsets=skel,
-                                              loss=loss[t:t + n] if loss is not None else None, **extra(t, n), **kw)
+                                              loss=loss[t:t + n] if loss is not None else None, scratch=hist[t:t + n] if hist is not None else None,
+                                              **extra(t, n), **kw)
 
         if ar is not None:  # one launch, no stretches: the targets come from inside it; the loss's third part is lambda_temporal times the pull towards last_z_tgt
             loss = launch(0, T, None, (0, 0), float(lambda_temporal), ar=ar, z_tgt_trace=self.last_z_tgt)["loss"]
@@ -499,10 +506,12 @@ class DragPose:
         self.last_status = status  # [T,S] DP_STATUS_* bits (include/dragposer.h): non-zero where a frame's inputs were not finite
         if loss is not None:
             self.last_loss = loss
+        if hist is not None:
+            self.last_latents = hist[..., :LATENT].contiguous()
         return poses, gpos, iters
 
     def _run_frames_lm(self, solver, dense_p, dense_r, root, trk, adjust, poses, gpos, iters, status, stop_eps_pos, stop_eps_rot, lambda_rot,
-                       lambda_temporal, temporal_future_window, height_indices, terms=None):
+                       lambda_temporal, temporal_future_window, height_indices, terms=None, hist=None):
         """run_frames(solver=LM(...)) behind its preparation: the stretches of run_frames through dp_optimize_sequence_lm (with `terms`,
         dp_optimize_sequence_lm_terms); with a predictor, one launch"""
         dev, S, T = self.device, self.S, int(dense_p.shape[0])
@@ -524,7 +533,8 @@ class DragPose:
                                           self.displacement_buffer, self.heights_buffer, heights, lm=solver, lambda_rot=float(lambda_rot),
                                           lambda_tmp=lam, stop_eps_pos=stop_eps_pos, stop_eps_rot=stop_eps_rot, mu=self.lm_mu, adjust=adjust,
                                           pose_ret=poses[t:t + n], pos_ret=gpos[t:t + n], iters=iters[t:t + n], status=status[t:t + n],
-                                          loss=loss[t:t + n], joint_pos=self.last_joint_pos[t:t + n], outputs=names, **kw)
+                                          loss=loss[t:t + n], joint_pos=self.last_joint_pos[t:t + n], outputs=names,
+                                          scratch=hist[t:t + n] if hist is not None else None, **kw)
 
         if solver.predictor is not None:  # one launch, no stretches: the targets come from inside it
             self.last_z_tgt = torch.zeros(T, S, LATENT, device=dev)

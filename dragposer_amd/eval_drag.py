@@ -302,6 +302,9 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
     drag.set_initial_state(torch.cat([q["z0"] for q in seqs], dim=0), np.stack([q["m"]["global_pos"][0] for q in seqs]),
                            np.stack([q["m"]["global_rot"][0] for q in seqs]), np.stack([q["m"]["heights"][0] for q in seqs]))
     ja = tuple(cfg["joint_adjustment_indices"]) if cfg["enable_joint_adjustment"] else None
+    smooth = getattr(args, "smooth_spec", None) is not None
+    drag.keep_latents = smooth  # (--smooth's second pass starts from every frame's latent)
+    latents = torch.zeros(T, S, 24, device=dev) if smooth else None
     cons = None
     if getattr(args, "constraints", None) == "reference":  # the reference's `# Additional Losses` block (drag_pose.py:129-183), un-commented
         cons = Constraints.reference()
@@ -340,6 +343,8 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
                                                 stop_eps_rot=0.01, max_iter=args.max_iter, min_loss_incr=0.00001, learning_rate=1e-2, lambda_rot=1,
                                                 lambda_temporal=lam_tmp, temporal_future_window=window, height_indices=HEIGHT_INDICES,
                                                 joint_adjustment_indices=ja, joint_adjustment_weight=cfg["joint_adjustment_weight"], offsets=offsets, **extra)
+        if smooth:
+            latents = drag.last_latents
     for i in range(T if getattr(args, "per_frame", False) else 0):
         if i % 1000 == 0:
             print(f"Frame: {i + 1} out of {T}", flush=True)
@@ -349,10 +354,58 @@ def run_sequences(args, seqs, opt, temporal_pack, cfg):
                  temporal_future_window=window, height_indices=HEIGHT_INDICES, joint_adjustment_indices=ja,
                  joint_adjustment_weight=cfg["joint_adjustment_weight"], verbose=args.verbose, out_pose=poses[i], out_pos=out_pos[i], **extra)
         iters[i] = drag.last["iters"]
+        if smooth:
+            latents[i] = drag.latent
     torch.cuda.synchronize()
     elapsed = time.time() - t0
     poses, out_pos, iters = poses.cpu().numpy(), out_pos.cpu().numpy(), iters.cpu().numpy()
-    return [dict(poses=poses[:q["n_frames"], k], pos=out_pos[:q["n_frames"], k], iters=iters[:q["n_frames"], k]) for k, q in enumerate(seqs)], elapsed, lam_tmp, temporal is not None or ar is not None
+    res = [dict(poses=poses[:q["n_frames"], k], pos=out_pos[:q["n_frames"], k], iters=iters[:q["n_frames"], k]) for k, q in enumerate(seqs)]
+    if smooth:
+        for k, q in enumerate(seqs):
+            res[k]["latents"] = latents[:q["n_frames"], k].contiguous()
+    return res, elapsed, lam_tmp, temporal is not None or ar is not None
+
+
+def smooth_file(args, q, res, opt, cfg):
+    """--smooth: the clip's frames once more, as ONE sequence solved jointly (LatentOptimizer.optimize_clip_lm, include/dragposer_clip_lm.h).  Frame
+    t runs under what the first pass left before it -- cur_rot = the world root rotation it returned for frame t-1 (read back from the pose's
+    root channels; the clip's own before frame 0), position targets shifted by its global position before frame t -- with z0 = z_tgt = its
+    latent and lambda_tmp = ANCHOR.  -> dict(poses [T,88] with the world root rotation in the root channels, pos [T,3] advanced from the first
+    pass's positions as the frame loop advances them, and the call's per-sequence outputs)"""
+    clip, anchor = args.smooth_spec
+    dev, m, T = opt.device, q["m"], q["n_frames"]
+    if not np.allclose(np.asarray(m["offsets"], np.float64).reshape(NJ, 3)[1:], np.asarray(opt.host_model.arrays["offsets"], np.float64).reshape(NJ, 3)[1:], atol=1e-6):
+        raise SystemExit(f"--smooth: {q['path']} has another skeleton than the context's; the joint pass has no per-frame skeletons "
+                         "(include/dragposer_clip_lm.h, Not covered)")
+    mask_idx = np.nonzero(np.asarray(cfg["mask"]))[0]
+    mt = torch.as_tensor(mask_idx, device=dev)
+    sd4 = q["stds"]["dqs"].reshape(NJ, 8)[:, :4].reshape(88)[:4].astype(np.float32)
+    mu4 = q["means"]["dqs"].reshape(NJ, 8)[:, :4].reshape(88)[:4].astype(np.float32)
+    rot_before = np.concatenate((np.asarray(m["global_rot"][0:1], np.float32), res["poses"][:T - 1, :4] * sd4 + mu4)).astype(np.float32)
+    pos_before = torch.as_tensor(np.concatenate((np.asarray(m["global_pos"][0:1], np.float32), res["pos"][:T - 1])).astype(np.float32), device=dev)
+    tgt_pos = torch.zeros(T, NJ, 3, device=dev)
+    tgt_pos[:, mt] = q["tp_rel"][:T] + (q["gpos"][:T] - pos_before).unsqueeze(1)
+    tgt_rot = torch.zeros(T, NJ, 9, device=dev)
+    tgt_rot[:, mt] = q["tR"][:T]
+    w = torch.zeros(T, NJ, 2, device=dev)
+    w[:, mt] = torch.as_tensor(np.asarray(cfg["weights"], np.float32)[mask_idx], device=dev)
+    tracked = torch.zeros(T, NJ, dtype=torch.uint8, device=dev)
+    tracked[:, mt] = 1
+    z = res["latents"]
+    torch.cuda.synchronize()
+    t0 = time.time()
+    out = opt.optimize_clip_lm(z, z.clone(), torch.as_tensor(rot_before, device=dev).contiguous(), tgt_pos, tgt_rot, w, tracked, n_sequences=1, clip=clip,
+                               lambda_rot=1.0, lambda_tmp=anchor)
+    torch.cuda.synchronize()
+    elapsed = time.time() - t0
+    pos = pos_before + out["world_disp"]  # drag_pose.py:370, then the joint adjustment (drag_pose.py:377-384)
+    if cfg["enable_joint_adjustment"]:
+        j, k = cfg["joint_adjustment_indices"]
+        pos = pos + (tgt_pos[:, int(mask_idx[k])] - out["pos"][:, int(j)]) * float(cfg["joint_adjustment_weight"])
+    poses = out["pose"].clone()
+    poses[:, :4] = (out["world_rot"] - torch.as_tensor(mu4, device=dev)) / torch.as_tensor(sd4, device=dev)
+    return dict(poses=poses.cpu().numpy(), pos=pos.cpu().numpy(), time=elapsed, n_accepted=int(out["n_accepted"][0]), info=int(out["info"][0]),
+                loss_hist=out["loss_hist"][0].cpu().numpy(), clip_loss=out["clip_loss"][0].cpu().numpy(), bad=int((out["status"] != 0).sum()))
 
 
 def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
@@ -401,6 +454,19 @@ def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
         jit, jit_gt = jitter(BVH().load(q["path"]), BVH().load(out_path))
         print(f"Jitter: {jit} (mean |W(t+1) - 2 W(t) + W(t-1)| over the inner frames and all {NJ} joints; the ground truth's own: {jit_gt})")
         out.update(jitter=jit, jitter_gt=jit_gt)
+    if res.get("smooth") is not None:
+        sm, (clip, anchor) = res["smooth"], args.smooth_spec
+        sm_path = os.path.join(args.out_dir, "eval_smooth_" + name)
+        result_to_bvh(sm["poses"], sm["pos"], q["means"], q["stds"], q["bvh"], sm_path)
+        mpjpe2, mpeepe2 = eval_pos_error(BVH().load(q["path"]), BVH().load(sm_path))
+        jit1, jit_gt = jitter(BVH().load(q["path"]), BVH().load(out_path))
+        jit2, _ = jitter(BVH().load(q["path"]), BVH().load(sm_path))
+        print(f"Smooth: lambda {clip.smooth} steps {clip.steps} anchor {anchor} (LatentOptimizer.optimize_clip_lm, include/dragposer_clip_lm.h): "
+              f"Mean Per Joint Position Error {mpjpe} -> {mpjpe2}, Mean End Effector Position Error {mpeepe} -> {mpeepe2}, jitter {jit1} -> {jit2} "
+              f"(the ground truth's own: {jit_gt}); accepted {sm['n_accepted']} of {clip.steps} steps, sequence loss {sm['loss_hist'][0]:.6g} -> "
+              f"{sm['loss_hist'][-1]:.6g} (coupling part {sm['clip_loss'][1]:.6g}), info {sm['info']}, frames with a status {sm['bad']}, {sm['time']:.3f} s")
+        out.update(mpjpe_smooth=mpjpe2, mpeepe_smooth=mpeepe2, jitter=jit1, jitter_smooth=jit2, jitter_gt=jit_gt, out_smooth=sm_path,
+                   smooth_accepted=sm["n_accepted"], smooth_loss_hist=sm["loss_hist"])
     if getattr(args, "keep_frames", False):
         out.update(poses=res["poses"], pos=res["pos"], iters=res["iters"])
     return out
@@ -419,6 +485,8 @@ def evaluate_files(args, paths, opt, encoder, temporal_pack, cfg, raw):
     for q, r in zip(seqs, results):
         if len(seqs) > 1:
             print(f"Result {q['path']} ------------------------")
+        if getattr(args, "smooth_spec", None) is not None:
+            r["smooth"] = smooth_file(args, q, r, opt, cfg)
         out.append(finish_file(args, q, r, elapsed, lam_tmp, has_temporal, shared=len(seqs)))
     return out
 
@@ -524,6 +592,14 @@ def main(argv=None):
                          "the reference's extra terms join the LM loss as the solver's table, LM(terms=Terms.from_constraints(Constraints.reference())) "
                          "(dp_optimize_sequence_lm_terms, include/dragposer_sequence_lm_terms.h; --per-frame: dp_optimize_lm_terms).  Not with "
                          "--foot-lock, --tether, --balance or --gaps, and for a BVH with the model's own skeleton")
+    ap.add_argument("--smooth", default=None, metavar="LAMBDA[:STEPS[:ANCHOR]]",
+                    help="after the clip's normal pass, a second pass over all its frames as ONE sequence solved jointly, the latents tied frame to "
+                         "frame by LAMBDA |z_t - z_(t-1)|^2 / 24 inside the loss (LatentOptimizer.optimize_clip_lm, include/dragposer_clip_lm.h): "
+                         "STEPS joint Levenberg-Marquardt steps (default 4) from the first pass's latents, each frame under the root rotation and "
+                         "position the first pass left before it, with a pull of weight ANCHOR (default 0) towards the first pass's latent.  "
+                         "Prints MPJPE and jitter before and after beside the ground truth's jitter and writes eval_smooth_<name>.  No default "
+                         "LAMBDA: none has been found that helps on every clip.  Allowed after --solver and --latent-ar; not with --constraints, "
+                         "--foot-lock, --tether, --balance, --gaps, --drop or --calibrate, and for a BVH with the model's own skeleton")
     ap.add_argument("--calibrate", default=None, metavar="GROUPS[:FRAMES[:ROUNDS]]",
                     help="a performer without a BVH file: ignore the clip's OFFSET table for the optimisation and fit the bone lengths from the "
                          "tracker targets first -- GROUPS uniform | limbs | symmetric | per_bone (dragposer_amd.BoneGroups), FRAMES frames drawn "
@@ -609,6 +685,26 @@ def main(argv=None):
             args.solver_model.predictor = args.latent_ar_model
         print(f"Solver: Levenberg-Marquardt, {args.solver_model.steps} steps per frame (DragPose.{'run' if args.per_frame else 'run_frames'}(solver=), "
               f"include/dragposer_{'lm' if args.per_frame else 'sequence_lm'}{'_terms' if args.constraints else ''}.h)")
+    args.smooth_spec = None
+    if args.smooth is not None:
+        from .clip import ClipLM
+
+        for flag, given in (("--constraints", args.constraints), ("--foot-lock", args.foot_lock), ("--tether", args.tether), ("--balance", args.balance),
+                            ("--gaps", args.gaps), ("--drop", args.drop), ("--calibrate", args.calibrate)):
+            if given:
+                raise SystemExit(f"--smooth and {flag}: the clip loss has the trackers, the anchor and the coupling only (include/dragposer_clip_lm.h, Not covered)")
+        if args.model_skeleton:
+            raise SystemExit("--smooth and --model-skeleton: the joint pass runs on the context's skeleton only (include/dragposer_clip_lm.h, Not covered)")
+        parts = args.smooth.split(":")
+        try:
+            if not 1 <= len(parts) <= 3:
+                raise ValueError("one to three fields")
+            anchor = float(parts[2]) if len(parts) > 2 else 0.0
+            if not (anchor >= 0.0 and anchor < float("inf")):
+                raise ValueError("ANCHOR is negative or not finite")
+            args.smooth_spec = (ClipLM(steps=int(parts[1]) if len(parts) > 1 and parts[1] else 4, smooth=float(parts[0])).check(), anchor)
+        except ValueError as e:
+            raise SystemExit(f"--smooth: expected LAMBDA[:STEPS[:ANCHOR]] with LAMBDA >= 0, 1 <= STEPS <= 64 and ANCHOR >= 0 ({e})")
     args.gaps_model = None
     if args.gaps is not None:
         from .gaps import Gaps

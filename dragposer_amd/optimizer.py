@@ -491,6 +491,50 @@ class LatentOptimizer:
         del keep
         return tensors
 
+    def optimize_clip_lm(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, n_sequences, clip=None, lambda_rot=1.0, lambda_tmp=0.0, mu=None,
+                         outputs=None, out=None):
+        """A clip solved jointly (`clip`: a dragposer_amd.ClipLM; None = ClipLM()): include/dragposer_clip_lm.h, dp_optimize_clip_lm.  The B rows
+        are `n_sequences` sequences of T = B / n_sequences frames, frame t of sequence s in row t * n_sequences + s; each row is `optimize_lm`'s
+        frame, and the latents of a sequence are tied frame to frame by clip.smooth |z_t - z_(t-1)|^2 / 24 inside the loss.  `mu` [S] fp32 on the
+        device: the damping of every sequence, read and updated IN PLACE; None: every sequence starts at clip.mu0.  Returns `optimize_lm`'s
+        per-frame dict (every array belongs to the returned z; iters = the steps run; loss = the fp32 pass's numbers; no loss0) plus
+        `clip_loss` [S,2] float64 (the sequence's loss at the returned latents, its coupling part), `loss_hist` [S, steps+1] float64,
+        `n_accepted` [S] int32, `mu` [S] and `info` [S] int32 (DP_CLIP_* flags).  The workspace is a buffer this optimiser keeps, by size.
+        Asynchronous on torch's current stream, no host synchronisation."""
+        from .clip import ClipLM
+
+        clip = (clip if clip is not None else ClipLM()).check()
+        B, dev, S = int(z0.shape[0]), self.device, int(n_sequences)
+        if S <= 0 or B % S != 0:
+            raise ValueError(f"optimize_clip_lm: n_sequences {n_sequences!r} must be positive and divide the {B} rows")
+        batch = self._batch(z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked)
+        p = clip.to_struct(lambda_rot, lambda_tmp)
+        own = {"clip_loss": ((S, 2), torch.float64), "loss_hist": ((S, clip.steps + 1), torch.float64), "n_accepted": ((S,), torch.int32),
+               "mu": ((S,), torch.float32), "info": ((S,), torch.int32)}
+        names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS) + tuple(own)
+        unknown = [n for n in names if n not in own and n not in _OUT_SPECS]
+        if unknown:
+            raise ValueError(f"optimize_clip_lm: unknown output {unknown[0]!r}")
+        res, tensors = self._outputs(B, [n for n in names if n not in own], out)
+        ex = _lib.DpClipLmExtra()
+        for name, (shape, dtype) in own.items():
+            if name == "mu":
+                t = mu if mu is not None else torch.full(shape, float(clip.mu0), dtype=dtype, device=dev)
+            elif name in names:
+                t = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
+            else:
+                continue
+            setattr(ex, name, _check(t, name, shape, dtype, dev))
+            tensors[name] = t
+        need = int(self.lib.dp_clip_lm_workspace_bytes(S, B))
+        cache = self.__dict__.setdefault("_clip_workspaces", {})
+        ws = cache.get(need)
+        if ws is None:
+            ws = cache[need] = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+        ex.workspace, ex.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        self._call(self.lib.dp_optimize_clip_lm, C.byref(batch), S, C.byref(p), C.byref(res), C.byref(ex))
+        return tensors
+
     def fit_bones(self, z, cur_rot, tgt_pos, w, tracked, groups, base=None, prior=None, ridge=1e-3, outputs=None, out=None):
         """Per-group bone scales from B frames of tracker data in one call (include/dragposer_calibration.h, dp_fit_bones): with the joint
         rotations fixed at decode + FK of `z` [B,24] under `cur_rot` [B,4], the scales s of off_b = s[group(b)] * base_b that minimise the
