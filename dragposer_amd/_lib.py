@@ -361,6 +361,15 @@ class DpClipLmParams(_Sized):
                                          mu_min=1e-6, mu_max=1e6), **k))
 
 
+# every symbol include/dragposer_clip_accel.h declares (tests/test_clip_accel_abi.py)
+CLIP_ACCEL_SYMBOLS = ("dp_clip_lm_accel_workspace_bytes", "dp_optimize_clip_lm_accel")
+
+
+class DpClipAccelParams(_Sized):
+    """include/dragposer_clip_accel.h: dp_clip_accel_params, with DP_CLIP_ACCEL_PARAMS_INIT's defaults (accel_loss: a device pointer)"""
+    _fields_ = [("struct_size", C.c_uint), ("lambda_accel", C.c_float), ("accel_loss", C.c_void_p)]
+
+
 class DpClipLmExtra(_Sized):
     """include/dragposer_clip_lm.h: dp_clip_lm_extra (device pointers)"""
     _fields_ = [("struct_size", C.c_uint), ("reserved0", C.c_uint), ("mu", C.c_void_p), ("n_accepted", C.c_void_p), ("clip_loss", C.c_void_p),
@@ -486,6 +495,10 @@ def load(path=None):
     lib.dp_clip_lm_workspace_bytes.restype = C.c_size_t
     lib.dp_optimize_clip_lm.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.c_int, C.POINTER(DpClipLmParams), C.POINTER(DpResult),
                                         C.POINTER(DpClipLmExtra), C.c_void_p]
+    lib.dp_clip_lm_accel_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.dp_clip_lm_accel_workspace_bytes.restype = C.c_size_t
+    lib.dp_optimize_clip_lm_accel.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.c_int, C.POINTER(DpClipLmParams), C.POINTER(DpClipAccelParams),
+                                              C.POINTER(DpResult), C.POINTER(DpClipLmExtra), C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

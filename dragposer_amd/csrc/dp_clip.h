@@ -106,3 +106,4 @@ struct Args {
 } // namespace dpclip
 
 hipError_t dp_launch_clip(const dpclip::Args* args, hipStream_t stream);
+hipError_t dp_launch_clip_rows(const dpclip::Args* args, int mode, hipStream_t stream);

@@ -760,15 +760,20 @@ __global__ __launch_bounds__(64) void dp_clip_decide_kernel(K::Args a)
     }
 }
 
+// one pass of the rows kernel in `mode` (M_*): also what another unit's launch train (dp_clip_accel.hip) runs between its own kernels
+hipError_t dp_launch_clip_rows(const K::Args* args, int mode, hipStream_t stream)
+{
+    K::Args k = *args;
+    k.mode = mode;
+    hipLaunchKernelGGL(dp_clip_rows_kernel, dim3((unsigned)((k.n_frames + WPB - 1) / WPB)), dim3(WPB * 64), 0, stream, k);
+    return hipGetLastError();
+}
+
 hipError_t dp_launch_clip(const K::Args* args, hipStream_t stream)
 {
     K::Args k = *args;
-    const dim3 rows((unsigned)((k.n_frames + WPB - 1) / WPB)), seqs((unsigned)k.n_seq);
-    const auto run_rows = [&](int mode) {
-        k.mode = mode;
-        hipLaunchKernelGGL(dp_clip_rows_kernel, rows, dim3(WPB * 64), 0, stream, k);
-        return hipGetLastError();
-    };
+    const dim3 seqs((unsigned)k.n_seq);
+    const auto run_rows = [&](int mode) { return dp_launch_clip_rows(&k, mode, stream); };
     const auto run_decide = [&](int step) {
         k.step = step;
         hipLaunchKernelGGL(dp_clip_decide_kernel, seqs, dim3(64), 0, stream, k);

@@ -31,8 +31,10 @@
 #include "../../include/dragposer_lm_terms.h"
 #include "../../include/dragposer_sequence_lm_terms.h"
 #include "../../include/dragposer_calibration.h"
+#include "../../include/dragposer_clip_accel.h"
 #include "../../include/dragposer_clip_lm.h"
 #include "dp_clip.h"
+#include "dp_clip_accel.h"
 #include "dp_cons_live.h"
 #include "dp_cons_tether.h"
 #include "dp_cons_points.h"
@@ -1408,8 +1410,67 @@ extern "C" int dp_fit_bones(dp_ctx* ctx, const dp_batch* in, const dp_bone_fit* 
 
 // include/dragposer_clip_lm.h: dp_optimize_clip_lm, in the header's order of refusals.  dp_clip_lm_params has dp_lm_params' fields without the
 // early stop and lambda_smooth among them: its values pass through take_lm_params as a dp_lm_params, so the two calls refuse alike.  (Its
-// launcher is a weak reference, like dp_launch_lm.)
+// launcher is a weak reference, like dp_launch_lm.)  include/dragposer_clip_accel.h: dp_optimize_clip_lm_accel is the same call with one more
+// struct, a wider workspace and its own launch train; what the two share is take_clip (every refusal up to lambda_smooth), clip_workspace and
+// fill_clip.
 hipError_t dp_launch_clip(const dpclip::Args* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_clip_accel(const dpclipacc::Args* args, hipStream_t stream) __attribute__((weak));
+struct ClipCall {
+    dp_result out;
+    dp_clip_lm_extra e;
+    dp_clip_lm_params p;
+    dplm::Args la;
+};
+static int take_clip(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_result* out_in, const dp_clip_lm_extra* e_in,
+                     ClipCall& c, const char* who)
+{
+    const std::string w = who;
+    if (!in || !p_in || !e_in) return fail(ctx, DP_ERR_INVALID, w + ": NULL batch, params or extra");
+    constexpr unsigned min_size = (unsigned)(offsetof(dp_clip_lm_params, mu_max) + sizeof(float));
+    if (p_in->struct_size < min_size || p_in->struct_size > 4096u)
+        return fail(ctx, DP_ERR_INVALID, w + ": dp_clip_lm_params.struct_size is " + std::to_string(p_in->struct_size) + ", this library expects at least " +
+                                             std::to_string(min_size) + "  (dp_clip_lm_params p = DP_CLIP_LM_PARAMS_INIT;)");
+    if (int rc = take_result(ctx, out_in, c.out, who)) return rc;
+    if (int rc = take_sized(ctx, e_in, c.e, CLIP_LM_EXTRA_V510, who)) return rc;
+    copy_sized(p_in, c.p);
+    dp_lm_params lp = DP_LM_PARAMS_INIT;
+    lp.n_steps = c.p.n_steps; lp.lambda_rot = c.p.lambda_rot; lp.lambda_tmp = c.p.lambda_tmp;
+    lp.mu0 = c.p.mu0; lp.mu_up = c.p.mu_up; lp.mu_down = c.p.mu_down; lp.mu_min = c.p.mu_min; lp.mu_max = c.p.mu_max;
+    std::memset(&c.la, 0, sizeof(c.la));
+    if (int rc = take_lm_params(ctx, &lp, c.la, who)) return rc;
+    if (int rc = check_batch(ctx, in, who)) return rc;
+    if (n_seq <= 0 || in->n_frames % n_seq != 0)
+        return fail(ctx, DP_ERR_INVALID, w + ": n_sequences " + std::to_string(n_seq) + " must be positive and divide n_frames " + std::to_string(in->n_frames));
+    if (!(c.p.lambda_smooth >= 0.f && std::fabs(c.p.lambda_smooth) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": lambda_smooth is negative or not finite");
+    return DP_OK;
+}
+static int clip_workspace(dp_ctx* ctx, const dp_clip_lm_extra& e, size_t need, const char* size_fn, int n_seq, int n_frames, const char* who)
+{
+    if (!e.workspace || e.workspace_bytes < need)
+        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": the workspace is NULL or holds " + std::to_string(e.workspace_bytes) + " bytes, fewer than the " +
+                                             std::to_string(need) + " of " + size_fn + "(" + std::to_string(n_seq) + ", " + std::to_string(n_frames) + ")");
+    return DP_OK;
+}
+// (L: dp_clip.h's Layout or dp_clip_accel.h's -- the same names)
+template <class L>
+static void fill_clip(dpclip::Args& a, const dp_ctx* ctx, const dp_batch* in, int n_seq, const ClipCall& c, const L& l)
+{
+    std::memset(&a, 0, sizeof(a));
+    a.img = ctx->d_vjpimg.get();
+    fill_batch(a, *in);
+    fill_results(a, c.out);
+    const dp_clip_lm_extra& e = c.e;
+    a.mu = e.mu; a.n_accepted = e.n_accepted; a.clip_loss = e.clip_loss; a.loss_hist = e.loss_hist; a.info = e.info;
+    char* const ws = (char*)e.workspace;
+    for (int i = 0; i < 2; ++i) {
+        a.wz[i] = (float*)(ws + l.z[i]); a.wloss[i] = (float*)(ws + l.loss[i]); a.wcpl[i] = (double*)(ws + l.cpl[i]);
+    }
+    a.wag = (float*)(ws + l.ag); a.wli = (float*)(ws + l.li); a.wflags = (int*)(ws + l.flags); a.wtot = (double*)(ws + l.tot);
+    a.wword = (int*)(ws + l.word); a.wsolved = (int*)(ws + l.solved); a.wmu = (float*)(ws + l.mu); a.wnacc = (int*)(ws + l.nacc);
+    a.n_seq = n_seq; a.n_t = in->n_frames / n_seq; a.n_steps = c.la.n_steps;
+    a.lam_rot = c.la.lam_rot; a.lam_tmp = c.la.lam_tmp; a.lam_smooth = c.p.lambda_smooth;
+    a.mu0 = c.la.mu0; a.mu_up = c.la.mu_up; a.mu_down = c.la.mu_down; a.mu_min = c.la.mu_min; a.mu_max = c.la.mu_max;
+}
 extern "C" size_t dp_clip_lm_workspace_bytes(int n_sequences, int n_frames)
 {
     if (n_sequences <= 0 || n_frames <= 0 || n_frames % n_sequences != 0) return 0;
@@ -1421,52 +1482,53 @@ extern "C" int dp_optimize_clip_lm(dp_ctx* ctx, const dp_batch* in, int n_seq, c
     const char* who = "dp_optimize_clip_lm";
     return entry(ctx, who, [&] {
         const std::string w = who;
-        if (!in || !p_in || !e_in) return fail(ctx, DP_ERR_INVALID, w + ": NULL batch, params or extra");
-        constexpr unsigned min_size = (unsigned)(offsetof(dp_clip_lm_params, mu_max) + sizeof(float));
-        if (p_in->struct_size < min_size || p_in->struct_size > 4096u)
-            return fail(ctx, DP_ERR_INVALID, w + ": dp_clip_lm_params.struct_size is " + std::to_string(p_in->struct_size) + ", this library expects at least " +
-                                                 std::to_string(min_size) + "  (dp_clip_lm_params p = DP_CLIP_LM_PARAMS_INIT;)");
-        dp_result out;
-        if (int rc = take_result(ctx, out_in, out, who)) return rc;
-        dp_clip_lm_extra e;
-        if (int rc = take_sized(ctx, e_in, e, CLIP_LM_EXTRA_V510, who)) return rc;
-        dp_clip_lm_params p;
-        copy_sized(p_in, p);
-        dp_lm_params lp = DP_LM_PARAMS_INIT;
-        lp.n_steps = p.n_steps; lp.lambda_rot = p.lambda_rot; lp.lambda_tmp = p.lambda_tmp;
-        lp.mu0 = p.mu0; lp.mu_up = p.mu_up; lp.mu_down = p.mu_down; lp.mu_min = p.mu_min; lp.mu_max = p.mu_max;
-        dplm::Args la;
-        std::memset(&la, 0, sizeof(la));
-        if (int rc = take_lm_params(ctx, &lp, la, who)) return rc;
-        if (int rc = check_batch(ctx, in, who)) return rc;
-        if (n_seq <= 0 || in->n_frames % n_seq != 0)
-            return fail(ctx, DP_ERR_INVALID, w + ": n_sequences " + std::to_string(n_seq) + " must be positive and divide n_frames " + std::to_string(in->n_frames));
-        if (!(p.lambda_smooth >= 0.f && std::fabs(p.lambda_smooth) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": lambda_smooth is negative or not finite");
+        ClipCall c;
+        if (int rc = take_clip(ctx, in, n_seq, p_in, out_in, e_in, c, who)) return rc;
         const dpclip::Layout l = dpclip::layout(n_seq, in->n_frames);
-        if (!e.workspace || e.workspace_bytes < l.bytes)
-            return fail(ctx, DP_ERR_INVALID, w + ": the workspace is NULL or holds " + std::to_string(e.workspace_bytes) + " bytes, fewer than the " +
-                                                 std::to_string(l.bytes) + " of dp_clip_lm_workspace_bytes(" + std::to_string(n_seq) + ", " +
-                                                 std::to_string(in->n_frames) + ")");
+        if (int rc = clip_workspace(ctx, c.e, l.bytes, "dp_clip_lm_workspace_bytes", n_seq, in->n_frames, who)) return rc;
         if (REF8_BUILD) return refuse_ref8(ctx, who);
         if (!dp_launch_clip) return fail(ctx, DP_ERR_UNSUPPORTED, w + ": this library was linked without dp_clip.hip");
         if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
         DEVICE_GUARD(ctx);
         dpclip::Args a;
-        std::memset(&a, 0, sizeof(a));
-        a.img = ctx->d_vjpimg.get();
-        fill_batch(a, *in);
-        fill_results(a, out);
-        a.mu = e.mu; a.n_accepted = e.n_accepted; a.clip_loss = e.clip_loss; a.loss_hist = e.loss_hist; a.info = e.info;
-        char* const ws = (char*)e.workspace;
-        for (int i = 0; i < 2; ++i) {
-            a.wz[i] = (float*)(ws + l.z[i]); a.wloss[i] = (float*)(ws + l.loss[i]); a.wcpl[i] = (double*)(ws + l.cpl[i]);
-        }
-        a.wag = (float*)(ws + l.ag); a.wli = (float*)(ws + l.li); a.wflags = (int*)(ws + l.flags); a.wtot = (double*)(ws + l.tot);
-        a.wword = (int*)(ws + l.word); a.wsolved = (int*)(ws + l.solved); a.wmu = (float*)(ws + l.mu); a.wnacc = (int*)(ws + l.nacc);
-        a.n_seq = n_seq; a.n_t = in->n_frames / n_seq; a.n_steps = la.n_steps;
-        a.lam_rot = la.lam_rot; a.lam_tmp = la.lam_tmp; a.lam_smooth = p.lambda_smooth;
-        a.mu0 = la.mu0; a.mu_up = la.mu_up; a.mu_down = la.mu_down; a.mu_min = la.mu_min; a.mu_max = la.mu_max;
+        fill_clip(a, ctx, in, n_seq, c, l);
         const hipError_t err = dp_launch_clip(&a, (hipStream_t)stream);
+        if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(err));
+        return (int)DP_OK;
+    });
+}
+extern "C" size_t dp_clip_lm_accel_workspace_bytes(int n_sequences, int n_frames)
+{
+    if (n_sequences <= 0 || n_frames <= 0 || n_frames % n_sequences != 0) return 0;
+    return dpclipacc::layout(n_sequences, n_frames).bytes;
+}
+extern "C" int dp_optimize_clip_lm_accel(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_clip_accel_params* a_in,
+                                         const dp_result* out_in, const dp_clip_lm_extra* e_in, void* stream)
+{
+    const char* who = "dp_optimize_clip_lm_accel";
+    return entry(ctx, who, [&] {
+        const std::string w = who;
+        ClipCall c;
+        if (int rc = take_clip(ctx, in, n_seq, p_in, out_in, e_in, c, who)) return rc;
+        constexpr unsigned min_size = (unsigned)(offsetof(dp_clip_accel_params, accel_loss) + sizeof(double*));
+        if (!a_in || a_in->struct_size < min_size || a_in->struct_size > 4096u)
+            return fail(ctx, DP_ERR_INVALID, w + (a_in ? ": dp_clip_accel_params.struct_size is " + std::to_string(a_in->struct_size) : ": dp_clip_accel_params is NULL") +
+                                                 ", this library expects at least " + std::to_string(min_size) + "  (dp_clip_accel_params a = DP_CLIP_ACCEL_PARAMS_INIT;)");
+        dp_clip_accel_params ap;
+        copy_sized(a_in, ap);
+        if (!(ap.lambda_accel >= 0.f && std::fabs(ap.lambda_accel) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": lambda_accel is negative or not finite");
+        const dpclipacc::Layout l = dpclipacc::layout(n_seq, in->n_frames);
+        if (int rc = clip_workspace(ctx, c.e, l.bytes, "dp_clip_lm_accel_workspace_bytes", n_seq, in->n_frames, who)) return rc;
+        if (REF8_BUILD) return refuse_ref8(ctx, who);
+        if (!dp_launch_clip_accel) return fail(ctx, DP_ERR_UNSUPPORTED, w + ": this library was linked without dp_clip_accel.hip");
+        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+        DEVICE_GUARD(ctx);
+        dpclipacc::Args a;
+        fill_clip(a.c, ctx, in, n_seq, c, l);
+        a.lam_accel = ap.lambda_accel;
+        a.accel_loss = ap.accel_loss;
+        a.wacc = (double*)((char*)c.e.workspace + l.acc);
+        const hipError_t err = dp_launch_clip_accel(&a, (hipStream_t)stream);
         if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(err));
         return (int)DP_OK;
     });

@@ -461,12 +461,13 @@ def finish_file(args, q, res, elapsed, lam_tmp, has_temporal, shared=1):
         mpjpe2, mpeepe2 = eval_pos_error(BVH().load(q["path"]), BVH().load(sm_path))
         jit1, jit_gt = jitter(BVH().load(q["path"]), BVH().load(out_path))
         jit2, _ = jitter(BVH().load(q["path"]), BVH().load(sm_path))
-        print(f"Smooth: lambda {clip.smooth} steps {clip.steps} anchor {anchor} (LatentOptimizer.optimize_clip_lm, include/dragposer_clip_lm.h): "
+        accel = "" if clip.accel is None else f" lambda_accel {clip.accel:g} (include/dragposer_clip_accel.h)"
+        print(f"Smooth: lambda {clip.smooth} steps {clip.steps} anchor {anchor}{accel} (LatentOptimizer.optimize_clip_lm, include/dragposer_clip_lm.h): "
               f"Mean Per Joint Position Error {mpjpe} -> {mpjpe2}, Mean End Effector Position Error {mpeepe} -> {mpeepe2}, jitter {jit1} -> {jit2} "
               f"(the ground truth's own: {jit_gt}); accepted {sm['n_accepted']} of {clip.steps} steps, sequence loss {sm['loss_hist'][0]:.6g} -> "
               f"{sm['loss_hist'][-1]:.6g} (coupling part {sm['clip_loss'][1]:.6g}), info {sm['info']}, frames with a status {sm['bad']}, {sm['time']:.3f} s")
         out.update(mpjpe_smooth=mpjpe2, mpeepe_smooth=mpeepe2, jitter=jit1, jitter_smooth=jit2, jitter_gt=jit_gt, out_smooth=sm_path,
-                   smooth_accepted=sm["n_accepted"], smooth_loss_hist=sm["loss_hist"])
+                   smooth_accepted=sm["n_accepted"], smooth_loss_hist=sm["loss_hist"], smooth_accel=clip.accel)
     if getattr(args, "keep_frames", False):
         out.update(poses=res["poses"], pos=res["pos"], iters=res["iters"])
     return out
@@ -600,6 +601,10 @@ def main(argv=None):
                          "Prints MPJPE and jitter before and after beside the ground truth's jitter and writes eval_smooth_<name>.  No default "
                          "LAMBDA: none has been found that helps on every clip.  Allowed after --solver and --latent-ar; not with --constraints, "
                          "--foot-lock, --tether, --balance, --gaps, --drop or --calibrate, and for a BVH with the model's own skeleton")
+    ap.add_argument("--smooth-accel", default=None, metavar="ACCEL",
+                    help="with --smooth: ACCEL |z_(t+1) - 2 z_t + z_(t-1)|^2 / 24 joins the second pass's loss, an acceleration penalty beside "
+                         "--smooth's velocity penalty (dp_optimize_clip_lm_accel, include/dragposer_clip_accel.h); --smooth 0:4 --smooth-accel 5 is "
+                         "the acceleration-only pass.  No default: none has been found that helps on every clip")
     ap.add_argument("--calibrate", default=None, metavar="GROUPS[:FRAMES[:ROUNDS]]",
                     help="a performer without a BVH file: ignore the clip's OFFSET table for the optimisation and fit the bone lengths from the "
                          "tracker targets first -- GROUPS uniform | limbs | symmetric | per_bone (dragposer_amd.BoneGroups), FRAMES frames drawn "
@@ -705,6 +710,14 @@ def main(argv=None):
             args.smooth_spec = (ClipLM(steps=int(parts[1]) if len(parts) > 1 and parts[1] else 4, smooth=float(parts[0])).check(), anchor)
         except ValueError as e:
             raise SystemExit(f"--smooth: expected LAMBDA[:STEPS[:ANCHOR]] with LAMBDA >= 0, 1 <= STEPS <= 64 and ANCHOR >= 0 ({e})")
+    if args.smooth_accel is not None:
+        if args.smooth_spec is None:
+            raise SystemExit("--smooth-accel requires --smooth (--smooth 0:4 --smooth-accel 5 is the acceleration-only pass)")
+        try:
+            args.smooth_spec[0].accel = float(args.smooth_accel)
+            args.smooth_spec[0].check()
+        except ValueError as e:
+            raise SystemExit(f"--smooth-accel: expected ACCEL >= 0 and finite ({e})")
     args.gaps_model = None
     if args.gaps is not None:
         from .gaps import Gaps

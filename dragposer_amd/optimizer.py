@@ -499,7 +499,10 @@ class LatentOptimizer:
         device: the damping of every sequence, read and updated IN PLACE; None: every sequence starts at clip.mu0.  Returns `optimize_lm`'s
         per-frame dict (every array belongs to the returned z; iters = the steps run; loss = the fp32 pass's numbers; no loss0) plus
         `clip_loss` [S,2] float64 (the sequence's loss at the returned latents, its coupling part), `loss_hist` [S, steps+1] float64,
-        `n_accepted` [S] int32, `mu` [S] and `info` [S] int32 (DP_CLIP_* flags).  The workspace is a buffer this optimiser keeps, by size.
+        `n_accepted` [S] int32, `mu` [S] and `info` [S] int32 (DP_CLIP_* flags).  With clip.accel a number the call is
+        dp_optimize_clip_lm_accel (include/dragposer_clip_accel.h): clip.accel |z_(t+1) - 2 z_t + z_(t-1)|^2 / 24 joins the loss, clip_loss[:, 1]
+        is both coupling sums and `accel_loss` [S] float64, the second-difference one, is one more output.  The workspace is a buffer this
+        optimiser keeps, by size.
         Asynchronous on torch's current stream, no host synchronisation."""
         from .clip import ClipLM
 
@@ -511,6 +514,9 @@ class LatentOptimizer:
         p = clip.to_struct(lambda_rot, lambda_tmp)
         own = {"clip_loss": ((S, 2), torch.float64), "loss_hist": ((S, clip.steps + 1), torch.float64), "n_accepted": ((S,), torch.int32),
                "mu": ((S,), torch.float32), "info": ((S,), torch.int32)}
+        accel = clip.accel_struct() if clip.accel is not None else None
+        if accel is not None:
+            own["accel_loss"] = ((S,), torch.float64)
         names = tuple(outputs) if outputs is not None else tuple(_OUT_SPECS) + tuple(own)
         unknown = [n for n in names if n not in own and n not in _OUT_SPECS]
         if unknown:
@@ -524,15 +530,18 @@ class LatentOptimizer:
                 t = out[name] if out is not None and name in out else torch.empty(shape, dtype=dtype, device=dev)
             else:
                 continue
-            setattr(ex, name, _check(t, name, shape, dtype, dev))
+            setattr(accel if name == "accel_loss" else ex, name, _check(t, name, shape, dtype, dev))
             tensors[name] = t
-        need = int(self.lib.dp_clip_lm_workspace_bytes(S, B))
+        need = int((self.lib.dp_clip_lm_workspace_bytes if accel is None else self.lib.dp_clip_lm_accel_workspace_bytes)(S, B))
         cache = self.__dict__.setdefault("_clip_workspaces", {})
         ws = cache.get(need)
         if ws is None:
             ws = cache[need] = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
         ex.workspace, ex.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        self._call(self.lib.dp_optimize_clip_lm, C.byref(batch), S, C.byref(p), C.byref(res), C.byref(ex))
+        if accel is None:
+            self._call(self.lib.dp_optimize_clip_lm, C.byref(batch), S, C.byref(p), C.byref(res), C.byref(ex))
+        else:
+            self._call(self.lib.dp_optimize_clip_lm_accel, C.byref(batch), S, C.byref(p), C.byref(accel), C.byref(res), C.byref(ex))
         return tensors
 
     def fit_bones(self, z, cur_rot, tgt_pos, w, tracked, groups, base=None, prior=None, ridge=1e-3, outputs=None, out=None):

@@ -43,9 +43,9 @@
  * batch refuses (n_frames, a NULL input array); n_sequences <= 0 or not dividing n_frames; lambda_smooth negative or not finite; a NULL
  * or short workspace.  Then DP_ERR_UNSUPPORTED from the test-only library, DP_ERR_DEVICE from a context without a device image.
  *
- * Not covered: a second-difference (acceleration) coupling, which would make the system block-pentadiagonal; term tables, points, holds,
- * gaps, tethers and per-frame skeletons in the clip loss; a parallel (cyclic-reduction) chain for one very long sequence -- the chain is
- * T dependent factorisations in one wave; DragPose and the plug-in.
+ * Not covered: term tables, points, holds, gaps, tethers and per-frame skeletons in the clip loss; a parallel (cyclic-reduction) chain for
+ * one very long sequence -- the chain is T dependent factorisations in one wave; DragPose and the plug-in.  (A second-difference
+ * (acceleration) coupling beside the first-difference one is dp_optimize_clip_lm_accel, include/dragposer_clip_accel.h.)
  */
 #ifndef DRAGPOSER_CLIP_LM_H
 #define DRAGPOSER_CLIP_LM_H

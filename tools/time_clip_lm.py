@@ -6,7 +6,10 @@ dp_optimize_sequence_lm's on the same clip in the same run.  Per shape (S, T) on
 is a fixed train of launches (dp_clip.hip: dp_launch_clip), so each launch's part is known from its place in the train.  Per part: the
 median over the calls (the first left out) of the part's summed kernel time, (max - min) / median, and the same per step.
     python tools/time_clip_lm.py [--out profiles/clip_lm_times.txt]
-Shapes: (1, 240) and (64, 240) on tests/data/example_clip.bvh, (1, 5052) on the example (tests/data/_local/example.bvh)."""
+Shapes: (1, 240) and (64, 240) on tests/data/example_clip.bvh, (1, 5052) on the example (tests/data/_local/example.bvh).
+    python tools/time_clip_lm.py --accel 5 [--out profiles/clip_accel_times.txt]
+also runs, in the same processes and after those calls, as many of dp_optimize_clip_lm_accel (include/dragposer_clip_accel.h, DESIGN.md section
+18a: lambda_smooth 0, lambda_accel ACCEL) and reports both trains and the ratio of the two chains."""
 import argparse
 import csv
 import glob
@@ -30,7 +33,7 @@ def train(steps):
     return t + ["rows: results"]
 
 
-def worker(S, T, rounds):
+def worker(S, T, rounds, accel=None):
     import torch
 
     sys.path.insert(0, ROOT)
@@ -84,9 +87,16 @@ def worker(S, T, rounds):
                                    clip=ClipLM(steps=STEPS, smooth=SMOOTH), lambda_rot=1.0, lambda_tmp=0.0)
     torch.cuda.synchronize()
     print(f"WORKER S {S} T {T}: accepted {out['n_accepted'].tolist()[:4]}, sequence loss {out['loss_hist'][0].tolist()}", flush=True)
+    if accel is not None:
+        for _ in range(rounds + 1):
+            out = opt.optimize_clip_lm(z, z.clone(), rot_before, tgt_pos.reshape(T * S, 22, 3), tgt_rot.reshape(T * S, 22, 9), w, tracked, n_sequences=S,
+                                       clip=ClipLM(steps=STEPS, smooth=0.0, accel=accel), lambda_rot=1.0, lambda_tmp=0.0)
+        torch.cuda.synchronize()
+        print(f"WORKER S {S} T {T} lambda_accel {accel:g}: accepted {out['n_accepted'].tolist()[:4]}, sequence loss {out['loss_hist'][0].tolist()}, "
+              f"its second-difference part {out['accel_loss'].tolist()[:4]}", flush=True)
 
 
-def summarise(path, S, T, rounds, lines):
+def summarise(path, S, T, rounds, lines, accel=None):
     rows = []
     with open(path, newline="") as f:
         for row in csv.DictReader(f):
@@ -95,9 +105,26 @@ def summarise(path, S, T, rounds, lines):
     clip = [(n, d) for _, n, d in rows if "dp_clip_" in n]
     seq = np.asarray([d for _, n, d in rows if "dp_lm_seq_kernel" in n])
     parts = train(STEPS)
-    assert len(clip) == (rounds + 1) * len(parts), (len(clip), len(parts))
-    lines.append(f"(S, T) = ({S}, {T}): {rounds} calls of {STEPS} steps, lambda_smooth {SMOOTH}; kernel time per call, microseconds")
+    n_train = (rounds + 1) * len(parts)
+    assert len(clip) == n_train * (1 if accel is None else 2), (len(clip), len(parts))
+    chain = summarise_train(clip[:n_train], f"lambda_smooth {SMOOTH}", S, T, rounds, lines)
+    if accel is not None:  # the second half of the trace: the same train, dp_clip_accel.hip's chain and decision in their places
+        assert all(("accel" in n) == (("chain" in n) or ("decide" in n)) for n, _ in clip[n_train:])
+        chain_accel = summarise_train(clip[n_train:], f"lambda_smooth 0, lambda_accel {accel:g} (dp_optimize_clip_lm_accel)", S, T, rounds, lines)
+        lines.append(f"  chain, dp_optimize_clip_lm_accel / dp_optimize_clip_lm: {chain_accel / chain:.3f}  ({chain_accel / STEPS / T:.2f} against {chain / STEPS / T:.2f} "
+                     "microseconds per frame per step)")
+    if len(seq) > 1:
+        v = seq[1:]
+        lines.append(f"  dp_lm_seq_kernel (dp_optimize_sequence_lm, LM({STEPS}), the same clip, this run) n {len(v)}  median {np.median(v):11.2f}  "
+                     f"(max - min) / median {(v.max() - v.min()) / np.median(v):.4f}  per frame of a sequence {np.median(v) / T:8.3f}")
+
+
+def summarise_train(clip, label, S, T, rounds, lines):
+    """one entry point's calls (the first left out) -> lines; returns the chain's median time per call"""
+    parts = train(STEPS)
+    lines.append(f"(S, T) = ({S}, {T}): {rounds} calls of {STEPS} steps, {label}; kernel time per call, microseconds")
     total = np.zeros(rounds)
+    chain = 0.0
     for part in ("rows: z0's pass, A | g", "rows: A | g", "rows: trial", "rows: results", "chain", "decision"):
         idx = [i for i, p in enumerate(parts) if p == part]
         want = "rows" if part.startswith("rows") else "chain" if part == "chain" else "decide"
@@ -108,38 +135,42 @@ def summarise(path, S, T, rounds, lines):
             per_call.append(sum(chunk[i][1] for i in idx))
         v = np.asarray(per_call)
         total += v
+        if part == "chain":
+            chain = float(np.median(v))
         lines.append(f"  {part:24s} launches {len(idx)}  median {np.median(v):11.2f}  (max - min) / median {(v.max() - v.min()) / np.median(v):.4f}  "
                      f"per launch {np.median(v) / len(idx):10.2f}  per launch and frame {np.median(v) / len(idx) / T:8.3f}")
     lines.append(f"  {'the call':24s} launches {len(parts)}  median {np.median(total):11.2f}  (max - min) / median {(total.max() - total.min()) / np.median(total):.4f}  "
                  f"per step {np.median(total) / STEPS:10.2f}  per step and frame of a sequence {np.median(total) / STEPS / T:8.3f}")
-    if len(seq) > 1:
-        v = seq[1:]
-        lines.append(f"  dp_lm_seq_kernel (dp_optimize_sequence_lm, LM({STEPS}), the same clip, this run) n {len(v)}  median {np.median(v):11.2f}  "
-                     f"(max - min) / median {(v.max() - v.min()) / np.median(v):.4f}  per frame of a sequence {np.median(v) / T:8.3f}")
+    return chain
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worker", type=int, nargs=2, default=None, metavar=("S", "T"))
     ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "clip_lm_times.txt"))
+    ap.add_argument("--accel", type=float, default=None, metavar="ACCEL", help="also time dp_optimize_clip_lm_accel at lambda_smooth 0, lambda_accel ACCEL (> 0)")
+    ap.add_argument("--out", default=None, help="default: profiles/clip_lm_times.txt, with --accel profiles/clip_accel_times.txt")
     args = ap.parse_args()
+    if args.accel is not None and not args.accel > 0:
+        raise SystemExit("--accel: expected ACCEL > 0 (0 runs dp_optimize_clip_lm's own train)")
     if args.worker:
-        return worker(args.worker[0], args.worker[1], args.rounds)
-    lines = ["dp_optimize_clip_lm: kernel times from rocprofv3 --kernel-trace --stats, one profiled process per shape (tools/time_clip_lm.py)"]
+        return worker(args.worker[0], args.worker[1], args.rounds, args.accel)
+    args.out = args.out or os.path.join(ROOT, "profiles", "clip_lm_times.txt" if args.accel is None else "clip_accel_times.txt")
+    lines = [("dp_optimize_clip_lm" if args.accel is None else "dp_optimize_clip_lm and dp_optimize_clip_lm_accel, the same processes")
+             + ": kernel times from rocprofv3 --kernel-trace --stats, one profiled process per shape (tools/time_clip_lm.py)"]
     for S, T in SHAPES:
         with tempfile.TemporaryDirectory() as d:
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "t", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-                   "--worker", str(S), str(T), "--rounds", str(args.rounds)]
+                   "--worker", str(S), str(T), "--rounds", str(args.rounds)] + (["--accel", str(args.accel)] if args.accel is not None else [])
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
             if r.returncode != 0:
                 raise SystemExit(f"({S}, {T}): the profiled process ended with {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
             found = glob.glob(os.path.join(d, "**", "t_kernel_trace.csv"), recursive=True)
             if len(found) != 1:
                 raise SystemExit(f"({S}, {T}): expected one kernel trace under {d}, found {found}")
-            summarise(found[0], S, T, args.rounds, lines)
+            summarise(found[0], S, T, args.rounds, lines, args.accel)
             lines += ["  " + l for l in r.stdout.splitlines() if l.startswith("WORKER")]
-        print("\n".join(lines[-12:]), flush=True)
+        print("\n".join(lines[-24:]), flush=True)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
