@@ -363,6 +363,8 @@ class DpClipLmParams(_Sized):
 
 # every symbol include/dragposer_clip_accel.h declares (tests/test_clip_accel_abi.py)
 CLIP_ACCEL_SYMBOLS = ("dp_clip_lm_accel_workspace_bytes", "dp_optimize_clip_lm_accel")
+# every symbol include/dragposer_clip_skeleton.h declares (tests/test_clip_skeleton_abi.py)
+CLIP_SKELETON_SYMBOLS = ("dp_optimize_clip_lm_skeleton", "dp_optimize_lm_skeleton")
 
 
 class DpClipAccelParams(_Sized):
@@ -499,6 +501,10 @@ def load(path=None):
     lib.dp_clip_lm_accel_workspace_bytes.restype = C.c_size_t
     lib.dp_optimize_clip_lm_accel.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.c_int, C.POINTER(DpClipLmParams), C.POINTER(DpClipAccelParams),
                                               C.POINTER(DpResult), C.POINTER(DpClipLmExtra), C.c_void_p]
+    lib.dp_optimize_clip_lm_skeleton.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.c_int, C.POINTER(DpClipLmParams), C.POINTER(DpClipAccelParams),
+                                                 C.POINTER(DpSkeletonIn), C.POINTER(DpResult), C.POINTER(DpClipLmExtra), C.c_void_p]
+    lib.dp_optimize_lm_skeleton.argtypes = [C.c_void_p, C.POINTER(DpBatch), C.POINTER(DpLmParams), C.POINTER(DpSkeletonIn), C.POINTER(DpResult),
+                                            C.POINTER(DpLmExtra), C.c_void_p]
     lib.dp_sequence_advance.argtypes = [C.c_void_p, C.c_int, C.POINTER(DpResult), C.POINTER(DpSeqState), C.POINTER(DpSeqStep), C.c_void_p]
     lib.dp_optimize_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DpSeqFrames), C.POINTER(DpParams), C.POINTER(DpSeqState),
                                          C.POINTER(DpSeqStep), C.POINTER(DpSeqResults), C.c_void_p]

@@ -103,7 +103,15 @@ struct Args {
     float mu0, mu_up, mu_down, mu_min, mu_max;
 };
 
+// The rows pass of a launch train (host side only): dp_launch_clip_rows, or another unit's kernel on the same argument block with what that
+// unit adds behind `own` (dp_clip_skel.hip).  The chain and the decision do not depend on it.
+struct Rows {
+    hipError_t (*launch)(const Args* args, int mode, const void* own, hipStream_t stream);
+    const void* own;
+};
+
 } // namespace dpclip
 
 hipError_t dp_launch_clip(const dpclip::Args* args, hipStream_t stream);
 hipError_t dp_launch_clip_rows(const dpclip::Args* args, int mode, hipStream_t stream);
+hipError_t dp_launch_clip_train(const dpclip::Args* args, const dpclip::Rows* rows, hipStream_t stream); // dp_launch_clip with `rows` as its rows pass

@@ -78,3 +78,4 @@ struct Args {
 } // namespace dpclipacc
 
 hipError_t dp_launch_clip_accel(const dpclipacc::Args* args, hipStream_t stream);
+hipError_t dp_launch_clip_accel_train(const dpclipacc::Args* args, const dpclip::Rows* rows, hipStream_t stream); // ... with `rows` as its rows pass

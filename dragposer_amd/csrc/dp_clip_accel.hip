@@ -367,11 +367,20 @@ __global__ __launch_bounds__(64) void dp_clip_accel_decide_kernel(KA::Args aa)
     }
 }
 
+static hipError_t plain_rows(const K::Args* args, int mode, const void*, hipStream_t stream) { return dp_launch_clip_rows(args, mode, stream); }
+
 hipError_t dp_launch_clip_accel(const KA::Args* args, hipStream_t stream)
 {
+    const K::Rows rows = {plain_rows, nullptr};
+    return dp_launch_clip_accel_train(args, &rows, stream);
+}
+
+hipError_t dp_launch_clip_accel_train(const KA::Args* args, const K::Rows* rows, hipStream_t stream)
+{
     KA::Args k = *args;
+    const auto run_rows = [&](int mode) { return rows->launch(&k.c, mode, rows->own, stream); };
     if (k.lam_accel == 0.f) { // dp_optimize_clip_lm's own train (its chain reads the first 600 floats of a frame's factor block), the new output 0
-        hipError_t e = dp_launch_clip(&k.c, stream);
+        hipError_t e = dp_launch_clip_train(&k.c, rows, stream);
         if (e == hipSuccess && k.accel_loss) e = hipMemsetAsync(k.accel_loss, 0, sizeof(double) * (size_t)k.c.n_seq, stream);
         return e;
     }
@@ -381,16 +390,16 @@ hipError_t dp_launch_clip_accel(const KA::Args* args, hipStream_t stream)
         hipLaunchKernelGGL(dp_clip_accel_decide_kernel, seqs, dim3(64), 0, stream, k);
         return hipGetLastError();
     };
-    hipError_t e = dp_launch_clip_rows(&k.c, K::M_INIT, stream);
+    hipError_t e = run_rows(K::M_INIT);
     if (e == hipSuccess) e = run_decide(-1);
     for (int st = 0; st < k.c.n_steps && e == hipSuccess; ++st) {
-        if (st > 0) e = dp_launch_clip_rows(&k.c, K::M_NORMAL, stream);
+        if (st > 0) e = run_rows(K::M_NORMAL);
         if (e != hipSuccess) break;
         hipLaunchKernelGGL(dp_clip_accel_chain_kernel, seqs, dim3(64), 0, stream, k);
         e = hipGetLastError();
-        if (e == hipSuccess) e = dp_launch_clip_rows(&k.c, K::M_TRIAL, stream);
+        if (e == hipSuccess) e = run_rows(K::M_TRIAL);
         if (e == hipSuccess) e = run_decide(st);
     }
-    if (e == hipSuccess) e = dp_launch_clip_rows(&k.c, K::M_RESULTS, stream);
+    if (e == hipSuccess) e = run_rows(K::M_RESULTS);
     return e;
 }

@@ -33,8 +33,10 @@
 #include "../../include/dragposer_calibration.h"
 #include "../../include/dragposer_clip_accel.h"
 #include "../../include/dragposer_clip_lm.h"
+#include "../../include/dragposer_clip_skeleton.h"
 #include "dp_clip.h"
 #include "dp_clip_accel.h"
+#include "dp_clip_skel.h"
 #include "dp_cons_live.h"
 #include "dp_cons_tether.h"
 #include "dp_cons_points.h"
@@ -1280,29 +1282,50 @@ static int take_lm(dp_ctx* ctx, const dp_lm_params* p_in, const dp_lm_extra* e_i
     return DP_OK;
 }
 
-extern "C" int dp_optimize_lm(dp_ctx* ctx, const dp_batch* in, const dp_lm_params* p_in, const dp_result* out_in, const dp_lm_extra* e_in, void* stream)
+// (A: dplm::Args or what a unit derives from it; own(a): that unit's refusals and fields, behind dp_optimize_lm's own; unit: its file, for the message)
+template <class A, class Own>
+static int lm_impl(dp_ctx* ctx, const dp_batch* in, const dp_lm_params* p_in, const dp_result* out_in, const dp_lm_extra* e_in, void* stream,
+                   const char* who, const Own& own, hipError_t (*launch)(const A*, hipStream_t), const char* unit)
 {
-    const char* who = "dp_optimize_lm";
     return entry(ctx, who, [&] {
-        if (!in || !p_in) return fail(ctx, DP_ERR_INVALID, "dp_optimize_lm: NULL batch or params");
+        if (!in || !p_in) return fail(ctx, DP_ERR_INVALID, std::string(who) + ": NULL batch or params");
         if (int rc = check_lm_params_size(ctx, p_in, who)) return rc;
         dp_result out;
         if (int rc = take_result(ctx, out_in, out, who)) return rc;
-        dplm::Args a;
+        A a;
         std::memset(&a, 0, sizeof(a));
         if (int rc = take_lm(ctx, p_in, e_in, a, who)) return rc;
         if (int rc = check_batch(ctx, in, who)) return rc;
+        if (int rc = own(a)) return rc;
         if (REF8_BUILD) return refuse_ref8(ctx, who);
-        if (!dp_launch_lm) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without dp_lm.hip");
+        if (!launch) return fail(ctx, DP_ERR_UNSUPPORTED, std::string(who) + ": this library was linked without " + unit);
         if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
         DEVICE_GUARD(ctx);
         a.img = ctx->d_vjpimg.get();
         fill_batch(a, *in);
         fill_results(a, out);
-        const hipError_t e = dp_launch_lm(&a, (hipStream_t)stream);
+        const hipError_t e = launch(&a, (hipStream_t)stream);
         if (e != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, std::string(who) + ": kernel launch: " + hipGetErrorString(e));
         return (int)DP_OK;
     });
+}
+extern "C" int dp_optimize_lm(dp_ctx* ctx, const dp_batch* in, const dp_lm_params* p_in, const dp_result* out_in, const dp_lm_extra* e_in, void* stream)
+{
+    return lm_impl<dplm::Args>(ctx, in, p_in, out_in, e_in, stream, "dp_optimize_lm", [](dplm::Args&) { return (int)DP_OK; }, dp_launch_lm, "dp_lm.hip");
+}
+
+// include/dragposer_clip_skeleton.h: dp_optimize_lm with the bones of each frame's own skeleton -- dp_optimize_lm's refusals, all of them, then
+// dp_skeleton_in's.  (Its launcher is a weak reference, like dp_launch_lm.)
+hipError_t dp_launch_lm_skel(const dplm::SkelArgs* args, hipStream_t stream) __attribute__((weak));
+extern "C" int dp_optimize_lm_skeleton(dp_ctx* ctx, const dp_batch* in, const dp_lm_params* p_in, const dp_skeleton_in* skel, const dp_result* out_in,
+                                       const dp_lm_extra* e_in, void* stream)
+{
+    const char* who = "dp_optimize_lm_skeleton";
+    const auto own = [&](dplm::SkelArgs& a) -> int {
+        if (!skel) return refuse_null_skeleton(ctx, who);
+        return take_skeleton(ctx, skel, a.skel, a.skel_stride, who);
+    };
+    return lm_impl<dplm::SkelArgs>(ctx, in, p_in, out_in, e_in, stream, who, own, dp_launch_lm_skel, "dp_lm_skel.hip");
 }
 
 // include/dragposer_lm_terms.h: dp_optimize_lm with a term table in its loss, in the header's order of refusals -- dp_optimize_lm's up to and
@@ -1497,6 +1520,18 @@ extern "C" int dp_optimize_clip_lm(dp_ctx* ctx, const dp_batch* in, int n_seq, c
         return (int)DP_OK;
     });
 }
+// dp_clip_accel_params as the caller compiled it: NULL or a bad size word, then lambda_accel
+static int take_clip_accel(dp_ctx* ctx, const dp_clip_accel_params* a_in, dp_clip_accel_params& ap, const char* who)
+{
+    const std::string w = who;
+    constexpr unsigned min_size = (unsigned)(offsetof(dp_clip_accel_params, accel_loss) + sizeof(double*));
+    if (!a_in || a_in->struct_size < min_size || a_in->struct_size > 4096u)
+        return fail(ctx, DP_ERR_INVALID, w + (a_in ? ": dp_clip_accel_params.struct_size is " + std::to_string(a_in->struct_size) : ": dp_clip_accel_params is NULL") +
+                                             ", this library expects at least " + std::to_string(min_size) + "  (dp_clip_accel_params a = DP_CLIP_ACCEL_PARAMS_INIT;)");
+    copy_sized(a_in, ap);
+    if (!(ap.lambda_accel >= 0.f && std::fabs(ap.lambda_accel) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": lambda_accel is negative or not finite");
+    return DP_OK;
+}
 extern "C" size_t dp_clip_lm_accel_workspace_bytes(int n_sequences, int n_frames)
 {
     if (n_sequences <= 0 || n_frames <= 0 || n_frames % n_sequences != 0) return 0;
@@ -1510,13 +1545,8 @@ extern "C" int dp_optimize_clip_lm_accel(dp_ctx* ctx, const dp_batch* in, int n_
         const std::string w = who;
         ClipCall c;
         if (int rc = take_clip(ctx, in, n_seq, p_in, out_in, e_in, c, who)) return rc;
-        constexpr unsigned min_size = (unsigned)(offsetof(dp_clip_accel_params, accel_loss) + sizeof(double*));
-        if (!a_in || a_in->struct_size < min_size || a_in->struct_size > 4096u)
-            return fail(ctx, DP_ERR_INVALID, w + (a_in ? ": dp_clip_accel_params.struct_size is " + std::to_string(a_in->struct_size) : ": dp_clip_accel_params is NULL") +
-                                                 ", this library expects at least " + std::to_string(min_size) + "  (dp_clip_accel_params a = DP_CLIP_ACCEL_PARAMS_INIT;)");
         dp_clip_accel_params ap;
-        copy_sized(a_in, ap);
-        if (!(ap.lambda_accel >= 0.f && std::fabs(ap.lambda_accel) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": lambda_accel is negative or not finite");
+        if (int rc = take_clip_accel(ctx, a_in, ap, who)) return rc;
         const dpclipacc::Layout l = dpclipacc::layout(n_seq, in->n_frames);
         if (int rc = clip_workspace(ctx, c.e, l.bytes, "dp_clip_lm_accel_workspace_bytes", n_seq, in->n_frames, who)) return rc;
         if (REF8_BUILD) return refuse_ref8(ctx, who);
@@ -1529,6 +1559,55 @@ extern "C" int dp_optimize_clip_lm_accel(dp_ctx* ctx, const dp_batch* in, int n_
         a.accel_loss = ap.accel_loss;
         a.wacc = (double*)((char*)c.e.workspace + l.acc);
         const hipError_t err = dp_launch_clip_accel(&a, (hipStream_t)stream);
+        if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(err));
+        return (int)DP_OK;
+    });
+}
+
+// include/dragposer_clip_skeleton.h: either clip call (a_in NULL: dp_optimize_clip_lm's problem and workspace) with the bones of each sequence's
+// own skeleton, in the header's order of refusals -- the plain call's own, dp_skeleton_in's, the workspace.  The launch trains are the plain
+// calls' with dp_clip_skel.hip's rows kernel as their rows pass.  (The launchers are weak references, like dp_launch_clip.)
+hipError_t dp_launch_clip_train(const dpclip::Args* args, const dpclip::Rows* rows, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_clip_accel_train(const dpclipacc::Args* args, const dpclip::Rows* rows, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_clip_rows_skel(const dpclip::Args* args, int mode, const void* own, hipStream_t stream) __attribute__((weak));
+extern "C" int dp_optimize_clip_lm_skeleton(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_clip_accel_params* a_in,
+                                            const dp_skeleton_in* skel, const dp_result* out_in, const dp_clip_lm_extra* e_in, void* stream)
+{
+    const char* who = "dp_optimize_clip_lm_skeleton";
+    return entry(ctx, who, [&] {
+        const std::string w = who;
+        ClipCall c;
+        if (int rc = take_clip(ctx, in, n_seq, p_in, out_in, e_in, c, who)) return rc;
+        dp_clip_accel_params ap = DP_CLIP_ACCEL_PARAMS_INIT;
+        if (a_in)
+            if (int rc = take_clip_accel(ctx, a_in, ap, who)) return rc;
+        if (!skel) return refuse_null_skeleton(ctx, who);
+        dpclip::SkelOwn own;
+        if (int rc = take_skeleton(ctx, skel, own.skel, own.skel_stride, who)) return rc;
+        const dpclip::Layout l = dpclip::layout(n_seq, in->n_frames);
+        const dpclipacc::Layout la = dpclipacc::layout(n_seq, in->n_frames);
+        if (int rc = clip_workspace(ctx, c.e, a_in ? la.bytes : l.bytes, a_in ? "dp_clip_lm_accel_workspace_bytes" : "dp_clip_lm_workspace_bytes", n_seq,
+                                    in->n_frames, who))
+            return rc;
+        if (REF8_BUILD) return refuse_ref8(ctx, who);
+        if (!dp_launch_clip_rows_skel || !dp_launch_clip_train || !dp_launch_clip_accel_train)
+            return fail(ctx, DP_ERR_UNSUPPORTED, w + ": this library was linked without dp_clip_skel.hip, dp_clip.hip or dp_clip_accel.hip");
+        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
+        DEVICE_GUARD(ctx);
+        const dpclip::Rows rows = {dp_launch_clip_rows_skel, &own};
+        hipError_t err;
+        if (a_in) {
+            dpclipacc::Args a;
+            fill_clip(a.c, ctx, in, n_seq, c, la);
+            a.lam_accel = ap.lambda_accel;
+            a.accel_loss = ap.accel_loss;
+            a.wacc = (double*)((char*)c.e.workspace + la.acc);
+            err = dp_launch_clip_accel_train(&a, &rows, (hipStream_t)stream);
+        } else {
+            dpclip::Args a;
+            fill_clip(a, ctx, in, n_seq, c, l);
+            err = dp_launch_clip_train(&a, &rows, (hipStream_t)stream);
+        }
         if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(err));
         return (int)DP_OK;
     });

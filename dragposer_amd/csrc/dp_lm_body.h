@@ -5,9 +5,23 @@
 //                 everything it adds stands behind this switch, so the other two kernels keep their instructions
 //   DP_LM_SEQ 1 and DP_LM_TERMS 1  dp_lm_seq_terms_kernel(SeqTermArgs): the step loop around the frame with the table (dp_lm_seq_terms.hip).
 //                 What only the two together need stands behind both switches, so the three kernels above keep their instructions
+//   DP_LM_SKEL 1 (with DP_LM_SEQ 0, DP_LM_TERMS 0)  dp_lm_skel_kernel(SkelArgs): the frame on its own skeleton's bones, taken by each wave into a
+//                 block of its own (dp_lm_skel.hip); what it adds stands behind this switch, so the four kernels above keep their instructions
 // TGT_POS(jj, c) / TGT_ROT(jj, k) are joint jj's targets of the frame at hand: the batch's row, or the step's row with the step's shift.
+// BONES is where the frame's [22][3] bone offsets are read from, by the lane's own off[] and by the tangents, which read another joint's bone.
 #ifndef DP_LM_TERMS
 #define DP_LM_TERMS 0
+#endif
+#ifndef DP_LM_SKEL
+#define DP_LM_SKEL 0
+#endif
+#if DP_LM_SKEL && (DP_LM_SEQ || DP_LM_TERMS)
+#error "per-frame skeletons: the plain frame only (include/dragposer_clip_skeleton.h, Not covered)"
+#endif
+#if DP_LM_SKEL
+#define BONES (skb + wv * SK_W)
+#else
+#define BONES (lds + L_OFF)
 #endif
 #if DP_LM_SEQ
 #define TGT_POS(jj, c) (a.q.tgt_root ? __fadd_rn(a.tgt_pos[(ft * NJ + (jj)) * 3 + (c)], sh[c]) : a.tgt_pos[(ft * NJ + (jj)) * 3 + (c)])
@@ -24,6 +38,9 @@
 #if DP_LM_TERMS
     __shared__ __attribute__((aligned(16))) float tl[TERM_LDS_FLOATS]; // the term table, then a block of rows per wave (dp_lm_terms.h)
 #endif
+#if DP_LM_SKEL
+    __shared__ float skb[WPB * SK_W]; // [22][3] bones per wave (dp_lm_skel.h)
+#endif
     const float* __restrict__ W = a.img;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int* par = (int*)(lds + L_PAR);
@@ -35,7 +52,9 @@
     for (int i = tid; i < dpvjp::NY * H1; i += WPB * 64) lds[L_A2 + (i / H1) * S2 + i % H1] = W[dpvjp::OFF_A2 + i];
     if (tid < dpvjp::NY) lds[L_SD + tid] = W[dpvjp::OFF_SD + tid];
     if (tid < NJ) par[tid] = Ti[dpvjp::OFF_PARENT + tid];
+#if !DP_LM_SKEL
     if (tid < 3 * NJ) lds[L_OFF + tid] = W[dpvjp::OFF_BONE + tid];
+#endif
 #if DP_LM_TERMS
     for (int i = tid; i < a.n_terms * TW; i += WPB * 64) ((unsigned*)tl)[TL_TBL + i] = a.tbl[i];
 #endif
@@ -103,6 +122,24 @@
     const float zt = lane < LAT ? a.z_tgt[f * LAT + lane] : 0.f;
     const bool trk = jl && a.tracked[f * NJ + j] != 0;
 #endif
+#if DP_LM_SKEL
+    // lane j: row j of this frame's skeleton (stride 0: the launch's one) into the wave's own block.  One unconditional load per row with the
+    // frame's other loads, the lanes beyond the joints on the last row; what is no bone (row 0, those lanes) is selected away afterwards.  A
+    // component out of range refuses the frame (include/dragposer_skeleton.h's rule).
+    bool bsk = false;
+    {
+        const float* __restrict__ sk = a.skel + f * (long long)a.skel_stride + 3 * (jl ? j : NJ - 1);
+        float o[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = sk[c];
+        const bool bone = jl && j != 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) bsk = bsk || (bone && refused(o[c]));
+        if (jl)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) BONES[3 * j + c] = bone ? o[c] : 0.f;
+    }
+#endif
 #if DP_LM_TERMS
     float gp[3] = {0.f, 0.f, 0.f}; // global_pos: read, and screened, only when an active PLANE or point-DISTANCE term exists
     if (a.need_gp)
@@ -114,6 +151,8 @@
 #endif
     const bool bs = refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]) || refused(gp[0]) || refused(gp[1]) ||
                     refused(gp[2]);
+#elif DP_LM_SKEL
+    const bool bs = bsk || refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]);
 #else
     const bool bs = refused(z0) || refused(cr[0]) || refused(cr[1]) || refused(cr[2]) || refused(cr[3]);
 #endif
@@ -251,7 +290,7 @@
     float sdj[4] = {1.f, 1.f, 1.f, 1.f}, muj[4] = {0.f, 0.f, 0.f, 0.f};
     if (jl) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) off[c] = lds[L_OFF + 3 * j + c];
+        for (int c = 0; c < 3; ++c) off[c] = BONES[3 * j + c];
 #pragma unroll
         for (int c = 0; c < 4; ++c) { sdj[c] = W[dpvjp::OFF_SD + 4 * j + c]; muj[c] = W[dpvjp::OFF_MU + 4 * j + c]; }
         SW[2 * j] = trk ? sqrtf(wp / (3.f * (float)E)) : 0.f;
@@ -783,7 +822,7 @@
                                 for (int e = 0; e < 4; ++e) dq[e] = TB[(4 * p + e) * ST + cn];
                                 unit_jvp(QN + 4 * p, RN[p], dq, dqn);
                                 rotmat_jvp(QN + 4 * p, dqn, dRp);
-                                mv(dRp, lds + L_OFF + 3 * c, t);
+                                mv(dRp, BONES + 3 * c, t);
                                 dv[0] += t[0]; dv[1] += t[1]; dv[2] += t[2];
                             }
                             c = p;
@@ -848,7 +887,7 @@
                     float r3[3] = {0.f, 0.f, 0.f};
                     if (mine != 0u && cn <= LAT) {
                         const int t = __builtin_ctz(mine);
-                        term_rows(tl + TL_TBL + t * TW, RW + 4 * t, cn, PB, GB, gp, a.up, par, lds + L_OFF, TB, QN, RN, RB, VB, R0, dR0, dwd, r3);
+                        term_rows(tl + TL_TBL + t * TW, RW + 4 * t, cn, PB, GB, gp, a.up, par, BONES, TB, QN, RN, RB, VB, R0, dR0, dwd, r3);
                     }
                     mine &= mine - 1u;
 #pragma unroll
@@ -952,4 +991,5 @@
 }
 #undef TGT_POS
 #undef TGT_ROT
+#undef BONES
 

@@ -374,9 +374,11 @@ def smooth_file(args, q, res, opt, cfg):
     pass's positions as the frame loop advances them, and the call's per-sequence outputs)"""
     clip, anchor = args.smooth_spec
     dev, m, T = opt.device, q["m"], q["n_frames"]
-    if not np.allclose(np.asarray(m["offsets"], np.float64).reshape(NJ, 3)[1:], np.asarray(opt.host_model.arrays["offsets"], np.float64).reshape(NJ, 3)[1:], atol=1e-6):
-        raise SystemExit(f"--smooth: {q['path']} has another skeleton than the context's; the joint pass has no per-frame skeletons "
-                         "(include/dragposer_clip_lm.h, Not covered)")
+    # the clip's own bones, as the first pass ran on them: passed to the joint pass when they differ from the context's
+    # (dp_optimize_clip_lm_skeleton, include/dragposer_clip_skeleton.h); when they agree the plain call is made, the same bits as ever
+    own = np.asarray(m["offsets"], np.float32).reshape(NJ, 3)
+    same = np.allclose(own[1:].astype(np.float64), np.asarray(opt.host_model.arrays["offsets"], np.float64).reshape(NJ, 3)[1:], atol=1e-6)
+    offsets = None if same else torch.as_tensor(np.ascontiguousarray(own), device=dev)
     mask_idx = np.nonzero(np.asarray(cfg["mask"]))[0]
     mt = torch.as_tensor(mask_idx, device=dev)
     sd4 = q["stds"]["dqs"].reshape(NJ, 8)[:, :4].reshape(88)[:4].astype(np.float32)
@@ -395,7 +397,7 @@ def smooth_file(args, q, res, opt, cfg):
     torch.cuda.synchronize()
     t0 = time.time()
     out = opt.optimize_clip_lm(z, z.clone(), torch.as_tensor(rot_before, device=dev).contiguous(), tgt_pos, tgt_rot, w, tracked, n_sequences=1, clip=clip,
-                               lambda_rot=1.0, lambda_tmp=anchor)
+                               lambda_rot=1.0, lambda_tmp=anchor, offsets=offsets)
     torch.cuda.synchronize()
     elapsed = time.time() - t0
     pos = pos_before + out["world_disp"]  # drag_pose.py:370, then the joint adjustment (drag_pose.py:377-384)
@@ -600,7 +602,8 @@ def main(argv=None):
                          "position the first pass left before it, with a pull of weight ANCHOR (default 0) towards the first pass's latent.  "
                          "Prints MPJPE and jitter before and after beside the ground truth's jitter and writes eval_smooth_<name>.  No default "
                          "LAMBDA: none has been found that helps on every clip.  Allowed after --solver and --latent-ar; not with --constraints, "
-                         "--foot-lock, --tether, --balance, --gaps, --drop or --calibrate, and for a BVH with the model's own skeleton")
+                         "--foot-lock, --tether, --balance, --gaps, --drop, --calibrate or --model-skeleton.  A BVH with another skeleton than "
+                         "the model's runs the joint pass on its own bones (dp_optimize_clip_lm_skeleton, include/dragposer_clip_skeleton.h)")
     ap.add_argument("--smooth-accel", default=None, metavar="ACCEL",
                     help="with --smooth: ACCEL |z_(t+1) - 2 z_t + z_(t-1)|^2 / 24 joins the second pass's loss, an acceleration penalty beside "
                          "--smooth's velocity penalty (dp_optimize_clip_lm_accel, include/dragposer_clip_accel.h); --smooth 0:4 --smooth-accel 5 is "

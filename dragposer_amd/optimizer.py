@@ -449,7 +449,7 @@ class LatentOptimizer:
             lambda gp, lt: terms.to_struct(int(z0.shape[0]), self.device, gp, lt), skel=skel, mid=mid)
 
     def optimize_lm(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, lm=None, lambda_rot=1.0, lambda_tmp=0.02, mu=None, stop_eps_pos=0.0,
-                    stop_eps_rot=0.0, outputs=None, out=None, terms=None, global_pos=None):
+                    stop_eps_rot=0.0, outputs=None, out=None, terms=None, global_pos=None, offsets=None):
         """`optimize`'s problem solved by Levenberg-Marquardt steps instead of Adam (`lm`: a dragposer_amd.LM; None = LM()):
         include/dragposer_lm.h, dp_optimize_lm (one launch).  Inputs as in `optimize`.  `mu` [B] fp32 on the device: the damping of every
         frame, read and updated IN PLACE (a caller keeps it from frame to frame); None: every frame starts at lm.mu0.  Returns `optimize`'s
@@ -459,11 +459,16 @@ class LatentOptimizer:
         `terms` (a dragposer_amd.Terms without points): the table's terms in the LM loss, include/dragposer_lm_terms.h,
         dp_optimize_lm_terms (one launch); `global_pos` [B,3] as in `optimize_terms`, required when an active PLANE or point-DISTANCE term
         exists.  The dict then also holds `loss_terms` [B, len(terms)], each weighted term at the returned z.  terms=None: dp_optimize_lm,
-        unchanged."""
+        unchanged.
+        `offsets` [22,3] / [B,22,3]: the performers' bone offsets, one skeleton for the launch or one per frame, as in `optimize`:
+        dp_optimize_lm_skeleton (include/dragposer_clip_skeleton.h).  Not together with `terms`.  None: the context's skeleton."""
         from .lm import LM
 
-        lm = (lm if lm is not None else LM()).check()
+        if offsets is not None and terms is not None:
+            raise ValueError("optimize_lm: offsets does not go with terms (include/dragposer_clip_skeleton.h, \"Not covered\")")
         B, dev = int(z0.shape[0]), self.device
+        skel = self._skeleton(offsets, B, "optimize_lm") if offsets is not None else None
+        lm = (lm if lm is not None else LM()).check()
         batch = self._batch(z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked)
         p = lm.to_struct(lambda_rot, lambda_tmp, stop_eps_pos, stop_eps_rot)
         own = {"n_accepted": ((B,), torch.int32), "loss0": ((B, 3), torch.float32), "mu": ((B,), torch.float32)}
@@ -479,6 +484,9 @@ class LatentOptimizer:
                 continue
             setattr(ex, name, _check(t, name, shape, dtype, dev))
             tensors[name] = t
+        if skel is not None:
+            self._call(self.lib.dp_optimize_lm_skeleton, C.byref(batch), C.byref(p), C.byref(skel), C.byref(res), C.byref(ex))
+            return tensors
         if terms is None:
             self._call(self.lib.dp_optimize_lm, C.byref(batch), C.byref(p), C.byref(res), C.byref(ex))
             return tensors
@@ -492,7 +500,7 @@ class LatentOptimizer:
         return tensors
 
     def optimize_clip_lm(self, z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked, n_sequences, clip=None, lambda_rot=1.0, lambda_tmp=0.0, mu=None,
-                         outputs=None, out=None):
+                         outputs=None, out=None, offsets=None):
         """A clip solved jointly (`clip`: a dragposer_amd.ClipLM; None = ClipLM()): include/dragposer_clip_lm.h, dp_optimize_clip_lm.  The B rows
         are `n_sequences` sequences of T = B / n_sequences frames, frame t of sequence s in row t * n_sequences + s; each row is `optimize_lm`'s
         frame, and the latents of a sequence are tied frame to frame by clip.smooth |z_t - z_(t-1)|^2 / 24 inside the loss.  `mu` [S] fp32 on the
@@ -503,6 +511,9 @@ class LatentOptimizer:
         dp_optimize_clip_lm_accel (include/dragposer_clip_accel.h): clip.accel |z_(t+1) - 2 z_t + z_(t-1)|^2 / 24 joins the loss, clip_loss[:, 1]
         is both coupling sums and `accel_loss` [S] float64, the second-difference one, is one more output.  The workspace is a buffer this
         optimiser keeps, by size.
+        `offsets` [22,3] / [S,22,3]: the performers' bone offsets, one skeleton for the launch or one per SEQUENCE, held for all its frames
+        (what `fit_bones` / dragposer_amd.calibrate return goes here): dp_optimize_clip_lm_skeleton (include/dragposer_clip_skeleton.h), with
+        or without clip.accel.  The tensor is read during the launch.  None: the context's skeleton, the plain calls, unchanged.
         Asynchronous on torch's current stream, no host synchronisation."""
         from .clip import ClipLM
 
@@ -510,6 +521,7 @@ class LatentOptimizer:
         B, dev, S = int(z0.shape[0]), self.device, int(n_sequences)
         if S <= 0 or B % S != 0:
             raise ValueError(f"optimize_clip_lm: n_sequences {n_sequences!r} must be positive and divide the {B} rows")
+        skel = self._skeleton(offsets, S, "optimize_clip_lm") if offsets is not None else None
         batch = self._batch(z0, z_tgt, cur_rot, tgt_pos, tgt_rot, w, tracked)
         p = clip.to_struct(lambda_rot, lambda_tmp)
         own = {"clip_loss": ((S, 2), torch.float64), "loss_hist": ((S, clip.steps + 1), torch.float64), "n_accepted": ((S,), torch.int32),
@@ -538,7 +550,10 @@ class LatentOptimizer:
         if ws is None:
             ws = cache[need] = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
         ex.workspace, ex.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        if accel is None:
+        if skel is not None:
+            self._call(self.lib.dp_optimize_clip_lm_skeleton, C.byref(batch), S, C.byref(p), C.byref(accel) if accel is not None else None, C.byref(skel),
+                       C.byref(res), C.byref(ex))
+        elif accel is None:
             self._call(self.lib.dp_optimize_clip_lm, C.byref(batch), S, C.byref(p), C.byref(res), C.byref(ex))
         else:
             self._call(self.lib.dp_optimize_clip_lm_accel, C.byref(batch), S, C.byref(p), C.byref(accel), C.byref(res), C.byref(ex))

@@ -9,7 +9,11 @@ median over the calls (the first left out) of the part's summed kernel time, (ma
 Shapes: (1, 240) and (64, 240) on tests/data/example_clip.bvh, (1, 5052) on the example (tests/data/_local/example.bvh).
     python tools/time_clip_lm.py --accel 5 [--out profiles/clip_accel_times.txt]
 also runs, in the same processes and after those calls, as many of dp_optimize_clip_lm_accel (include/dragposer_clip_accel.h, DESIGN.md section
-18a: lambda_smooth 0, lambda_accel ACCEL) and reports both trains and the ratio of the two chains."""
+18a: lambda_smooth 0, lambda_accel ACCEL) and reports both trains and the ratio of the two chains.
+    python tools/time_clip_lm.py --skeleton [--out profiles/clip_skel_times.txt]
+also runs, in the same processes and after the plain calls, as many of dp_optimize_clip_lm_skeleton (include/dragposer_clip_skeleton.h, DESIGN.md
+section 18b) on the same clip with the context's own offsets passed per sequence (stride 66: the same problem and the same bits, so the two trains
+do the same work), and reports both trains and, per part, the skeleton call's time over the plain call's with both spreads."""
 import argparse
 import csv
 import glob
@@ -33,7 +37,7 @@ def train(steps):
     return t + ["rows: results"]
 
 
-def worker(S, T, rounds, accel=None):
+def worker(S, T, rounds, accel=None, skeleton=False):
     import torch
 
     sys.path.insert(0, ROOT)
@@ -87,6 +91,14 @@ def worker(S, T, rounds, accel=None):
                                    clip=ClipLM(steps=STEPS, smooth=SMOOTH), lambda_rot=1.0, lambda_tmp=0.0)
     torch.cuda.synchronize()
     print(f"WORKER S {S} T {T}: accepted {out['n_accepted'].tolist()[:4]}, sequence loss {out['loss_hist'][0].tolist()}", flush=True)
+    if skeleton:
+        own = torch.as_tensor(np.asarray(raw["offsets"], np.float32).reshape(1, 22, 3), device=dev).expand(S, 22, 3).contiguous()
+        for _ in range(rounds + 1):
+            sk = opt.optimize_clip_lm(z, z.clone(), rot_before, tgt_pos.reshape(T * S, 22, 3), tgt_rot.reshape(T * S, 22, 9), w, tracked, n_sequences=S,
+                                      clip=ClipLM(steps=STEPS, smooth=SMOOTH), lambda_rot=1.0, lambda_tmp=0.0, offsets=own)
+        torch.cuda.synchronize()
+        print(f"WORKER S {S} T {T} offsets [{S}, 22, 3] (the context's own): accepted {sk['n_accepted'].tolist()[:4]}, sequence loss {sk['loss_hist'][0].tolist()}, "
+              f"the plain call's bits: {bool(torch.equal(sk['z'], out['z']) and torch.equal(sk['loss_hist'], out['loss_hist']))}", flush=True)
     if accel is not None:
         for _ in range(rounds + 1):
             out = opt.optimize_clip_lm(z, z.clone(), rot_before, tgt_pos.reshape(T * S, 22, 3), tgt_rot.reshape(T * S, 22, 9), w, tracked, n_sequences=S,
@@ -96,7 +108,7 @@ def worker(S, T, rounds, accel=None):
               f"its second-difference part {out['accel_loss'].tolist()[:4]}", flush=True)
 
 
-def summarise(path, S, T, rounds, lines, accel=None):
+def summarise(path, S, T, rounds, lines, accel=None, skeleton=False):
     rows = []
     with open(path, newline="") as f:
         for row in csv.DictReader(f):
@@ -106,8 +118,18 @@ def summarise(path, S, T, rounds, lines, accel=None):
     seq = np.asarray([d for _, n, d in rows if "dp_lm_seq_kernel" in n])
     parts = train(STEPS)
     n_train = (rounds + 1) * len(parts)
-    assert len(clip) == n_train * (1 if accel is None else 2), (len(clip), len(parts))
-    chain = summarise_train(clip[:n_train], f"lambda_smooth {SMOOTH}", S, T, rounds, lines)
+    assert len(clip) == n_train * (1 if accel is None and not skeleton else 2), (len(clip), len(parts))
+    plain = {}
+    chain = summarise_train(clip[:n_train], f"lambda_smooth {SMOOTH}", S, T, rounds, lines, plain)
+    if skeleton:  # the second half of the trace: the same train with dp_clip_skel.hip's rows kernel, the chain and the decision as they are
+        assert all(("skel" in n) == ("rows" in n) for n, _ in clip[n_train:]) and not any("skel" in n for n, _ in clip[:n_train])
+        skel = {}
+        summarise_train(clip[n_train:], f"lambda_smooth {SMOOTH}, offsets [{S}, 22, 3] (dp_optimize_clip_lm_skeleton)", S, T, rounds, lines, skel)
+        spread = lambda v: (v.max() - v.min()) / np.median(v)
+        for name, keys in (("rows kernel, all four passes", [k for k in plain if k.startswith("rows")]), ("chain", ["chain"]), ("decision", ["decision"])):
+            a, b = sum(skel[k] for k in keys), sum(plain[k] for k in keys)
+            lines.append(f"  {name}, dp_optimize_clip_lm_skeleton / dp_optimize_clip_lm: {np.median(a) / np.median(b):.4f}  (medians {np.median(a):.2f} / {np.median(b):.2f} "
+                         f"microseconds per call; (max - min) / median {spread(a):.4f} / {spread(b):.4f})")
     if accel is not None:  # the second half of the trace: the same train, dp_clip_accel.hip's chain and decision in their places
         assert all(("accel" in n) == (("chain" in n) or ("decide" in n)) for n, _ in clip[n_train:])
         chain_accel = summarise_train(clip[n_train:], f"lambda_smooth 0, lambda_accel {accel:g} (dp_optimize_clip_lm_accel)", S, T, rounds, lines)
@@ -119,8 +141,9 @@ def summarise(path, S, T, rounds, lines, accel=None):
                      f"(max - min) / median {(v.max() - v.min()) / np.median(v):.4f}  per frame of a sequence {np.median(v) / T:8.3f}")
 
 
-def summarise_train(clip, label, S, T, rounds, lines):
-    """one entry point's calls (the first left out) -> lines; returns the chain's median time per call"""
+def summarise_train(clip, label, S, T, rounds, lines, keep=None):
+    """one entry point's calls (the first left out) -> lines; returns the chain's median time per call (keep: a dict that takes every part's
+    times per call)"""
     parts = train(STEPS)
     lines.append(f"(S, T) = ({S}, {T}): {rounds} calls of {STEPS} steps, {label}; kernel time per call, microseconds")
     total = np.zeros(rounds)
@@ -135,6 +158,8 @@ def summarise_train(clip, label, S, T, rounds, lines):
             per_call.append(sum(chunk[i][1] for i in idx))
         v = np.asarray(per_call)
         total += v
+        if keep is not None:
+            keep[part] = v
         if part == "chain":
             chain = float(np.median(v))
         lines.append(f"  {part:24s} launches {len(idx)}  median {np.median(v):11.2f}  (max - min) / median {(v.max() - v.min()) / np.median(v):.4f}  "
@@ -149,26 +174,30 @@ def main():
     ap.add_argument("--worker", type=int, nargs=2, default=None, metavar=("S", "T"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--accel", type=float, default=None, metavar="ACCEL", help="also time dp_optimize_clip_lm_accel at lambda_smooth 0, lambda_accel ACCEL (> 0)")
-    ap.add_argument("--out", default=None, help="default: profiles/clip_lm_times.txt, with --accel profiles/clip_accel_times.txt")
+    ap.add_argument("--skeleton", action="store_true", help="also time dp_optimize_clip_lm_skeleton on the same clip, the context's own offsets passed per sequence")
+    ap.add_argument("--out", default=None, help="default: profiles/clip_lm_times.txt, with --accel profiles/clip_accel_times.txt, with --skeleton profiles/clip_skel_times.txt")
     args = ap.parse_args()
     if args.accel is not None and not args.accel > 0:
         raise SystemExit("--accel: expected ACCEL > 0 (0 runs dp_optimize_clip_lm's own train)")
+    if args.accel is not None and args.skeleton:
+        raise SystemExit("--accel and --skeleton: one comparison per run")
     if args.worker:
-        return worker(args.worker[0], args.worker[1], args.rounds, args.accel)
-    args.out = args.out or os.path.join(ROOT, "profiles", "clip_lm_times.txt" if args.accel is None else "clip_accel_times.txt")
-    lines = [("dp_optimize_clip_lm" if args.accel is None else "dp_optimize_clip_lm and dp_optimize_clip_lm_accel, the same processes")
+        return worker(args.worker[0], args.worker[1], args.rounds, args.accel, args.skeleton)
+    args.out = args.out or os.path.join(ROOT, "profiles", "clip_skel_times.txt" if args.skeleton else "clip_lm_times.txt" if args.accel is None else "clip_accel_times.txt")
+    lines = [("dp_optimize_clip_lm and dp_optimize_clip_lm_skeleton, the same processes" if args.skeleton else
+              "dp_optimize_clip_lm" if args.accel is None else "dp_optimize_clip_lm and dp_optimize_clip_lm_accel, the same processes")
              + ": kernel times from rocprofv3 --kernel-trace --stats, one profiled process per shape (tools/time_clip_lm.py)"]
     for S, T in SHAPES:
         with tempfile.TemporaryDirectory() as d:
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "t", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-                   "--worker", str(S), str(T), "--rounds", str(args.rounds)] + (["--accel", str(args.accel)] if args.accel is not None else [])
+                   "--worker", str(S), str(T), "--rounds", str(args.rounds)] + (["--accel", str(args.accel)] if args.accel is not None else []) + (["--skeleton"] if args.skeleton else [])
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
             if r.returncode != 0:
                 raise SystemExit(f"({S}, {T}): the profiled process ended with {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
             found = glob.glob(os.path.join(d, "**", "t_kernel_trace.csv"), recursive=True)
             if len(found) != 1:
                 raise SystemExit(f"({S}, {T}): expected one kernel trace under {d}, found {found}")
-            summarise(found[0], S, T, args.rounds, lines, args.accel)
+            summarise(found[0], S, T, args.rounds, lines, args.accel, args.skeleton)
             lines += ["  " + l for l in r.stdout.splitlines() if l.startswith("WORKER")]
         print("\n".join(lines[-24:]), flush=True)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
