@@ -3,7 +3,7 @@
 // blocks -c I.  Three kernels in a fixed train on the caller's stream (dp_launch_clip); what connects them is the caller's workspace (dp_clip.h).
 //
 // dp_clip_rows_kernel    one frame per wave, dp_lm.hip's layout: the forward pass, the tangents through the folded decoder and [J r]^T [J r]
-//                        on v_mfma_f32_16x16x4_f32 are dp_lm_body.h's, statement for statement.  By mode it writes A_t | g_t and the frame's
+//                        on v_mfma_f32_16x16x4_f32 are the text dp_lm_body.h includes, dp_lm_frame_*.h.  By mode it writes A_t | g_t and the frame's
 //                        loss numbers (the pass of z0, and again wherever Z has moved), the loss alone (a trial), or every dp_result array (at
 //                        the end).  A frame of a sequence whose last trial was rejected is skipped: its A and g stand.  Its text is
 //                        dp_clip_rows_body.h, shared with dp_clip_skel.hip's kernel (the bones of each sequence's own skeleton).

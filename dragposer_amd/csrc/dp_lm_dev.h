@@ -1,4 +1,6 @@
-// dp_lm_dev.h -- device helpers of dp_lm_body.h's kernels (dp_lm.hip, dp_lm_seq.hip); included once per unit, after dp_lm.h, dp_math.h and dp_vjp.h.
+// dp_lm_dev.h -- device helpers of the LM frame (dp_lm_frame_*.h) and of the two bodies around it: dp_lm_body.h's five units (dp_lm.hip,
+// dp_lm_seq.hip, dp_lm_terms.hip, dp_lm_seq_terms.hip, dp_lm_skel.hip) and dp_clip_rows_body.h's two (dp_clip.hip, dp_clip_skel.hip); included
+// once per unit, after dp_lm.h, dp_math.h and dp_vjp.h.
 #pragma once
 using namespace dplm;
 
