@@ -6,6 +6,8 @@
 // dp_clip_chain_kernel   one wave per sequence: the block recursion over the sequence's frames, forwards and backwards.
 // dp_clip_decide_kernel  one wave per sequence: the totals in double in index order, the decision, mu and the per-sequence word.
 // A call is a fixed train of these on the caller's stream (dp_launch_clip); what connects them is the workspace.
+// What dp_optimize_clip_lm_accel's unit (dp_clip_accel.h) takes from here instead of repeating it: the workspace's one list (Layout, layout()),
+// the launch train (train(), its chain and decision launches as parameters) and plain_rows.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,30 +42,32 @@ constexpr int CHAIN_LDS_FLOATS = C_V + 4 * 32;
 constexpr int CHAIN_LDS_BYTES = 4 * CHAIN_LDS_FLOATS;
 static_assert(CHAIN_LDS_BYTES == 8480, "the LDS budget stated in DESIGN.md section 18");
 
-// The workspace (bytes from its start; every part 16-byte aligned).  B = S T.
+// The workspace (bytes from its start; every part 16-byte aligned).  B = S T.  One list for both clip solves: what differs is the width of a
+// frame's factor block (LI_FLOATS here, dp_clip_accel.h's LF_FLOATS there) and whether the last part exists.
 struct Layout {
     size_t z[2];    // float [B][24] the kept latents and the trial's, by W_CUR
     size_t ag;      // float [B][AG_FLOATS]
-    size_t li;      // float [B][LI_FLOATS]
+    size_t li;      // float [B][factor_floats]
     size_t loss[2]; // float [B][4] a frame's three loss numbers and their fp32 sum, by W_CUR
     size_t cpl[2];  // double [B] |z_t - z_(t-1)|^2 (0 for t = 0), by W_CUR
     size_t flags;   // int [B] DP_STATUS_BAD_STATE / DP_STATUS_BAD_TARGETS of the frame
-    size_t tot;     // double [S][2] L_s of the kept Z, its coupling part
+    size_t tot;     // double [S][2] L_s of the kept Z, its coupling part (every coupling sum the call has)
     size_t word;    // int [S]
     size_t solved;  // int [S] the chain's last solve went through
     size_t mu;      // float [S]
     size_t nacc;    // int [S]
+    size_t acc;     // double [S] the second-difference part of L_s of the kept Z (with_acc; else no bytes)
     size_t bytes;
 };
 inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-inline Layout layout(int S, long long B)
+inline Layout layout(int S, long long B, int factor_floats = LI_FLOATS, bool with_acc = false)
 {
     Layout l;
     size_t at = 0;
     const auto take = [&](size_t bytes) { const size_t o = at; at = up16(at + bytes); return o; };
     for (int i = 0; i < 2; ++i) l.z[i] = take((size_t)B * LAT * 4);
     l.ag = take((size_t)B * AG_FLOATS * 4);
-    l.li = take((size_t)B * LI_FLOATS * 4);
+    l.li = take((size_t)B * factor_floats * 4);
     for (int i = 0; i < 2; ++i) l.loss[i] = take((size_t)B * 16);
     for (int i = 0; i < 2; ++i) l.cpl[i] = take((size_t)B * 8);
     l.flags = take((size_t)B * 4);
@@ -72,6 +76,7 @@ inline Layout layout(int S, long long B)
     l.solved = take((size_t)S * 4);
     l.mu = take((size_t)S * 4);
     l.nacc = take((size_t)S * 4);
+    l.acc = take(with_acc ? (size_t)S * 8 : 0);
     l.bytes = at;
     return l;
 }
@@ -103,8 +108,8 @@ struct Args {
     float mu0, mu_up, mu_down, mu_min, mu_max;
 };
 
-// The rows pass of a launch train (host side only): dp_launch_clip_rows, or another unit's kernel on the same argument block with what that
-// unit adds behind `own` (dp_clip_skel.hip).  The chain and the decision do not depend on it.
+// The rows pass of a launch train (host side only): plain_rows, or another unit's kernel on the same argument block with what that unit adds
+// behind `own` (dp_clip_skel.hip).  The chain and the decision do not depend on it.
 struct Rows {
     hipError_t (*launch)(const Args* args, int mode, const void* own, hipStream_t stream);
     const void* own;
@@ -115,3 +120,32 @@ struct Rows {
 hipError_t dp_launch_clip(const dpclip::Args* args, hipStream_t stream);
 hipError_t dp_launch_clip_rows(const dpclip::Args* args, int mode, hipStream_t stream);
 hipError_t dp_launch_clip_train(const dpclip::Args* args, const dpclip::Rows* rows, hipStream_t stream); // dp_launch_clip with `rows` as its rows pass
+
+namespace dpclip {
+
+static inline hipError_t plain_rows(const Args* args, int mode, const void*, hipStream_t stream) { return dp_launch_clip_rows(args, mode, stream); }
+
+// The launch train of a clip solve (host side only), once for every unit: rows(z0) . decide | per step: [rows(A, g) unless it is the first
+// step] . chain . rows(trial) . decide | rows(results).  `k` is dp_clip.h's part of the caller's own copy of its argument block; `chain()`
+// and `decide()` launch the unit's two kernels on that copy as it then stands (k->step is set before each decision) and return the error.
+template <class Chain, class Decide>
+inline hipError_t train(Args* k, const Rows* rows, hipStream_t stream, const Chain& chain, const Decide& decide)
+{
+    const auto run_rows = [&](int mode) { return rows->launch(k, mode, rows->own, stream); };
+    const auto run_decide = [&](int step) {
+        k->step = step;
+        return decide();
+    };
+    hipError_t e = run_rows(M_INIT);
+    if (e == hipSuccess) e = run_decide(-1);
+    for (int st = 0; st < k->n_steps && e == hipSuccess; ++st) {
+        if (st > 0) e = run_rows(M_NORMAL);
+        if (e == hipSuccess) e = chain();
+        if (e == hipSuccess) e = run_rows(M_TRIAL);
+        if (e == hipSuccess) e = run_decide(st);
+    }
+    if (e == hipSuccess) e = run_rows(M_RESULTS);
+    return e;
+}
+
+} // namespace dpclip

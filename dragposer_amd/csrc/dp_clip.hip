@@ -14,6 +14,10 @@
 //                        frame's is worked on.  The recursion is fp32.
 // dp_clip_decide_kernel  one wave per sequence: the frames' numbers added in double in index order, L_s(Z') < L_s(Z), mu, the word.
 // No atomics, no host synchronisation, no allocation: two launches give the same bits.
+//
+// Shared with dp_clip_accel.hip, each written once: the chain's factor step (Cholesky with the pivot screen, L_t^-1, y_t) is the text
+// dp_clip_factor.h, the block fetch dp_clip_dev.h's fetch64; the totals and the decision are the texts dp_clip_total.h and
+// dp_clip_decide_body.h (DP_CLIP_ACCEL); the launch train is dp_clip.h's train(), with this unit's chain and decision as its parameters.
 #include <hip/hip_runtime.h>
 
 #include "../../include/dragposer.h"
@@ -23,6 +27,7 @@
 #include "dp_vjp.h"
 
 #include "dp_lm_dev.h"
+#include "dp_clip_dev.h"
 
 namespace K = dpclip;
 static_assert(K::LAT == LAT && K::WPB == WPB, "dp_lm.h's frame");
@@ -53,13 +58,7 @@ __global__ __launch_bounds__(64) void dp_clip_chain_kernel(K::Args a)
 
     for (int e = lane; e < LAT * 8; e += 64) IB[(e >> 3) * CI + LAT + (e & 7)] = 0.f; // columns 24..31 of L^-1 as the matrix pipe reads it
     float pre[NPRE]; // the next frame's block, in flight while this frame's is worked on
-    const auto fetch = [&](const float* __restrict__ src) {
-#pragma unroll
-        for (int i = 0; i < NPRE; ++i) {
-            const int e = lane + 64 * i;
-            pre[i] = e < K::AG_FLOATS ? src[e] : 0.f;
-        }
-    };
+    const auto fetch = [&](const float* __restrict__ src) { fetch64(pre, src, K::AG_FLOATS, lane); }; // (= LI_FLOATS)
     fetch(a.wag + (long long)sq * K::AG_FLOATS);
     float zp = 0.f, zc = Z[(long long)sq * LAT + li], zn = 0.f;
     float xp[LAT]; // column `lane` of L_(t-1)^-1
@@ -87,21 +86,10 @@ __global__ __launch_bounds__(64) void dp_clip_chain_kernel(K::Args a)
             fetch(a.wag + (f + S) * K::AG_FLOATS);
             zn = Z[(f + S) * LAT + li];
         }
-        // ---- Cholesky in place, left-looking: lane i >= k forms s = S_ik - sum_(m<k) L_im L_km from its own row and row k
-        float myinv = 0.f;
-        for (int k = 0; k < LAT; ++k) {
-            wave_sync();
-            float s = SB[li * CS + k];
-#pragma unroll 4
-            for (int m = 0; m < k; ++m) s = fmaf(-SB[li * CS + m], SB[k * CS + m], s);
-            const float piv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), k));
-            ok = ok && piv > 0.f && piv <= 3.0e38f;
-            const float inv = 1.f / sqrtf(piv);
-            if (lane == k) myinv = inv;
-            if (lane > k && in) SB[lane * CS + k] = s * inv;
-        }
-        if (!ok) break; // (wave-uniform: the pivots are)
-        if (in) NV[lane] = myinv;
+        // ---- Cholesky in place, 1 / L_kk (dp_clip_factor.h: the text dp_clip_accel.hip's chain runs)
+#define CLIP_FACTOR 1
+#include "dp_clip_factor.h"
+#undef CLIP_FACTOR
         // the right-hand side: -G_t + c L_(t-1)^-T y_(t-1), lane i on component i (y_(t-1) is still in its place)
         float rhs = -(GV[li] + c * ((t > 0 ? zc - zp : 0.f) + (t < T - 1 ? zc - zn : 0.f)));
         if (t > 0) {
@@ -110,33 +98,14 @@ __global__ __launch_bounds__(64) void dp_clip_chain_kernel(K::Args a)
             for (int r = 0; r < LAT; ++r) u = fmaf(xp[r], YV[r], u);
             rhs = fmaf(c, u, rhs);
         }
-        wave_sync();
-        if (in) GV[lane] = rhs;
-        // ---- L_t^-1: lane i solves L x = e_i (what lies above the diagonal comes out as 0)
-        float x[LAT];
-#pragma unroll
-        for (int r = 0; r < LAT; ++r) {
-            float s = r == lane ? 1.f : 0.f;
-#pragma unroll
-            for (int m = 0; m < r; ++m) s = fmaf(-SB[r * CS + m], x[m], s);
-            x[r] = s * NV[r];
-        }
-        float* const lo = a.wli + f * K::LI_FLOATS;
-        if (in)
-#pragma unroll
-            for (int r = 0; r < LAT; ++r) {
-                IB[r * CI + lane] = x[r];
-                lo[r * LAT + lane] = x[r];
-            }
-        wave_sync();
-        // ---- y_t = L_t^-1 rhs, lane i on row i
-        float y = 0.f;
-#pragma unroll
-        for (int m = 0; m < LAT; ++m) y = fmaf(IB[li * CI + m], GV[m], y);
-        if (in) {
-            YV[lane] = y;
-            lo[LAT * LAT + lane] = y;
-        }
+        // ---- L_t^-1 | y_t into registers, LDS and the workspace
+#define CLIP_FACTOR 2
+#define CLIP_LI CI
+#define CLIP_WS (a.wli + f * K::LI_FLOATS)
+#include "dp_clip_factor.h"
+#undef CLIP_WS
+#undef CLIP_LI
+#undef CLIP_FACTOR
         // ---- P_t = L_t^-T L_t^-1 on the matrix pipe (K = the 24 rows, both operands the same values)
         if (t + 1 < T) {
             f4 na[2][2];
@@ -207,88 +176,13 @@ __global__ __launch_bounds__(64) void dp_clip_chain_kernel(K::Args a)
     }
 }
 
-// the frames' numbers of sequence sq in buffer b, added in double in index order: -> L_s, and the sum of the coupling parts in `cp`
-__device__ __forceinline__ double clip_total(const K::Args& a, int b, int sq, int lane, double& cp)
-{
-    const int S = a.n_seq, T = a.n_t;
-    double tot = 0.0, cs = 0.0;
-    for (int t0 = 0; t0 < T; t0 += 64) {
-        const int t = t0 + lane;
-        const float l = t < T ? a.wloss[b][((long long)t * S + sq) * 4 + 3] : 0.f;
-        const double q = t < T ? a.wcpl[b][(long long)t * S + sq] : 0.0;
-        const int lo = __double2loint(q), hi = __double2hiint(q);
-        const int n = T - t0 < 64 ? T - t0 : 64;
-        for (int i = 0; i < n; ++i) {
-            tot += (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(l), i));
-            cs += __hiloint2double(__builtin_amdgcn_readlane(hi, i), __builtin_amdgcn_readlane(lo, i));
-        }
-    }
-    cp = ((double)a.lam_smooth / 24.0) * cs;
-    return tot + cp;
-}
-
-// One wave per sequence.  step -1: after the pass of z0 -- is a frame refused, the damping the sequence starts from, L_s(Z0).  step k: trial
-// k's decision.  The last step's also hands the per-sequence outputs over.
+// the per-sequence totals and the decision: shared with dp_clip_accel.hip (DP_CLIP_ACCEL 1: the second-difference part beside them)
+#define DP_CLIP_ACCEL 0
+DEV double clip_total(const K::Args& a, int b, int sq, int lane, double& cp)
+#include "dp_clip_total.h"
 __global__ __launch_bounds__(64) void dp_clip_decide_kernel(K::Args a)
-{
-    const int lane = threadIdx.x, sq = blockIdx.x, S = a.n_seq, T = a.n_t, NH = a.n_steps + 1;
-    const double nan = __builtin_nan("");
-    if (a.step < 0) {
-        int fl = 0;
-        for (int t = lane; t < T; t += 64) fl |= a.wflags[(long long)t * S + sq];
-        const bool ref = __ballot(fl != 0) != 0ull;
-        float mu = a.mu ? a.mu[sq] : a.mu0;
-        if (!(mu >= a.mu_min && mu <= a.mu_max)) mu = a.mu0;
-        double cp = nan, tot = nan;
-        if (!ref) tot = clip_total(a, 0, sq, lane, cp);
-        if (lane == 0) {
-            a.wword[sq] = ref ? K::W_REFUSED : 0;
-            a.wmu[sq] = mu;
-            a.wnacc[sq] = 0;
-            a.wtot[2 * sq] = tot;
-            a.wtot[2 * sq + 1] = cp;
-            if (a.loss_hist) a.loss_hist[(long long)sq * NH] = tot;
-            if (ref) { // no step runs: what the sequence returns (mu stays as the caller holds it)
-                if (a.n_accepted) a.n_accepted[sq] = 0;
-                if (a.clip_loss) { a.clip_loss[2 * sq] = nan; a.clip_loss[2 * sq + 1] = nan; }
-                if (a.info) a.info[sq] = DP_CLIP_REFUSED_FRAME;
-            }
-        }
-        if (ref && a.loss_hist)
-            for (int k = 1 + lane; k < NH; k += 64) a.loss_hist[(long long)sq * NH + k] = nan;
-        return;
-    }
-    const int word = a.wword[sq];
-    if ((word & K::W_REFUSED) != 0) return;
-    const int cur = (word & K::W_CUR) != 0 ? 1 : 0;
-    double tot = a.wtot[2 * sq], cp = a.wtot[2 * sq + 1], cpn = nan, totn = nan;
-    if (a.wsolved[sq] != 0) totn = clip_total(a, cur ^ 1, sq, lane, cpn);
-    const bool acc = totn < tot; // (a NaN rejects)
-    if (lane == 0) {
-        float mu = a.wmu[sq];
-        int nacc = a.wnacc[sq];
-        if (acc) {
-            tot = totn; cp = cpn;
-            ++nacc;
-            mu = fmaxf(mu * a.mu_down, a.mu_min);
-            a.wword[sq] = cur ? 0 : K::W_CUR;
-            a.wtot[2 * sq] = tot;
-            a.wtot[2 * sq + 1] = cp;
-            a.wnacc[sq] = nacc;
-        } else {
-            mu = fminf(mu * a.mu_up, a.mu_max);
-            a.wword[sq] = (cur ? K::W_CUR : 0) | K::W_REJECTED;
-        }
-        a.wmu[sq] = mu;
-        if (a.loss_hist) a.loss_hist[(long long)sq * NH + a.step + 1] = tot;
-        if (a.step == a.n_steps - 1) {
-            if (a.mu) a.mu[sq] = mu;
-            if (a.n_accepted) a.n_accepted[sq] = nacc;
-            if (a.clip_loss) { a.clip_loss[2 * sq] = tot; a.clip_loss[2 * sq + 1] = cp; }
-            if (a.info) a.info[sq] = 0;
-        }
-    }
-}
+#include "dp_clip_decide_body.h"
+#undef DP_CLIP_ACCEL
 
 // one pass of the rows kernel in `mode` (M_*): also what another unit's launch train (dp_clip_accel.hip) runs between its own kernels
 hipError_t dp_launch_clip_rows(const K::Args* args, int mode, hipStream_t stream)
@@ -299,34 +193,18 @@ hipError_t dp_launch_clip_rows(const K::Args* args, int mode, hipStream_t stream
     return hipGetLastError();
 }
 
-static hipError_t plain_rows(const K::Args* args, int mode, const void*, hipStream_t stream) { return dp_launch_clip_rows(args, mode, stream); }
-
 hipError_t dp_launch_clip(const K::Args* args, hipStream_t stream)
 {
-    const K::Rows rows = {plain_rows, nullptr};
+    const K::Rows rows = {K::plain_rows, nullptr};
     return dp_launch_clip_train(args, &rows, stream);
 }
 
 hipError_t dp_launch_clip_train(const K::Args* args, const K::Rows* rows, hipStream_t stream)
 {
     K::Args k = *args;
-    const dim3 seqs((unsigned)k.n_seq);
-    const auto run_rows = [&](int mode) { return rows->launch(&k, mode, rows->own, stream); };
-    const auto run_decide = [&](int step) {
-        k.step = step;
-        hipLaunchKernelGGL(dp_clip_decide_kernel, seqs, dim3(64), 0, stream, k);
+    const auto launch = [&](void (*kernel)(K::Args)) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)k.n_seq), dim3(64), 0, stream, k);
         return hipGetLastError();
     };
-    hipError_t e = run_rows(K::M_INIT);
-    if (e == hipSuccess) e = run_decide(-1);
-    for (int st = 0; st < k.n_steps && e == hipSuccess; ++st) {
-        if (st > 0) e = run_rows(K::M_NORMAL);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(dp_clip_chain_kernel, seqs, dim3(64), 0, stream, k);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = run_rows(K::M_TRIAL);
-        if (e == hipSuccess) e = run_decide(st);
-    }
-    if (e == hipSuccess) e = run_rows(K::M_RESULTS);
-    return e;
+    return K::train(&k, rows, stream, [&] { return launch(dp_clip_chain_kernel); }, [&] { return launch(dp_clip_decide_kernel); });
 }

@@ -1,16 +1,17 @@
 // dp_clip_accel.hip -- dp_optimize_clip_lm_accel (include/dragposer_clip_accel.h): dp_optimize_clip_lm's problem with a second-difference
 // (acceleration) term beside the first-difference one.  The Gauss-Newton system of a sequence is block-pentadiagonal with 24 x 24 blocks; its
 // off-diagonal blocks are K[t,t-1] I and K[t,t-2] I, and its Cholesky factor has dense blocks F_t and E_t = k2 L_(t-2)^-T below the diagonal.
-// The rows kernel is dp_clip.hip's, unchanged; the launch train is dp_launch_clip's with this unit's chain and decision in their places.
+// The rows kernel is dp_clip.hip's, unchanged; the launch train is dp_clip.h's train() with this unit's chain and decision as its parameters.
 //
 // dp_clip_accel_chain_kernel   one wave per sequence.  Forwards over t, four 24 x 24 x 24 products on v_mfma_f32_16x16x4_f32:
 //                              F_t = (k1 I - k2 Q_t) L_(t-1)^-T,  F_t F_t^T,  Q_(t+1) = L_(t-1)^-T F_t^T (formed a frame ahead, while L_(t-1)^-1
-//                              is still in its place),  P_t = L_t^-T L_t^-1.  S_t = M_tt - k2^2 P_(t-2) - F_t F_t^T; Cholesky, L_t^-1 and y_t as
-//                              dp_clip_chain_kernel has them.  L_t^-1 | y_t | F_t go to the workspace.  Backwards over t:
+//                              is still in its place),  P_t = L_t^-T L_t^-1.  S_t = M_tt - k2^2 P_(t-2) - F_t F_t^T; Cholesky, L_t^-1 and y_t are
+//                              dp_clip_chain_kernel's text (dp_clip_factor.h).  L_t^-1 | y_t | F_t go to the workspace.  Backwards over t:
 //                              Delta_t = L_t^-T (y_t - F_(t+1)^T Delta_(t+1) - K[t+2,t] L_t^-1 Delta_(t+2)), Z' = Z + Delta.  The next frame's
 //                              block is fetched while this frame's is worked on, in both sweeps.  The recursion is fp32.
-// dp_clip_accel_decide_kernel  one wave per sequence: dp_clip_decide_kernel's sums, with |z_(t+1) - 2 z_t + z_(t-1)|^2 of the kept and of the
-//                              trial latents read from the latent buffers and added in double, each component in index order.
+// dp_clip_accel_decide_kernel  one wave per sequence: dp_clip_decide_kernel's text (dp_clip_total.h, dp_clip_decide_body.h) with DP_CLIP_ACCEL 1:
+//                              |z_(t+1) - 2 z_t + z_(t-1)|^2 of the kept and of the trial latents read from the latent buffers and added in
+//                              double, each component in index order.
 // No atomics, no host synchronisation, no allocation: two launches give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include "dp_vjp.h"
 
 #include "dp_lm_dev.h"
+#include "dp_clip_dev.h"
 
 namespace K = dpclip;
 namespace KA = dpclipacc;
@@ -41,42 +43,6 @@ DEV Band band(int t, int T, float c1, float c2)
     b.k1 = t > 0 ? -c1 - 2.f * c2 * (b.w[0] + b.w[1]) : 0.f;
     b.k2 = c2 * b.w[0]; // (t-1 a centre: t >= 2)
     return b;
-}
-
-// acc[mt][nt] += sum_k a(16 mt + i, k) b(k, 16 nt + j) over k < 24 on the fp32 matrix pipe.  Lane l: row l & 15 of an A tile, K-slot l >> 4;
-// column l & 15 of a B tile.  Rows and columns 24..31 of the second tiles repeat row / column 23: their results are not kept.
-template <class FA, class FB>
-DEV void mm24(const FA& a, const FB& b, f4 (&acc)[2][2], int lr16, int lk)
-{
-    const int r1 = 16 + lr16 < LAT ? 16 + lr16 : LAT - 1;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        const int k = 4 * s + lk;
-        const float a0 = a(lr16, k), a1 = a(r1, k), b0 = b(k, lr16), b1 = b(k, r1);
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-}
-// what a lane holds of a product: f(row, column, value) for its elements inside 24 x 24
-template <class F>
-DEV void each24(const f4 (&acc)[2][2], int lr16, int lk, const F& f)
-{
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 16 * mt + 4 * lk + r;
-            if (row < LAT) {
-                f(row, lr16, acc[mt][0][r]);
-                if (lr16 < LAT - 16) f(row, 16 + lr16, acc[mt][1][r]);
-            }
-        }
 }
 
 // One wave per sequence: M Delta = -G by the block recursion of include/dragposer_clip_accel.h, then Z' = Z + Delta.
@@ -102,13 +68,7 @@ __global__ __launch_bounds__(64) void dp_clip_accel_chain_kernel(KA::Args aa)
     // before frame 0 there is nothing: P, L^-1, F, Q and y are 0, and frames 0 and 1 run the same statements as every other
     for (int e = lane; e < KA::CHAIN_LDS_FLOATS; e += 64) lds[e] = 0.f;
     float pre[NPF]; // the next frame's block, in flight while this frame's is worked on
-    const auto fetch = [&](const float* __restrict__ src, int n) {
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            const int e = lane + 64 * i;
-            if (64 * i < n) pre[i] = e < n ? src[e] : 0.f;
-        }
-    };
+    const auto fetch = [&](const float* __restrict__ src, int n) { fetch64(pre, src, n, lane); };
     fetch(a.wag + (long long)sq * K::AG_FLOATS, K::AG_FLOATS);
     const auto zat = [&](int t) { return t < T ? Z[((long long)t * S + sq) * LAT + li] : 0.f; };
     float zm2 = 0.f, zm1 = 0.f, zc = zat(0), zp1 = zat(1), zp2 = zat(2); // component `lane` of z_(t-2) .. z_(t+2)
@@ -150,21 +110,10 @@ __global__ __launch_bounds__(64) void dp_clip_accel_chain_kernel(KA::Args aa)
         mm24([&](int i, int m) { return FB[i * CS + m]; }, [&](int m, int j) { return FB[j * CS + m]; }, acc, lr16, lk);
         wave_sync();
         each24(acc, lr16, lk, [&](int r, int cc, float v) { SB[r * CS + cc] -= v; });
-        // ---- Cholesky in place, left-looking: lane i >= k forms s = S_ik - sum_(m<k) L_im L_km from its own row and row k
-        float myinv = 0.f;
-        for (int k = 0; k < LAT; ++k) {
-            wave_sync();
-            float s = SB[li * CS + k];
-#pragma unroll 4
-            for (int m = 0; m < k; ++m) s = fmaf(-SB[li * CS + m], SB[k * CS + m], s);
-            const float piv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), k));
-            ok = ok && piv > 0.f && piv <= 3.0e38f;
-            const float inv = 1.f / sqrtf(piv);
-            if (lane == k) myinv = inv;
-            if (lane > k && in) SB[lane * CS + k] = s * inv;
-        }
-        if (!ok) break; // (wave-uniform: the pivots are)
-        if (in) NV[lane] = myinv;
+        // ---- Cholesky in place, 1 / L_kk (dp_clip_factor.h: dp_clip_chain_kernel's text)
+#define CLIP_FACTOR 1
+#include "dp_clip_factor.h"
+#undef CLIP_FACTOR
         // the right-hand side: -G_t - E_t y_(t-2) - F_t y_(t-1), lane i on component i (y_(t-1) is still in its place).  (K Z)_t is formed from
         // the differences, not from K's entries: the windows centred on t-1, t and t+1
         const float at_m = (zc - 2.f * zm1) + zm2, at_0 = (zp1 - 2.f * zc) + zm1, at_p = (zp2 - 2.f * zp1) + zc;
@@ -173,32 +122,14 @@ __global__ __launch_bounds__(64) void dp_clip_accel_chain_kernel(KA::Args aa)
 #pragma unroll
         for (int m = 0; m < LAT; ++m) fy = fmaf(FB[li * CS + m], YV[m], fy);
         const float rhs = fmaf(-kb.k2, u2, -(GV[li] + kz)) - fy;
-        wave_sync();
-        if (in) GV[lane] = rhs;
-        // ---- L_t^-1: lane i solves L x = e_i (what lies above the diagonal comes out as 0)
-        float x[LAT];
-#pragma unroll
-        for (int r = 0; r < LAT; ++r) {
-            float s = r == lane ? 1.f : 0.f;
-#pragma unroll
-            for (int m = 0; m < r; ++m) s = fmaf(-SB[r * CS + m], x[m], s);
-            x[r] = s * NV[r];
-        }
-        if (in)
-#pragma unroll
-            for (int r = 0; r < LAT; ++r) {
-                IB[r * CS + lane] = x[r];
-                lo[r * LAT + lane] = x[r];
-            }
-        wave_sync();
-        // ---- y_t = L_t^-1 rhs, lane i on row i
-        float y = 0.f;
-#pragma unroll
-        for (int m = 0; m < LAT; ++m) y = fmaf(IB[li * CS + m], GV[m], y);
-        if (in) {
-            YV[lane] = y;
-            lo[LAT * LAT + lane] = y;
-        }
+        // ---- L_t^-1 | y_t into registers, LDS and the workspace
+#define CLIP_FACTOR 2
+#define CLIP_LI CS
+#define CLIP_WS lo
+#include "dp_clip_factor.h"
+#undef CLIP_WS
+#undef CLIP_LI
+#undef CLIP_FACTOR
         // ---- P_t = L_t^-T L_t^-1, for frame t+2
         if (t + 2 < T) {
             mm24([&](int i, int m) { return IB[m * CS + i]; }, [&](int m, int j) { return IB[m * CS + j]; }, acc, lr16, lk);
@@ -257,149 +188,31 @@ __global__ __launch_bounds__(64) void dp_clip_accel_chain_kernel(KA::Args aa)
     }
 }
 
-// the frames' numbers of sequence sq in buffer b, added in double in index order: -> L_s; `cp`: both coupling sums; `ap`: the second-difference one
-DEV double accel_total(const KA::Args& aa, int b, int sq, int lane, double& cp, double& ap)
-{
-    const K::Args& a = aa.c;
-    const int S = a.n_seq, T = a.n_t;
-    double tot = 0.0, cs = 0.0, as = 0.0;
-    for (int t0 = 0; t0 < T; t0 += 64) {
-        const int t = t0 + lane;
-        const float l = t < T ? a.wloss[b][((long long)t * S + sq) * 4 + 3] : 0.f;
-        const double q = t < T ? a.wcpl[b][(long long)t * S + sq] : 0.0;
-        const int lo = __double2loint(q), hi = __double2hiint(q);
-        const int n = T - t0 < 64 ? T - t0 : 64;
-        for (int i = 0; i < n; ++i) {
-            tot += (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(l), i));
-            cs += __hiloint2double(__builtin_amdgcn_readlane(hi, i), __builtin_amdgcn_readlane(lo, i));
-        }
-    }
-    // |z_(t+1) - 2 z_t + z_(t-1)|^2 from the latents themselves: lane k adds component k's squares over the frames in index order, and the 24
-    // sums meet once at the end (a wave sum per frame, five dependent shuffles of a double, cost 0.35 us per frame)
-    const float* __restrict__ Z = a.wz[b];
-    const int li = lane < LAT ? lane : LAT - 1;
-    const auto zat = [&](int t) { return (double)Z[((long long)t * S + sq) * LAT + li]; };
-    double zm = T > 2 ? zat(0) : 0.0, zc = T > 2 ? zat(1) : 0.0;
-    constexpr int AHEAD = 8; // frames loaded together
-    for (int t0 = 1; t0 + 1 < T; t0 += AHEAD) {
-        double zn[AHEAD];
-#pragma unroll
-        for (int u = 0; u < AHEAD; ++u) zn[u] = t0 + u + 1 < T ? zat(t0 + u + 1) : 0.0;
-#pragma unroll
-        for (int u = 0; u < AHEAD; ++u)
-            if (t0 + u + 1 < T) { // (wave-uniform)
-                const double d = (zn[u] - 2.0 * zc) + zm;
-                as = fma(d, d, as);
-                zm = zc;
-                zc = zn[u];
-            }
-    }
-    as = wsum_d(lane < LAT ? as : 0.0);
-    ap = ((double)aa.lam_accel / 24.0) * as;
-    cp = ((double)a.lam_smooth / 24.0) * cs + ap;
-    return tot + cp;
-}
-
-// One wave per sequence: dp_clip_decide_kernel's steps, with the second-difference part in the totals and kept beside them.
+// dp_clip.hip's totals and decision, with the second-difference part in the totals and kept beside them
+#define DP_CLIP_ACCEL 1
+DEV double clip_total(const KA::Args& aa, int b, int sq, int lane, double& cp, double& ap)
+#include "dp_clip_total.h"
 __global__ __launch_bounds__(64) void dp_clip_accel_decide_kernel(KA::Args aa)
-{
-    const K::Args& a = aa.c;
-    const int lane = threadIdx.x, sq = blockIdx.x, S = a.n_seq, T = a.n_t, NH = a.n_steps + 1;
-    const double nan = __builtin_nan("");
-    if (a.step < 0) {
-        int fl = 0;
-        for (int t = lane; t < T; t += 64) fl |= a.wflags[(long long)t * S + sq];
-        const bool ref = __ballot(fl != 0) != 0ull;
-        float mu = a.mu ? a.mu[sq] : a.mu0;
-        if (!(mu >= a.mu_min && mu <= a.mu_max)) mu = a.mu0;
-        double cp = nan, ap = nan, tot = nan;
-        if (!ref) tot = accel_total(aa, 0, sq, lane, cp, ap);
-        if (lane == 0) {
-            a.wword[sq] = ref ? K::W_REFUSED : 0;
-            a.wmu[sq] = mu;
-            a.wnacc[sq] = 0;
-            a.wtot[2 * sq] = tot;
-            a.wtot[2 * sq + 1] = cp;
-            aa.wacc[sq] = ap;
-            if (a.loss_hist) a.loss_hist[(long long)sq * NH] = tot;
-            if (ref) { // no step runs: what the sequence returns (mu stays as the caller holds it)
-                if (a.n_accepted) a.n_accepted[sq] = 0;
-                if (a.clip_loss) { a.clip_loss[2 * sq] = nan; a.clip_loss[2 * sq + 1] = nan; }
-                if (aa.accel_loss) aa.accel_loss[sq] = nan;
-                if (a.info) a.info[sq] = DP_CLIP_REFUSED_FRAME;
-            }
-        }
-        if (ref && a.loss_hist)
-            for (int k = 1 + lane; k < NH; k += 64) a.loss_hist[(long long)sq * NH + k] = nan;
-        return;
-    }
-    const int word = a.wword[sq];
-    if ((word & K::W_REFUSED) != 0) return;
-    const int cur = (word & K::W_CUR) != 0 ? 1 : 0;
-    double tot = a.wtot[2 * sq], cp = a.wtot[2 * sq + 1], ap = aa.wacc[sq], cpn = nan, apn = nan, totn = nan;
-    if (a.wsolved[sq] != 0) totn = accel_total(aa, cur ^ 1, sq, lane, cpn, apn);
-    const bool acc = totn < tot; // (a NaN rejects)
-    if (lane == 0) {
-        float mu = a.wmu[sq];
-        int nacc = a.wnacc[sq];
-        if (acc) {
-            tot = totn; cp = cpn; ap = apn;
-            ++nacc;
-            mu = fmaxf(mu * a.mu_down, a.mu_min);
-            a.wword[sq] = cur ? 0 : K::W_CUR;
-            a.wtot[2 * sq] = tot;
-            a.wtot[2 * sq + 1] = cp;
-            aa.wacc[sq] = ap;
-            a.wnacc[sq] = nacc;
-        } else {
-            mu = fminf(mu * a.mu_up, a.mu_max);
-            a.wword[sq] = (cur ? K::W_CUR : 0) | K::W_REJECTED;
-        }
-        a.wmu[sq] = mu;
-        if (a.loss_hist) a.loss_hist[(long long)sq * NH + a.step + 1] = tot;
-        if (a.step == a.n_steps - 1) {
-            if (a.mu) a.mu[sq] = mu;
-            if (a.n_accepted) a.n_accepted[sq] = nacc;
-            if (a.clip_loss) { a.clip_loss[2 * sq] = tot; a.clip_loss[2 * sq + 1] = cp; }
-            if (aa.accel_loss) aa.accel_loss[sq] = ap;
-            if (a.info) a.info[sq] = 0;
-        }
-    }
-}
-
-static hipError_t plain_rows(const K::Args* args, int mode, const void*, hipStream_t stream) { return dp_launch_clip_rows(args, mode, stream); }
+#include "dp_clip_decide_body.h"
+#undef DP_CLIP_ACCEL
 
 hipError_t dp_launch_clip_accel(const KA::Args* args, hipStream_t stream)
 {
-    const K::Rows rows = {plain_rows, nullptr};
+    const K::Rows rows = {K::plain_rows, nullptr};
     return dp_launch_clip_accel_train(args, &rows, stream);
 }
 
 hipError_t dp_launch_clip_accel_train(const KA::Args* args, const K::Rows* rows, hipStream_t stream)
 {
     KA::Args k = *args;
-    const auto run_rows = [&](int mode) { return rows->launch(&k.c, mode, rows->own, stream); };
     if (k.lam_accel == 0.f) { // dp_optimize_clip_lm's own train (its chain reads the first 600 floats of a frame's factor block), the new output 0
         hipError_t e = dp_launch_clip_train(&k.c, rows, stream);
         if (e == hipSuccess && k.accel_loss) e = hipMemsetAsync(k.accel_loss, 0, sizeof(double) * (size_t)k.c.n_seq, stream);
         return e;
     }
-    const dim3 seqs((unsigned)k.c.n_seq);
-    const auto run_decide = [&](int step) {
-        k.c.step = step;
-        hipLaunchKernelGGL(dp_clip_accel_decide_kernel, seqs, dim3(64), 0, stream, k);
+    const auto launch = [&](void (*kernel)(KA::Args)) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)k.c.n_seq), dim3(64), 0, stream, k);
         return hipGetLastError();
     };
-    hipError_t e = run_rows(K::M_INIT);
-    if (e == hipSuccess) e = run_decide(-1);
-    for (int st = 0; st < k.c.n_steps && e == hipSuccess; ++st) {
-        if (st > 0) e = run_rows(K::M_NORMAL);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(dp_clip_accel_chain_kernel, seqs, dim3(64), 0, stream, k);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = run_rows(K::M_TRIAL);
-        if (e == hipSuccess) e = run_decide(st);
-    }
-    if (e == hipSuccess) e = run_rows(K::M_RESULTS);
-    return e;
+    return K::train(&k.c, rows, stream, [&] { return launch(dp_clip_accel_chain_kernel); }, [&] { return launch(dp_clip_accel_decide_kernel); });
 }

@@ -1431,13 +1431,17 @@ extern "C" int dp_fit_bones(dp_ctx* ctx, const dp_batch* in, const dp_bone_fit* 
     });
 }
 
-// include/dragposer_clip_lm.h: dp_optimize_clip_lm, in the header's order of refusals.  dp_clip_lm_params has dp_lm_params' fields without the
-// early stop and lambda_smooth among them: its values pass through take_lm_params as a dp_lm_params, so the two calls refuse alike.  (Its
-// launcher is a weak reference, like dp_launch_lm.)  include/dragposer_clip_accel.h: dp_optimize_clip_lm_accel is the same call with one more
-// struct, a wider workspace and its own launch train; what the two share is take_clip (every refusal up to lambda_smooth), clip_workspace and
-// fill_clip.
+// include/dragposer_clip_lm.h, dragposer_clip_accel.h, dragposer_clip_skeleton.h: dp_optimize_clip_lm, dp_optimize_clip_lm_accel (the same call
+// with one more struct, a wider workspace and its own chain and decision) and dp_optimize_clip_lm_skeleton (either, with the bones of each
+// sequence's own skeleton in the rows pass) are one path, clip_impl, in the headers' order of refusals: take_clip; take_clip_accel where the
+// call has the struct; the skeleton's; the workspace; the test-only library; the missing unit; the missing image.  dp_clip_lm_params has
+// dp_lm_params' fields without the early stop and lambda_smooth among them: its values pass through take_lm_params as a dp_lm_params, so the
+// calls refuse as dp_optimize_lm does.  (The launchers are weak references, like dp_launch_lm.)
 hipError_t dp_launch_clip(const dpclip::Args* args, hipStream_t stream) __attribute__((weak));
 hipError_t dp_launch_clip_accel(const dpclipacc::Args* args, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_clip_train(const dpclip::Args* args, const dpclip::Rows* rows, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_clip_accel_train(const dpclipacc::Args* args, const dpclip::Rows* rows, hipStream_t stream) __attribute__((weak));
+hipError_t dp_launch_clip_rows_skel(const dpclip::Args* args, int mode, const void* own, hipStream_t stream) __attribute__((weak));
 struct ClipCall {
     dp_result out;
     dp_clip_lm_extra e;
@@ -1467,16 +1471,31 @@ static int take_clip(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_l
     if (!(c.p.lambda_smooth >= 0.f && std::fabs(c.p.lambda_smooth) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": lambda_smooth is negative or not finite");
     return DP_OK;
 }
-static int clip_workspace(dp_ctx* ctx, const dp_clip_lm_extra& e, size_t need, const char* size_fn, int n_seq, int n_frames, const char* who)
+// dp_clip_accel_params as the caller compiled it: NULL or a bad size word, then lambda_accel
+static int take_clip_accel(dp_ctx* ctx, const dp_clip_accel_params* a_in, dp_clip_accel_params& ap, const char* who)
 {
-    if (!e.workspace || e.workspace_bytes < need)
-        return fail(ctx, DP_ERR_INVALID, std::string(who) + ": the workspace is NULL or holds " + std::to_string(e.workspace_bytes) + " bytes, fewer than the " +
-                                             std::to_string(need) + " of " + size_fn + "(" + std::to_string(n_seq) + ", " + std::to_string(n_frames) + ")");
+    const std::string w = who;
+    constexpr unsigned min_size = (unsigned)(offsetof(dp_clip_accel_params, accel_loss) + sizeof(double*));
+    if (!a_in || a_in->struct_size < min_size || a_in->struct_size > 4096u)
+        return fail(ctx, DP_ERR_INVALID, w + (a_in ? ": dp_clip_accel_params.struct_size is " + std::to_string(a_in->struct_size) : ": dp_clip_accel_params is NULL") +
+                                             ", this library expects at least " + std::to_string(min_size) + "  (dp_clip_accel_params a = DP_CLIP_ACCEL_PARAMS_INIT;)");
+    copy_sized(a_in, ap);
+    if (!(ap.lambda_accel >= 0.f && std::fabs(ap.lambda_accel) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": lambda_accel is negative or not finite");
     return DP_OK;
 }
-// (L: dp_clip.h's Layout or dp_clip_accel.h's -- the same names)
-template <class L>
-static void fill_clip(dpclip::Args& a, const dp_ctx* ctx, const dp_batch* in, int n_seq, const ClipCall& c, const L& l)
+// the workspace of either problem (dp_clip.h's one list): with the acceleration term the factor block is wider and `acc` exists
+static dpclip::Layout clip_layout(int n_seq, int n_frames, bool accel)
+{
+    return accel ? dpclip::layout(n_seq, n_frames, dpclipacc::LF_FLOATS, true) : dpclip::layout(n_seq, n_frames);
+}
+static size_t clip_workspace_bytes(int n_sequences, int n_frames, bool accel)
+{
+    if (n_sequences <= 0 || n_frames <= 0 || n_frames % n_sequences != 0) return 0;
+    return clip_layout(n_sequences, n_frames, accel).bytes;
+}
+extern "C" size_t dp_clip_lm_workspace_bytes(int n_sequences, int n_frames) { return clip_workspace_bytes(n_sequences, n_frames, false); }
+extern "C" size_t dp_clip_lm_accel_workspace_bytes(int n_sequences, int n_frames) { return clip_workspace_bytes(n_sequences, n_frames, true); }
+static void fill_clip(dpclip::Args& a, const dp_ctx* ctx, const dp_batch* in, int n_seq, const ClipCall& c, const dpclip::Layout& l)
 {
     std::memset(&a, 0, sizeof(a));
     a.img = ctx->d_vjpimg.get();
@@ -1494,123 +1513,64 @@ static void fill_clip(dpclip::Args& a, const dp_ctx* ctx, const dp_batch* in, in
     a.lam_rot = c.la.lam_rot; a.lam_tmp = c.la.lam_tmp; a.lam_smooth = c.p.lambda_smooth;
     a.mu0 = c.la.mu0; a.mu_up = c.la.mu_up; a.mu_down = c.la.mu_down; a.mu_min = c.la.mu_min; a.mu_max = c.la.mu_max;
 }
-extern "C" size_t dp_clip_lm_workspace_bytes(int n_sequences, int n_frames)
+// accel: the call has a dp_clip_accel_params and solves its problem on its workspace (a_in NULL is then take_clip_accel's refusal).
+// skeleton: the call has a dp_skeleton_in, and the launch trains run with dp_clip_skel.hip's rows kernel as their rows pass.
+static int clip_impl(dp_ctx* ctx, const char* who, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, bool accel, const dp_clip_accel_params* a_in,
+                     bool skeleton, const dp_skeleton_in* skel, const dp_result* out_in, const dp_clip_lm_extra* e_in, void* stream)
 {
-    if (n_sequences <= 0 || n_frames <= 0 || n_frames % n_sequences != 0) return 0;
-    return dpclip::layout(n_sequences, n_frames).bytes;
-}
-extern "C" int dp_optimize_clip_lm(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_result* out_in,
-                                   const dp_clip_lm_extra* e_in, void* stream)
-{
-    const char* who = "dp_optimize_clip_lm";
-    return entry(ctx, who, [&] {
-        const std::string w = who;
-        ClipCall c;
-        if (int rc = take_clip(ctx, in, n_seq, p_in, out_in, e_in, c, who)) return rc;
-        const dpclip::Layout l = dpclip::layout(n_seq, in->n_frames);
-        if (int rc = clip_workspace(ctx, c.e, l.bytes, "dp_clip_lm_workspace_bytes", n_seq, in->n_frames, who)) return rc;
-        if (REF8_BUILD) return refuse_ref8(ctx, who);
-        if (!dp_launch_clip) return fail(ctx, DP_ERR_UNSUPPORTED, w + ": this library was linked without dp_clip.hip");
-        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
-        DEVICE_GUARD(ctx);
-        dpclip::Args a;
-        fill_clip(a, ctx, in, n_seq, c, l);
-        const hipError_t err = dp_launch_clip(&a, (hipStream_t)stream);
-        if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(err));
-        return (int)DP_OK;
-    });
-}
-// dp_clip_accel_params as the caller compiled it: NULL or a bad size word, then lambda_accel
-static int take_clip_accel(dp_ctx* ctx, const dp_clip_accel_params* a_in, dp_clip_accel_params& ap, const char* who)
-{
-    const std::string w = who;
-    constexpr unsigned min_size = (unsigned)(offsetof(dp_clip_accel_params, accel_loss) + sizeof(double*));
-    if (!a_in || a_in->struct_size < min_size || a_in->struct_size > 4096u)
-        return fail(ctx, DP_ERR_INVALID, w + (a_in ? ": dp_clip_accel_params.struct_size is " + std::to_string(a_in->struct_size) : ": dp_clip_accel_params is NULL") +
-                                             ", this library expects at least " + std::to_string(min_size) + "  (dp_clip_accel_params a = DP_CLIP_ACCEL_PARAMS_INIT;)");
-    copy_sized(a_in, ap);
-    if (!(ap.lambda_accel >= 0.f && std::fabs(ap.lambda_accel) <= 3.0e38f)) return fail(ctx, DP_ERR_INVALID, w + ": lambda_accel is negative or not finite");
-    return DP_OK;
-}
-extern "C" size_t dp_clip_lm_accel_workspace_bytes(int n_sequences, int n_frames)
-{
-    if (n_sequences <= 0 || n_frames <= 0 || n_frames % n_sequences != 0) return 0;
-    return dpclipacc::layout(n_sequences, n_frames).bytes;
-}
-extern "C" int dp_optimize_clip_lm_accel(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_clip_accel_params* a_in,
-                                         const dp_result* out_in, const dp_clip_lm_extra* e_in, void* stream)
-{
-    const char* who = "dp_optimize_clip_lm_accel";
-    return entry(ctx, who, [&] {
-        const std::string w = who;
-        ClipCall c;
-        if (int rc = take_clip(ctx, in, n_seq, p_in, out_in, e_in, c, who)) return rc;
-        dp_clip_accel_params ap;
-        if (int rc = take_clip_accel(ctx, a_in, ap, who)) return rc;
-        const dpclipacc::Layout l = dpclipacc::layout(n_seq, in->n_frames);
-        if (int rc = clip_workspace(ctx, c.e, l.bytes, "dp_clip_lm_accel_workspace_bytes", n_seq, in->n_frames, who)) return rc;
-        if (REF8_BUILD) return refuse_ref8(ctx, who);
-        if (!dp_launch_clip_accel) return fail(ctx, DP_ERR_UNSUPPORTED, w + ": this library was linked without dp_clip_accel.hip");
-        if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
-        DEVICE_GUARD(ctx);
-        dpclipacc::Args a;
-        fill_clip(a.c, ctx, in, n_seq, c, l);
-        a.lam_accel = ap.lambda_accel;
-        a.accel_loss = ap.accel_loss;
-        a.wacc = (double*)((char*)c.e.workspace + l.acc);
-        const hipError_t err = dp_launch_clip_accel(&a, (hipStream_t)stream);
-        if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(err));
-        return (int)DP_OK;
-    });
-}
-
-// include/dragposer_clip_skeleton.h: either clip call (a_in NULL: dp_optimize_clip_lm's problem and workspace) with the bones of each sequence's
-// own skeleton, in the header's order of refusals -- the plain call's own, dp_skeleton_in's, the workspace.  The launch trains are the plain
-// calls' with dp_clip_skel.hip's rows kernel as their rows pass.  (The launchers are weak references, like dp_launch_clip.)
-hipError_t dp_launch_clip_train(const dpclip::Args* args, const dpclip::Rows* rows, hipStream_t stream) __attribute__((weak));
-hipError_t dp_launch_clip_accel_train(const dpclipacc::Args* args, const dpclip::Rows* rows, hipStream_t stream) __attribute__((weak));
-hipError_t dp_launch_clip_rows_skel(const dpclip::Args* args, int mode, const void* own, hipStream_t stream) __attribute__((weak));
-extern "C" int dp_optimize_clip_lm_skeleton(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_clip_accel_params* a_in,
-                                            const dp_skeleton_in* skel, const dp_result* out_in, const dp_clip_lm_extra* e_in, void* stream)
-{
-    const char* who = "dp_optimize_clip_lm_skeleton";
     return entry(ctx, who, [&] {
         const std::string w = who;
         ClipCall c;
         if (int rc = take_clip(ctx, in, n_seq, p_in, out_in, e_in, c, who)) return rc;
         dp_clip_accel_params ap = DP_CLIP_ACCEL_PARAMS_INIT;
-        if (a_in)
+        if (accel)
             if (int rc = take_clip_accel(ctx, a_in, ap, who)) return rc;
-        if (!skel) return refuse_null_skeleton(ctx, who);
         dpclip::SkelOwn own;
-        if (int rc = take_skeleton(ctx, skel, own.skel, own.skel_stride, who)) return rc;
-        const dpclip::Layout l = dpclip::layout(n_seq, in->n_frames);
-        const dpclipacc::Layout la = dpclipacc::layout(n_seq, in->n_frames);
-        if (int rc = clip_workspace(ctx, c.e, a_in ? la.bytes : l.bytes, a_in ? "dp_clip_lm_accel_workspace_bytes" : "dp_clip_lm_workspace_bytes", n_seq,
-                                    in->n_frames, who))
-            return rc;
+        if (skeleton) {
+            if (!skel) return refuse_null_skeleton(ctx, who);
+            if (int rc = take_skeleton(ctx, skel, own.skel, own.skel_stride, who)) return rc;
+        }
+        const dpclip::Layout l = clip_layout(n_seq, in->n_frames, accel);
+        if (!c.e.workspace || c.e.workspace_bytes < l.bytes)
+            return fail(ctx, DP_ERR_INVALID, w + ": the workspace is NULL or holds " + std::to_string(c.e.workspace_bytes) + " bytes, fewer than the " +
+                                                 std::to_string(l.bytes) + " of " + (accel ? "dp_clip_lm_accel_workspace_bytes" : "dp_clip_lm_workspace_bytes") + "(" +
+                                                 std::to_string(n_seq) + ", " + std::to_string(in->n_frames) + ")");
         if (REF8_BUILD) return refuse_ref8(ctx, who);
-        if (!dp_launch_clip_rows_skel || !dp_launch_clip_train || !dp_launch_clip_accel_train)
-            return fail(ctx, DP_ERR_UNSUPPORTED, w + ": this library was linked without dp_clip_skel.hip, dp_clip.hip or dp_clip_accel.hip");
+        if (skeleton ? !dp_launch_clip_rows_skel || !dp_launch_clip_train || !dp_launch_clip_accel_train : accel ? !dp_launch_clip_accel : !dp_launch_clip)
+            return fail(ctx, DP_ERR_UNSUPPORTED, w + ": this library was linked without " +
+                                                     (skeleton ? "dp_clip_skel.hip, dp_clip.hip or dp_clip_accel.hip" : accel ? "dp_clip_accel.hip" : "dp_clip.hip"));
         if (!ctx->d_vjpimg.get()) return refuse_no_image(ctx, who);
         DEVICE_GUARD(ctx);
-        const dpclip::Rows rows = {dp_launch_clip_rows_skel, &own};
-        hipError_t err;
-        if (a_in) {
-            dpclipacc::Args a;
-            fill_clip(a.c, ctx, in, n_seq, c, la);
+        dpclipacc::Args a; // (without the acceleration term only its dp_clip.h part is filled and launched)
+        fill_clip(a.c, ctx, in, n_seq, c, l);
+        if (accel) {
             a.lam_accel = ap.lambda_accel;
             a.accel_loss = ap.accel_loss;
-            a.wacc = (double*)((char*)c.e.workspace + la.acc);
-            err = dp_launch_clip_accel_train(&a, &rows, (hipStream_t)stream);
-        } else {
-            dpclip::Args a;
-            fill_clip(a, ctx, in, n_seq, c, l);
-            err = dp_launch_clip_train(&a, &rows, (hipStream_t)stream);
+            a.wacc = (double*)((char*)c.e.workspace + l.acc);
         }
+        const dpclip::Rows rows = {dp_launch_clip_rows_skel, &own};
+        const hipStream_t s = (hipStream_t)stream;
+        const hipError_t err = skeleton ? (accel ? dp_launch_clip_accel_train(&a, &rows, s) : dp_launch_clip_train(&a.c, &rows, s))
+                                        : (accel ? dp_launch_clip_accel(&a, s) : dp_launch_clip(&a.c, s));
         if (err != hipSuccess) return fail(ctx, DP_ERR_LAUNCH, w + ": kernel launch: " + hipGetErrorString(err));
         return (int)DP_OK;
     });
+}
+extern "C" int dp_optimize_clip_lm(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_result* out_in,
+                                   const dp_clip_lm_extra* e_in, void* stream)
+{
+    return clip_impl(ctx, "dp_optimize_clip_lm", in, n_seq, p_in, false, nullptr, false, nullptr, out_in, e_in, stream);
+}
+extern "C" int dp_optimize_clip_lm_accel(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_clip_accel_params* a_in,
+                                         const dp_result* out_in, const dp_clip_lm_extra* e_in, void* stream)
+{
+    return clip_impl(ctx, "dp_optimize_clip_lm_accel", in, n_seq, p_in, true, a_in, false, nullptr, out_in, e_in, stream);
+}
+// (a_in NULL: dp_optimize_clip_lm's problem and workspace)
+extern "C" int dp_optimize_clip_lm_skeleton(dp_ctx* ctx, const dp_batch* in, int n_seq, const dp_clip_lm_params* p_in, const dp_clip_accel_params* a_in,
+                                            const dp_skeleton_in* skel, const dp_result* out_in, const dp_clip_lm_extra* e_in, void* stream)
+{
+    return clip_impl(ctx, "dp_optimize_clip_lm_skeleton", in, n_seq, p_in, a_in != nullptr, a_in, true, skel, out_in, e_in, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -184,6 +184,8 @@ def test_workspace_bytes_is_monotone_and_zero_for_what_the_call_refuses():
         assert ws(1, T) > prev
         prev = ws(1, T)
     assert ws(3, 6) < ws(3, 9) and ws(2, 6) != 0 and ws(1, 5052) < 2 ** 31
+    # the byte counts themselves (n_sequences, n_frames): both calls size one list, dp_clip.h's, and a caller's allocation must keep fitting
+    assert [ws(*a) for a in ((1, 1), (3, 9), (2, 130), (1, 5052))] == [7472, 66304, 955360, 37122192]
 
 
 def test_the_test_only_library_declines():
